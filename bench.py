@@ -14,14 +14,22 @@ relays rank 0's one JSON line and returns the launcher's exit code.  Every line 
 (SUM-all-reduce of ones), config.rank_devices (PCI bus id / UUID / arch of the card each rank held), config.per_rank_frames_per_s, and
 both north-star shapes as barrier-aligned whole-job legs (config.kitti2000_frames_per_s, config.tum640_frames_per_s).
 
-Rank 0 prints ONE JSON line.  `roofline` prices the dominant kernel (largest share of the HIP-event
+A plain run does only what the headline figure needs: set-up, `--warmup` steps, the `--steps` timed steps, the outputs of the last
+step when `--dump-outputs DIR` is given, and rank 0's JSON line (metric, value, unit, higher_is_better, dtype, ms_per_step = ms of
+one timed step, the workload and the rank evidence).  Everything below -- the stage breakdown and roofline, the oracle verification,
+the extra legs, the CPU baseline -- runs only with `--full`; `--extras`, `--no-verify` and `--cpu-frames` trim a `--full` run.
+
+`--dump-outputs DIR` (rank 0) writes what the timed path computed in its LAST step as float32 .npy files (dump_outputs): the inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
+
+Rank 0 prints ONE JSON line.  With `--full`, `roofline` prices the dominant kernel (largest share of the HIP-event
 time measured live on the launch stream during the timed region) by its ALGORITHMIC bytes
 (DESIGN.md section "Kernels") and, under `roofline.issue`, by its measured VALU instruction count against
 the chip's wave-instruction issue rate (the bound these integer kernels actually run into);
 `cpu_baseline` times the CPU oracle (oracle/, a port: the reference itself needs OpenCV and cannot be
 built) on a bounded sample of the same workload on rank 0, N=1.
 
-Outside the timed region the headline run also (rank 0 / every rank as noted):
+Outside the timed region a `--full` headline run also (rank 0 / every rank as noted):
   * compares the LAST step's device outputs of every frame of the batch (keypoints, descriptors, uRight, depth) with the
     CPU oracle's results for the distinct synthetic pairs -> "verified"; a mismatch makes the exit code non-zero;
   * sweeps the batch size (frames per launch set) -> config.batch_sweep_frames_per_s;
@@ -375,8 +383,55 @@ def host_fed_c_client(streams, frames=1500):
         return {"error": str(exc)[:200]}
 
 
+DUMP_BYTES = 56 << 20      # --dump-outputs: the sampled frames' arrays stay under this (64 MB in all with the rest)
+DUMP_MAX_FRAMES = 64
+
+
+def dump_outputs(out_dir, pkg, B, stereo, nout, kps, desc, ur=None, dp=None, bow=None):
+    """--dump-outputs: the last timed step's results as the arrays a caller receives, float32 .npy files in out_dir.
+
+    n_keypoints [images]          keypoints found in every image of the step (stereo: left eyes 0..B-1, then the right eyes)
+    sample_images [m]             the images of a fixed seeded sample of frames (stereo: left, right per frame), in dump order
+    keypoints [sum n, 7]          x, y, size, angle, response, octave, class_id of the sampled images, concatenated in that order
+    descriptors [sum n, 32]       their 32 descriptor bytes
+    u_right, depth [sum n_left]   stereo: per keypoint of the sampled frames' left eyes
+    bow_matches [B, keyframes]    BoW device chain: matches per (frame, keyframe), every frame of the step
+    bow_frame0_matches [k, 3]     BoW device chain: frame 0's (keyframe, frame feature, keyframe feature) matches"""
+    os.makedirs(out_dir, exist_ok=True)
+    cap = kps.shape[1]
+    n = nout.cpu().numpy().astype(np.int64)
+    per_frame = (2 if stereo else 1) * cap * (7 + 32 + 2) * 4
+    S = max(1, min(B, DUMP_MAX_FRAMES, DUMP_BYTES // per_frame))
+    frames = np.sort(np.random.Generator(np.random.PCG64(12345)).choice(B, S, replace=False))
+    imgs = np.stack([frames, frames + B], 1).reshape(-1) if stereo else frames
+    k_h = kps[imgs].cpu().numpy().view(pkg.KP_DTYPE).reshape(len(imgs), cap)
+    d_h = desc[imgs].cpu().numpy()
+    rows = [k_h[j, :n[i]] for j, i in enumerate(imgs)]
+    k_all = np.concatenate(rows) if rows else np.zeros(0, pkg.KP_DTYPE)
+    out = {"n_keypoints": n, "sample_images": imgs,
+           "keypoints": np.stack([k_all[f].astype(np.float32) for f in pkg.KP_DTYPE.names], 1),
+           "descriptors": np.concatenate([d_h[j, :n[i]] for j, i in enumerate(imgs)])}
+    if stereo:
+        ur_h, dp_h = ur[frames].cpu().numpy(), dp[frames].cpu().numpy()
+        out["u_right"] = np.concatenate([ur_h[j, :n[f]] for j, f in enumerate(frames)])
+        out["depth"] = np.concatenate([dp_h[j, :n[f]] for j, f in enumerate(frames)])
+    if bow is not None:
+        nkf = bow["d_nm"].shape[1]
+        nm = bow["d_nm"][:B].cpu().numpy()
+        out["bow_matches"] = nm
+        if bow["compact"]:
+            pr = bow["d_pairs"][0].cpu().numpy()
+            trip = [np.column_stack([np.full(nm[0, k], k), pr[k, :nm[0, k]]]) for k in range(nkf)]
+        else:
+            mr = bow["d_match"][0].cpu().numpy()
+            trip = [np.column_stack([np.full(int((mr[k] >= 0).sum()), k), np.nonzero(mr[k] >= 0)[0], mr[k][mr[k] >= 0]]) for k in range(nkf)]
+        out["bow_frame0_matches"] = np.concatenate(trip) if trip else np.zeros((0, 3))
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def run_workload(ctx, args):
-    """one workload: warm-up, stage breakdown, timed region, verification, roofline -> the dict of its JSON line"""
+    """one workload: warm-up, timed region (and with --full: stage breakdown, verification, roofline) -> the dict of its JSON line"""
     global W, H, NFEAT
     W, H, NFEAT, kind, def_batch, metric = WORKLOADS[args.workload]
     if args.batch <= 0:
@@ -385,6 +440,7 @@ def run_workload(ctx, args):
     from tools import synth
 
     B = args.batch
+    full = args.full
     stream_id = st.owned_streams(rank, world)[0]      # one camera stream per GPU
     seed0 = st.stream_seed(stream_id)
     pitch = (W + 63) // 64 * 64
@@ -464,16 +520,20 @@ def run_workload(ctx, args):
         extract()
         if bow is not None and not bow["host_path"]:
             # device-resident chain: Frame::ComputeBoW for the batch, then every keyframe against every frame, all on `sp`
-            e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
-            e0.record(stream)
+            # (--full: events around both launches -> config.bow_device_chain)
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if full else None
+            if ev:
+                ev[0].record(stream)
             bow["fr"].transform(bow["voc"], kps.data_ptr(), desc.data_ptr(), nout.data_ptr(), B, 4, sp)
-            e1.record(stream)
+            if ev:
+                ev[1].record(stream)
             if bow["compact"]:
                 bow["fr"].search_compact(bow["db"], B, bow["d_pairs"].data_ptr(), bow["cap_pairs"], bow["d_nm"].data_ptr(), 0.75, True, sp)
             else:
                 bow["fr"].search(bow["db"], B, bow["d_match"].data_ptr(), bow["d_nm"].data_ptr(), 0.75, True, sp)
-            e2.record(stream)
-            bow["ev"].append((e0, e1, e2))
+            if ev:
+                ev[2].record(stream)
+                bow["ev"].append(tuple(ev))
             bow["queries"] += B
         elif bow is not None:
             tq = time.perf_counter()
@@ -500,32 +560,66 @@ def run_workload(ctx, args):
     if bow is not None:
         bow["ms"], bow["tms"], bow["queries"], bow["matches"] = 0.0, 0.0, 0, 0
         bow["ev"] = []
-    # Stage breakdown: a few UNTIMED steps with events at every stage boundary (`roofline.stage_ms_per_step`).  An event between
-    # two kernels is a barrier packet, ~6 us of idle GPU each (13 launches per step: 3-4 % of a step), so the TIMED region only
-    # brackets the kernel whose duration the roofline divides by -- the dominant stage of that breakdown -- live, on its stream.
-    ex.profile_read(reset=True)
-    prof_on[0] = True
-    ex.profile_stages(0xFFFFFFFF)
-    ex.profile_enable(True)
-    n_prof = max(2, min(10, args.steps))
-    for _ in range(n_prof):
-        step()
-    local_sync()
-    prof_all = ex.profile_read(reset=True)
-    stage_all_ms = {k: v[0] / n_prof for k, v in prof_all.items()}
-    dom_stage = max(stage_all_ms, key=stage_all_ms.get)
-    ex.profile_stages(1 << pkg.orbx.STAGES.index(dom_stage))
+    if full:
+        # Stage breakdown: a few UNTIMED steps with events at every stage boundary (`roofline.stage_ms_per_step`).  An event between
+        # two kernels is a barrier packet, ~6 us of idle GPU each (13 launches per step: 3-4 % of a step), so the TIMED region only
+        # brackets the kernel whose duration the roofline divides by -- the dominant stage of that breakdown -- live, on its stream.
+        ex.profile_read(reset=True)
+        prof_on[0] = True
+        ex.profile_stages(0xFFFFFFFF)
+        ex.profile_enable(True)
+        n_prof = max(2, min(10, args.steps))
+        for _ in range(n_prof):
+            step()
+        local_sync()
+        prof_all = ex.profile_read(reset=True)
+        stage_all_ms = {k: v[0] / n_prof for k, v in prof_all.items()}
+        dom_stage = max(stage_all_ms, key=stage_all_ms.get)
+        ex.profile_stages(1 << pkg.orbx.STAGES.index(dom_stage))
     tdet = {}
     elapsed = st.timed_steps(step, args.steps, local_sync, world, device=dist_dev, detail=tdet)   # barrier + sync both sides, MAX over ranks
-    ex.profile_enable(False)
-    prof = ex.profile_read(reset=True)
-    ex.profile_stages(0xFFFFFFFF)
+    if full:
+        ex.profile_enable(False)
+        prof = ex.profile_read(reset=True)
+        ex.profile_stages(0xFFFFFFFF)
     ex.sync(sp)
 
     n_h = nout.cpu().numpy()
     nkp_avg = float(n_h.mean())
     matched = float((ur.cpu().numpy() >= 0).sum() / B) if stereo else 0.0
     value = st.aggregate_rate(B, args.steps, world, elapsed)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, pkg, B, stereo, nout, kps, desc, ur=rig.ur if stereo else None, dp=rig.dp if stereo else None,
+                     bow=bow if bow is not None and not bow["host_path"] else None)
+
+    sha_now = csrc_sha()
+    desc_txt = {"stereo": f"KITTI-shape stereo {W}x{H}, nFeatures={NFEAT}/eye, 8 levels, FAST 20/7: "
+                          "extract(L)+extract(R)+ComputeStereoMatches; 1 frame = 1 stereo pair; images RESIDENT IN HBM when the timed region "
+                          "starts (kernel throughput: excludes PCIe; fed from pinned host memory the same path runs at config.host_fed_batched_frames_per_s "
+                          "-- the PCIe Gen5 x16 link, 0.96 MB per frame -- and one camera stream at config.host_fed_single_stream_frames_per_s)",
+                "mono": f"mono {W}x{H}, nFeatures={NFEAT}, 8 levels, FAST 20/7: extract only",
+                "bow": f"mono {W}x{H}, nFeatures={NFEAT}: extract + ComputeBoW (synthetic k=10 L=6 vocabulary on device) + SearchByBoW(ratio 0.75, "
+                       f"checkOri) of every frame against a device-resident {NKF}-keyframe synthetic map; device-resident chain "
+                       "(orbx_bow_transform_batch_device -> orbx_bowdb_search_batch_device[_compact]), matches stay in HBM as " +
+                       ("dense match rows" if args.bow_dense else "compact (frame feature, keyframe feature) lists, what Tracking::Relocalization hands to its PnP solver")}[kind]
+    out = {"metric": metric, "value": round(value, 2),
+           "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+           "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
+           "vs_baseline": None, "dtype": "u8", "data": "synthetic",
+           "config": {"workload": desc_txt, "name": args.workload, "csrc_sha": sha_now,
+                      "frames_per_step_per_gpu": B, "images_per_step_per_gpu": NI,
+                      "keypoints_per_image": round(nkp_avg, 1), "stereo_matches_per_frame": round(matched, 1),
+                      "parallelism": f"{world} independent camera-stream batches, one per GPU"}}
+    if args.workload == "stereo1000" or world > 1:
+        # what makes an N-rank line self-evidencing: how many ranks met (SUM of ones), which card each held, each rank's own rate
+        out["config"]["ranks_seen"] = st.ranks_seen(world, dist_dev)
+        out["config"]["rank_devices"] = st.gather_strings(pkg.orbx.device_identity(local), world, dist_dev)
+        out["config"]["per_rank_frames_per_s"] = [round(B * args.steps / t, 1) for t in tdet["per_rank"]]
+        out["config"]["backend"] = ctx.get("backend", "none")
+    if bow is not None:
+        out["config"]["keyframes"] = NKF
+    if not full:
+        return out
 
     # ---- outside the timed region: the last step's outputs against the CPU oracle (rank 0)
     verified, expect = None, None
@@ -614,7 +708,6 @@ def run_workload(ctx, args):
     # HBM bytes per launch from the rocprofv3 PMC passes (tools/collect_pmc.py): a committed file, not this run -- stamped with its
     # source and nulled when the kernel sources have changed since it was collected
     traffic, traffic_src = None, None
-    sha_now = csrc_sha()
     tpath, tj = newest_profile("traffic.json" if args.workload == "stereo1000" else "traffic_" + args.workload + ".json")
     if tj:
         kern = tj.get("kernels", {}).get("k_" + dom.split("<")[0])
@@ -657,30 +750,7 @@ def run_workload(ctx, args):
                 # counter-only figure (no price list): SIMD-cycles the vector ALUs were busy / SIMD-cycles of the launch, both from the counter run
                 roofline["issue"]["valu_busy_frac_counters"] = round(kk["SQ_ACTIVE_INST_VALU"] * 4 / (im["issue_model"]["simds"] * kk["launch_ms"] * 1e-3 * im["issue_model"]["clock_ghz"] * 1e9), 4)
 
-    desc_txt = {"stereo": f"KITTI-shape stereo {W}x{H}, nFeatures={NFEAT}/eye, 8 levels, FAST 20/7: "
-                          "extract(L)+extract(R)+ComputeStereoMatches; 1 frame = 1 stereo pair; images RESIDENT IN HBM when the timed region "
-                          "starts (kernel throughput: excludes PCIe; fed from pinned host memory the same path runs at config.host_fed_batched_frames_per_s "
-                          "-- the PCIe Gen5 x16 link, 0.96 MB per frame -- and one camera stream at config.host_fed_single_stream_frames_per_s)",
-                "mono": f"mono {W}x{H}, nFeatures={NFEAT}, 8 levels, FAST 20/7: extract only",
-                "bow": f"mono {W}x{H}, nFeatures={NFEAT}: extract + ComputeBoW (synthetic k=10 L=6 vocabulary on device) + SearchByBoW(ratio 0.75, "
-                       f"checkOri) of every frame against a device-resident {NKF}-keyframe synthetic map; device-resident chain "
-                       "(orbx_bow_transform_batch_device -> orbx_bowdb_search_batch_device[_compact]), matches stay in HBM as " +
-                       ("dense match rows" if args.bow_dense else "compact (frame feature, keyframe feature) lists, what Tracking::Relocalization hands to its PnP solver")}[kind]
-    out = {"metric": metric, "value": round(value, 2),
-           "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-           "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
-           "vs_baseline": None, "dtype": "u8", "data": "synthetic",
-           "config": {"workload": desc_txt, "name": args.workload, "csrc_sha": sha_now,
-                      "frames_per_step_per_gpu": B, "images_per_step_per_gpu": NI,
-                      "keypoints_per_image": round(nkp_avg, 1), "stereo_matches_per_frame": round(matched, 1),
-                      "parallelism": f"{world} independent camera-stream batches, one per GPU"},
-           "roofline": roofline}
-    if args.workload == "stereo1000" or world > 1:
-        # what makes an N-rank line self-evidencing: how many ranks met (SUM of ones), which card each held, each rank's own rate
-        out["config"]["ranks_seen"] = st.ranks_seen(world, dist_dev)
-        out["config"]["rank_devices"] = st.gather_strings(pkg.orbx.device_identity(local), world, dist_dev)
-        out["config"]["per_rank_frames_per_s"] = [round(B * args.steps / t, 1) for t in tdet["per_rank"]]
-        out["config"]["backend"] = ctx.get("backend", "none")
+    out["roofline"] = roofline
     if verified is not None:
         out["verified"] = verified
     if bow is not None and bow["queries"]:
@@ -828,16 +898,21 @@ def main():
     ap.add_argument("--batch", type=int, default=0, help="frames per step per GPU (0 = the workload's default)")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="stereo1000",
                     help="stereo1000 is the BASELINE.json headline metric; the others are the remaining single-GPU configs")
-    ap.add_argument("--cpu-frames", type=int, default=-1, help="frames of the CPU-baseline sample (0 = skip; default 240 stereo / 6 otherwise)")
+    ap.add_argument("--full", action="store_true", help="also the stage breakdown + roofline, the oracle verification of the last step, the extra "
+                                                         "legs (batch sweep, host-fed, other configs, matchers) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs to DIR/<name>.npy (float32)")
+    ap.add_argument("--cpu-frames", type=int, default=-1, help="--full: frames of the CPU-baseline sample (0 = skip; default 240 stereo / 6 otherwise)")
     ap.add_argument("--bow-host-path", action="store_true", help="euroc_bow: per-frame host-pointer ComputeBoW + search (round-1 form)")
     ap.add_argument("--bow-dense", action="store_true", help="BoW workloads: time the dense match rows instead of the compact (frame feature, keyframe feature) lists")
     ap.add_argument("--keyframes", type=int, default=0, help="BoW workloads: keyframes of the synthetic map (0 = 500; euroc_track: 1)")
     ap.add_argument("--distinct", type=int, default=8, help="distinct synthetic stereo pairs / images (tiled to the batch)")
-    ap.add_argument("--extras", type=int, default=1, help="0 = only the timed headline region (profiling runs): no batch sweep, host-fed, other-config or matcher legs")
-    ap.add_argument("--no-verify", action="store_true", help="skip the oracle comparison of the last step's outputs")
+    ap.add_argument("--extras", type=int, default=1, help="--full: 0 = only the timed headline region (profiling runs): no batch sweep, host-fed, other-config or matcher legs")
+    ap.add_argument("--no-verify", action="store_true", help="--full: skip the oracle comparison of the last step's outputs")
     args = ap.parse_args()
     if args.cpu_frames < 0:
         args.cpu_frames = 240 if WORKLOADS[args.workload][3] == "stereo" else 6
+    if not args.full:     # a plain run: the timed steps and the headline line only
+        args.extras, args.no_verify, args.cpu_frames = 0, True, 0
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         sys.exit(launch_ranks(args.gpus))     # no launcher on the command line: start the ranks ourselves, before anything touches the GPU
 
@@ -872,6 +947,7 @@ def main():
                                                         ("fhd4000", 6, 0, 2, 3, 0), ("euroc_track", 8, 0, 4, 4, 1)):
             a2 = argparse.Namespace(**vars(args))
             a2.workload, a2.steps, a2.warmup, a2.batch, a2.distinct, a2.cpu_frames, a2.extras, a2.keyframes = name, steps, 2, batch, distinct, cpuf, 0, nkf
+            a2.dump_outputs = None                  # --dump-outputs holds the headline's last step
             torch.cuda.empty_cache()
             o = run_workload(ctx, a2)
             r = o["roofline"]

@@ -8,12 +8,14 @@ ORBmatcher searches over the C ABI) is real code that a compiler sees:
 * GPU: the driver runs a stereo frame through the compiled adaptor classes exactly as Tracking / LocalMapping /
   LoopClosing call them; every output is compared with the CPU oracle bit for bit.
 Reference interfaces: include/ORBextractor.h:58-139, include/ORBmatcher.h:41-103, src/Frame.cc:577-751."""
+import json
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
+from tools import gen_reference_fixtures as rf
 from tools import synth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -48,30 +50,17 @@ def test_cv_keypoint_stub_is_28_bytes(tmp_path):
     subprocess.check_call(["g++", "-std=c++11", "-fsyntax-only"] + INC + [src])
 
 
-def _decls(text, names):
-    """{method name: [normalised parameter lists]} of the member declarations `int name(...);` in a header"""
-    import re
-    out = {}
-    for m in re.finditer(r"\bint\s+(\w+)\s*\(([^;{]*)\)\s*;", text):
-        if m.group(1) in names:
-            params = []
-            for prm in m.group(2).split(","):
-                prm = re.sub(r"=[^,]*$", "", prm)                      # default value
-                prm = re.sub(r"\bstd::", "", prm)
-                prm = re.sub(r"\s*([*&<>])\s*", r"\1", " ".join(prm.split()))
-                prm = re.sub(r"[*&]?\s*\w+$", lambda t: t.group(0)[0] if t.group(0)[0] in "*&" else "", prm).strip()   # drop the parameter name
-                params.append(prm)
-            out.setdefault(m.group(1), []).append(tuple(params))
-    return out
-
-
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF, "include/ORBmatcher.h")), reason="reference checkout absent")
 def test_signatures_match_the_reference_header():
     """every ORBmatcher method an adaptor defines is declared in tests/cvstub/ORBmatcher.h with the parameter types the reference's
-    include/ORBmatcher.h (:41-83) gives it: the stand-in header cannot drift from the interface the drop-in has to meet"""
-    names = {"SearchByProjection", "SearchByBoW", "SearchForInitialization", "SearchForTriangulation", "SearchBySim3", "Fuse"}
-    ref = _decls(open(os.path.join(REF, "include/ORBmatcher.h"), errors="replace").read(), names)
-    stub = _decls(open(os.path.join(ROOT, "tests/cvstub/ORBmatcher.h")).read(), names)
+    include/ORBmatcher.h (:41-83) gives it: the stand-in header cannot drift from the interface the drop-in has to meet.  The reference's
+    types are recorded in tests/golden/reference_orbmatcher_signatures.json (tools/gen_reference_fixtures.py); where the reference
+    checkout is present the record is re-derived from its header first"""
+    ref = {k: [tuple(s) for s in v] for k, v in json.load(open(rf.SIGNATURES)).items()}
+    assert ref, "no reference signatures recorded"
+    hdr = os.path.join(REF, "include/ORBmatcher.h")
+    if os.path.exists(hdr):
+        assert rf.orbmatcher_decls(open(hdr, errors="replace").read()) == ref, "the recorded signatures are not the reference header's"
+    stub = rf.orbmatcher_decls(open(os.path.join(ROOT, "tests/cvstub/ORBmatcher.h")).read())
     assert stub, "no declarations parsed"
     for name, sigs in stub.items():
         for sig in sigs:
@@ -93,9 +82,17 @@ def test_feature_vector_roundtrip(pkg, tmp_path):
     _check_csr(_build_driver(str(tmp_path)), pkg.lib().orbx_device_count() > 0)
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF, "Thirdparty/DBoW2/DBoW2/FeatureVector.cpp")), reason="reference checkout absent")
 def test_feature_vector_roundtrip_with_reference_dbow2(pkg, tmp_path):
-    _check_csr(_build_driver(str(tmp_path), real_dbow2=True), pkg.lib().orbx_device_count() > 0)
+    """the DBoW2 stand-in headers the adaptor is compiled against (tests/cvstub) declare the typedefs, std::map bases and addFeature the
+    reference's BowVector.h / FeatureVector.h declare (recorded in tests/golden/reference_dbow2_interface.json); where the reference
+    checkout is present the record is re-derived from its headers and the driver is built against its REAL FeatureVector / BowVector"""
+    fix = json.load(open(rf.DBOW2_INTERFACE))
+    assert fix["typedefs"] and fix["bases"] and fix["FeatureVector::addFeature"]
+    assert rf.dbow2_interface(os.path.join(ROOT, "tests", "cvstub", "Thirdparty", "DBoW2", "DBoW2")) == fix
+    ref_dbow2 = os.path.join(REF, "Thirdparty/DBoW2/DBoW2")
+    if os.path.exists(os.path.join(ref_dbow2, "FeatureVector.cpp")):
+        assert rf.dbow2_interface(ref_dbow2) == fix, "the recorded DBoW2 interface is not the reference's"
+        _check_csr(_build_driver(str(tmp_path), real_dbow2=True), pkg.lib().orbx_device_count() > 0)
 
 
 # ------------------------------------------------------------------------------------------------ GPU

@@ -4,11 +4,11 @@
   FeatureVector.cpp compiled unmodified into oracle/_ref/libdbow2_ref.so (oracle/Makefile, target ref).  The CPU
   oracle's accumulation (oracle_bow_accumulate = the second half of oracle_bow_transform) must reproduce the
   BowVector doubles and the FeatureVector order bit for bit; so must orbx_bow_transform on the GPU.
-* when oracle/_ref/libdbow2_ref.so is present (build container, and the GPU box via the snapshot) the same comparison
-  also runs live on fresh random sequences.
+* seeded random sequences with the reference's results for them are stored in tests/golden/dbow2_ref_accumulate_s77.npz;
+  when oracle/_ref/libdbow2_ref.so is present the same sequences also run through the reference's classes live.
 * the rBRIEF table: SHA-256 of the 1024 values of bit_pattern_31_ (reference src/ORBextractor.cc:160-418, order
-  x0,y0,x1,y1 per pair, as int8) is committed here; both orb_pattern.inc copies must hash to it, and when the reference
-  checkout is present the hash is recomputed from its text.
+  x0,y0,x1,y1 per pair, as int8) is committed here; both orb_pattern.inc copies must hash to it, and so must the table's
+  values as extracted from the reference's text (tests/golden/reference_bit_pattern_31.npy, re-extracted when the checkout is present).
 
 What stays unpinned: the vocabulary-tree DESCENT (TemplatedVocabulary.h needs OpenCV) and all OpenCV arithmetic."""
 import hashlib
@@ -18,8 +18,12 @@ import re
 import numpy as np
 import pytest
 
+from tools import gen_reference_fixtures as rf
+from tools import gen_settings_fixture as gsf
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden", "dbow2_ref_s301.npz")
+ACC_GOLD = os.path.join(ROOT, "tests", "golden", "dbow2_ref_accumulate_s77.npz")
 REF_SO = os.path.join(ROOT, "oracle", "_ref", "libdbow2_ref.so")
 PATTERN_SHA256 = "2164181aea6ff9ac426ca512d5130d15e1f6e3cd47b1cbdd568bbe1e55d49023"
 KEYS = ("bow_id", "bow_val", "fv_node_id", "fv_node_off", "fv_feat")
@@ -57,16 +61,21 @@ def test_oracle_transform_equals_reference_fixture(oracle):
     assert len(t["bow_id"]) < (g["voc_word_weight"] > 0).sum()      # words repeat: addWeight's += path is exercised
 
 
-@pytest.mark.skipif(not os.path.exists(REF_SO), reason="oracle/_ref not built (needs the reference checkout)")
 def test_oracle_accumulate_equals_reference_live(oracle):
+    """seeded sequences of 0 .. 5000 words (tools/gen_dbow2_golden.accumulate_cases) against what the reference's classes made of them
+    (tests/golden/dbow2_ref_accumulate_s77.npz); where oracle/_ref is built, against the reference's classes run now as well"""
     from tools import gen_dbow2_golden as gg
-    L = gg.ref_lib()
-    rng = np.random.Generator(np.random.PCG64(77))
-    for n in (0, 1, 2, 33, 1000, 5000):
-        wid = rng.integers(0, max(2, n // 13), n).astype(np.uint32)
-        ww = 10.0 ** rng.uniform(-8, 8, n); ww[rng.random(n) < 0.1] = 0.0
-        nid = rng.integers(0, 100, n).astype(np.uint32)
-        _same(oracle.bow_accumulate(wid, ww, nid), gg.ref_accumulate(L, wid, ww, nid), f"live n={n}")
+    g = np.load(ACC_GOLD)
+    L = gg.ref_lib() if os.path.exists(REF_SO) else None
+    assert list(g["sizes"]) == list(gg.ACCUMULATE_SIZES)
+    for n in g["sizes"]:
+        pre = f"n{n}_"
+        wid, ww, nid = g[pre + "word_id"], g[pre + "word_weight"], g[pre + "node_id"]
+        assert len(wid) == len(ww) == len(nid) == n
+        got = oracle.bow_accumulate(wid, ww, nid)
+        _same(got, {k: g[pre + k] for k in KEYS}, f"stored n={n}")
+        if L is not None:
+            _same(got, gg.ref_accumulate(L, wid, ww, nid), f"live n={n}")
 
 
 @pytest.mark.gpu
@@ -97,11 +106,13 @@ def test_pattern_table_is_the_references(path):
     assert hashlib.sha256(vals.tobytes()).hexdigest() == PATTERN_SHA256
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/src/ORBextractor.cc"), reason="reference checkout absent")
 def test_pattern_hash_recomputed_from_reference_text():
-    src = open("/root/reference/src/ORBextractor.cc", encoding="utf-8", errors="replace").read()
-    m = re.search(r"bit_pattern_31_\[256\*4\]\s*=\s*\{(.*?)\};", src, re.S)
-    body = re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S)
-    vals = np.array([int(t) for t in re.findall(r"-?\d+", body)], np.int8)
-    assert len(vals) == 1024
+    """the committed hash recomputed from the reference's table: its 1024 values as extracted from src/ORBextractor.cc are recorded in
+    tests/golden/reference_bit_pattern_31.npy (tools/gen_reference_fixtures.py); where the reference checkout is present they are
+    re-extracted from its text first"""
+    vals = np.load(rf.PATTERN)
+    assert vals.dtype == np.int8 and vals.shape == (1024,)
+    src = os.path.join(os.path.dirname(gsf.REF), "src", "ORBextractor.cc")
+    if os.path.exists(src):
+        assert np.array_equal(rf.pattern_values(open(src, encoding="utf-8", errors="replace").read()), vals)
     assert hashlib.sha256(vals.tobytes()).hexdigest() == PATTERN_SHA256

@@ -4,7 +4,7 @@ import os, sys, subprocess, ctypes as C
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 os.environ["ORBX_SO"] = os.path.join(ROOT, "diag", "liborbx_diag.so")
 sys.path.insert(0, ROOT)
-sys.argv = [sys.argv[0], "--workload", "euroc_bow", "--steps", "2", "--warmup", "0", "--cpu-frames", "0"]
+sys.argv = [sys.argv[0], "--workload", "euroc_bow", "--steps", "2", "--warmup", "0", "--cpu-frames", "0", "--full"]
 import bench
 import __graft_entry__ as ge
 L = ge.load_pkg().lib()

@@ -79,5 +79,33 @@ def main(seed=301):
     print("wrote", path, os.path.getsize(path), "bytes")
 
 
+ACCUMULATE_SIZES = (0, 1, 2, 33, 1000, 5000)
+
+
+def accumulate_cases(seed=77):
+    """the sequences of tests/test_dbow2_ref.py::test_oracle_accumulate_equals_reference_live: (n, word ids, word weights spanning
+    16 decades with 10 % zeros, node ids) for every n of ACCUMULATE_SIZES"""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    for n in ACCUMULATE_SIZES:
+        wid = rng.integers(0, max(2, n // 13), n).astype(np.uint32)
+        ww = 10.0 ** rng.uniform(-8, 8, n); ww[rng.random(n) < 0.1] = 0.0
+        nid = rng.integers(0, 100, n).astype(np.uint32)
+        yield n, wid, ww, nid
+
+
+def main_accumulate(seed=77):
+    """tests/golden/dbow2_ref_accumulate_s<seed>.npz: accumulate_cases() and what the reference's classes make of each"""
+    L = ref_lib()
+    out = {"sizes": np.array(ACCUMULATE_SIZES, np.int32)}
+    for n, wid, ww, nid in accumulate_cases(seed):
+        pre = f"n{n}_"
+        out[pre + "word_id"], out[pre + "word_weight"], out[pre + "node_id"] = wid, ww, nid
+        for k, v in ref_accumulate(L, wid, ww, nid).items():
+            out[pre + k] = v
+    path = os.path.join(ROOT, "tests", "golden", f"dbow2_ref_accumulate_s{seed}.npz")
+    np.savez_compressed(path, **out)
+    print("wrote", path, os.path.getsize(path), "bytes")
+
+
 if __name__ == "__main__":
-    main()
+    main_accumulate() if "--accumulate" in sys.argv else main()

@@ -15,7 +15,10 @@ KEYS = ("Camera.fx", "Camera.bf", "Camera.width", "Camera.height", "Camera.fps",
 
 
 def parse(path):
-    txt = open(path, encoding="utf-8", errors="replace").read()
+    return parse_text(open(path, encoding="utf-8", errors="replace").read())
+
+
+def parse_text(txt):
     out = {}
     for k in KEYS:
         m = re.search(r"^%s\s*:\s*([-+0-9.eE]+)" % re.escape(k), txt, re.M)
