@@ -100,8 +100,10 @@ int ORBmatcher::SearchByProjection(Frame &CurrentFrame, KeyFrame *pKF, const set
     const cv::Mat tcw = CurrentFrame.mTcw.rowRange(0, 3).col(3);
     const cv::Mat Ow = -Rcw.t() * tcw;
     const vector<MapPoint *> vpMPs = pKF->GetMapPointMatches();
+    orbx_frame *rf = orbx_adapter::ResidentFrame(CurrentFrame);   // NULL: resident frames switched off
     FrameSide cur;
-    frame_side_any_point(CurrentFrame, cur);
+    if (!rf || orbx_adapter::kCapture)
+        frame_side_any_point(CurrentFrame, cur);
     PointSide pts(vpMPs.size());
     for (size_t i = 0; i < vpMPs.size(); i++) {
         MapPoint *pMP = vpMPs[i];
@@ -126,8 +128,18 @@ int ORBmatcher::SearchByProjection(Frame &CurrentFrame, KeyFrame *pKF, const set
     vector<int32_t> match((size_t)(CurrentFrame.N > 0 ? CurrentFrame.N : 1));
     int nmatches = 0;
     ORBX_CAPTURE(cur.ff, &pts.pp);
-    if (orbx_search_by_projection_keyframe(orbx_adapter::Device(), &cur.ff, &pts.pp, &CurrentFrame.mvScaleFactors[0], (int)CurrentFrame.mvScaleFactors.size(), th, ORBdist,
-                                           mbCheckOrientation ? 3 : 0, &match[0], &nmatches) != ORBX_OK)
+    int rc;
+    if (rf) {
+        vector<uint8_t> occ((size_t)(CurrentFrame.N > 0 ? CurrentFrame.N : 1), 0);
+        for (int i = 0; i < CurrentFrame.N; i++)
+            occ[i] = CurrentFrame.mvpMapPoints[i] ? 1 : 0;             // :1617-1618
+        rc = orbx_frame_search_by_projection_keyframe(rf, &occ[0], &pts.pp, &CurrentFrame.mvScaleFactors[0], (int)CurrentFrame.mvScaleFactors.size(), th, ORBdist,
+                                                      mbCheckOrientation ? 3 : 0, &match[0], &nmatches);
+    } else {
+        rc = orbx_search_by_projection_keyframe(orbx_adapter::Device(), &cur.ff, &pts.pp, &CurrentFrame.mvScaleFactors[0], (int)CurrentFrame.mvScaleFactors.size(), th, ORBdist,
+                                                mbCheckOrientation ? 3 : 0, &match[0], &nmatches);
+    }
+    if (rc != ORBX_OK)
         throw std::runtime_error(orbx_last_error());
     for (int f = 0; f < CurrentFrame.N; f++) {
         if (match[f] >= 0)

@@ -18,6 +18,95 @@
 
 using namespace std;
 
+namespace orbx_adapter
+{
+
+// the calling thread's resident frame with the host shadow of what it was made from (see orbx_adapter.h).  The orbx_frame is not given
+// back when the thread ends (no HIP call from a thread-exit destructor); SetResidentFrames(false) gives it back now.
+struct ResidentFrameCache {
+    orbx_frame *frame;
+    int device, n, creates, hits;
+    float bounds[4];
+    std::vector<cv::KeyPoint> keys;
+    std::vector<float> u_right;
+    std::vector<uint8_t> desc;
+    ResidentFrameCache() : frame(NULL), device(-1), n(-1), creates(0), hits(0) { memset(bounds, 0, sizeof bounds); }
+};
+static ResidentFrameCache &frame_cache()
+{
+    static thread_local ResidentFrameCache c;
+    return c;
+}
+static bool &resident_frames_on()
+{
+    static bool on = true;
+    return on;
+}
+
+void SetResidentFrames(bool on)
+{
+    resident_frames_on() = on;
+    ResidentFrameCache &c = frame_cache();
+    if (!on && c.frame) {
+        orbx_frame_destroy(c.frame);
+        c.frame = NULL;
+        c.n = -1;
+    }
+}
+
+void ResidentFrameStats(int *creates, int *hits)
+{
+    const ResidentFrameCache &c = frame_cache();
+    if (creates) *creates = c.creates;
+    if (hits) *hits = c.hits;
+}
+
+orbx_frame *ResidentFrame(const ORB_SLAM2::Frame &F)
+{
+    if (!resident_frames_on())
+        return NULL;
+    ResidentFrameCache &c = frame_cache();
+    const size_t n = (size_t)F.N;
+    const uint8_t *desc = dense_descriptors(F.mDescriptors, F.N);
+    const float bounds[4] = { ORB_SLAM2::Frame::mnMinX, ORB_SLAM2::Frame::mnMinY, ORB_SLAM2::Frame::mnMaxX, ORB_SLAM2::Frame::mnMaxY };
+    // the whole cv::KeyPoint records are compared (x / y / octave / angle and the fields the searches do not read): a frame differs in all of them
+    if (c.frame && c.device == Device() && c.n == F.N && memcmp(c.bounds, bounds, sizeof bounds) == 0 &&
+        (n == 0 || (memcmp(&c.keys[0], &F.mvKeysUn[0], n * sizeof(cv::KeyPoint)) == 0 &&
+                    memcmp(&c.u_right[0], &F.mvuRight[0], n * sizeof(float)) == 0 && memcmp(&c.desc[0], desc, 32 * n) == 0))) {
+        c.hits++;
+        return c.frame;
+    }
+    if (c.frame) {
+        orbx_frame_destroy(c.frame);
+        c.frame = NULL;
+        c.n = -1;
+    }
+    std::vector<float> x(n), y(n), angle(n);
+    std::vector<int32_t> octave(n);
+    for (size_t i = 0; i < n; i++) {
+        const cv::KeyPoint &kp = F.mvKeysUn[i];
+        x[i] = kp.pt.x; y[i] = kp.pt.y; angle[i] = kp.angle; octave[i] = kp.octave;
+    }
+    orbx_frame_feats ff;
+    memset(&ff, 0, sizeof ff);
+    ff.n = F.N;
+    if (n) {
+        ff.x = &x[0]; ff.y = &y[0]; ff.octave = &octave[0]; ff.angle = &angle[0]; ff.u_right = &F.mvuRight[0]; ff.desc = desc;
+    }
+    ff.min_x = bounds[0]; ff.min_y = bounds[1]; ff.max_x = bounds[2]; ff.max_y = bounds[3];
+    if (orbx_frame_create(Device(), &ff, &c.frame) != ORBX_OK)
+        throw std::runtime_error(orbx_last_error());
+    c.device = Device(); c.n = F.N;
+    memcpy(c.bounds, bounds, sizeof bounds);
+    c.keys.assign(F.mvKeysUn.begin(), F.mvKeysUn.begin() + n);
+    c.u_right.assign(F.mvuRight.begin(), F.mvuRight.begin() + n);
+    c.desc.assign(desc, desc + 32 * n);
+    c.creates++;
+    return c.frame;
+}
+
+} // namespace orbx_adapter
+
 namespace ORB_SLAM2
 {
 
@@ -45,6 +134,16 @@ static void frame_side(const Frame &F, FrameSide &s)
     s.ff.min_x = Frame::mnMinX; s.ff.min_y = Frame::mnMinY; s.ff.max_x = Frame::mnMaxX; s.ff.max_y = Frame::mnMaxY;
 }
 
+// occupied[] of the same rule for a resident frame (the other frame arrays are on the device already)
+static void occupied_with_observations(const Frame &F, vector<uint8_t> &occ)
+{
+    occ.assign((size_t)(F.N > 0 ? F.N : 1), 0);
+    for (int i = 0; i < F.N && i < (int)F.mvpMapPoints.size(); i++) {
+        MapPoint *pMP = F.mvpMapPoints[i];
+        occ[i] = (pMP && pMP->Observations() > 0) ? 1 : 0;
+    }
+}
+
 static void put_descriptor(MapPoint *pMP, uint8_t *dst)
 {
     const cv::Mat d = pMP->GetDescriptor();            // a clone taken under the point's mutex, as the reference reads it (:70, :1458)
@@ -54,8 +153,10 @@ static void put_descriptor(MapPoint *pMP, uint8_t *dst)
 
 int ORBmatcher::SearchByProjection(Frame &F, const vector<MapPoint *> &vpMapPoints, const float th)
 {
+    orbx_frame *rf = orbx_adapter::ResidentFrame(F);   // NULL: resident frames switched off
     FrameSide cur;
-    frame_side(F, cur);
+    if (!rf || orbx_adapter::kCapture)
+        frame_side(F, cur);
     PointSide pts(vpMapPoints.size());
     for (size_t i = 0; i < vpMapPoints.size(); i++) {
         MapPoint *pMP = vpMapPoints[i];
@@ -71,8 +172,16 @@ int ORBmatcher::SearchByProjection(Frame &F, const vector<MapPoint *> &vpMapPoin
     vector<int32_t> match((size_t)(F.N > 0 ? F.N : 1));
     int nmatches = 0;
     ORBX_CAPTURE(cur.ff, &pts.pp);
-    if (orbx_search_by_projection_map_points(orbx_adapter::Device(), &cur.ff, &pts.pp, &F.mvScaleFactors[0], (int)F.mvScaleFactors.size(), th, mfNNratio, &match[0],
-                                             &nmatches) != ORBX_OK)
+    int rc;
+    if (rf) {
+        vector<uint8_t> occ;
+        occupied_with_observations(F, occ);
+        rc = orbx_frame_search_by_projection_map_points(rf, &occ[0], &pts.pp, &F.mvScaleFactors[0], (int)F.mvScaleFactors.size(), th, mfNNratio, &match[0], &nmatches);
+    } else {
+        rc = orbx_search_by_projection_map_points(orbx_adapter::Device(), &cur.ff, &pts.pp, &F.mvScaleFactors[0], (int)F.mvScaleFactors.size(), th, mfNNratio, &match[0],
+                                                  &nmatches);
+    }
+    if (rc != ORBX_OK)
         throw std::runtime_error(orbx_last_error());
     for (int f = 0; f < F.N; f++)
         if (match[f] >= 0)
@@ -92,8 +201,10 @@ int ORBmatcher::SearchByProjection(Frame &CurrentFrame, const Frame &LastFrame, 
     const bool bForward = tlc.at<float>(2) > CurrentFrame.mb && !bMono;
     const bool bBackward = -tlc.at<float>(2) > CurrentFrame.mb && !bMono;
 
+    orbx_frame *rf = orbx_adapter::ResidentFrame(CurrentFrame);   // NULL: resident frames switched off
     FrameSide cur;
-    frame_side(CurrentFrame, cur);
+    if (!rf || orbx_adapter::kCapture)
+        frame_side(CurrentFrame, cur);
     PointSide pts((size_t)LastFrame.N);
     for (int i = 0; i < LastFrame.N; i++) {
         MapPoint *pMP = LastFrame.mvpMapPoints[i];
@@ -116,9 +227,17 @@ int ORBmatcher::SearchByProjection(Frame &CurrentFrame, const Frame &LastFrame, 
     vector<int32_t> match((size_t)(CurrentFrame.N > 0 ? CurrentFrame.N : 1));
     int nmatches = 0;
     ORBX_CAPTURE(cur.ff, &pts.pp);
-    if (orbx_search_by_projection_last_frame(orbx_adapter::Device(), &cur.ff, &pts.pp, &CurrentFrame.mvScaleFactors[0], (int)CurrentFrame.mvScaleFactors.size(), th,
-                                             bForward ? 1 : bBackward ? 2 : 0, CurrentFrame.mbf, mbCheckOrientation ? 3 : 0, &match[0],
-                                             &nmatches) != ORBX_OK)
+    int rc;
+    if (rf) {
+        vector<uint8_t> occ;
+        occupied_with_observations(CurrentFrame, occ);
+        rc = orbx_frame_search_by_projection_last_frame(rf, &occ[0], &pts.pp, &CurrentFrame.mvScaleFactors[0], (int)CurrentFrame.mvScaleFactors.size(), th,
+                                                        bForward ? 1 : bBackward ? 2 : 0, CurrentFrame.mbf, mbCheckOrientation ? 3 : 0, &match[0], &nmatches);
+    } else {
+        rc = orbx_search_by_projection_last_frame(orbx_adapter::Device(), &cur.ff, &pts.pp, &CurrentFrame.mvScaleFactors[0], (int)CurrentFrame.mvScaleFactors.size(), th,
+                                                  bForward ? 1 : bBackward ? 2 : 0, CurrentFrame.mbf, mbCheckOrientation ? 3 : 0, &match[0], &nmatches);
+    }
+    if (rc != ORBX_OK)
         throw std::runtime_error(orbx_last_error());
     for (int f = 0; f < CurrentFrame.N; f++) {
         if (match[f] >= 0)

@@ -17,6 +17,11 @@
 
 #include <Thirdparty/DBoW2/DBoW2/FeatureVector.h>
 
+namespace ORB_SLAM2
+{
+class Frame;
+}
+
 namespace orbx_adapter
 {
 
@@ -108,6 +113,21 @@ struct PointSide {
     }
 };
 
+// ---- resident current frame (orbx_frame) behind the per-frame projection searches: SearchByProjection(Frame&, const Frame&, ...),
+// SearchByProjection(Frame&, const vector<MapPoint*>&, ...) and SearchByProjection(Frame&, KeyFrame*, ...) run two to four times on
+// one Frame (src/Tracking.cc:1065,:1072,:1463,:1763,:1777).  A per-THREAD cache holds the last frame uploaded: the first search of a
+// frame uploads it and builds its grid once, the later ones send only the points and the per-call `occupied` bytes.  The cache is keyed
+// by CONTENT, never by address or mnId (Tracking reassigns mCurrentFrame in place every frame, src/Tracking.cc:204,235,273, and
+// Tracking::Reset restarts Frame::nNextId, :1845): it keeps a host shadow of what it uploaded -- N, the image bounds, the mvKeysUn
+// records, mvuRight and the descriptor bytes -- and compares it with memcmp (a few microseconds at 1000 features); any difference
+// rebuilds the resident frame.  Defined in ORBmatcher_proj.cc.
+//   ResidentFrame(F)          the calling thread's resident copy of F (made or reused), NULL when resident frames are switched off
+//   SetResidentFrames(on)     runtime switch for A/B runs (default on); off also releases the calling thread's frame
+//   ResidentFrameStats(c, h)  the calling thread's counts: frames created, searches that reused the resident frame
+orbx_frame *ResidentFrame(const ORB_SLAM2::Frame &F);
+void SetResidentFrames(bool on);
+void ResidentFrameStats(int *creates, int *hits);
+
 // The device vocabulary behind Frame::ComputeBoW / KeyFrame::ComputeBoW: loaded once where the reference loads its
 // ORBVocabulary (src/System.cc:67-77, mpVocabulary->loadFromTextFile), from the same ORBvoc.txt.
 inline orbx_vocab *&vocabulary()
@@ -141,9 +161,11 @@ inline void capture_call(const orbx_frame_feats &f, const orbx_proj_points *p, i
         c.pvalid.assign(p->valid, p->valid + m); c.phas_obs.assign(p->has_obs, p->has_obs + m);
     }
 }
+const bool kCapture = true;   // the projection adaptors build the host-pointer frame side for the capture even when the frame is resident
 #define ORBX_CAPTURE(f, p) orbx_adapter::capture_call(f, p)
 #define ORBX_CAPTURE2(f, p) orbx_adapter::capture_call(f, p, 1)
 #else
+const bool kCapture = false;
 #define ORBX_CAPTURE(f, p) do { } while (0)
 #define ORBX_CAPTURE2(f, p) do { } while (0)
 #endif

@@ -351,7 +351,8 @@ int orbx_bow_transform(orbx_vocab *v, const uint8_t *desc, int n, int levelsup,
 /* ---- projection-guided tracking matchers -------------------------------- */
 
 /* the current Frame: undistorted keypoints, right coordinates, descriptors, image bounds (the 64x48 feature
- * grid of Frame::AssignFeaturesToGrid / GetFeaturesInArea, src/Frame.cc:261-279,:386-457, is rebuilt on device) */
+ * grid of Frame::AssignFeaturesToGrid / GetFeaturesInArea, src/Frame.cc:261-279,:386-457, is rebuilt on device by every
+ * host-pointer call; orbx_frame below keeps frame and grid resident across the searches of one frame) */
 /* ---- batched, device-resident ComputeBoW + relocalisation search (BASELINE config 3 at throughput) ----
  * orbx_bow_frames holds, in HBM, what Frame::ComputeBoW produces (mBowVec, mFeatVec) for a batch of frames whose
  * keypoints / descriptors / counts are the device outputs of orbx_extract_batch_device (same cap).  Nothing crosses
@@ -397,6 +398,48 @@ typedef struct {
     const uint8_t *valid;      /* last-frame: pMP && !mvbOutlier[i] ; map-point: mbTrackInView && !isBad() */
     const uint8_t *has_obs;    /* pMP->Observations() > 0: a match by this point blocks the feature for later points */
 } orbx_proj_points;
+
+/* ---- resident current frame ------------------------------------------------------------------------
+ * Tracking searches one Frame by projection two to four times (TrackWithMotionModel at th and again at 2*th,
+ * src/Tracking.cc:1065,:1072; SearchLocalPoints :1463; Relocalization :1763,:1777), and the frame's keypoints, descriptors
+ * and 64x48 grid (Frame::AssignFeaturesToGrid, src/Frame.cc:261-279) never change in between.  orbx_frame keeps that
+ * immutable part in HBM -- undistorted x / y, octave, angle, u_right, descriptors, bounds and the grid, built once at
+ * creation -- and the searches below move only the projected points, the per-call `occupied` bytes and the results.
+ * One frame is used by one thread at a time (as the extractor handles); distinct frames may be used concurrently. */
+typedef struct orbx_frame orbx_frame;
+/* from host pointers: one upload, then the grid build; synchronises.  f->occupied is ignored; f->angle may be NULL (then only
+ * searches without the orientation check accept the frame).  Refused as the host-pointer searches refuse the frame: n >= 65536,
+ * empty bounds, missing arrays. */
+int orbx_frame_create(int device, const orbx_frame_feats *f, orbx_frame **out);
+/* from the device outputs of orbx_extract_batch_device (image `index` of a launch with capacity `cap`): keypoints
+ * d_kps + index*cap (orbx_keypoint records), descriptors d_desc + index*cap*32, count d_n[index] (int32).  d_u_right = that
+ * image's [cap] row of orbx_stereo_match_batch_device's u_right output, or NULL for a monocular frame (every u_right = -1).
+ * K = fx fy cx cy (may be NULL: positions are taken as they are); with K and dist_coef[0] != 0 (ndist 4 or 5) the positions are
+ * undistorted on the device with the arithmetic of orbx_undistort_keypoints, bit for bit; dist_coef[0] == 0 copies them
+ * (src/Frame.cc:472-476).  Bounds = mnMinX, mnMinY, mnMaxX, mnMaxY.  The work is enqueued on `stream` (the stream the
+ * extraction ran on; NULL = the null stream) and nothing but the count passes through host memory: the call synchronises
+ * `stream` ONCE to read those 4 bytes (the count sizes the frame), then enqueues the copy and the grid build and returns.  The
+ * frame owns a copy: the extraction buffers may be overwritten afterwards.  Its first search waits for the creation through an
+ * event, not a device synchronisation.  Refused: index < 0, cap < 1, a count outside [0, cap]. */
+int orbx_frame_create_from_extraction(int device, const void *d_kps, const void *d_desc, const void *d_n, int cap, int index,
+                                      const void *d_u_right, const float *K, const float *dist_coef, int ndist,
+                                      float min_x, float min_y, float max_x, float max_y, void *stream, orbx_frame **out);
+int orbx_frame_size(const orbx_frame *f);
+/* tests and debugging: copies the frame's arrays to host memory ([n] each, desc [n][32]); NULL arguments are skipped */
+int orbx_frame_read(const orbx_frame *f, float *x, float *y, int32_t *octave, float *angle, float *u_right, uint8_t *desc);
+void orbx_frame_destroy(orbx_frame *f);
+/* The three per-frame searches on a resident frame: arguments, semantics and results of orbx_search_by_projection_last_frame /
+ * _map_points / _keyframe, with the frame given by handle and occupied[n] (the meaning each host-pointer twin gives
+ * orbx_frame_feats::occupied) passed per call; occupied = NULL: no feature is occupied. */
+int orbx_frame_search_by_projection_last_frame(orbx_frame *cur, const uint8_t *occupied, const orbx_proj_points *pts,
+                                               const float *scale_factors, int nlevels, float th, int direction, float mbf,
+                                               int check_orientation, int32_t *match_cur, int *nmatches);
+int orbx_frame_search_by_projection_map_points(orbx_frame *cur, const uint8_t *occupied, const orbx_proj_points *pts,
+                                               const float *scale_factors, int nlevels, float th, float nnratio,
+                                               int32_t *match_cur, int *nmatches);
+int orbx_frame_search_by_projection_keyframe(orbx_frame *cur, const uint8_t *occupied, const orbx_proj_points *pts,
+                                             const float *scale_factors, int nlevels, float th, int orb_dist,
+                                             int check_orientation, int32_t *match_cur, int *nmatches);
 
 /* ORBmatcher::SearchByProjection(Frame &CurrentFrame, const Frame &LastFrame, th, bMono) (src/ORBmatcher.cc:1396-1553;
  * Tracking::TrackWithMotionModel).  direction: 0 none, 1 bForward, 2 bBackward (:1412-1413).  match_cur[cur->n] =

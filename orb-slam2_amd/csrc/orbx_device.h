@@ -233,3 +233,33 @@ __device__ __forceinline__ int hamming256(const uint32_t *a, const uint32_t *b)
     for (int i = 0; i < 8; i++) d += __popc(a[i] ^ b[i]);
     return d;
 }
+
+// ---- Frame::UndistortKeyPoints (src/Frame.cc:470-515) on one point: cv::undistortPoints(mat, mat, mK, mDistCoef, cv::Mat(), mK).  Shared by
+// k_undistort (orbx_frame.hip) and the resident-frame ingest (orbx_proj.hip) so that both give the same bits (-ffp-contract=off in both).
+struct UndistortParams { double fx, fy, ifx, ify, cx, cy, k[5]; };
+
+static inline UndistortParams orbx_undistort_params(float fx, float fy, float cx, float cy, const float *dist_coef, int ndist)
+{
+    UndistortParams p;
+    p.fx = fx; p.fy = fy; p.ifx = 1. / p.fx; p.ify = 1. / p.fy; p.cx = cx; p.cy = cy;
+    for (int i = 0; i < 5; i++) p.k[i] = i < ndist ? (double)dist_coef[i] : 0.0;
+    return p;
+}
+
+__device__ __forceinline__ float2 dev_undistort(float2 s, const UndistortParams &p)
+{
+    double x = ((double)s.x - p.cx) * p.ifx, y = ((double)s.y - p.cy) * p.ify;
+    const double x0 = x, y0 = y;
+    for (int j = 0; j < 5; j++) {
+        const double r2 = x * x + y * y;
+        const double icdist = 1.0 / (1 + ((p.k[4] * r2 + p.k[1]) * r2 + p.k[0]) * r2);
+        const double dx = 2 * p.k[2] * x * y + p.k[3] * (r2 + 2 * x * x);
+        const double dy = p.k[2] * (r2 + 2 * y * y) + 2 * p.k[3] * x * y;
+        x = (x0 - dx) * icdist;
+        y = (y0 - dy) * icdist;
+    }
+    float2 o;
+    o.x = (float)(p.fx * x + p.cx);
+    o.y = (float)(p.fy * y + p.cy);
+    return o;
+}

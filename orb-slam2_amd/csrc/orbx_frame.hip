@@ -9,27 +9,11 @@
 #include <string.h>
 #include <vector>
 
-struct UndistortParams { double fx, fy, ifx, ify, cx, cy, k[5]; };
-
 __global__ __launch_bounds__(256) void k_undistort(const float2 *__restrict__ in, float2 *__restrict__ out, int n, UndistortParams p)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const float2 s = in[i];
-    double x = ((double)s.x - p.cx) * p.ifx, y = ((double)s.y - p.cy) * p.ify;
-    const double x0 = x, y0 = y;
-    for (int j = 0; j < 5; j++) {
-        const double r2 = x * x + y * y;
-        const double icdist = 1.0 / (1 + ((p.k[4] * r2 + p.k[1]) * r2 + p.k[0]) * r2);
-        const double dx = 2 * p.k[2] * x * y + p.k[3] * (r2 + 2 * x * x);
-        const double dy = p.k[2] * (r2 + 2 * y * y) + 2 * p.k[3] * x * y;
-        x = (x0 - dx) * icdist;
-        y = (y0 - dy) * icdist;
-    }
-    float2 o;
-    o.x = (float)(p.fx * x + p.cx);
-    o.y = (float)(p.fy * y + p.cy);
-    out[i] = o;
+    out[i] = dev_undistort(in[i], p);   // orbx_device.h: the same arithmetic the resident-frame ingest runs (orbx_proj.hip)
 }
 
 struct FrameCtx { hipStream_t stream = nullptr; float2 *d_in = nullptr, *d_out = nullptr; float2 *h = nullptr; size_t cap = 0; };
@@ -66,9 +50,7 @@ extern "C" int orbx_undistort_keypoints(int device, const float *xy, int n, floa
         ORBX_HIP(hipHostMalloc((void **)&c->h, sizeof(float2) * cap, hipHostMallocDefault));
         c->cap = cap;
     }
-    UndistortParams p;
-    p.fx = fx; p.fy = fy; p.ifx = 1. / p.fx; p.ify = 1. / p.fy; p.cx = cx; p.cy = cy;
-    for (int i = 0; i < 5; i++) p.k[i] = i < ndist ? (double)dist_coef[i] : 0.0;
+    const UndistortParams p = orbx_undistort_params(fx, fy, cx, cy, dist_coef, ndist);
     memcpy(c->h, xy, sizeof(float2) * (size_t)n);
     ORBX_HIP(hipMemcpyAsync(c->d_in, c->h, sizeof(float2) * (size_t)n, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_undistort, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->d_in, c->d_out, n, p);

@@ -14,6 +14,7 @@
 // per link of the longest conflict chain).  Projections (u, v, 1/z) come from the adaptor, which has the
 // poses: restating cv::gemm's accumulation is not needed.
 #include "orbx_device.h"
+#include <mutex>
 #include <string.h>
 #include <vector>
 
@@ -58,29 +59,41 @@ struct ProjParams {
 };
 
 #define PG_LDS_FEATS 8192
-// ---- Frame::AssignFeaturesToGrid: CSR over the 64x48 cells, ascending feature index inside a cell
-__global__ __launch_bounds__(256) void k_grid_build(DevFrame F, int *__restrict__ cell_off, int *__restrict__ cell_idx)
+// ---- Frame::AssignFeaturesToGrid: CSR over the 64x48 cells, ascending feature index inside a cell.  cell_of(i) = the cell of feature i
+// (PosInGrid, src/Frame.cc:444-457) or -1; one 256-thread workgroup.
+struct GridLds {
+    int cnt[PG_CELLS];
+    int cur[PG_CELLS];
+    int s_w[4];
+    uint16_t idx_l[PG_LDS_FEATS];     // the cell lists while they are being ordered (frames of up to PG_LDS_FEATS features)
+};
+
+__device__ __forceinline__ int grid_cell(float x, float y, float min_x, float min_y, float inv_w, float inv_h)
 {
-    __shared__ int cnt[PG_CELLS];
-    __shared__ int cur[PG_CELLS];
-    __shared__ int s_w[4];
-    __shared__ uint16_t idx_l[PG_LDS_FEATS];     // the cell lists while they are being ordered (frames of up to PG_LDS_FEATS features)
+    const int px = (int)roundf((x - min_x) * inv_w), py = (int)roundf((y - min_y) * inv_h); // PosInGrid :444-457
+    return (px >= 0 && px < PG_COLS && py >= 0 && py < PG_ROWS) ? px * PG_ROWS + py : -1;
+}
+
+template <typename CellOf>
+__device__ __forceinline__ void grid_build_body(int n, CellOf cell_of, GridLds &L, int *__restrict__ cell_off, int *__restrict__ cell_idx)
+{
+    int *cnt = L.cnt, *cur = L.cur;
+    uint16_t *idx_l = L.idx_l;
     const int tid = threadIdx.x;
-    const bool in_lds = F.n <= PG_LDS_FEATS;
+    const bool in_lds = n <= PG_LDS_FEATS;
     for (int c = tid; c < PG_CELLS; c += 256) { cnt[c] = 0; cur[c] = 0; }
     __syncthreads();
-    for (int i = tid; i < F.n; i += 256) {
-        const int px = (int)roundf((F.x[i] - F.min_x) * F.inv_w), py = (int)roundf((F.y[i] - F.min_y) * F.inv_h); // PosInGrid :444-457
-        if (px >= 0 && px < PG_COLS && py >= 0 && py < PG_ROWS) atomicAdd(&cnt[px * PG_ROWS + py], 1);
+    for (int i = tid; i < n; i += 256) {
+        const int c = cell_of(i);
+        if (c >= 0) atomicAdd(&cnt[c], 1);
     }
     __syncthreads();
-    const int total = lds_excl_scan(cnt, PG_CELLS, s_w);
+    const int total = lds_excl_scan(cnt, PG_CELLS, L.s_w);
     for (int c = tid; c < PG_CELLS; c += 256) cell_off[c] = cnt[c];
     if (tid == 0) cell_off[PG_CELLS] = total;
-    for (int i = tid; i < F.n; i += 256) {
-        const int px = (int)roundf((F.x[i] - F.min_x) * F.inv_w), py = (int)roundf((F.y[i] - F.min_y) * F.inv_h);
-        if (px >= 0 && px < PG_COLS && py >= 0 && py < PG_ROWS) {
-            const int c = px * PG_ROWS + py;
+    for (int i = tid; i < n; i += 256) {
+        const int c = cell_of(i);
+        if (c >= 0) {
             const int slot = cnt[c] + atomicAdd(&cur[c], 1);
             if (in_lds) idx_l[slot] = (uint16_t)i; else cell_idx[slot] = i;
         }
@@ -112,6 +125,64 @@ __global__ __launch_bounds__(256) void k_grid_build(DevFrame F, int *__restrict_
             cell_idx[j + 1] = v;
         }
     }
+}
+
+__global__ __launch_bounds__(256) void k_grid_build(DevFrame F, int *__restrict__ cell_off, int *__restrict__ cell_idx)
+{
+    __shared__ GridLds L;
+    grid_build_body(F.n, [&](int i) { return grid_cell(F.x[i], F.y[i], F.min_x, F.min_y, F.inv_w, F.inv_h); }, L, cell_off, cell_idx);
+}
+
+// ---- resident frame (orbx_frame): the frame's block in HBM is x[n] y[n] octave[n] angle[n] u_right[n] desc[n][32] cell_off[3073]
+// cell_idx[n].  The ingest turns orbx_extract_batch_device's keypoint records (28 B, orbx_keypoint) into those arrays, undistorts the
+// positions when asked (dev_undistort: orbx_undistort_keypoints' arithmetic), copies the descriptors and u_right (-1 without one).
+struct FrameIngest {
+    const float *kps;        // [n][7] orbx_keypoint
+    const uint4 *desc;       // [n][2]
+    const float *u_right;    // [n] or NULL (monocular)
+    int undistort;
+    UndistortParams up;
+};
+struct FrameBlockPtrs {
+    float *x, *y, *angle, *u_right;
+    int32_t *octave;
+    uint4 *desc;
+    int *cell_off, *cell_idx;
+};
+
+__device__ __forceinline__ float2 ingest_feature(const FrameIngest &in, const FrameBlockPtrs &o, int i)
+{
+    const float *k = in.kps + 7 * (long long)i;
+    float2 p = make_float2(k[0], k[1]);
+    if (in.undistort) p = dev_undistort(p, in.up);
+    o.x[i] = p.x; o.y[i] = p.y; o.angle[i] = k[3]; o.octave[i] = __float_as_int(k[5]);
+    o.u_right[i] = in.u_right ? in.u_right[i] : -1.0f;
+    return p;
+}
+
+// frames of more than PG_LDS_FEATS features: the ingest on its own (k_grid_build follows)
+__global__ __launch_bounds__(256) void k_frame_ingest(FrameIngest in, FrameBlockPtrs o, int n)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t < n) ingest_feature(in, o, t);
+    if (t < 2 * n) o.desc[t] = in.desc[t];
+}
+
+// A frame's creation is a chain of dependent launches; up to PG_LDS_FEATS features ingest and grid build are ONE workgroup: the cell of
+// every feature is taken from the position the ingest has in a register and parked in LDS, so the grid never reads back what the
+// ingest wrote (one launch and one dependent global round trip less than ingest + k_grid_build).
+__global__ __launch_bounds__(256) void k_frame_ingest_grid(FrameIngest in, FrameBlockPtrs o, int n, float min_x, float min_y, float inv_w,
+                                                           float inv_h)
+{
+    __shared__ GridLds L;
+    __shared__ uint16_t cell_l[PG_LDS_FEATS];
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const float2 p = ingest_feature(in, o, i);
+        cell_l[i] = (uint16_t)grid_cell(p.x, p.y, min_x, min_y, inv_w, inv_h);   // -1 -> 0xFFFF
+    }
+    for (int t = threadIdx.x; t < 2 * n; t += 256) o.desc[t] = in.desc[t];
+    __syncthreads();
+    grid_build_body(n, [&](int i) { const int c = cell_l[i]; return c == 0xFFFF ? -1 : c; }, L, o.cell_off, o.cell_idx);
 }
 
 // window of a point: radius, level range, cell range; false if the point takes no part
@@ -514,38 +585,14 @@ struct ProjCtx {
     uint8_t *d_work = nullptr; size_t work_cap = 0;
     uint32_t *d_entries = nullptr; size_t ent_cap = 0;
     int32_t *h_out = nullptr; size_t out_cap = 0;
+    int32_t *h_n = nullptr;    // pinned: the feature count a frame created from extraction outputs reads back
 };
 static thread_local ProjCtx g_proj[16];
 
 static size_t pa16(size_t v) { return (v + 15) & ~(size_t)15; }
 
-static int proj_run(int device, const orbx_frame_feats *cur, const orbx_proj_points *pts, const float *sf, int nlevels,
-                    const ProjParams &pp_in, int32_t *match_cur, int *nmatches, const float *inv_sigma2 = nullptr,
-                    int32_t *pt_choice = nullptr, int32_t *pt_dist = nullptr)
+static int proj_ctx(int device, ProjCtx **out)
 {
-    int nm_dummy = 0;
-    std::vector<int32_t> mc_dummy;
-    if (!nmatches) nmatches = &nm_dummy;
-    if (!match_cur && cur && cur->n >= 0) { mc_dummy.resize((size_t)cur->n + 1); match_cur = mc_dummy.data(); }
-    if (!cur || !pts || !sf || !match_cur || !nmatches || nlevels < 1 || nlevels > ORBX_MAX_LEVELS || cur->n < 0 || pts->n < 0 ||
-        cur->n >= 65536 || pts->n > (1 << 20)) {
-        orbx_set_error("search_by_projection: invalid argument");
-        return ORBX_E_INVALID;
-    }
-    const bool need_aux = pp_in.need_pos_aux || pp_in.ur_mode || pp_in.chi2;
-    if (cur->n && (!cur->x || !cur->y || !cur->octave || !cur->u_right || !cur->desc || (pp_in.check_ori && !cur->angle) ||
-                   (pp_in.claims && !cur->occupied))) { orbx_set_error("frame arrays missing"); return ORBX_E_INVALID; }
-    if (pts->n && (!pts->u || !pts->v || !pts->level || !pts->desc || !pts->valid || (need_aux && !pts->aux) ||
-                   (pp_in.claims == 1 && !pts->has_obs) || (pp_in.check_ori && !pts->angle) ||
-                   (pp_in.radius_mode == 1 && !pts->view_cos))) { orbx_set_error("point arrays missing"); return ORBX_E_INVALID; }
-    if (pp_in.chi2 && !inv_sigma2) { orbx_set_error("inv_sigma2 missing"); return ORBX_E_INVALID; }
-    if (!(cur->max_x > cur->min_x) || !(cur->max_y > cur->min_y)) { orbx_set_error("empty image bounds"); return ORBX_E_INVALID; }
-    for (int i = 0; i < pts->n; i++)
-        if (pts->valid[i] && (pts->level[i] < 0 || pts->level[i] >= nlevels)) { orbx_set_error("point %d: level %d out of range", i, pts->level[i]); return ORBX_E_INVALID; }
-    for (int i = 0; i < cur->n; i++) match_cur[i] = -1;
-    *nmatches = 0;
-    for (int i = 0; i < pts->n; i++) { if (pt_choice) pt_choice[i] = -1; if (pt_dist) pt_dist[i] = 256; }
-    if (cur->n == 0 || pts->n == 0) return ORBX_OK;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev || device >= 16) {
         orbx_set_error("no usable HIP device %d (liborbx has no CPU fallback)", device);
@@ -554,14 +601,13 @@ static int proj_run(int device, const orbx_frame_feats *cur, const orbx_proj_poi
     ORBX_HIP(hipSetDevice(device));
     ProjCtx *c = &g_proj[device];
     if (!c->stream) ORBX_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    const size_t nc = (size_t)cur->n, np = (size_t)pts->n;
-    // blob: frame arrays then point arrays
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t r = o; o += pa16(bytes); return r; };
-    const size_t fx = take(4 * nc), fy = take(4 * nc), fo = take(4 * nc), fa = take(4 * nc), fu = take(4 * nc), fd = take(32 * nc), fq = take(nc);
-    const size_t pu = take(4 * np), pv = take(4 * np), pa = take(4 * np), pl = take(4 * np), pg = take(4 * np), pc = take(4 * np),
-                 pd = take(32 * np), pval = take(np), pobs = take(np);
-    const size_t blob = o;
+    *out = c;
+    return ORBX_OK;
+}
+
+// the staging blob of one call: [frame arrays (host-pointer calls only)] [occupied] [point arrays], one upload
+static int proj_blob_reserve(ProjCtx *c, size_t blob)
+{
     if (blob > c->cap) {
         if (c->h_blob) ORBX_HIP(hipHostFree(c->h_blob));
         if (c->d_blob) ORBX_HIP(hipFree(c->d_blob));
@@ -570,11 +616,48 @@ static int proj_run(int device, const orbx_frame_feats *cur, const orbx_proj_poi
         ORBX_HIP(hipMalloc((void **)&c->d_blob, blob * 2));
         c->cap = blob * 2;
     }
+    return ORBX_OK;
+}
+static size_t proj_head_bytes(size_t nc) { return 5 * pa16(4 * nc) + pa16(32 * nc); }
+static size_t proj_tail_bytes(size_t nc, size_t np) { return pa16(nc) + 6 * pa16(4 * np) + pa16(32 * np) + 2 * pa16(np); }
+
+// ---- part 1 of a host-pointer search: the frame's arrays into the head of the staging blob; F addresses them where the upload of part 2
+// will put them (the grid is then built by part 2 into its work area)
+static void proj_stage_frame(ProjCtx *c, const orbx_frame_feats *cur, DevFrame *F)
+{
+    const size_t nc = (size_t)cur->n;
     uint8_t *h = c->h_blob;
+    const uint8_t *d = c->d_blob;
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t r = o; o += pa16(bytes); return r; };
+    const size_t fx = take(4 * nc), fy = take(4 * nc), fo = take(4 * nc), fa = take(4 * nc), fu = take(4 * nc), fd = take(32 * nc);
     memcpy(h + fx, cur->x, 4 * nc); memcpy(h + fy, cur->y, 4 * nc); memcpy(h + fo, cur->octave, 4 * nc);
     if (cur->angle) memcpy(h + fa, cur->angle, 4 * nc); else memset(h + fa, 0, 4 * nc);
     memcpy(h + fu, cur->u_right, 4 * nc); memcpy(h + fd, cur->desc, 32 * nc);
-    if (cur->occupied) memcpy(h + fq, cur->occupied, nc); else memset(h + fq, 0, nc);
+    F->n = cur->n; F->x = (const float *)(d + fx); F->y = (const float *)(d + fy); F->octave = (const int32_t *)(d + fo);
+    F->angle = (const float *)(d + fa); F->u_right = (const float *)(d + fu); F->desc = (const uint32_t *)(d + fd);
+    F->min_x = cur->min_x; F->min_y = cur->min_y; F->max_x = cur->max_x; F->max_y = cur->max_y;
+    F->inv_w = (float)PG_COLS / (cur->max_x - cur->min_x);  // src/Frame.cc:164-165
+    F->inv_h = (float)PG_ROWS / (cur->max_y - cur->min_y);
+}
+
+// ---- part 2: occupied + points staged behind `head` bytes, one upload of the whole blob, the grid build when the frame is not resident
+// (grid == NULL), lists, resolve, download.  F.occupied is set here (it points into the blob).
+static int proj_search(ProjCtx *c, DevFrame F, size_t head, const int *grid_off, const int *grid_idx, const uint8_t *occupied,
+                       const orbx_proj_points *pts, const float *sf, int nlevels, const ProjParams &pp_in, int32_t *match_cur,
+                       int *nmatches, const float *inv_sigma2, int32_t *pt_choice, int32_t *pt_dist)
+{
+    const size_t nc = (size_t)F.n, np = (size_t)pts->n;
+    const size_t blob = head + proj_tail_bytes(nc, np);
+    int rc = proj_blob_reserve(c, blob);
+    if (rc) return rc;
+    size_t o = head;
+    auto take = [&](size_t bytes) { const size_t r = o; o += pa16(bytes); return r; };
+    const size_t fq = take(nc);
+    const size_t pu = take(4 * np), pv = take(4 * np), pa = take(4 * np), pl = take(4 * np), pg = take(4 * np), pc = take(4 * np),
+                 pd = take(32 * np), pval = take(np), pobs = take(np);
+    uint8_t *h = c->h_blob;
+    if (occupied) memcpy(h + fq, occupied, nc); else memset(h + fq, 0, nc);
     memcpy(h + pu, pts->u, 4 * np); memcpy(h + pv, pts->v, 4 * np); memcpy(h + pl, pts->level, 4 * np);
     if (pts->aux) memcpy(h + pa, pts->aux, 4 * np); else memset(h + pa, 0, 4 * np);
     if (pts->angle) memcpy(h + pg, pts->angle, 4 * np); else memset(h + pg, 0, 4 * np);
@@ -583,12 +666,7 @@ static int proj_run(int device, const orbx_frame_feats *cur, const orbx_proj_poi
     if (pts->has_obs) memcpy(h + pobs, pts->has_obs, np); else memset(h + pobs, 1, np);
     ORBX_HIP(hipMemcpyAsync(c->d_blob, h, blob, hipMemcpyHostToDevice, c->stream));
     const uint8_t *d = c->d_blob;
-    DevFrame F;
-    F.n = cur->n; F.x = (const float *)(d + fx); F.y = (const float *)(d + fy); F.octave = (const int32_t *)(d + fo);
-    F.angle = (const float *)(d + fa); F.u_right = (const float *)(d + fu); F.desc = (const uint32_t *)(d + fd); F.occupied = d + fq;
-    F.min_x = cur->min_x; F.min_y = cur->min_y; F.max_x = cur->max_x; F.max_y = cur->max_y;
-    F.inv_w = (float)PG_COLS / (cur->max_x - cur->min_x);  // src/Frame.cc:164-165
-    F.inv_h = (float)PG_ROWS / (cur->max_y - cur->min_y);
+    F.occupied = d + fq;
     DevPoints P;
     P.n = pts->n; P.u = (const float *)(d + pu); P.v = (const float *)(d + pv); P.aux = (const float *)(d + pa);
     P.level = (const int32_t *)(d + pl); P.angle = (const float *)(d + pg); P.view_cos = (const float *)(d + pc);
@@ -624,16 +702,19 @@ static int proj_run(int device, const orbx_frame_feats *cur, const orbx_proj_poi
     else
         ORBX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_proj_resolve), hipFuncAttributeMaxDynamicSharedMemorySize, (int)resolve_lds));
     uint8_t *wk = c->d_work;
-    int *d_coff = (int *)(wk + w_coff), *d_cidx = (int *)(wk + w_cidx), *d_beg = (int *)(wk + w_beg), *d_cnt = (int *)(wk + w_cnt),
-        *d_used = (int *)(wk + w_used);
-    if (!c->d_entries) { // entry pool: grown on demand, the whole call is simply repeated after an overflow
+    int *d_beg = (int *)(wk + w_beg), *d_cnt = (int *)(wk + w_cnt), *d_used = (int *)(wk + w_used);
+    const int *d_coff = grid_off, *d_cidx = grid_idx;
+    if (!grid_off) {   // a host-pointer frame: Frame::AssignFeaturesToGrid, once per call
+        d_coff = (int *)(wk + w_coff); d_cidx = (int *)(wk + w_cidx);
+        hipLaunchKernelGGL(k_grid_build, dim3(1), dim3(256), 0, c->stream, F, (int *)(wk + w_coff), (int *)(wk + w_cidx));
+    }
+    if (!c->d_entries) { // entry pool: grown on demand, the lists and the resolve are simply repeated after an overflow
         const size_t init = 1u << 20;
         ORBX_HIP(hipMalloc((void **)&c->d_entries, sizeof(uint32_t) * init));
         c->ent_cap = init;
     }
     for (int attempt = 0; attempt < 2; attempt++) {
         ORBX_HIP(hipMemsetAsync(d_used, 0, 16, c->stream));
-        hipLaunchKernelGGL(k_grid_build, dim3(1), dim3(256), 0, c->stream, F, d_coff, d_cidx);
         hipLaunchKernelGGL(k_proj_lists, dim3((pts->n + 3) / 4), dim3(256), 0, c->stream, F, P, pp, d_coff, d_cidx, d_beg, d_cnt,
                            c->d_entries, (int)c->ent_cap, d_used);
         if (pp.init_search)
@@ -665,39 +746,92 @@ static int proj_run(int device, const orbx_frame_feats *cur, const orbx_proj_poi
     return ORBX_OK;
 }
 
-extern "C" int orbx_search_by_projection_last_frame(int device, const orbx_frame_feats *cur, const orbx_proj_points *pts,
-                                                    const float *scale_factors, int nlevels, float th, int direction, float mbf,
-                                                    int check_orientation, int32_t *match_cur, int *nmatches)
+static int proj_run(int device, const orbx_frame_feats *cur, const orbx_proj_points *pts, const float *sf, int nlevels,
+                    const ProjParams &pp_in, int32_t *match_cur, int *nmatches, const float *inv_sigma2 = nullptr,
+                    int32_t *pt_choice = nullptr, int32_t *pt_dist = nullptr)
 {
-    if (direction < 0 || direction > 2) { orbx_set_error("direction must be 0 (none), 1 (forward) or 2 (backward)"); return ORBX_E_INVALID; }
+    int nm_dummy = 0;
+    std::vector<int32_t> mc_dummy;
+    if (!nmatches) nmatches = &nm_dummy;
+    if (!match_cur && cur && cur->n >= 0) { mc_dummy.resize((size_t)cur->n + 1); match_cur = mc_dummy.data(); }
+    if (!cur || !pts || !sf || !match_cur || !nmatches || nlevels < 1 || nlevels > ORBX_MAX_LEVELS || cur->n < 0 || pts->n < 0 ||
+        cur->n >= 65536 || pts->n > (1 << 20)) {
+        orbx_set_error("search_by_projection: invalid argument");
+        return ORBX_E_INVALID;
+    }
+    const bool need_aux = pp_in.need_pos_aux || pp_in.ur_mode || pp_in.chi2;
+    if (cur->n && (!cur->x || !cur->y || !cur->octave || !cur->u_right || !cur->desc || (pp_in.check_ori && !cur->angle) ||
+                   (pp_in.claims && !cur->occupied))) { orbx_set_error("frame arrays missing"); return ORBX_E_INVALID; }
+    if (pts->n && (!pts->u || !pts->v || !pts->level || !pts->desc || !pts->valid || (need_aux && !pts->aux) ||
+                   (pp_in.claims == 1 && !pts->has_obs) || (pp_in.check_ori && !pts->angle) ||
+                   (pp_in.radius_mode == 1 && !pts->view_cos))) { orbx_set_error("point arrays missing"); return ORBX_E_INVALID; }
+    if (pp_in.chi2 && !inv_sigma2) { orbx_set_error("inv_sigma2 missing"); return ORBX_E_INVALID; }
+    if (!(cur->max_x > cur->min_x) || !(cur->max_y > cur->min_y)) { orbx_set_error("empty image bounds"); return ORBX_E_INVALID; }
+    for (int i = 0; i < pts->n; i++)
+        if (pts->valid[i] && (pts->level[i] < 0 || pts->level[i] >= nlevels)) { orbx_set_error("point %d: level %d out of range", i, pts->level[i]); return ORBX_E_INVALID; }
+    for (int i = 0; i < cur->n; i++) match_cur[i] = -1;
+    *nmatches = 0;
+    for (int i = 0; i < pts->n; i++) { if (pt_choice) pt_choice[i] = -1; if (pt_dist) pt_dist[i] = 256; }
+    if (cur->n == 0 || pts->n == 0) return ORBX_OK;
+    ProjCtx *c;
+    int rc = proj_ctx(device, &c);
+    if (rc) return rc;
+    const size_t head = proj_head_bytes((size_t)cur->n);
+    rc = proj_blob_reserve(c, head + proj_tail_bytes((size_t)cur->n, (size_t)pts->n));
+    if (rc) return rc;
+    DevFrame F;
+    proj_stage_frame(c, cur, &F);                                                  // part 1
+    return proj_search(c, F, head, nullptr, nullptr, cur->occupied, pts, sf, nlevels, pp_in, match_cur, nmatches, inv_sigma2,
+                       pt_choice, pt_dist);                                        // part 2
+}
+
+// the parameter blocks of the three per-frame searches (shared by the host-pointer and the resident entry points)
+static ProjParams params_last_frame(float th, int direction, float mbf, int check_orientation)
+{
     ProjParams pp;
     memset(&pp, 0, sizeof pp);
     pp.radius_mode = 0; pp.bounds = 1; pp.need_pos_aux = 1; pp.lo_off = -1; pp.hi_off = 1; pp.direction = direction;
     pp.ur_mode = 1; pp.max_dist = 100; pp.check_ori = check_orientation & 1; pp.mark_cleared = (check_orientation >> 1) & 1; pp.claims = 1;
     pp.th = th; pp.mbf = mbf;
-    return proj_run(device, cur, pts, scale_factors, nlevels, pp, match_cur, nmatches);
+    return pp;
+}
+static ProjParams params_map_points(float th, float nnratio)
+{
+    ProjParams pp;
+    memset(&pp, 0, sizeof pp);
+    pp.radius_mode = 1; pp.lo_off = -1; pp.hi_off = 0; pp.ur_mode = 2; pp.max_dist = 100; pp.ratio = 1; pp.claims = 1;
+    pp.th = th; pp.nnratio = nnratio;
+    return pp;
+}
+static ProjParams params_keyframe(float th, int orb_dist, int check_orientation)
+{
+    ProjParams pp;
+    memset(&pp, 0, sizeof pp);
+    pp.bounds = 1; pp.lo_off = -1; pp.hi_off = 1; pp.max_dist = orb_dist; pp.check_ori = check_orientation & 1; pp.mark_cleared = (check_orientation >> 1) & 1; pp.claims = 2;
+    pp.th = th;
+    return pp;
+}
+
+extern "C" int orbx_search_by_projection_last_frame(int device, const orbx_frame_feats *cur, const orbx_proj_points *pts,
+                                                    const float *scale_factors, int nlevels, float th, int direction, float mbf,
+                                                    int check_orientation, int32_t *match_cur, int *nmatches)
+{
+    if (direction < 0 || direction > 2) { orbx_set_error("direction must be 0 (none), 1 (forward) or 2 (backward)"); return ORBX_E_INVALID; }
+    return proj_run(device, cur, pts, scale_factors, nlevels, params_last_frame(th, direction, mbf, check_orientation), match_cur, nmatches);
 }
 
 extern "C" int orbx_search_by_projection_map_points(int device, const orbx_frame_feats *cur, const orbx_proj_points *pts,
                                                     const float *scale_factors, int nlevels, float th, float nnratio,
                                                     int32_t *match_cur, int *nmatches)
 {
-    ProjParams pp;
-    memset(&pp, 0, sizeof pp);
-    pp.radius_mode = 1; pp.lo_off = -1; pp.hi_off = 0; pp.ur_mode = 2; pp.max_dist = 100; pp.ratio = 1; pp.claims = 1;
-    pp.th = th; pp.nnratio = nnratio;
-    return proj_run(device, cur, pts, scale_factors, nlevels, pp, match_cur, nmatches);
+    return proj_run(device, cur, pts, scale_factors, nlevels, params_map_points(th, nnratio), match_cur, nmatches);
 }
 
 extern "C" int orbx_search_by_projection_keyframe(int device, const orbx_frame_feats *cur, const orbx_proj_points *pts,
                                                   const float *scale_factors, int nlevels, float th, int orb_dist,
                                                   int check_orientation, int32_t *match_cur, int *nmatches)
 {
-    ProjParams pp;
-    memset(&pp, 0, sizeof pp);
-    pp.bounds = 1; pp.lo_off = -1; pp.hi_off = 1; pp.max_dist = orb_dist; pp.check_ori = check_orientation & 1; pp.mark_cleared = (check_orientation >> 1) & 1; pp.claims = 2;
-    pp.th = th;
-    return proj_run(device, cur, pts, scale_factors, nlevels, pp, match_cur, nmatches);
+    return proj_run(device, cur, pts, scale_factors, nlevels, params_keyframe(th, orb_dist, check_orientation), match_cur, nmatches);
 }
 
 extern "C" int orbx_search_by_projection_sim3(int device, const orbx_frame_feats *kf, const orbx_proj_points *pts,
@@ -773,4 +907,253 @@ extern "C" int orbx_search_by_sim3(int device, const orbx_frame_feats *kf1, cons
     }
     *nfound = found;
     return ORBX_OK;
+}
+
+// ---------------------------------------------------------------- resident current frame (include/orbx.h: orbx_frame)
+
+// Frame blocks and their events are recycled: a frame lives one frame time, and hipFree would synchronise the device every frame.  A block
+// returns to its device's pool only after the work that wrote it has completed (its event).
+struct FrameBlock { uint8_t *d = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; };
+static std::mutex g_fpool_mu;
+static std::vector<FrameBlock> g_fpool[16];
+#define FRAME_POOL_MAX 8
+
+static int frame_block_get(int device, size_t bytes, FrameBlock *out)
+{
+    {
+        std::lock_guard<std::mutex> lk(g_fpool_mu);
+        std::vector<FrameBlock> &v = g_fpool[device];
+        int best = -1;
+        for (int i = 0; i < (int)v.size(); i++)
+            if (v[i].cap >= bytes && (best < 0 || v[i].cap < v[best].cap)) best = i;
+        if (best >= 0) { *out = v[best]; v.erase(v.begin() + best); return ORBX_OK; }
+    }
+    FrameBlock b;
+    b.cap = (bytes + 65535) & ~(size_t)65535;   // frames of similar size share blocks
+    ORBX_HIP(hipMalloc((void **)&b.d, b.cap));
+    if (hipEventCreateWithFlags(&b.ev, hipEventDisableTiming) != hipSuccess) {
+        hipFree(b.d);
+        orbx_set_error("orbx_frame: hipEventCreateWithFlags failed");
+        return ORBX_E_HIP;
+    }
+    *out = b;
+    return ORBX_OK;
+}
+
+static void frame_block_put(int device, FrameBlock b)
+{
+    hipEventSynchronize(b.ev);   // the creation that wrote the block (searches of the frame have synchronised already)
+    std::lock_guard<std::mutex> lk(g_fpool_mu);
+    std::vector<FrameBlock> &v = g_fpool[device];
+    if (v.size() < FRAME_POOL_MAX) { v.push_back(b); return; }
+    hipEventDestroy(b.ev);
+    hipFree(b.d);
+}
+
+struct orbx_frame {
+    int device, n, has_angle;
+    float min_x, min_y, max_x, max_y;
+    FrameBlock blk;
+    size_t o_x, o_y, o_oct, o_ang, o_ur, o_desc, o_coff, o_cidx;
+    bool pending;   // the creation may still be running: the first search waits for blk.ev on its own stream
+};
+
+static size_t frame_layout(orbx_frame *f)
+{
+    const size_t nc = (size_t)f->n;
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t r = o; o += pa16(bytes); return r; };
+    f->o_x = take(4 * nc); f->o_y = take(4 * nc); f->o_oct = take(4 * nc); f->o_ang = take(4 * nc); f->o_ur = take(4 * nc);
+    f->o_desc = take(32 * nc); f->o_coff = take(4 * (PG_CELLS + 1)); f->o_cidx = take(4 * nc);
+    return o;
+}
+
+static DevFrame frame_dev(const orbx_frame *f)
+{
+    const uint8_t *d = f->blk.d;
+    DevFrame F;
+    F.n = f->n; F.x = (const float *)(d + f->o_x); F.y = (const float *)(d + f->o_y); F.octave = (const int32_t *)(d + f->o_oct);
+    F.angle = (const float *)(d + f->o_ang); F.u_right = (const float *)(d + f->o_ur); F.desc = (const uint32_t *)(d + f->o_desc);
+    F.occupied = nullptr;
+    F.min_x = f->min_x; F.min_y = f->min_y; F.max_x = f->max_x; F.max_y = f->max_y;
+    F.inv_w = (float)PG_COLS / (f->max_x - f->min_x);  // src/Frame.cc:164-165, as part 1 of the host-pointer calls
+    F.inv_h = (float)PG_ROWS / (f->max_y - f->min_y);
+    return F;
+}
+
+static orbx_frame *frame_new(int device, int n, int has_angle, float min_x, float min_y, float max_x, float max_y)
+{
+    orbx_frame *f = new orbx_frame();
+    f->device = device; f->n = n; f->has_angle = has_angle;
+    f->min_x = min_x; f->min_y = min_y; f->max_x = max_x; f->max_y = max_y;
+    f->pending = false;
+    return f;
+}
+
+extern "C" int orbx_frame_create(int device, const orbx_frame_feats *cur, orbx_frame **out)
+{
+    if (!out || !cur || cur->n < 0 || cur->n >= 65536) { orbx_set_error("orbx_frame_create: invalid argument"); return ORBX_E_INVALID; }
+    *out = nullptr;
+    if (cur->n && (!cur->x || !cur->y || !cur->octave || !cur->u_right || !cur->desc)) { orbx_set_error("orbx_frame_create: frame arrays missing"); return ORBX_E_INVALID; }
+    if (!(cur->max_x > cur->min_x) || !(cur->max_y > cur->min_y)) { orbx_set_error("orbx_frame_create: empty image bounds"); return ORBX_E_INVALID; }
+    ProjCtx *c;
+    int rc = proj_ctx(device, &c);
+    if (rc) return rc;
+    orbx_frame *f = frame_new(device, cur->n, cur->n == 0 || cur->angle ? 1 : 0, cur->min_x, cur->min_y, cur->max_x, cur->max_y);
+    const size_t bytes = frame_layout(f);
+    rc = frame_block_get(device, bytes, &f->blk);
+    if (rc) { delete f; return rc; }
+    // the frame arrays of the block are laid out as the head of a host-pointer call's staging blob: part 1 stages them, one upload
+    rc = proj_blob_reserve(c, f->o_coff);
+    if (!rc) {
+        const DevFrame F = frame_dev(f);
+        if (cur->n) {
+            DevFrame Fs;
+            proj_stage_frame(c, cur, &Fs);
+            if (hipMemcpyAsync(f->blk.d, c->h_blob, f->o_coff, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = ORBX_E_HIP;
+        }
+        if (!rc) hipLaunchKernelGGL(k_grid_build, dim3(1), dim3(256), 0, c->stream, F, (int *)(f->blk.d + f->o_coff), (int *)(f->blk.d + f->o_cidx));
+        if (!rc && (hipGetLastError() != hipSuccess || hipEventRecord(f->blk.ev, c->stream) != hipSuccess ||
+                    hipStreamSynchronize(c->stream) != hipSuccess)) rc = ORBX_E_HIP;   // the staging blob is reused by the next call
+        if (rc) orbx_set_error("orbx_frame_create: upload / grid build failed");
+    }
+    if (rc) { frame_block_put(device, f->blk); delete f; return rc; }
+    *out = f;
+    return ORBX_OK;
+}
+
+extern "C" int orbx_frame_create_from_extraction(int device, const void *d_kps, const void *d_desc, const void *d_n, int cap, int index,
+                                                 const void *d_u_right, const float *K, const float *dist_coef, int ndist,
+                                                 float min_x, float min_y, float max_x, float max_y, void *stream, orbx_frame **out)
+{
+    if (!out || !d_kps || !d_desc || !d_n || cap < 1 || index < 0) {
+        orbx_set_error("orbx_frame_create_from_extraction: invalid argument (null buffer, cap < 1 or index < 0)");
+        return ORBX_E_INVALID;
+    }
+    *out = nullptr;
+    if (K && (!dist_coef || (ndist != 4 && ndist != 5) || K[0] == 0.f || K[1] == 0.f)) {
+        orbx_set_error("orbx_frame_create_from_extraction: K needs fx, fy != 0 and 4 or 5 distortion coefficients");
+        return ORBX_E_INVALID;
+    }
+    if (!(max_x > min_x) || !(max_y > min_y)) { orbx_set_error("orbx_frame_create_from_extraction: empty image bounds"); return ORBX_E_INVALID; }
+    ProjCtx *c;
+    int rc = proj_ctx(device, &c);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (!c->h_n) ORBX_HIP(hipHostMalloc((void **)&c->h_n, 64, hipHostMallocDefault));
+    ORBX_HIP(hipMemcpyAsync(c->h_n, (const int32_t *)d_n + index, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    ORBX_HIP(hipStreamSynchronize(st));   // the one synchronisation: the count sizes the frame
+    const int n = c->h_n[0];
+    if (n < 0 || n > cap || n >= 65536) {
+        orbx_set_error("orbx_frame_create_from_extraction: image %d holds %d keypoints, outside [0, cap = %d] (wrong index / cap?)", index, n, cap);
+        return ORBX_E_INVALID;
+    }
+    orbx_frame *f = frame_new(device, n, 1, min_x, min_y, max_x, max_y);
+    const size_t bytes = frame_layout(f);
+    rc = frame_block_get(device, bytes, &f->blk);
+    if (rc) { delete f; return rc; }
+    FrameIngest in;
+    memset(&in, 0, sizeof in);
+    in.kps = (const float *)((const uint8_t *)d_kps + (size_t)index * cap * sizeof(orbx_keypoint));
+    in.desc = (const uint4 *)((const uint8_t *)d_desc + (size_t)index * cap * 32);
+    in.u_right = (const float *)d_u_right;
+    in.undistort = K && dist_coef[0] != 0.0f;   // src/Frame.cc:472-476: mvKeysUn = mvKeys
+    if (in.undistort) in.up = orbx_undistort_params(K[0], K[1], K[2], K[3], dist_coef, ndist);
+    uint8_t *d = f->blk.d;
+    FrameBlockPtrs o;
+    o.x = (float *)(d + f->o_x); o.y = (float *)(d + f->o_y); o.octave = (int32_t *)(d + f->o_oct); o.angle = (float *)(d + f->o_ang);
+    o.u_right = (float *)(d + f->o_ur); o.desc = (uint4 *)(d + f->o_desc); o.cell_off = (int *)(d + f->o_coff); o.cell_idx = (int *)(d + f->o_cidx);
+    const DevFrame F = frame_dev(f);
+    if (n <= PG_LDS_FEATS) {
+        hipLaunchKernelGGL(k_frame_ingest_grid, dim3(1), dim3(256), 0, st, in, o, n, F.min_x, F.min_y, F.inv_w, F.inv_h);
+    } else {
+        hipLaunchKernelGGL(k_frame_ingest, dim3((2 * n + 255) / 256), dim3(256), 0, st, in, o, n);
+        hipLaunchKernelGGL(k_grid_build, dim3(1), dim3(256), 0, st, F, o.cell_off, o.cell_idx);
+    }
+    if (hipGetLastError() != hipSuccess || hipEventRecord(f->blk.ev, st) != hipSuccess) {
+        orbx_set_error("orbx_frame_create_from_extraction: launch failed");
+        frame_block_put(device, f->blk);
+        delete f;
+        return ORBX_E_HIP;
+    }
+    f->pending = true;
+    *out = f;
+    return ORBX_OK;
+}
+
+extern "C" int orbx_frame_size(const orbx_frame *f) { return f ? f->n : ORBX_E_INVALID; }
+
+extern "C" int orbx_frame_read(const orbx_frame *f, float *x, float *y, int32_t *octave, float *angle, float *u_right, uint8_t *desc)
+{
+    if (!f) { orbx_set_error("orbx_frame_read: null frame"); return ORBX_E_INVALID; }
+    if (f->n == 0) return ORBX_OK;
+    ORBX_HIP(orbx_use_device(f->device));
+    ORBX_HIP(hipEventSynchronize(f->blk.ev));
+    const size_t nc = (size_t)f->n;
+    const uint8_t *d = f->blk.d;
+    if (x) ORBX_HIP(hipMemcpy(x, d + f->o_x, 4 * nc, hipMemcpyDeviceToHost));
+    if (y) ORBX_HIP(hipMemcpy(y, d + f->o_y, 4 * nc, hipMemcpyDeviceToHost));
+    if (octave) ORBX_HIP(hipMemcpy(octave, d + f->o_oct, 4 * nc, hipMemcpyDeviceToHost));
+    if (angle) ORBX_HIP(hipMemcpy(angle, d + f->o_ang, 4 * nc, hipMemcpyDeviceToHost));
+    if (u_right) ORBX_HIP(hipMemcpy(u_right, d + f->o_ur, 4 * nc, hipMemcpyDeviceToHost));
+    if (desc) ORBX_HIP(hipMemcpy(desc, d + f->o_desc, 32 * nc, hipMemcpyDeviceToHost));
+    return ORBX_OK;
+}
+
+extern "C" void orbx_frame_destroy(orbx_frame *f)
+{
+    if (!f) return;
+    if (orbx_use_device(f->device) == hipSuccess) frame_block_put(f->device, f->blk);
+    delete f;
+}
+
+// the resident twin of proj_run: the same point validation; the frame's arrays and grid come from its block, only part 2 runs
+static int proj_run_resident(orbx_frame *f, const uint8_t *occupied, const orbx_proj_points *pts, const float *sf, int nlevels,
+                             const ProjParams &pp, int32_t *match_cur, int *nmatches)
+{
+    if (!f || !pts || !sf || !match_cur || !nmatches || nlevels < 1 || nlevels > ORBX_MAX_LEVELS || pts->n < 0 || pts->n > (1 << 20)) {
+        orbx_set_error("orbx_frame_search_by_projection: invalid argument");
+        return ORBX_E_INVALID;
+    }
+    const bool need_aux = pp.need_pos_aux || pp.ur_mode || pp.chi2;
+    if (pp.check_ori && !f->has_angle) { orbx_set_error("orbx_frame_search_by_projection: the frame was created without angles"); return ORBX_E_INVALID; }
+    if (pts->n && (!pts->u || !pts->v || !pts->level || !pts->desc || !pts->valid || (need_aux && !pts->aux) ||
+                   (pp.claims == 1 && !pts->has_obs) || (pp.check_ori && !pts->angle) ||
+                   (pp.radius_mode == 1 && !pts->view_cos))) { orbx_set_error("point arrays missing"); return ORBX_E_INVALID; }
+    for (int i = 0; i < pts->n; i++)
+        if (pts->valid[i] && (pts->level[i] < 0 || pts->level[i] >= nlevels)) { orbx_set_error("point %d: level %d out of range", i, pts->level[i]); return ORBX_E_INVALID; }
+    for (int i = 0; i < f->n; i++) match_cur[i] = -1;
+    *nmatches = 0;
+    if (f->n == 0 || pts->n == 0) return ORBX_OK;
+    ProjCtx *c;
+    int rc = proj_ctx(f->device, &c);
+    if (rc) return rc;
+    if (f->pending) ORBX_HIP(hipStreamWaitEvent(c->stream, f->blk.ev, 0));   // the creation, ordered by its event (no device synchronisation)
+    const uint8_t *d = f->blk.d;
+    rc = proj_search(c, frame_dev(f), 0, (const int *)(d + f->o_coff), (const int *)(d + f->o_cidx), occupied, pts, sf, nlevels, pp,
+                     match_cur, nmatches, nullptr, nullptr, nullptr);
+    if (!rc) f->pending = false;   // this search synchronised behind the creation
+    return rc;
+}
+
+extern "C" int orbx_frame_search_by_projection_last_frame(orbx_frame *cur, const uint8_t *occupied, const orbx_proj_points *pts,
+                                                          const float *scale_factors, int nlevels, float th, int direction, float mbf,
+                                                          int check_orientation, int32_t *match_cur, int *nmatches)
+{
+    if (direction < 0 || direction > 2) { orbx_set_error("direction must be 0 (none), 1 (forward) or 2 (backward)"); return ORBX_E_INVALID; }
+    return proj_run_resident(cur, occupied, pts, scale_factors, nlevels, params_last_frame(th, direction, mbf, check_orientation), match_cur, nmatches);
+}
+
+extern "C" int orbx_frame_search_by_projection_map_points(orbx_frame *cur, const uint8_t *occupied, const orbx_proj_points *pts,
+                                                          const float *scale_factors, int nlevels, float th, float nnratio,
+                                                          int32_t *match_cur, int *nmatches)
+{
+    return proj_run_resident(cur, occupied, pts, scale_factors, nlevels, params_map_points(th, nnratio), match_cur, nmatches);
+}
+
+extern "C" int orbx_frame_search_by_projection_keyframe(orbx_frame *cur, const uint8_t *occupied, const orbx_proj_points *pts,
+                                                        const float *scale_factors, int nlevels, float th, int orb_dist,
+                                                        int check_orientation, int32_t *match_cur, int *nmatches)
+{
+    return proj_run_resident(cur, occupied, pts, scale_factors, nlevels, params_keyframe(th, orb_dist, check_orientation), match_cur, nmatches);
 }

@@ -118,6 +118,14 @@ def lib():
     L.orbx_search_by_projection_keyframe.argtypes = [i, C.POINTER(FrameFeats), C.POINTER(ProjPoints), vp, i, f, i, i, vp, ip]
     L.orbx_search_by_projection_sim3.argtypes = [i, C.POINTER(FrameFeats), C.POINTER(ProjPoints), vp, i, f, vp, ip]
     L.orbx_window_best.argtypes = [i, C.POINTER(FrameFeats), C.POINTER(ProjPoints), vp, vp, i, f, i, i, vp, vp, ip]
+    L.orbx_frame_create.argtypes = [i, C.POINTER(FrameFeats), C.POINTER(vp)]
+    L.orbx_frame_create_from_extraction.argtypes = [i, vp, vp, vp, i, i, vp, vp, vp, i, f, f, f, f, vp, C.POINTER(vp)]
+    L.orbx_frame_size.argtypes = [vp]
+    L.orbx_frame_read.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.orbx_frame_destroy.argtypes = [vp]; L.orbx_frame_destroy.restype = None
+    L.orbx_frame_search_by_projection_last_frame.argtypes = [vp, vp, C.POINTER(ProjPoints), vp, i, f, i, f, i, vp, ip]
+    L.orbx_frame_search_by_projection_map_points.argtypes = [vp, vp, C.POINTER(ProjPoints), vp, i, f, f, vp, ip]
+    L.orbx_frame_search_by_projection_keyframe.argtypes = [vp, vp, C.POINTER(ProjPoints), vp, i, f, i, i, vp, ip]
     L.orbx_bow_frames_create.argtypes = [i, i, i, C.POINTER(vp)]
     L.orbx_bow_frames_destroy.argtypes = [vp]; L.orbx_bow_frames_destroy.restype = None
     L.orbx_bow_transform_batch_device.argtypes = [vp, vp, vp, vp, vp, i, i, vp]
@@ -538,6 +546,61 @@ def _flags_for(flag, kf, who):
     return fl
 
 
+class DeviceFrame:
+    """orbx_frame: the current frame's immutable part resident in HBM -- undistorted x / y, octave, angle, u_right, descriptors, bounds and
+    the 64x48 grid, built once -- for the two to four projection searches Tracking runs on it.  `occupied` is passed per search."""
+
+    def __init__(self, frame, device=0):
+        s_, keep = ORBmatcher._frame(dict(frame, occupied=None))
+        h = C.c_void_p()
+        _check(lib().orbx_frame_create(device, C.byref(s_), C.byref(h)))
+        self._h, self.n, self.device = h, s_.n, device
+
+    @classmethod
+    def from_extraction(cls, device, d_kps, d_desc, d_n, cap, index, d_u_right=None, K=None, dist_coef=None, bounds=(0.0, 0.0, 0.0, 0.0),
+                        stream=None):
+        """from orbx_extract_batch_device's device outputs (image `index`, capacity `cap`) and optionally the [cap] u_right row of
+        orbx_stereo_match_batch_device; K = (fx, fy, cx, cy) with dist_coef undistorts on the device.  Synchronises `stream` once (the count)."""
+        kk = None if K is None else np.ascontiguousarray(K, np.float32).reshape(4)
+        dc = None if dist_coef is None else np.ascontiguousarray(dist_coef, np.float32).reshape(-1)
+        h = C.c_void_p()
+        _check(lib().orbx_frame_create_from_extraction(device, d_kps, d_desc, d_n, int(cap), int(index), d_u_right,
+                                                       None if kk is None else _p(kk), None if dc is None else _p(dc), 0 if dc is None else len(dc),
+                                                       *[float(v) for v in bounds], stream, C.byref(h)))
+        self = cls.__new__(cls)
+        self._h, self.device = h, device
+        self.n = lib().orbx_frame_size(h)
+        self.bounds = tuple(float(v) for v in bounds)
+        return self
+
+    def read(self):
+        """-> dict(x, y, octave, angle, u_right, desc) as tests/test_projection.py builds a frame (no occupied, no bounds)"""
+        n = self.n
+        x = np.zeros(n, np.float32); y = np.zeros(n, np.float32); o = np.zeros(n, np.int32); a = np.zeros(n, np.float32)
+        u = np.zeros(n, np.float32); d = np.zeros((n, 32), np.uint8)
+        _check(lib().orbx_frame_read(self._h, _p(x), _p(y), _p(o), _p(a), _p(u), _p(d)))
+        return dict(x=x, y=y, octave=o, angle=a, u_right=u, desc=d)
+
+    def __del__(self):
+        try:
+            h, L = getattr(self, "_h", None), _lib
+            if h and L is not None:
+                L.orbx_frame_destroy(h)
+            self._h = None
+        except Exception:
+            pass
+
+
+def _occupied_for(occupied, frame, who):
+    """per-call occupied bytes of a resident frame (None: no feature occupied); one byte per feature of THAT frame"""
+    if occupied is None:
+        return None
+    oc = np.ascontiguousarray(occupied, np.uint8)
+    if oc.ndim != 1 or len(oc) != frame.n:
+        raise OrbxError(-1, f"{who}: occupied has {oc.size} entries, the frame has {frame.n} features")
+    return oc
+
+
 class BowDatabase:
     """Device-resident keyframe set (include/orbx.h: orbx_bowdb_*): upload once, search many frames."""
 
@@ -761,6 +824,37 @@ class ORBmatcher:
         out = np.full(a.n, -1, np.int32); n = C.c_int()
         _check(lib().orbx_search_by_projection_keyframe(self.device, C.byref(a), C.byref(b), _p(sf), len(sf), th, int(ORBdist),
                                                         int(self.mbCheckOrientation), _p(out), C.byref(n)))
+        return out, n.value
+
+    # ---- the per-frame searches on a resident frame (DeviceFrame): only the points and `occupied` travel per call
+    def SearchByProjectionLastFrameResident(self, frame, occupied, LastFramePoints, scaleFactors, th, direction=0, mbf=0.0, check_orientation=None):
+        """SearchByProjectionLastFrame on a DeviceFrame; check_orientation (0, 1, 3) defaults to mbCheckOrientation -> (match_cur, nmatches)"""
+        oc = _occupied_for(occupied, frame, "SearchByProjectionLastFrameResident")
+        b, kb = self._points(LastFramePoints)
+        sf = np.ascontiguousarray(scaleFactors, np.float32)
+        co = int(self.mbCheckOrientation) if check_orientation is None else int(check_orientation)
+        out = np.full(frame.n, -1, np.int32); n = C.c_int()
+        _check(lib().orbx_frame_search_by_projection_last_frame(frame._h, None if oc is None else _p(oc), C.byref(b), _p(sf), len(sf), th,
+                                                                direction, mbf, co, _p(out), C.byref(n)))
+        return out, n.value
+
+    def SearchByProjectionMapPointsResident(self, frame, occupied, vpMapPoints, scaleFactors, th=3.0):
+        oc = _occupied_for(occupied, frame, "SearchByProjectionMapPointsResident")
+        b, kb = self._points(vpMapPoints)
+        sf = np.ascontiguousarray(scaleFactors, np.float32)
+        out = np.full(frame.n, -1, np.int32); n = C.c_int()
+        _check(lib().orbx_frame_search_by_projection_map_points(frame._h, None if oc is None else _p(oc), C.byref(b), _p(sf), len(sf), th,
+                                                                self.mfNNratio, _p(out), C.byref(n)))
+        return out, n.value
+
+    def SearchByProjectionKeyFrameResident(self, frame, occupied, KFPoints, scaleFactors, th, ORBdist, check_orientation=None):
+        oc = _occupied_for(occupied, frame, "SearchByProjectionKeyFrameResident")
+        b, kb = self._points(KFPoints)
+        sf = np.ascontiguousarray(scaleFactors, np.float32)
+        co = int(self.mbCheckOrientation) if check_orientation is None else int(check_orientation)
+        out = np.full(frame.n, -1, np.int32); n = C.c_int()
+        _check(lib().orbx_frame_search_by_projection_keyframe(frame._h, None if oc is None else _p(oc), C.byref(b), _p(sf), len(sf), th,
+                                                              int(ORBdist), co, _p(out), C.byref(n)))
         return out, n.value
 
     def SearchByProjectionSim3(self, pKF, vpPoints, scaleFactors, th):
