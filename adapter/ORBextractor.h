@@ -46,6 +46,12 @@ public:
     void ExtractStereo(const cv::Mat &imLeft, const cv::Mat &imRight, float bf, float b, std::vector<cv::KeyPoint> &keysLeft,
                        cv::Mat &descLeft, std::vector<cv::KeyPoint> &keysRight, cv::Mat &descRight, std::vector<float> &uRight,
                        std::vector<float> &depth);
+    // orbx_extract_rgbd on THIS extractor (adapter/ORBextractor_rgbd.cc): the RGB-D constructor's lines :145-154 (ExtractORB,
+    // UndistortKeyPoints, ComputeStereoFromRGBD) and GrabImageRGBD's depth convertTo (src/Tracking.cc:232-233) in one call.
+    // imDepth: the RAW CV_16U or CV_32F depth map (continuous or not); depthScale = Tracking::mDepthMapFactor; K = mK, distCoef = mDistCoef.
+    void ExtractRGBD(const cv::Mat &imGray, const cv::Mat &imDepth, float depthScale, const cv::Mat &K, const cv::Mat &distCoef, float bf,
+                     std::vector<cv::KeyPoint> &keys, std::vector<cv::KeyPoint> &keysUn, cv::Mat &descriptors, std::vector<float> &uRight,
+                     std::vector<float> &depth);
 
 protected:
     int nfeatures;

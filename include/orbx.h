@@ -116,6 +116,57 @@ int orbx_extract(orbx_extractor *e, const uint8_t *img, int w, int h, size_t str
 int orbx_extract_color(orbx_extractor *e, const uint8_t *img, int w, int h, size_t stride, int channels, int rgb_order,
                        orbx_keypoint *kps, uint8_t *desc, int cap, int *n_out, uint8_t *gray_out, size_t gray_stride);
 
+/* ---- RGB-D frames (Frame::Frame(imGray, imDepth, ...), src/Frame.cc:127-180) -------------------------
+ * After ExtractORB (:146) the RGB-D constructor runs UndistortKeyPoints (:152) and ComputeStereoFromRGBD (:154, :754-774): per
+ * keypoint i, with kp its extractor position (level-0 coordinates, distorted) and kpU = its undistorted position,
+ *     d = imDepth.at<float>((int)kp.y, (int)kp.x)       -- the lookup uses the DISTORTED position, truncated (:764-767)
+ *     d > 0:  mvDepth[i] = d, mvuRight[i] = kpU.x - mbf / d  (fp32, correctly rounded division);  else both -1.
+ * imDepth is what Tracking::GrabImageRGBD (src/Tracking.cc:232-233) leaves: CV_16U depth is always converted to float as
+ * d = (float)raw * depth_scale (one fp32 multiply); CV_32F depth is multiplied only when fabs(depth_scale - 1.0f) > 1e-5, else used as it is.
+ * kpU is the arithmetic of orbx_undistort_keypoints, bit for bit; dist_coef[0] == 0 leaves it kp (src/Frame.cc:472-476).
+ * Defined deviation: a keypoint whose truncated position lies outside the depth image gets -1 / -1 (the reference reads outside
+ * the matrix; extraction never produces such a point, but orbx_rgbd_depth_batch_device accepts caller-supplied keypoints). */
+#define ORBX_DEPTH_U16 0   /* CV_16U (the TUM PNG depth maps) */
+#define ORBX_DEPTH_F32 1   /* CV_32F */
+typedef struct {
+    int depth_type;            /* ORBX_DEPTH_* */
+    float depth_scale;         /* Tracking::mDepthMapFactor after src/Tracking.cc:147-151: 1.0f/DepthMapFactor, or 1 when |DepthMapFactor| < 1e-5 */
+    float bf;                  /* mbf */
+    float fx, fy, cx, cy;      /* mK */
+    float dist_coef[5]; int ndist;   /* mDistCoef (k1 k2 p1 p2 [k3]), ndist 4 or 5; dist_coef[0] == 0: no undistortion */
+} orbx_rgbd_params;
+
+/* One RGB-D frame in one call (host pointers): the image preparation of Tracking::GrabImageRGBD (src/Tracking.cc:217-233: cvtColor,
+ * depth convertTo) and lines :145-154 of the RGB-D constructor.  img: channels 1 (grey), 3 or 4 (colour through the cvtColor of
+ * orbx_extract_color; rgb_order 1 = mbRGB); depth: h rows of w uint16 (ORBX_DEPTH_U16) or float (ORBX_DEPTH_F32) at depth_stride
+ * bytes (at least a row, a multiple of the element size).  kps[cap] / desc[cap*32] / *n_out as orbx_extract; xy_un[cap][2]
+ * (optional, may be NULL) = mvKeysUn positions, u_right[cap] = mvuRight, depth_out[cap] = mvDepth.  The depth is uploaded with the image
+ * and everything comes back in one group of copies behind one synchronisation.  ORBX_E_INVALID: NULL / inconsistent arguments, unknown
+ * depth_type, ndist not 4 or 5, bad depth_stride; ORBX_E_CAPACITY: cap < orbx_max_keypoints. */
+int orbx_extract_rgbd(orbx_extractor *e, const uint8_t *img, int w, int h, size_t stride, int channels, int rgb_order,
+                      const void *depth, size_t depth_stride, const orbx_rgbd_params *p,
+                      orbx_keypoint *kps, uint8_t *desc, int cap, int *n_out,
+                      float *xy_un, float *u_right, float *depth_out);
+/* Pipelined form (the frame loop of Examples/RGB-D/rgbd_tum.cc:77-119): the third mode of the pipelined forms below.  RGB-D tickets share
+ * the handle's slots and submission order with mono and stereo tickets; a ticket must be waited for through the form it was submitted
+ * with.  The depth travels with the frame: gathered by the depth kernel straight from pinned host memory (default: only the values at the
+ * keypoints cross PCIe) or, with ORBX_PIPE_RGBD_GATHER=0 in the environment when the handle is created, uploaded whole into the slot.  img and
+ * depth lying in orbx_pinned_alloc memory with stride == row bytes are read in place (untouched until _wait returns); other input is
+ * staged inside _submit.  The first RGB-D submit of a size makes and touches what the RGB-D mode adds to every slot and lane.  e must have
+ * been created with max_batch >= 2 (as the other pipelined forms). */
+int orbx_extract_rgbd_submit(orbx_extractor *e, const uint8_t *img, int w, int h, size_t stride, int channels, int rgb_order,
+                             const void *depth, size_t depth_stride, const orbx_rgbd_params *p, int *ticket);
+int orbx_extract_rgbd_wait(orbx_extractor *e, int ticket, orbx_keypoint *kps, uint8_t *desc, int cap, int *n_out,
+                           float *xy_un, float *u_right, float *depth_out);
+/* Batched, device-resident (after orbx_extract_batch_device): image b has keypoints d_kps + b*cap (orbx_keypoint records), count d_n[b]
+ * (int32, read on the device) and depth d_depth + b*depth_img_stride with row pitch depth_pitch bytes (w x h elements of p->depth_type).
+ * Outputs are [batch*cap] rows in the layout of orbx_stereo_match_batch_device: d_u_right / d_depth_out floats, d_xy_un (may be NULL)
+ * float pairs; a row goes straight into orbx_frame_create_from_extraction(..., d_u_right = row, K, dist_coef, ...).  Entries at or beyond
+ * an image's count are left untouched.  Asynchronous on `stream` (a hipStream_t; NULL = the null stream). */
+int orbx_rgbd_depth_batch_device(int device, const void *d_kps, const void *d_n, int cap, int batch,
+                                 const void *d_depth, size_t depth_img_stride, size_t depth_pitch, int w, int h,
+                                 const orbx_rgbd_params *p, void *d_xy_un, void *d_u_right, void *d_depth_out, void *stream);
+
 /* ---- stereo rectification (second half) ----------------------------------
  * cv::remap(imLeft, imLeftRect, M1l, M2l, cv::INTER_LINEAR) of Examples/Stereo/stereo_euroc.cc:136-137 (8-bit grey,
  * BORDER_CONSTANT 0).  map_x / map_y = the CV_32FC1 pair cv::initUndistortRectifyMap returns (:103-104), dst_h x dst_w

@@ -263,3 +263,18 @@ __device__ __forceinline__ float2 dev_undistort(float2 s, const UndistortParams 
     o.y = (float)(p.fy * y + p.cy);
     return o;
 }
+
+// ---- Frame::ComputeStereoFromRGBD (src/Frame.cc:754-774) after Tracking::GrabImageRGBD's depth conversion (src/Tracking.cc:232-233): k_rgbd_depth
+// (orbx_frame.hip) behind orbx_extract_rgbd, the pipelined RGB-D form (orbx_extract.hip) and orbx_rgbd_depth_batch_device.
+struct RgbdArgs {
+    UndistortParams up; int undistort;   // undistort: dist_coef[0] != 0 (src/Frame.cc:472-476)
+    int depth_type, apply_scale; float scale, bf;
+    int w, h; long long depth_img_stride, depth_pitch;   // bytes
+    const uint8_t *depth;                // device (or mapped pinned host) address of image 0
+    const orbx_keypoint *kps; const int *n; int cap;      // [batch][cap] keypoints, [batch] counts
+    float2 *xy_un; float *u_right, *z;   // [batch][cap]; xy_un may be null
+};
+// argument checks shared by the three entry points (ORBX_OK or ORBX_E_INVALID with the message set); fills everything but the pointers
+int orbx_rgbd_args(const char *fn, const orbx_rgbd_params *p, int w, int h, size_t depth_pitch, RgbdArgs *a);
+// enqueue k_rgbd_depth for `batch` images on stream s (no host synchronisation)
+int orbx_rgbd_launch(const RgbdArgs &a, int batch, hipStream_t s);

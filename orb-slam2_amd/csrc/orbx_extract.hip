@@ -2680,6 +2680,10 @@ extern "C" int orbx_extractor_create(orbx_extractor **out, int nfeatures, float 
         e->pipe_inline = !(pi && *pi == '0');
         const char *pk = getenv("ORBX_PIPE_KCOPY");
         e->pipe_kcopy = !(pk && *pk == '0');
+        // RGB-D depth transport of the pipelined form: gather by default (one stream, 4 in flight: 28.9 k frames/s against 20.4 k with the
+        // upload, profiles/r05_rgbd.txt); ORBX_PIPE_RGBD_GATHER=0 uploads the whole depth map into the slot
+        const char *pg = getenv("ORBX_PIPE_RGBD_GATHER");
+        e->pipe_rgbd_gather = !(pg && *pg == '0');
         const char *fw = getenv("ORBX_FAST_WAVES");      // tests / experiments: force k_fast's waves per cell
         e->fast_waves = fw && *fw >= '1' && *fw <= '4' ? *fw - '0' : 0;
         // ORBX_FAST_PAIR=1: the pair kernel (k_fast2) where the geometry allows.  Off by default: bit-exact, 4 % fewer VALU instructions per cell and
@@ -3215,6 +3219,69 @@ extern "C" int orbx_extract_stereo(orbx_extractor *e, const uint8_t *img_left, c
     return ORBX_OK;
 }
 
+// One RGB-D frame through host pointers in one call: Tracking::GrabImageRGBD's cvtColor and depth convertTo (src/Tracking.cc:217-233) and
+// the RGB-D constructor's ExtractORB / UndistortKeyPoints / ComputeStereoFromRGBD (src/Frame.cc:145-154).  The depth is uploaded right
+// behind the image, k_rgbd_depth runs on the still device-resident keypoints, and everything comes back behind ONE synchronisation.
+extern "C" int orbx_extract_rgbd(orbx_extractor *e, const uint8_t *img, int w, int h, size_t stride, int channels, int rgb_order,
+                                 const void *depth, size_t depth_stride, const orbx_rgbd_params *p,
+                                 orbx_keypoint *kps, uint8_t *desc, int cap, int *n_out, float *xy_un, float *u_right, float *depth_out)
+{
+    if (!e || !img || !depth || !kps || !desc || !n_out || !u_right || !depth_out || w < 1 || h < 1 ||
+        (channels != 1 && channels != 3 && channels != 4) || stride < (size_t)w * channels) {
+        orbx_set_error("orbx_extract_rgbd: invalid argument");
+        return ORBX_E_INVALID;
+    }
+    RgbdArgs a;
+    int rc = orbx_rgbd_args("orbx_extract_rgbd", p, w, h, depth_stride, &a);
+    if (rc) return rc;
+    ORBX_HIP(orbx_use_device(e->device));
+    if ((rc = orbx_prepare_geometry(e, w, h))) return rc;
+    const int need = e->geom.kp_total;
+    if (cap < need) { orbx_set_error("keypoint capacity %d < orbx_max_keypoints() = %d", cap, need); return ORBX_E_CAPACITY; }
+    const size_t pitch = align_up(w, 64), img_bytes = pitch * h;
+    const size_t cpitch = align_up((size_t)w * channels, 64), cbytes = cpitch * h;            // channels 1: cbytes == img_bytes
+    const size_t drow = (size_t)w * (p->depth_type == ORBX_DEPTH_U16 ? 2 : 4), dpitch = align_up(drow, 64), dbytes = dpitch * h;
+    if ((rc = ensure(&e->d_stage_in, &e->stage_in_cap, img_bytes * e->max_batch))) return rc;
+    const size_t stage = cbytes + dbytes > img_bytes * e->max_batch ? cbytes + dbytes : img_bytes * e->max_batch;
+    if ((rc = ensure_pinned(&e->h_stage_in, &e->h_stage_in_cap, stage))) return rc;
+    void *d_color = nullptr, *d_depth, *d_xy;
+    if (channels > 1 && (rc = orbx_scratch(e, 6, cbytes, &d_color))) return rc;
+    if ((rc = orbx_scratch(e, 8, dbytes, &d_depth)) || (rc = orbx_scratch(e, 9, 8 * (size_t)need, &d_xy))) return rc;
+    if ((rc = orbx_ensure_out_staging(e, e->max_batch, need))) return rc;
+    const size_t o_kps = 64, o_desc = o_kps + align_up(sizeof(orbx_keypoint) * (size_t)need, 64), o_ur = o_desc + align_up((size_t)32 * need, 64),
+                 o_z = o_ur + align_up(4 * (size_t)need, 64), o_xy = o_z + align_up(4 * (size_t)need, 64), out_bytes = o_xy + 8 * (size_t)need;
+    if ((rc = ensure_pinned(&e->h_out, &e->h_out_cap, out_bytes))) return rc;
+    for (int y = 0; y < h; y++) memcpy(e->h_stage_in + (size_t)y * cpitch, img + (size_t)y * stride, (size_t)w * channels);
+    const uint8_t *dsrc = (const uint8_t *)depth;
+    for (int y = 0; y < h; y++) memcpy(e->h_stage_in + cbytes + (size_t)y * dpitch, dsrc + (size_t)y * depth_stride, drow);
+    ORBX_HIP(hipMemcpyAsync(channels > 1 ? d_color : (void *)e->d_stage_in, e->h_stage_in, cbytes, hipMemcpyHostToDevice, e->stream));
+    ORBX_HIP(hipMemcpyAsync(d_depth, e->h_stage_in + cbytes, dbytes, hipMemcpyHostToDevice, e->stream));
+    if (channels > 1)
+        hipLaunchKernelGGL(k_gray, dim3((unsigned)((pitch / 4 + 63) / 64), (h + 3) / 4), dim3(256), 0, e->stream, (const uint8_t *)d_color, w, h, (int)cpitch,
+                           channels, rgb_order, e->d_stage_in, (int)pitch);
+    e->prof_chain = false;
+    if ((rc = orbx_extract_batch_device(e, e->d_stage_in, img_bytes, pitch, 1, w, h, e->d_out_kps, e->d_out_desc, need, e->d_out_n, nullptr))) return rc;
+    a.depth = (const uint8_t *)d_depth; a.depth_img_stride = (long long)dbytes; a.depth_pitch = (long long)dpitch;
+    a.kps = (const orbx_keypoint *)e->d_out_kps; a.n = (const int *)e->d_out_n; a.cap = need;
+    a.xy_un = (float2 *)d_xy; a.u_right = e->d_out_ur; a.z = e->d_out_depth;
+    if ((rc = orbx_rgbd_launch(a, 1, e->stream))) return rc;
+    ORBX_HIP(hipMemcpyAsync(e->h_out, e->d_out_n, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+    ORBX_HIP(hipMemcpyAsync(e->h_out + o_kps, e->d_out_kps, sizeof(orbx_keypoint) * (size_t)need, hipMemcpyDeviceToHost, e->stream));
+    ORBX_HIP(hipMemcpyAsync(e->h_out + o_desc, e->d_out_desc, (size_t)32 * need, hipMemcpyDeviceToHost, e->stream));
+    ORBX_HIP(hipMemcpyAsync(e->h_out + o_ur, e->d_out_ur, 4 * (size_t)need, hipMemcpyDeviceToHost, e->stream));
+    ORBX_HIP(hipMemcpyAsync(e->h_out + o_z, e->d_out_depth, 4 * (size_t)need, hipMemcpyDeviceToHost, e->stream));
+    if (xy_un) ORBX_HIP(hipMemcpyAsync(e->h_out + o_xy, d_xy, 8 * (size_t)need, hipMemcpyDeviceToHost, e->stream));
+    if ((rc = orbx_sync(e, nullptr))) return rc;
+    const int n = *reinterpret_cast<const int *>(e->h_out);
+    *n_out = n;
+    memcpy(kps, e->h_out + o_kps, sizeof(orbx_keypoint) * (size_t)n);
+    memcpy(desc, e->h_out + o_desc, (size_t)32 * n);
+    memcpy(u_right, e->h_out + o_ur, 4 * (size_t)n);
+    memcpy(depth_out, e->h_out + o_z, 4 * (size_t)n);
+    if (xy_un) memcpy(xy_un, e->h_out + o_xy, 8 * (size_t)n);
+    return ORBX_OK;
+}
+
 // ---- pipelined host-pointer stereo frames (a camera stream fed from host memory)
 
 extern "C" int orbx_pipeline_depth(void) { return ORBX_PIPE_DEPTH; }
@@ -3312,8 +3379,17 @@ extern "C" void orbx_debug_pipe_prof_print()
     for (int i = 0; i < 8; i++) fprintf(stderr, "pipe prof: %-28s %7.2f us per frame\n", nm[i], g_pp[i].load() * 1e-3 / frames);
 }
 
+// RGB-D slots keep the undistorted positions in the unused second-eye keypoint rows of the result block (64 + 28*need .. 64 + 56*need)
+static size_t pipe_rgbd_xy_off(int need) { return 64 + align_up(sizeof(orbx_keypoint) * (size_t)need, 64); }
+
+// the RGB-D part of a pipelined frame (eyes == ORBX_PIPE_RGBD): img_left is the grey or colour image, `depth` its depth map
+struct RgbdIn { const void *depth; size_t depth_stride; int channels, rgb_order; RgbdArgs a; };
+// an RGB-D slot's input block: level 0 (grey) | the colour image (up to 4 channels) | the depth map (up to 4 bytes a pixel), each row-aligned;
+// sized for the largest form whatever the frame, so that one warm-up frame per slot makes every later RGB-D frame of the size allocation-free
+static size_t rgbd_in_bytes(int w, int h) { return (align_up(w, 64) + 2 * align_up((size_t)w * 4, 64)) * (size_t)h; }
+
 static int pipe_submit(orbx_extractor *e, const uint8_t *img_left, const uint8_t *img_right, int eyes, int w, int h, size_t stride,
-                       float bf, float min_z, int *ticket)
+                       float bf, float min_z, int *ticket, const RgbdIn *rg = nullptr)
 {
     if (g_pp_on) g_pp_n.fetch_add(1, std::memory_order_relaxed);
     PpScope pp(0);
@@ -3343,14 +3419,22 @@ static int pipe_submit(orbx_extractor *e, const uint8_t *img_left, const uint8_t
     PipeSlot &s = e->pipe[e->pipe_next % ORBX_PIPE_DEPTH];
     if (s.busy) { orbx_set_error("all %d pipeline slots are in flight: wait for the oldest ticket first", ORBX_PIPE_DEPTH); return ORBX_E_INVALID; }
     const int need = x->geom.kp_total;
+    const int nimg = eyes == 2 ? 2 : 1;                 // images extracted per frame
+    if (rg && pipe_rgbd_xy_off(need) + 8 * (size_t)need > 64 + align_up(sizeof(orbx_keypoint) * 2 * (size_t)need, 64)) {
+        orbx_set_error("keypoint capacity %d too small for the RGB-D result block", need);
+        return ORBX_E_INVALID;
+    }
     const uint8_t *pin[2] = { stride == (size_t)w ? pinned_device_ptr(img_left) : nullptr, stride == (size_t)w && eyes == 2 ? pinned_device_ptr(img_right) : nullptr };
     const bool in_place = pin[0] && (eyes == 1 || pin[1]);
-    const size_t pitch = in_place ? (size_t)w : align_up(w, 64), img_bytes = pitch * h;
+    size_t pitch = in_place ? (size_t)w : align_up(w, 64), img_bytes = pitch * h;
     if (!e->copy_in) {
         ORBX_HIP(hipStreamCreateWithFlags(&e->copy_in, hipStreamNonBlocking));
         ORBX_HIP(hipStreamCreateWithFlags(&e->copy_out, hipStreamNonBlocking));
     }
-    if ((rc = pipe_slot_prepare(e, s, 2 * align_up(w, 64) * (size_t)h, need))) return rc;
+    {
+        const size_t in_bytes = 2 * align_up(w, 64) * (size_t)h, in_rgbd = rg ? rgbd_in_bytes(w, h) : 0;
+        if ((rc = pipe_slot_prepare(e, s, in_rgbd > in_bytes ? in_rgbd : in_bytes, need))) return rc;
+    }
     // upload: the slot's device input was last read by the kernels of the frame that used it ORBX_PIPE_DEPTH submissions ago,
     // which its _wait has already seen finish (ev_d2h follows ev_done), so the copy stream may overwrite it right away
     const uint8_t *eye_ptr[2] = { img_left, img_right };
@@ -3358,7 +3442,44 @@ static int pipe_submit(orbx_extractor *e, const uint8_t *img_left, const uint8_t
     // (inline form: upload, kernels and download of a frame all on its lane's stream -- no events, no stream hops; the lanes overlap each other)
     hipStream_t s_in = e->pipe_inline ? x->stream : e->copy_in, s_out = e->pipe_inline ? x->stream : e->copy_out;
     const bool kcopy = e->pipe_inline && e->pipe_kcopy;
-    if (in_place && kcopy) {
+    // host -> slot: pinned source (device-visible address `pin`, or nullptr) or staged through the slot's pinned h_in at offset `off`
+    auto upload = [&](const uint8_t *src, const uint8_t *pin_src, size_t spitch, size_t row, int rows, size_t dpitch, size_t off) -> int {
+        const size_t bytes = dpitch * rows;
+        if (!pin_src) {
+            uint8_t *dst = s.h_in + off;
+            if (spitch == dpitch) memcpy(dst, src, dpitch * (rows - 1) + row);   // (the source's last row may end at its row bytes)
+            else for (int y = 0; y < rows; y++) memcpy(dst + (size_t)y * dpitch, src + (size_t)y * spitch, row);
+        }
+        if (kcopy) hipLaunchKernelGGL(k_copy_bytes, dim3(128, 1), dim3(256), 0, x->stream, pin_src ? pin_src : (const uint8_t *)s.h_in_dev + off, (const uint8_t *)nullptr,
+                                      s.d_in + off, (uint8_t *)nullptr, (unsigned long long)bytes);
+        else ORBX_HIP(hipMemcpyAsync(s.d_in + off, pin_src ? src : s.h_in + off, bytes, hipMemcpyHostToDevice, s_in));
+        return ORBX_OK;
+    };
+    const uint8_t *rg_depth = nullptr;                  // RGB-D: where k_rgbd_depth reads the depth map (slot or mapped host memory)
+    size_t rg_dpitch = 0, rg_cpitch = 0, off_col = align_up(w, 64) * (size_t)h;
+    if (rg) {
+        // level 0 at s.d_in (pitch align_up(w, 64) after k_gray, or the grey image itself), the colour image behind it, the depth map last
+        const size_t row = (size_t)w * rg->channels, off_dep = off_col + align_up((size_t)w * 4, 64) * (size_t)h;
+        const uint8_t *ipin = stride == row ? pinned_device_ptr(img_left) : nullptr;
+        const size_t ipitch = ipin ? row : align_up(row, 64);
+        if (rg->channels == 1) { pitch = ipitch; img_bytes = pitch * h; }
+        else { pitch = align_up(w, 64); img_bytes = pitch * h; rg_cpitch = ipitch; }
+        if ((rc = upload(img_left, ipin, stride, row, h, ipitch, rg->channels == 1 ? 0 : off_col))) return rc;
+        const size_t drow = (size_t)w * (rg->a.depth_type == ORBX_DEPTH_U16 ? 2 : 4);
+        const uint8_t *dpin = rg->depth_stride == drow ? pinned_device_ptr(rg->depth) : nullptr;
+        rg_dpitch = drow;
+        if (e->pipe_rgbd_gather) {                      // the depth stays in host memory: only the values at the keypoints cross PCIe
+            if (!dpin) {
+                const uint8_t *src = (const uint8_t *)rg->depth;
+                if (rg->depth_stride == drow) memcpy(s.h_in + off_dep, src, drow * h);
+                else for (int y = 0; y < h; y++) memcpy(s.h_in + off_dep + (size_t)y * drow, src + (size_t)y * rg->depth_stride, drow);
+            }
+            rg_depth = dpin ? dpin : s.h_in_dev + off_dep;
+        } else {
+            if ((rc = upload((const uint8_t *)rg->depth, dpin, rg->depth_stride, drow, h, drow, off_dep))) return rc;
+            rg_depth = s.d_in + off_dep;
+        }
+    } else if (in_place && kcopy) {
         hipLaunchKernelGGL(k_copy_bytes, dim3(128, eyes), dim3(256), 0, x->stream, pin[0], pin[1], s.d_in, s.d_in + img_bytes, (unsigned long long)img_bytes);
     } else if (in_place) {
         for (int i = 0; i < eyes; i++) ORBX_HIP(hipMemcpyAsync(s.d_in + img_bytes * i, eye_ptr[i], img_bytes, hipMemcpyHostToDevice, s_in));
@@ -3376,6 +3497,9 @@ static int pipe_submit(orbx_extractor *e, const uint8_t *img_left, const uint8_t
         ORBX_HIP(hipEventRecord(s.ev_h2d, e->copy_in));
         ORBX_HIP(hipStreamWaitEvent(x->stream, s.ev_h2d, 0));
     }
+    if (rg && rg->channels > 1)     // cvtColor (src/Tracking.cc:217-231) from the slot's colour image into its level 0
+        hipLaunchKernelGGL(k_gray, dim3((unsigned)((pitch / 4 + 63) / 64), (h + 3) / 4), dim3(256), 0, x->stream, (const uint8_t *)s.d_in + off_col, w, h,
+                           (int)rg_cpitch, rg->channels, rg->rgb_order, s.d_in, (int)pitch);
     x->prof_chain = false;
     orbx_keypoint *dk = (orbx_keypoint *)s.d_kps;
     uint8_t *dd = (uint8_t *)s.d_desc;
@@ -3384,10 +3508,17 @@ static int pipe_submit(orbx_extractor *e, const uint8_t *img_left, const uint8_t
     // (a node-table overflow is a configuration error, not a per-frame event): pipe_wait clears it when it reports it
     x->flag_out = dn + 2;
     PP_NEXT(3);
-    rc = orbx_extract_batch_device(x, s.d_in, img_bytes, pitch, eyes, w, h, s.d_kps, s.d_desc, need, s.d_n, nullptr);
+    rc = orbx_extract_batch_device(x, s.d_in, img_bytes, pitch, nimg, w, h, s.d_kps, s.d_desc, need, s.d_n, nullptr);
     x->flag_out = nullptr;
     if (rc) return rc;
     PP_NEXT(4);
+    if (rg) {   // UndistortKeyPoints + ComputeStereoFromRGBD (src/Frame.cc:152-154); the undistorted positions take the unused second-eye keypoint rows
+        RgbdArgs a = rg->a;
+        a.depth = rg_depth; a.depth_img_stride = 0; a.depth_pitch = (long long)rg_dpitch;
+        a.kps = dk; a.n = dn; a.cap = need;
+        a.xy_un = reinterpret_cast<float2 *>(s.d_out + pipe_rgbd_xy_off(need)); a.u_right = s.d_ur; a.z = s.d_z;
+        if ((rc = orbx_rgbd_launch(a, 1, x->stream))) return rc;
+    }
     if (eyes == 2) {
         rc = orbx_stereo_match_batch_device(x, 0, x, 1, 1, dk, dd, dn, dk + need, dd + (size_t)32 * need, dn + 1, need, bf, min_z, s.d_ur, s.d_z,
                                             orbx_stereo_row_table_available(x, dk + need, 1, 1, need) ? ORBX_ROWTAB_OF_EXTRACTION : ORBX_ROWTAB_FROM_KEYPOINTS, nullptr);
@@ -3402,7 +3533,7 @@ static int pipe_submit(orbx_extractor *e, const uint8_t *img_left, const uint8_t
         ORBX_HIP(hipStreamWaitEvent(e->copy_out, s.ev_done, 0));
     }
     {
-        const size_t out_bytes = eyes == 2 ? o_z + 4 * (size_t)need : o_desc + (size_t)32 * eyes * need;
+        const size_t out_bytes = eyes != 1 ? o_z + 4 * (size_t)need : o_desc + (size_t)32 * need;
         if (kcopy) hipLaunchKernelGGL(k_copy_bytes, dim3(64, 1), dim3(256), 0, x->stream, (const uint8_t *)s.d_out, (const uint8_t *)nullptr, s.h_out_dev, (uint8_t *)nullptr,
                                       (unsigned long long)out_bytes);
         else ORBX_HIP(hipMemcpyAsync(s.h_out, s.d_out, out_bytes, hipMemcpyDeviceToHost, s_out));
@@ -3417,7 +3548,8 @@ static int pipe_submit(orbx_extractor *e, const uint8_t *img_left, const uint8_t
 #undef PP_NEXT
 }
 
-static int pipe_wait(orbx_extractor *e, int ticket, int eyes, orbx_keypoint *kps, uint8_t *desc, int cap, int *n_out, float *u_right, float *depth)
+static int pipe_wait(orbx_extractor *e, int ticket, int eyes, orbx_keypoint *kps, uint8_t *desc, int cap, int *n_out, float *u_right, float *depth,
+                     float *xy_un = nullptr)
 {
     PipeSlot &s = e->pipe[ticket % ORBX_PIPE_DEPTH];
     if (!s.busy || s.ticket != ticket || s.eyes != eyes) { orbx_set_error("ticket %d is not in flight (or was submitted through the other form)", ticket); return ORBX_E_INVALID; }
@@ -3436,15 +3568,16 @@ static int pipe_wait(orbx_extractor *e, int ticket, int eyes, orbx_keypoint *kps
         orbx_set_error("quadtree kernel reported a node-table overflow");
         return ORBX_E_CAPACITY;
     }
-    for (int i = 0; i < eyes; i++) {
+    for (int i = 0; i < (eyes == 2 ? 2 : 1); i++) {
         n_out[i] = hn[i];
         memcpy(kps + (size_t)i * cap, s.h_out + o_kps + sizeof(orbx_keypoint) * (size_t)need * i, sizeof(orbx_keypoint) * (size_t)hn[i]);
         memcpy(desc + (size_t)i * cap * 32, s.h_out + o_desc + (size_t)32 * need * i, (size_t)32 * hn[i]);
     }
-    if (eyes == 2) {
+    if (eyes != 1) {
         memcpy(u_right, s.h_out + o_ur, 4 * (size_t)hn[0]);
         memcpy(depth, s.h_out + o_z, 4 * (size_t)hn[0]);
     }
+    if (eyes == ORBX_PIPE_RGBD && xy_un) memcpy(xy_un, s.h_out + pipe_rgbd_xy_off(need), 8 * (size_t)hn[0]);
     return ORBX_OK;
 }
 
@@ -3506,6 +3639,53 @@ extern "C" int orbx_extract_stereo_wait(orbx_extractor *e, int ticket, orbx_keyp
 {
     if (!e || !kps || !desc || !n_out || !u_right || !depth || ticket < 0) { orbx_set_error("orbx_extract_stereo_wait: invalid argument"); return ORBX_E_INVALID; }
     return pipe_wait(e, ticket, 2, kps, desc, cap, n_out, u_right, depth);
+}
+
+extern "C" int orbx_extract_rgbd_submit(orbx_extractor *e, const uint8_t *img, int w, int h, size_t stride, int channels, int rgb_order,
+                                        const void *depth, size_t depth_stride, const orbx_rgbd_params *p, int *ticket)
+{
+    if (!e || !img || !depth || !ticket || w < 1 || h < 1 || (channels != 1 && channels != 3 && channels != 4) || stride < (size_t)w * channels) {
+        orbx_set_error("orbx_extract_rgbd_submit: invalid argument");
+        return ORBX_E_INVALID;
+    }
+    RgbdIn rg;
+    int rc = orbx_rgbd_args("orbx_extract_rgbd_submit", p, w, h, depth_stride, &rg.a);
+    if (rc) return rc;
+    if (e->max_batch < 2) { orbx_set_error("orbx_extract_rgbd_submit needs an extractor created with max_batch >= 2"); return ORBX_E_INVALID; }
+    rg.depth = depth; rg.depth_stride = depth_stride; rg.channels = channels; rg.rgb_order = rgb_order;
+    if (e->pipe_rgbd_warm_w != w || e->pipe_rgbd_warm_h != h) {
+        bool idle = true;
+        for (const PipeSlot &s : e->pipe) idle = idle && !s.busy;
+        if (idle) {
+            // first RGB-D frame of this size: every lane and slot as orbx_pipeline_warm makes them, then one RGB-D frame through each slot
+            // (the larger input block, k_gray and k_rgbd_depth on every lane) -- colour + float depth, the largest input form
+            if ((rc = orbx_pipeline_warm(e, w, h))) return rc;
+            e->pipe_rgbd_warm_w = w; e->pipe_rgbd_warm_h = h;
+            std::vector<uint8_t> img4((size_t)w * h * 4);
+            for (size_t i = 0; i < img4.size(); i++) img4[i] = (uint8_t)((((i / 4 % w) >> 4) * 37 + ((i / 4 / w) >> 4) * 91 + (i & 3) * 17) & 127) + 40;
+            std::vector<float> dep((size_t)w * h, 1.0f);
+            RgbdIn wr = rg;
+            wr.depth = dep.data(); wr.depth_stride = (size_t)w * 4; wr.channels = 4; wr.rgb_order = 1; wr.a.depth_type = ORBX_DEPTH_F32;
+            const int need = orbx_max_keypoints(e, w, h);
+            if (need < 0) return need;
+            std::vector<orbx_keypoint> kps(need); std::vector<uint8_t> desc((size_t)32 * need); std::vector<float> ur(need), z(need), xy(2 * (size_t)need);
+            int tickets[ORBX_PIPE_DEPTH], n = 0, nsub = 0;
+            for (int i = 0; i < ORBX_PIPE_DEPTH && !rc; i++) { rc = pipe_submit(e, img4.data(), nullptr, ORBX_PIPE_RGBD, w, h, (size_t)w * 4, 0.f, 1.f, &tickets[i], &wr); if (!rc) nsub++; }
+            for (int i = 0; i < nsub; i++) {
+                const int wrc = pipe_wait(e, tickets[i], ORBX_PIPE_RGBD, kps.data(), desc.data(), need, &n, ur.data(), z.data(), xy.data());
+                if (wrc && !rc) rc = wrc;
+            }
+            if (rc) { e->pipe_rgbd_warm_w = 0; e->pipe_rgbd_warm_h = 0; return rc; }
+        }
+    }
+    return pipe_submit(e, img, nullptr, ORBX_PIPE_RGBD, w, h, stride, 0.f, 1.f, ticket, &rg);
+}
+
+extern "C" int orbx_extract_rgbd_wait(orbx_extractor *e, int ticket, orbx_keypoint *kps, uint8_t *desc, int cap, int *n_out,
+                                      float *xy_un, float *u_right, float *depth_out)
+{
+    if (!e || !kps || !desc || !n_out || !u_right || !depth_out || ticket < 0) { orbx_set_error("orbx_extract_rgbd_wait: invalid argument"); return ORBX_E_INVALID; }
+    return pipe_wait(e, ticket, ORBX_PIPE_RGBD, kps, desc, cap, n_out, u_right, depth_out, xy_un);
 }
 
 extern "C" int orbx_extract_submit(orbx_extractor *e, const uint8_t *img, int w, int h, size_t stride, int *ticket)

@@ -60,3 +60,92 @@ extern "C" int orbx_undistort_keypoints(int device, const float *xy, int n, floa
     memcpy(xy_out, c->h, sizeof(float2) * (size_t)n);
     return ORBX_OK;
 }
+
+// ---- Frame::ComputeStereoFromRGBD (src/Frame.cc:754-774) with UndistortKeyPoints (:152) and Tracking::GrabImageRGBD's depth conversion
+// (src/Tracking.cc:232-233) folded in.  One thread per keypoint, a (ceil(cap/256), batch) grid; the count is read on the device, so a launch
+// needs no host synchronisation.  A latency-bound gather: one 28-byte record read, the fp64 undistortion of k_undistort (dev_undistort, same
+// bits), one 2- or 4-byte depth read, three stores.  -ffp-contract=off and the default correctly rounded fp32 division keep the reference's
+// rounding: d = raw * scale is one fp32 multiply, u_right = kpU.x - bf / d one division and one subtraction.
+__global__ __launch_bounds__(256) void k_rgbd_depth(const RgbdArgs a)
+{
+    const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.cap || i >= a.n[b]) return;
+    const long long k = (long long)b * a.cap + i;
+    const orbx_keypoint *kp = a.kps + k;
+    const float2 pos = make_float2(kp->x, kp->y);
+    const float2 un = a.undistort ? dev_undistort(pos, a.up) : pos;
+    if (a.xy_un) a.xy_un[k] = un;
+    float ur = -1.f, z = -1.f;
+    // imDepth.at<float>(v, u) with u = (int)kp.x, v = (int)kp.y (truncation).  A position whose truncation falls outside the image (NaN
+    // included) reads nothing and gets -1 / -1: the defined deviation for caller-supplied keypoints (the reference reads out of bounds)
+    if (pos.x > -1.f && pos.x < (float)a.w && pos.y > -1.f && pos.y < (float)a.h) {
+        const int u = (int)pos.x, v = (int)pos.y;
+        const uint8_t *row = a.depth + (long long)b * a.depth_img_stride + (long long)v * a.depth_pitch;
+        float d;
+        if (a.depth_type == ORBX_DEPTH_U16) d = (float)reinterpret_cast<const uint16_t *>(row)[u] * a.scale;   // convertTo(CV_32F, scale): always
+        else {
+            d = reinterpret_cast<const float *>(row)[u];
+            if (a.apply_scale) d = d * a.scale;       // only when fabs(mDepthMapFactor - 1.0f) > 1e-5 (src/Tracking.cc:232)
+        }
+        if (d > 0) { z = d; ur = un.x - a.bf / d; }
+    }
+    a.u_right[k] = ur;
+    a.z[k] = z;
+}
+
+int orbx_rgbd_args(const char *fn, const orbx_rgbd_params *p, int w, int h, size_t depth_pitch, RgbdArgs *a)
+{
+    if (!p || (p->depth_type != ORBX_DEPTH_U16 && p->depth_type != ORBX_DEPTH_F32) || (p->ndist != 4 && p->ndist != 5) || w < 1 || h < 1) {
+        orbx_set_error("%s: invalid argument (params, depth_type, ndist 4 or 5, image size)", fn);
+        return ORBX_E_INVALID;
+    }
+    const size_t es = p->depth_type == ORBX_DEPTH_U16 ? 2 : 4;
+    if (depth_pitch < (size_t)w * es || depth_pitch % es) {
+        orbx_set_error("%s: depth row stride %zu is below a row (%zu bytes) or not a multiple of the element size", fn, depth_pitch, (size_t)w * es);
+        return ORBX_E_INVALID;
+    }
+    memset(a, 0, sizeof(*a));
+    a->undistort = p->dist_coef[0] != 0.0f;
+    if (a->undistort) {
+        if (p->fx == 0.f || p->fy == 0.f) { orbx_set_error("%s: fx / fy is 0", fn); return ORBX_E_INVALID; }
+        a->up = orbx_undistort_params(p->fx, p->fy, p->cx, p->cy, p->dist_coef, p->ndist);
+    }
+    a->depth_type = p->depth_type;
+    a->scale = p->depth_scale;
+    // src/Tracking.cc:232: (fabs(mDepthMapFactor - 1.0f) > 1e-5) || imDepth.type() != CV_32F -- the difference in float, the compare in double
+    a->apply_scale = p->depth_type == ORBX_DEPTH_U16 || (double)fabsf(p->depth_scale - 1.0f) > 1e-5;
+    a->bf = p->bf;
+    a->w = w; a->h = h; a->depth_pitch = (long long)depth_pitch;
+    return ORBX_OK;
+}
+
+int orbx_rgbd_launch(const RgbdArgs &a, int batch, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_rgbd_depth, dim3((unsigned)((a.cap + 255) / 256), (unsigned)batch), dim3(256), 0, s, a);
+    ORBX_HIP(hipGetLastError());
+    return ORBX_OK;
+}
+
+extern "C" int orbx_rgbd_depth_batch_device(int device, const void *d_kps, const void *d_n, int cap, int batch,
+                                            const void *d_depth, size_t depth_img_stride, size_t depth_pitch, int w, int h,
+                                            const orbx_rgbd_params *p, void *d_xy_un, void *d_u_right, void *d_depth_out, void *stream)
+{
+    if (!d_kps || !d_n || !d_depth || !d_u_right || !d_depth_out || cap < 1 || batch < 1 || batch > 65535 ||
+        (batch > 1 && depth_img_stride < depth_pitch * (size_t)h)) {
+        orbx_set_error("orbx_rgbd_depth_batch_device: invalid argument");
+        return ORBX_E_INVALID;
+    }
+    RgbdArgs a;
+    int rc = orbx_rgbd_args("orbx_rgbd_depth_batch_device", p, w, h, depth_pitch, &a);
+    if (rc) return rc;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
+        orbx_set_error("no usable HIP device %d (liborbx has no CPU fallback)", device);
+        return ORBX_E_NO_DEVICE;
+    }
+    ORBX_HIP(orbx_use_device(device));
+    a.depth = (const uint8_t *)d_depth; a.depth_img_stride = (long long)depth_img_stride;
+    a.kps = (const orbx_keypoint *)d_kps; a.n = (const int *)d_n; a.cap = cap;
+    a.xy_un = (float2 *)d_xy_un; a.u_right = (float *)d_u_right; a.z = (float *)d_depth_out;
+    return orbx_rgbd_launch(a, batch, (hipStream_t)stream);
+}

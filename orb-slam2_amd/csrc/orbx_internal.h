@@ -83,10 +83,11 @@ struct PipeSlot {
     uint8_t *d_out;                          // one device block in the layout of h_out (a single download per frame)
     void *d_kps, *d_desc, *d_n; float *d_ur, *d_z; int out_cap;   // views into d_out
     hipEvent_t ev_h2d, ev_done, ev_d2h;      // input landed / kernels finished / results landed in h_out
-    int cap, ticket, eyes; bool busy;
+    int cap, ticket, eyes; bool busy;       // eyes: 1 mono, 2 stereo, ORBX_PIPE_RGBD (one image + its depth)
     struct orbx_extractor *lane;             // the kernel lane (the handle or its shadow) that ran the slot's frame
 };
 #define ORBX_PIPE_DEPTH 4
+#define ORBX_PIPE_RGBD 3                     // PipeSlot::eyes of an RGB-D frame
 
 struct orbx_extractor {
     int device;
@@ -129,10 +130,12 @@ struct orbx_extractor {
     // stereo scratch
     int *d_st_dist; size_t st_cap;         // SAD per left keypoint (or -1)
     void *d_st_entries; size_t st_ent_cap;  // row table entries of k_stereo_prep (one uint4 per right keypoint, see orbx_stereo.hip)
-    void *scratch[8]; size_t scratch_cap[8]; // host-API upload buffers
+    void *scratch[10]; size_t scratch_cap[10]; // host-API upload buffers (8, 9: orbx_extract_rgbd's depth image and undistorted positions)
     // pipelined stereo frames: copies ride their own streams so that frame i+1 uploads and frame i-1 downloads while frame i computes
     PipeSlot pipe[ORBX_PIPE_DEPTH]; hipStream_t copy_in, copy_out; unsigned pipe_next;
     int pipe_warm_w, pipe_warm_h;    // the image size every lane / slot of the pipelined forms has been run on once (orbx_pipeline_warm); 0 = none yet
+    int pipe_rgbd_warm_w, pipe_rgbd_warm_h;   // ... and through the RGB-D mode (its larger input block, k_gray, k_rgbd_depth); 0 = none yet
+    bool pipe_rgbd_gather;           // RGB-D depth transport: k_rgbd_depth reads the pinned host depth in place (default) or the slot's upload (ORBX_PIPE_RGBD_GATHER=0)
     bool pipe_counted;               // this handle is counted in the process-wide number of pipelined handles
     orbx_extractor *lanes[ORBX_PIPE_DEPTH - 1];   // further kernel lanes of the pipelined forms (shadow handles with their own stream and
                                      // workspaces): submission i runs on lane i % pipe_lanes, so the launch chains of neighbouring frames

@@ -31,6 +31,76 @@ class FrameFeats(C.Structure):
                 ("min_x", C.c_float), ("min_y", C.c_float), ("max_x", C.c_float), ("max_y", C.c_float)]
 
 
+DEPTH_U16, DEPTH_F32 = 0, 1   # ORBX_DEPTH_*: CV_16U (TUM PNG depth) / CV_32F
+
+
+class RGBDParamsStruct(C.Structure):
+    """orbx_rgbd_params (include/orbx.h)"""
+    _fields_ = [("depth_type", C.c_int), ("depth_scale", C.c_float), ("bf", C.c_float), ("fx", C.c_float), ("fy", C.c_float),
+                ("cx", C.c_float), ("cy", C.c_float), ("dist_coef", C.c_float * 5), ("ndist", C.c_int)]
+
+
+def depth_map_factor(DepthMapFactor):
+    """Tracking::mDepthMapFactor from the settings value (reference src/Tracking.cc:147-151), in float32 as the reference holds it:
+    1 when |DepthMapFactor| < 1e-5, else 1.0f / DepthMapFactor"""
+    f = np.float32(DepthMapFactor)
+    if abs(float(f)) < 1e-5:
+        return np.float32(1)
+    return np.float32(np.float32(1) / f)
+
+
+class RGBDParams:
+    """camera and depth settings of an RGB-D frame (Examples/RGB-D/TUM*.yaml: Camera.fx/fy/cx/cy, k1 k2 p1 p2 [k3], Camera.bf,
+    DepthMapFactor).  depth_scale defaults to depth_map_factor(DepthMapFactor); pass it to give Tracking::mDepthMapFactor directly."""
+
+    def __init__(self, fx, fy, cx, cy, dist_coef, bf, DepthMapFactor=None, depth_scale=None):
+        if (DepthMapFactor is None) == (depth_scale is None):
+            raise OrbxError(-1, "give exactly one of DepthMapFactor and depth_scale")
+        self.fx, self.fy, self.cx, self.cy = (np.float32(v) for v in (fx, fy, cx, cy))
+        self.dist_coef = np.ascontiguousarray(dist_coef, np.float32).reshape(-1)
+        self.bf = np.float32(bf)
+        self.depth_scale = depth_map_factor(DepthMapFactor) if depth_scale is None else np.float32(depth_scale)
+
+    @classmethod
+    def from_settings(cls, s):
+        """from a dict of the yaml keys (tests/golden/reference_settings_rgbd.json: one camera entry)"""
+        d = [s["Camera.k1"], s["Camera.k2"], s["Camera.p1"], s["Camera.p2"]] + ([s["Camera.k3"]] if "Camera.k3" in s else [])
+        return cls(s["Camera.fx"], s["Camera.fy"], s["Camera.cx"], s["Camera.cy"], d, s["Camera.bf"], DepthMapFactor=s["DepthMapFactor"])
+
+    def struct(self, depth_type):
+        p = RGBDParamsStruct()
+        p.depth_type = int(depth_type); p.depth_scale = float(self.depth_scale); p.bf = float(self.bf)
+        p.fx, p.fy, p.cx, p.cy = float(self.fx), float(self.fy), float(self.cx), float(self.cy)
+        for k, v in enumerate(self.dist_coef[:5]):
+            p.dist_coef[k] = float(v)
+        p.ndist = len(self.dist_coef)
+        return p
+
+
+def _depth_type(depth):
+    if depth.dtype == np.uint16:
+        return DEPTH_U16
+    if depth.dtype == np.float32:
+        return DEPTH_F32
+    raise OrbxError(-1, "depth must be uint16 (CV_16U) or float32 (CV_32F)")
+
+
+def _rgbd_image(image):
+    image = np.asarray(image)
+    if image.dtype != np.uint8 or image.ndim not in (2, 3) or (image.ndim == 3 and image.shape[2] not in (3, 4)):
+        raise OrbxError(-1, "image must be H x W uint8 or H x W x 3|4 uint8")
+    if image.strides[-1] != 1 or (image.ndim == 3 and image.strides[1] != image.shape[2]):
+        image = np.ascontiguousarray(image)
+    return image, (1 if image.ndim == 2 else image.shape[2])
+
+
+def _rgbd_depth(depth):
+    depth = np.asarray(depth)
+    if depth.ndim != 2 or depth.strides[1] != depth.itemsize:
+        depth = np.ascontiguousarray(depth)
+    return depth
+
+
 class ProjPoints(C.Structure):
     """orbx_proj_points (include/orbx.h)"""
     _fields_ = [("n", C.c_int), ("u", C.c_void_p), ("v", C.c_void_p), ("aux", C.c_void_p), ("level", C.c_void_p),
@@ -138,6 +208,11 @@ def lib():
     L.orbx_rectifier_size.argtypes = [vp, ip, ip]
     L.orbx_remap_batch_device.argtypes = [vp, vp, C.c_size_t, C.c_size_t, i, vp, C.c_size_t, C.c_size_t, vp]
     L.orbx_extract_rectified.argtypes = [vp, vp, vp, i, i, C.c_size_t, vp, vp, i, ip, vp, C.c_size_t]
+    RP = C.POINTER(RGBDParamsStruct)
+    L.orbx_extract_rgbd.argtypes = [vp, vp, i, i, sz, i, i, vp, sz, RP, vp, vp, i, ip, vp, vp, vp]
+    L.orbx_extract_rgbd_submit.argtypes = [vp, vp, i, i, sz, i, i, vp, sz, RP, ip]
+    L.orbx_extract_rgbd_wait.argtypes = [vp, i, vp, vp, i, ip, vp, vp, vp]
+    L.orbx_rgbd_depth_batch_device.argtypes = [i, vp, vp, i, i, vp, sz, sz, i, i, RP, vp, vp, vp, vp]
     L.orbx_search_for_initialization.argtypes = [i, C.POINTER(FrameFeats), C.POINTER(FrameFeats), vp, i, f, i, vp, ip]
     L.orbx_search_by_sim3.argtypes = [i, C.POINTER(FrameFeats), C.POINTER(FrameFeats), C.POINTER(ProjPoints), C.POINTER(ProjPoints),
                                       vp, vp, i, f, vp, ip]
@@ -369,6 +444,50 @@ class ORBextractor:
             return kps[0, :n[0]], desc[0, :n[0]], kps[1, :n[1]], desc[1, :n[1]], ur[:n[0]], z[:n[0]]
         return (kps[0, :n[0]].copy(), desc[0, :n[0]].copy(), kps[1, :n[1]].copy(), desc[1, :n[1]].copy(), ur[:n[0]].copy(), z[:n[0]].copy())
 
+    # -- RGB-D: Tracking::GrabImageRGBD's image preparation + Frame::Frame(imGray, imDepth, ...) up to ComputeStereoFromRGBD
+    #    (reference src/Tracking.cc:217-233, src/Frame.cc:145-154)
+    def extract_rgbd(self, image, depth, params, rgb=True):
+        """grey (H x W) or colour (H x W x 3|4, rgb = Camera.RGB) uint8 image + uint16 / float32 depth map, RGBDParams
+        -> (keypoints, descriptors, xy_un [n, 2], uRight, depth)"""
+        image, ch = _rgbd_image(image)
+        depth = _rgbd_depth(depth)
+        h, w = image.shape[:2]
+        if depth.shape != (h, w):
+            raise OrbxError(-1, "depth map and image differ in size")
+        p = params.struct(_depth_type(depth))
+        cap = self.max_keypoints(w, h)
+        kps = np.zeros(cap, KP_DTYPE); desc = np.zeros((cap, 32), np.uint8); n = C.c_int()
+        xy = np.zeros((cap, 2), np.float32); ur = np.zeros(cap, np.float32); z = np.zeros(cap, np.float32)
+        _check(self._L.orbx_extract_rgbd(self._h, _p(image), w, h, image.strides[0], ch, int(rgb), _p(depth), depth.strides[0], C.byref(p),
+                                         _p(kps), _p(desc), cap, C.byref(n), _p(xy), _p(ur), _p(z)))
+        k = n.value
+        return kps[:k].copy(), desc[:k].copy(), xy[:k].copy(), ur[:k].copy(), z[:k].copy()
+
+    def extract_rgbd_submit(self, image, depth, params, rgb=True):
+        """pipelined form of extract_rgbd -> ticket; image / depth are copied (or, if they live in pinned_array() memory with dense rows,
+        read in place and must stay untouched until the wait)"""
+        image, ch = _rgbd_image(image)
+        depth = _rgbd_depth(depth)
+        h, w = image.shape[:2]
+        if depth.shape != (h, w):
+            raise OrbxError(-1, "depth map and image differ in size")
+        p = params.struct(_depth_type(depth))
+        t = C.c_int()
+        _check(self._L.orbx_extract_rgbd_submit(self._h, image.ctypes.data, w, h, image.strides[0], ch, int(rgb), depth.ctypes.data,
+                                                depth.strides[0], C.byref(p), C.byref(t)))
+        self._pipe_shapes[t.value] = (w, h); self._pipe_last = (w, h)
+        return t.value
+
+    def extract_rgbd_wait(self, ticket):
+        """-> (keypoints, descriptors, xy_un, uRight, depth) of an extract_rgbd_submit ticket"""
+        w, h = self._pipe_shapes.pop(ticket, self._pipe_last)       # an unknown ticket is the library's error to report
+        cap = self.max_keypoints(w, h)
+        kps = np.zeros(cap, KP_DTYPE); desc = np.zeros((cap, 32), np.uint8); n = C.c_int()
+        xy = np.zeros((cap, 2), np.float32); ur = np.zeros(cap, np.float32); z = np.zeros(cap, np.float32)
+        _check(self._L.orbx_extract_rgbd_wait(self._h, ticket, _p(kps), _p(desc), cap, C.byref(n), _p(xy), _p(ur), _p(z)))
+        k = n.value
+        return kps[:k].copy(), desc[:k].copy(), xy[:k].copy(), ur[:k].copy(), z[:k].copy()
+
     def extract_color(self, image, rgb=True, want_gray=False):
         """colour frame (H x W x 3|4 uint8): cvtColor to grey on device (Tracking::GrabImage*, src/Tracking.cc:177-202), then operator()"""
         image = np.ascontiguousarray(image, np.uint8)
@@ -470,6 +589,16 @@ def stereo_match_batch_device(L, imgL0, R, imgR0, batch, d_kL, d_dL, d_nL, d_kR,
     d_kR still holds what R's last extract_batch_device wrote: that launch's by-product table is used; refused if it cannot be)"""
     _check(lib().orbx_stereo_match_batch_device(L._h, imgL0, R._h, imgR0, batch, d_kL, d_dL, d_nL, d_kR, d_dR, d_nR, cap,
                                                 bf, min_z, d_ur, d_depth, row_table, stream))
+
+
+def rgbd_depth_batch_device(device, d_kps, d_n, cap, batch, d_depth, depth_img_stride, depth_pitch, w, h, params, depth_type,
+                            d_u_right, d_depth_out, d_xy_un=None, stream=None):
+    """orbx_rgbd_depth_batch_device: UndistortKeyPoints + ComputeStereoFromRGBD (reference src/Frame.cc:152-154) for `batch` images of
+    orbx_extract_batch_device's outputs; device pointers (ints), outputs [batch*cap]; entries at or beyond a count stay untouched.
+    Asynchronous on `stream`."""
+    p = params.struct(depth_type)
+    _check(lib().orbx_rgbd_depth_batch_device(int(device), d_kps, d_n, int(cap), int(batch), d_depth, int(depth_img_stride), int(depth_pitch),
+                                              int(w), int(h), C.byref(p), d_xy_un, d_u_right, d_depth_out, stream))
 
 
 def stereo_row_table_available(R, d_kR, imgR0, batch, cap):

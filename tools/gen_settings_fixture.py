@@ -14,13 +14,21 @@ KEYS = ("Camera.fx", "Camera.bf", "Camera.width", "Camera.height", "Camera.fps",
         "ORBextractor.nLevels", "ORBextractor.iniThFAST", "ORBextractor.minThFAST")
 
 
-def parse(path):
-    return parse_text(open(path, encoding="utf-8", errors="replace").read())
+# the RGB-D sensor (Examples/RGB-D/TUM1-3.yaml) -> tests/golden/reference_settings_rgbd.json: camera, distortion, bf, ThDepth,
+# DepthMapFactor and Camera.RGB of Tracking::Tracking (src/Tracking.cc:60-151) -- the constants of tests/test_rgbd.py
+RGBD_FILES = {"TUM1 rgbd": "RGB-D/TUM1.yaml", "TUM2 rgbd": "RGB-D/TUM2.yaml", "TUM3 rgbd": "RGB-D/TUM3.yaml"}
+RGBD_KEYS = ("Camera.fx", "Camera.fy", "Camera.cx", "Camera.cy", "Camera.k1", "Camera.k2", "Camera.p1", "Camera.p2", "Camera.k3",
+             "Camera.width", "Camera.height", "Camera.bf", "Camera.RGB", "ThDepth", "DepthMapFactor", "ORBextractor.nFeatures")
+RGBD_JSON = os.path.join(ROOT, "tests", "golden", "reference_settings_rgbd.json")
 
 
-def parse_text(txt):
+def parse(path, keys=KEYS):
+    return parse_text(open(path, encoding="utf-8", errors="replace").read(), keys)
+
+
+def parse_text(txt, keys=KEYS):
     out = {}
-    for k in KEYS:
+    for k in keys:
         m = re.search(r"^%s\s*:\s*([-+0-9.eE]+)" % re.escape(k), txt, re.M)
         if m:
             out[k] = float(m.group(1))
@@ -31,3 +39,6 @@ if __name__ == "__main__":
     doc = {name: dict(parse(os.path.join(REF, rel)), file="Examples/" + rel) for name, rel in FILES.items()}
     json.dump(doc, open(os.path.join(ROOT, "tests", "golden", "reference_settings.json"), "w"), indent=1, sort_keys=True)
     print(json.dumps(doc, indent=1))
+    rgbd = {name: dict(parse(os.path.join(REF, rel), RGBD_KEYS), file="Examples/" + rel) for name, rel in RGBD_FILES.items()}
+    json.dump(rgbd, open(RGBD_JSON, "w"), indent=1, sort_keys=True)
+    print(json.dumps(rgbd, indent=1))
