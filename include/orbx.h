@@ -586,10 +586,23 @@ int orbx_debug_candidates(orbx_extractor *e, int image_index, int level, int32_t
 int orbx_debug_level_counts(orbx_extractor *e, int image_index, int32_t *counts /*[nlevels]*/);
 /* which FAST kernel the most recent extraction launched: 1 = a cell per wave (or several waves per cell), 2 = a pair of cells per wave */
 int orbx_debug_fast_form(const orbx_extractor *e);
+/* which form each size- and geometry-dependent launch of the handle took: the most recent extraction, and the most recent
+ * stereo launch with `e` as the left handle (launches of `e` itself: the pipelined forms run on internal lanes).  Writes the
+ * first min(n, 9) fields and returns 9 (the field count):
+ *   [0] pyramid regime: 2 = grouped launches, 1 = per level for the big levels + grouped small ones, 0 = one launch per level
+ *   [1] FAST waves per cell (1 .. 4; 0 = k_fast2)     [2] FAST grid order: 1 = image-major, 0 = cell-major
+ *   [3] quadtree threads (1024, 256)   [4] node tables in LDS (1) or HBM (0)   [5] register point form (1 / 0)
+ *   [6] k_desc level template (8, 16)
+ *   [7] stereo keypoints per wave (1, 4; 0 = no stereo launch yet)   [8] stereo XCD-owned pair grid (1 / 0)
+ * All 0 before the first launch. */
+int orbx_debug_launch_forms(const orbx_extractor *e, int32_t *out, int n);
 /* test hook: the SearchByBoW kernels exist in a latency form (one 16-wave workgroup per pair) and a throughput form
  * (LDS distance table + row fixpoint); a call picks by problem size.  form = 1 / 2 forces the wave / table form for
  * every later call of the process, 0 restores the automatic choice.  Both forms return identical matches. */
 int orbx_debug_set_bow_form(int form);
+/* process-wide, like orbx_debug_set_bow_form: the form the most recent SearchByBoW launch took.  out[0] = 1 wave / 2 table form
+ * (0 = none yet), out[1] = 1 if keyframes were placed on XCDs in whole groups, out[2] = 1 for compact (slot, value) lists */
+int orbx_debug_bow_last_form(int32_t out[3]);
 /* test hook: a per-call matcher search of ONE pair with at most 144 work items hands them to its kernel by value, in the kernel-argument
  * segment (one dependent PCIe read less per call); in_memory = 1 makes such calls read their items from mapped host memory as calls with
  * several pairs do, 0 restores the default.  Both forms return identical matches. */

@@ -534,6 +534,15 @@ extern "C" int orbx_debug_set_bow_form(int form)
 
 int orbx_bow_forced_form() { return g_bow_form.load(std::memory_order_relaxed); }
 
+// the form the most recent bow_launch of the process took: [0] 1 = wave / 2 = table, [1] XCD-owned keyframe grid, [2] compact lists
+static std::atomic<int> g_bow_last[3];
+extern "C" int orbx_debug_bow_last_form(int32_t out[3])
+{
+    if (!out) { orbx_set_error("orbx_debug_bow_last_form: invalid argument"); return ORBX_E_INVALID; }
+    for (int i = 0; i < 3; i++) out[i] = g_bow_last[i].load(std::memory_order_relaxed);
+    return ORBX_OK;
+}
+
 // pairs < BOW_TABLE_MIN_PAIRS: too few workgroups to fill 256 CUs, the 16-wave latency form is faster per call
 #define BOW_TABLE_MIN_PAIRS 4096
 // compact = 1: d_match receives (slot, value) lists of capacity `stride` pairs per (frame, pair) instead of dense rows of `stride` ints (k_bow2 only)
@@ -547,6 +556,8 @@ static int bow_launch(int npairs_x, int nframes_y, int max_b, int max_slots, hip
     if (forced && !compact) table = forced == 2;
     const size_t lds = table ? base + 4 * (size_t)((max_b + 3) & ~3) + 4 * (size_t)((max_slots + 3) & ~3) : base;
     if (lds > 120 * 1024) { orbx_set_error("feature sets too large for LDS"); return ORBX_E_INVALID; }
+    g_bow_last[0].store(table ? 2 : 1, std::memory_order_relaxed); g_bow_last[1].store(0, std::memory_order_relaxed);
+    g_bow_last[2].store(compact, std::memory_order_relaxed);
     if (table) {
         void (*kern)(const DevFeat *, const DevFeat *, int, float, int, int32_t *, int, int *, int, int) = compact ? k_bow2<MODE, 1> : k_bow2<MODE, 0>;
         ORBX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -555,6 +566,7 @@ static int bow_launch(int npairs_x, int nframes_y, int max_b, int max_slots, hip
 #else
         const bool xmap = b_shared && nframes_y >= 2 && npairs_x >= 8 && (long long)((npairs_x + 7) / 8) * 8 * nframes_y < (1ll << 30);
 #endif
+        g_bow_last[1].store(xmap ? 1 : 0, std::memory_order_relaxed);
         if (xmap)    // keyframes against a batch of frames: an XCD owns whole keyframes (see the kernel)
             hipLaunchKernelGGL(kern, dim3((unsigned)(((npairs_x + 8 * BOW2_XG - 1) / (8 * BOW2_XG)) * 8 * BOW2_XG * nframes_y)), dim3(256), lds, st, dA, dB, b_shared, nnratio, check_ori, d_match, stride, d_n,
                                npairs_x, nframes_y);

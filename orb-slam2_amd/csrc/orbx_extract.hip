@@ -2864,6 +2864,8 @@ extern "C" int orbx_extract_batch_device(orbx_extractor *e, const void *d_imgs, 
         hipLaunchKernelGGL(k_pyr_group, dim3(P.tiles_x, P.tiles_y, batch), dim3(PG_NT), (size_t)P.lds_bytes, s, ga, pr, e->d_pyr, e->d_tabs);
         orbx_prof_end(e, s);
     };
+    int32_t *forms = e->last_forms;     // orbx_debug_launch_forms: the form each decision below takes (stereo fields: orbx_stereo.hip)
+    forms[0] = regime;
     if (regime == 0) for (int l = 1; l < G.nlevels; l++) launch_level(l);
     else
         for (int gi = 0; gi < e->n_pyr_groups; gi++) {
@@ -2872,6 +2874,7 @@ extern "C" int orbx_extract_batch_device(orbx_extractor *e, const void *d_imgs, 
         }
     orbx_prof_begin(e, ORBX_STAGE_FAST, s);
     e->last_fast_form = 1;
+    forms[1] = 1; forms[2] = 0;         // waves per cell; grid order 0 = (cell, image), 1 = image-major (k_fast<48, 40, 1, true>)
     {
         FastArgs fa;
         fa.total_cells = G.total_cells; fa.lds_sc = G.fast_lds_sc; fa.lds_list = G.fast_lds_list; fa.lds_bm = G.fast_lds_bm;
@@ -2884,9 +2887,11 @@ extern "C" int orbx_extract_batch_device(orbx_extractor *e, const void *d_imgs, 
             const int nw = e->fast_waves ? e->fast_waves : waves1 * 4 <= 16384 ? 4 : waves1 * 2 <= 16384 ? 2 : 1;    // (tools/sweep_small.sh: one frame 4, two frames 2, more 1)
             int lds_bytes = G.fast_lds_bytes;
             if (nw > 1) { fa.list_cap = G.fast_list_cap_big; fa.lds_bm = G.fast_lds_bm_big; lds_bytes = G.fast_lds_bytes_big; }
+            forms[1] = nw; forms[2] = nw == 1 && grid.x <= 65535;
             // one wave per PAIR of horizontally adjacent cells (k_fast2): opt-in experiment form (ORBX_FAST_PAIR=1)
             if (G.fast2_ok && e->fast_pair == 1) {
                 e->last_fast_form = 2;
+                forms[1] = 0; forms[2] = 0;
                 fa.list_cap = FAST2_LIST_CAP;
                 for (int grp = 0; grp < 2; grp++) {
                     if (!G.fast2_count[grp]) continue;
@@ -2917,6 +2922,7 @@ extern "C" int orbx_extract_batch_device(orbx_extractor *e, const void *d_imgs, 
         void (*kern)(const Geom *, const int *, const uint32_t *, uint32_t *, uint16_t *, int *, uint32_t *, int, int *, unsigned char *, long long,
                      const uint32_t *, int) =
             big ? (lds ? k_tree<1024, true> : k_tree<1024, false>) : (lds ? k_tree<256, true> : k_tree<256, false>);
+        forms[3] = big ? 1024 : 256; forms[4] = lds; forms[5] = tree_reg_mode(G);
         hipLaunchKernelGGL(kern, dim3(batch, G.nlevels), dim3(big ? 1024 : 256), tree_launch_lds(G), s, e->d_geom,
                            e->d_cell_cnt, e->d_cand, e->d_tree_pts, e->d_tree_nid, e->d_lvl_cnt, e->d_lvl_kp, tree_launch_pts_cap(G), err_flag,
                            lds ? nullptr : e->d_tree_tab, (long long)align_up(tree_tab_bytes(G), 256), e->d_cand_prim, tree_reg_mode(G) ? 1 : 0);
@@ -2942,6 +2948,7 @@ extern "C" int orbx_extract_batch_device(orbx_extractor *e, const void *d_imgs, 
         rt.row_off = e->d_rt_off; rt.entries = (uint4 *)e->d_rt_entries; rt.ent_cap = e->rt_ent_cap; rt.rows = G.lv[0].h; rt.on = 1;
         e->rt_kps = d_kps; e->rt_cap = cap; e->rt_batch = batch;
     }
+    forms[6] = G.nlevels <= 8 ? 8 : ORBX_MAX_LEVELS;
     hipLaunchKernelGGL((G.nlevels <= 8 ? k_desc<8> : k_desc<ORBX_MAX_LEVELS>), dim3((batch < 8 ? batch : 8) * (G.kp_total + rt.on), (batch + 7) / 8), dim3(64), 0, s, da, pr, e->d_lvl_cnt, e->d_lvl_kp,
                        (orbx_keypoint *)d_kps, (uint8_t *)d_desc, (int *)d_n_out, cap, batch, rt, (const int *)err_flag, e->flag_out);
     orbx_prof_end(e, s);
@@ -3730,6 +3737,13 @@ extern "C" int orbx_pyramid_level(orbx_extractor *e, int image_index, int level,
 
 // which FAST kernel the most recent extraction launched: 1 = k_fast (a cell per wave, or several waves per cell), 2 = k_fast2 (a pair of cells per wave)
 extern "C" int orbx_debug_fast_form(const orbx_extractor *e) { return e ? e->last_fast_form : ORBX_E_INVALID; }
+
+extern "C" int orbx_debug_launch_forms(const orbx_extractor *e, int32_t *out, int n)
+{
+    if (!e || n < 0 || (n > 0 && !out)) { orbx_set_error("orbx_debug_launch_forms: invalid argument"); return ORBX_E_INVALID; }
+    for (int i = 0; i < n && i < ORBX_LAUNCH_FORM_FIELDS; i++) out[i] = e->last_forms[i];
+    return ORBX_LAUNCH_FORM_FIELDS;
+}
 
 extern "C" int orbx_debug_level_counts(orbx_extractor *e, int image_index, int32_t *counts)
 {

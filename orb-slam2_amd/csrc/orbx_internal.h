@@ -21,6 +21,7 @@
 #ifndef ORBX_TREE_OVER_PTS
 #define ORBX_TREE_OVER_PTS 1024 // register form: points of a level beyond the register capacity that an LDS overflow array takes
 #endif
+#define ORBX_LAUNCH_FORM_FIELDS 9 // orbx_debug_launch_forms: pyramid regime, FAST waves + grid order, quadtree threads / tables / register mode, k_desc levels, stereo kpw / XCD grid
 #define ORBX_FAST_LIST_CAP 512 // k_fast: pretest candidates listed per round (u16 each); denser cells take several rounds
 
 // Geometry of one pyramid level for one image size (host computes, device reads).
@@ -109,6 +110,7 @@ struct orbx_extractor {
     CellRec *d_cells; size_t cells_cap;    // per-cell records of k_fast
     void *d_pairs; size_t pairs_cap;       // per-pair records of k_fast2 (PairRec, orbx_extract.hip)
     int last_fast_form;                    // debug: 1 = k_fast, 2 = k_fast2 ran in the most recent extraction
+    int32_t last_forms[ORBX_LAUNCH_FORM_FIELDS]; // debug: launch forms of the most recent extraction / stereo launch (orbx_debug_launch_forms)
     int fast_pair;                         // ORBX_FAST_PAIR: -1 = k_fast2 for batches, 0 = never, 1 = always
     // workspace (sized for max_w x max_h x max_batch)
     uint8_t *d_pyr; size_t pyr_cap;        // levels >= 1, all images

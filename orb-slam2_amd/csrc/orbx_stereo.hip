@@ -504,6 +504,7 @@ extern "C" int orbx_stereo_match_batch_device(orbx_extractor *L, int img_l0, orb
     const bool xmap = !fold && batch >= 16 && (long long)gx * ((batch + 8 * STX_G - 1) / (8 * STX_G)) * 8 * STX_G < (1ll << 30);   // batches: an XCD owns whole pairs (see the kernel)
 #endif
     const dim3 grid = xmap ? dim3((unsigned)(gx * ((batch + 8 * STX_G - 1) / (8 * STX_G)) * 8 * STX_G)) : dim3(gx, batch);
+    L->last_forms[7] = kpw; L->last_forms[8] = xmap;     // orbx_debug_launch_forms
     hipLaunchKernelGGL((fold ? k_stereo<true> : k_stereo<false>), grid, dim3(256), 0, s, L->d_geom, pl, pr, img_l0, img_r0,
                        (const orbx_keypoint *)d_kL, (const uint32_t *)d_dL, (const int *)d_nL,
                        (const orbx_keypoint *)d_kR, (const uint32_t *)d_dR, (const int *)d_nR, cap, bf, max_d, tabs,

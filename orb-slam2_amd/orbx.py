@@ -223,6 +223,8 @@ def lib():
     L.orbx_debug_candidates.argtypes = [vp, i, i, vp, vp, vp, i, ip]
     L.orbx_debug_level_counts.argtypes = [vp, i, vp]
     L.orbx_debug_fast_form.argtypes = [vp]
+    L.orbx_debug_launch_forms.argtypes = [vp, vp, i]
+    L.orbx_debug_bow_last_form.argtypes = [vp]
     L.orbx_debug_set_bow_form.argtypes = [i]
     L.orbx_debug_set_match_items.argtypes = [i]
     L.orbx_debug_match_timing.argtypes = [vp]
@@ -274,6 +276,14 @@ def gaussian_taps(profile):
 def debug_set_bow_form(form):
     """test hook: "auto" / "wave" / "table" form of the SearchByBoW kernels (orbx_debug_set_bow_form)"""
     _check(lib().orbx_debug_set_bow_form({"auto": 0, "wave": 1, "table": 2}[form]))
+
+
+def debug_bow_last_form():
+    """form of the process's most recent SearchByBoW launch (orbx_debug_bow_last_form): dict with form ("wave" / "table" / None),
+    xcd_grid and compact (bools)"""
+    out = np.zeros(3, np.int32)
+    _check(lib().orbx_debug_bow_last_form(_p(out)))
+    return dict(form={0: None, 1: "wave", 2: "table"}[int(out[0])], xcd_grid=bool(out[1]), compact=bool(out[2]))
 
 
 def debug_set_match_items(in_memory):
@@ -350,6 +360,16 @@ class ORBextractor:
     def debug_fast_form(self):
         """1 = k_fast, 2 = k_fast2 (a pair of cells per wave) ran in the most recent extraction"""
         return self._L.orbx_debug_fast_form(self._h)
+
+    LAUNCH_FORM_FIELDS = ("pyramid_regime", "fast_waves", "fast_image_major", "tree_threads", "tree_tab_lds", "tree_reg",
+                          "desc_levels", "stereo_kpw", "stereo_xcd_grid")
+
+    def debug_launch_forms(self):
+        """the form each size- and geometry-dependent launch took in the most recent extraction and in the most recent stereo
+        launch with this handle as the left eye (orbx_debug_launch_forms), as a dict keyed by LAUNCH_FORM_FIELDS"""
+        out = np.zeros(len(self.LAUNCH_FORM_FIELDS), np.int32)
+        _check(min(self._L.orbx_debug_launch_forms(self._h, _p(out), len(out)), 0))
+        return dict(zip(self.LAUNCH_FORM_FIELDS, (int(v) for v in out)))
 
     def GetLevels(self): return self._L.orbx_get_levels(self._h)
     def GetScaleFactor(self): return self._L.orbx_get_scale_factor(self._h)

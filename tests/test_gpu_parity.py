@@ -171,7 +171,7 @@ def test_one_pixel_wide_cells(pkg, oracle):
     _check_stages(ex, orc, img, "783x814")
 
 
-@pytest.mark.parametrize("sf,nlevels", [(1.5, 4), (1.1, 6), (1.9, 3), (2.0, 3)])
+@pytest.mark.parametrize("sf,nlevels", [(1.5, 4), (1.1, 6), (1.9, 3), (2.0, 3), (1.1, 16), (1.2, 12)])
 def test_other_scale_factors(pkg, oracle, sf, nlevels):
     """non-default scaleFactor: resize tables, quotas and (for large factors) the non-LDS resize path"""
     img = synth.image(7, 640, 480)
@@ -355,11 +355,12 @@ def test_idempotent_and_deterministic(pkg):
 
 # ------------------------------------------------------------------------------- stereo
 
-def _stereo_case(pkg, oracle, seed, w, h, nf):
+def _stereo_case(pkg, oracle, seed, w, h, nf, sf=1.2, nlevels=8):
     left, right, disp = synth.stereo_pair(seed, w, h)
-    exL, exR = _extractor(pkg, nf, w, h), _extractor(pkg, nf, w, h)
+    exL = pkg.ORBextractor(nf, sf, nlevels, 20, 7, device=0, max_size=(w, h))
+    exR = pkg.ORBextractor(nf, sf, nlevels, 20, 7, device=0, max_size=(w, h))
     kL, dL = exL(left); kR, dR = exR(right)
-    oL, oR = oracle.Oracle(nf, 1.2, 8, 20, 7), oracle.Oracle(nf, 1.2, 8, 20, 7)
+    oL, oR = oracle.Oracle(nf, sf, nlevels, 20, 7), oracle.Oracle(nf, sf, nlevels, 20, 7)
     okL, odL = oL.extract(left); okR, odR = oR.extract(right)
     assert kL.tobytes() == okL.tobytes() and kR.tobytes() == okR.tobytes()
     bf, b = 386.1448, 386.1448 / 718.856  # Examples/Stereo/KITTI00-02.yaml:8,25
@@ -368,9 +369,12 @@ def _stereo_case(pkg, oracle, seed, w, h, nf):
     return ur, dp, our, odp, kL, disp
 
 
-@pytest.mark.parametrize("seed,w,h,nf", [(61, 640, 480, 1000), (62, 1241, 376, 2000)])
-def test_stereo_parity(pkg, oracle, seed, w, h, nf):
-    ur, dp, our, odp, kL, disp = _stereo_case(pkg, oracle, seed, w, h, nf)
+@pytest.mark.parametrize("seed,w,h,nf,sf,nlevels", [pytest.param(61, 640, 480, 1000, 1.2, 8, id="61-640-480-1000"),
+                                                   pytest.param(62, 1241, 376, 2000, 1.2, 8, id="62-1241-376-2000"),
+                                                   (65, 1241, 376, 2000, 1.1, 16), (66, 752, 480, 1000, 1.9, 4)])
+def test_stereo_parity(pkg, oracle, seed, w, h, nf, sf, nlevels):
+    """other scale factors change the per-level row reach of the band search (orbx_stereo.hip: tabs.reach_pk)"""
+    ur, dp, our, odp, kL, disp = _stereo_case(pkg, oracle, seed, w, h, nf, sf, nlevels)
     bad = np.nonzero(ur.view(np.uint32) != our.view(np.uint32))[0]
     assert len(bad) == 0, f"uRight differs at {bad[:5].tolist()}: {ur[bad[:5]]} vs {our[bad[:5]]}"
     assert dp.tobytes() == odp.tobytes()
