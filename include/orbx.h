@@ -427,6 +427,66 @@ int orbx_bowdb_search_batch_device(orbx_bowdb *db, const orbx_bow_frames *f, int
 int orbx_bowdb_search_batch_device_compact(orbx_bowdb *db, const orbx_bow_frames *f, int batch, float nnratio, int check_orientation,
                                            void *d_pairs, int cap_pairs, void *d_nmatches, void *stream);
 
+/* ---- KeyFrameDatabase: the place-recognition query in front of the relocalisation / loop-closing searches ----
+ * orbx_kfdb keeps the live keyframes' BowVectors (ascending uint32 word ids, the doubles orbx_bow_transform returns) in HBM, with up to
+ * 10 covisibility neighbours and one persistent relocalisation score per keyframe; the host needs the vectors no more after add.
+ * An id is the add sequence number: it grows monotonically and is not reused before orbx_kfdb_clear.  Candidates come back in the
+ * reference's return order, which is ascending (smallest common word id, id) of the group that first names them.
+ * Every call is a fresh query identity, and a keyframe's relocalisation score starts at 0.0f (the reference leaves it uninitialised).
+ * Calls on one handle serialise inside it (the reference holds mMutex).  ORBX_E_INVALID: ids not ascending, a word id >= nwords,
+ * a non-finite value, an unknown or erased id where a live one is required.  These checks read HOST vectors: a vector that is resident in an
+ * orbx_bow_frames (add_from_frames, the _frame and batch forms) is taken as orbx_bow_transform_batch_device wrote it -- ascending ids below
+ * the vocabulary's size, finite values -- and is not read back to be checked; no kernel indexes anything by a word id, so a malformed resident
+ * vector gives wrong candidates, never an access out of bounds. */
+typedef struct orbx_kfdb orbx_kfdb;
+/* KeyFrameDatabase::KeyFrameDatabase / clear (src/KeyFrameDatabase.cc:33-37, :69-73); nwords = the vocabulary's size */
+int orbx_kfdb_create(int device, int nwords, orbx_kfdb **out);
+void orbx_kfdb_destroy(orbx_kfdb *db);
+int orbx_kfdb_size(orbx_kfdb *db);       /* live keyframes */
+int orbx_kfdb_next_id(orbx_kfdb *db);    /* ids issued since create / clear: the length of the per-id arrays below */
+int orbx_kfdb_clear(orbx_kfdb *db);      /* ids restart at 0 */
+/* KeyFrameDatabase::add (:40-46) from host arrays, or device to device from frame `index` of an orbx_bow_frames (only the word
+ * count comes to the host; synchronises `stream`, NULL = the stream of the frames' last transform) */
+int orbx_kfdb_add(orbx_kfdb *db, const uint32_t *bow_id, const double *bow_val, int nbow, int *id);
+int orbx_kfdb_add_from_frames(orbx_kfdb *db, orbx_bow_frames *f, int index, void *stream, int *id);
+/* KeyFrameDatabase::erase (:48-67); the arena storage is reclaimed when the arena next grows */
+int orbx_kfdb_erase(orbx_kfdb *db, int id);
+/* KeyFrame::GetBestCovisibilityKeyFrames(10) of keyframe id, in its order (n <= 10); neighbour ids that are unknown or erased at
+ * query time are ignored (the reference's lists never hold an erased keyframe) */
+int orbx_kfdb_set_covisibility(orbx_kfdb *db, int id, const int32_t *neigh_ids, int n);
+/* ORBVocabulary::score(query, keyframe ids[i]) = L1Scoring::score (Thirdparty/DBoW2/DBoW2/ScoringObject.cpp:23-68), the loop of
+ * src/LoopClosing.cc:143-162: bit-exact doubles (terms added in ascending word order); the caller rounds to float as the reference does */
+int orbx_kfdb_score(orbx_kfdb *db, const uint32_t *bow_id, const double *bow_val, int nbow, const int32_t *ids, int n, double *scores);
+int orbx_kfdb_score_frame(orbx_kfdb *db, orbx_bow_frames *f, int index, const int32_t *ids, int n, double *scores);
+/* KeyFrameDatabase::DetectRelocalizationCandidates (:234-349) and DetectLoopCandidates (:80-229; connected_ids = pKF->GetConnectedKeyFrames(),
+ * min_score = minScore).  cand[cap] receives *ncand ids; ORBX_E_CAPACITY with *ncand = the true count when the list is longer.
+ * Optional stage outputs of orbx_kfdb_next_id entries each: words_out[id] = common words (mnRelocWords / mnLoopWords; 0 for erased and
+ * connected keyframes), score_out[id] = the float score of the keyframes this query scored, 0 elsewhere.  The query is a host BowVector
+ * or frame `index` of an orbx_bow_frames (the _frame forms).  A relocalisation query that ends in ORBX_E_CAPACITY has run like any other:
+ * the keyframes it scored keep those scores as their persistent ones (the list is known only after the query), and asking again with a
+ * larger cap returns the same list.  Cost note: the returned keyframes are ordered by a counting rank inside one workgroup, quadratic in the
+ * length of the LIST (not of the database): a handful in place recognition; a query built to return thousands (thousands of identical
+ * keyframes) spends milliseconds there. */
+int orbx_kfdb_detect_relocalization(orbx_kfdb *db, const uint32_t *bow_id, const double *bow_val, int nbow, int32_t *cand, int cap,
+                                    int *ncand, int32_t *words_out, float *score_out);
+int orbx_kfdb_detect_relocalization_frame(orbx_kfdb *db, orbx_bow_frames *f, int index, int32_t *cand, int cap, int *ncand,
+                                          int32_t *words_out, float *score_out);
+int orbx_kfdb_detect_loop(orbx_kfdb *db, const uint32_t *bow_id, const double *bow_val, int nbow, const int32_t *connected_ids, int nconnected,
+                          float min_score, int32_t *cand, int cap, int *ncand, int32_t *words_out, float *score_out);
+int orbx_kfdb_detect_loop_frame(orbx_kfdb *db, orbx_bow_frames *f, int index, const int32_t *connected_ids, int nconnected, float min_score,
+                                int32_t *cand, int cap, int *ncand, int32_t *words_out, float *score_out);
+/* frames 0..batch-1 of f as relocalisation queries, asynchronous on `stream`, nothing crosses PCIe: d_cand[batch][cap] (int32; the first
+ * min(count, cap) candidates) and d_ncand[batch] (true counts) are device memory.  Equals `batch` per-call queries issued in frame order,
+ * the persistent scores included (batch <= 1024).  The handle's next call waits for the stream. */
+int orbx_kfdb_detect_relocalization_batch_device(orbx_kfdb *db, orbx_bow_frames *f, int batch, void *d_cand, int cap, void *d_ncand, void *stream);
+/* Test and tool utility: a BowVector computed elsewhere into slot `index` of an orbx_bow_frames, so that the forms above that take frames can be
+ * driven with chosen vectors.  Checks nbow <= cap, ascending ids and finite values (it knows no vocabulary: word id < nwords is the caller's to
+ * keep).  The slot's FeatureVector is NOT touched and no longer belongs to the slot's BowVector: do not hand such a slot to the SearchByBoW
+ * forms.  stream = NULL: the stream of the frames' last transform (the default stream if there was none); synchronises it. */
+int orbx_bow_frames_set_bow(orbx_bow_frames *f, int index, const uint32_t *bow_id, const double *bow_val, int nbow, void *stream);
+/* the persistent relocalisation scores (mRelocScore, :289 / :315): scores[i] for ids 0..n-1, 0.0f past the ids issued */
+int orbx_kfdb_reloc_scores(orbx_kfdb *db, float *scores, int n);
+
 typedef struct {
     int n;
     const float *x, *y;        /* mvKeysUn[i].pt */

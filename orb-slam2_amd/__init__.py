@@ -6,6 +6,7 @@ sitting directly on the C ABI of liborbx.so (include/orbx.h):
   ORBextractor          <- reference include/ORBextractor.h:58-139
   ORBmatcher            <- reference include/ORBmatcher.h:41-103 (the three north-star searches)
   ComputeStereoMatches  <- reference src/Frame.cc:577-751
+  KeyFrameDatabase      <- reference include/KeyFrameDatabase.h:42-70 (relocalisation and loop candidate queries)
   ORBextractor.extract_rgbd / rgbd_depth_batch_device <- reference src/Frame.cc:145-154, :754-774 (RGB-D frames)
 
 There is NO CPU fallback: importing works without a GPU (so that the ABI can be inspected), but
@@ -14,9 +15,9 @@ The directory name contains a '-', so load it with importlib (see tests/conftest
 """
 from . import orbx, streams
 from .orbx import (OrbxError, KP_DTYPE, lib, lib_path, ORBextractor, ORBmatcher, ComputeStereoMatches,
-                   FeatSet, make_featset, STAGES, BowDatabase, DeviceKeyFrame, DeviceFrame, BowFrames, ORBVocabulary, ComputeDistinctiveDescriptors, Rectifier, UndistortKeyPoints,
+                   FeatSet, make_featset, STAGES, BowDatabase, DeviceKeyFrame, DeviceFrame, BowFrames, KeyFrameDatabase, ORBVocabulary, ComputeDistinctiveDescriptors, Rectifier, UndistortKeyPoints,
                    RGBDParams, depth_map_factor, rgbd_depth_batch_device, DEPTH_U16, DEPTH_F32)
 
 __all__ = ["OrbxError", "KP_DTYPE", "lib", "lib_path", "ORBextractor", "ORBmatcher", "ComputeStereoMatches",
-           "FeatSet", "make_featset", "STAGES", "BowDatabase", "DeviceKeyFrame", "DeviceFrame", "BowFrames", "ORBVocabulary", "ComputeDistinctiveDescriptors", "Rectifier", "UndistortKeyPoints",
+           "FeatSet", "make_featset", "STAGES", "BowDatabase", "DeviceKeyFrame", "DeviceFrame", "BowFrames", "KeyFrameDatabase", "ORBVocabulary", "ComputeDistinctiveDescriptors", "Rectifier", "UndistortKeyPoints",
            "RGBDParams", "depth_map_factor", "rgbd_depth_batch_device", "DEPTH_U16", "DEPTH_F32"]

@@ -202,6 +202,24 @@ def lib():
     L.orbx_bow_frames_read.argtypes = [vp, i, vp, vp, vp, ip, vp, vp, vp, ip]
     L.orbx_bowdb_search_batch_device.argtypes = [vp, vp, i, f, i, vp, vp, vp]
     L.orbx_bowdb_search_batch_device_compact.argtypes = [vp, vp, i, f, i, vp, i, vp, vp]
+    L.orbx_kfdb_create.argtypes = [i, i, C.POINTER(vp)]
+    L.orbx_kfdb_destroy.argtypes = [vp]; L.orbx_kfdb_destroy.restype = None
+    L.orbx_kfdb_size.argtypes = [vp]
+    L.orbx_kfdb_next_id.argtypes = [vp]
+    L.orbx_kfdb_clear.argtypes = [vp]
+    L.orbx_kfdb_add.argtypes = [vp, vp, vp, i, ip]
+    L.orbx_kfdb_add_from_frames.argtypes = [vp, vp, i, vp, ip]
+    L.orbx_kfdb_erase.argtypes = [vp, i]
+    L.orbx_kfdb_set_covisibility.argtypes = [vp, i, vp, i]
+    L.orbx_kfdb_score.argtypes = [vp, vp, vp, i, vp, i, vp]
+    L.orbx_kfdb_score_frame.argtypes = [vp, vp, i, vp, i, vp]
+    L.orbx_kfdb_detect_relocalization.argtypes = [vp, vp, vp, i, vp, i, ip, vp, vp]
+    L.orbx_kfdb_detect_relocalization_frame.argtypes = [vp, vp, i, vp, i, ip, vp, vp]
+    L.orbx_kfdb_detect_loop.argtypes = [vp, vp, vp, i, vp, i, f, vp, i, ip, vp, vp]
+    L.orbx_kfdb_detect_loop_frame.argtypes = [vp, vp, i, vp, i, f, vp, i, ip, vp, vp]
+    L.orbx_kfdb_detect_relocalization_batch_device.argtypes = [vp, vp, i, vp, i, vp, vp]
+    L.orbx_kfdb_reloc_scores.argtypes = [vp, vp, i]
+    L.orbx_bow_frames_set_bow.argtypes = [vp, i, vp, vp, i, vp]
     L.orbx_undistort_keypoints.argtypes = [i, vp, i, f, f, f, f, vp, i, vp]
     L.orbx_rectifier_create.argtypes = [i, i, i, i, i, vp, vp, C.POINTER(vp)]
     L.orbx_rectifier_destroy.argtypes = [vp]; L.orbx_rectifier_destroy.restype = None
@@ -801,6 +819,11 @@ class BowFrames:
         return dict(bow_id=bid[:nb.value].copy(), bow_val=bval[:nb.value].copy(), fv_node_id=fid[:fn.value].copy(),
                     fv_node_off=foff[:fn.value + 1].copy(), fv_feat=ffeat[:foff[fn.value]].copy())
 
+    def set_bow(self, index, bow, stream=None):
+        """a host BowVector into slot `index` (orbx_bow_frames_set_bow); the slot's FeatureVector is left alone"""
+        bid, bval = _bow_query(bow)
+        _check(self._L.orbx_bow_frames_set_bow(self._h, int(index), _p(bid), _p(bval), len(bid), stream))
+
     def search(self, db, batch, d_match, d_nmatches, nnratio=0.75, checkOri=True, stream=None):
         """every keyframe of a BowDatabase against frames 0..batch-1: d_match[batch][nkf][cap], d_nmatches[batch][nkf] (device)"""
         _check(self._L.orbx_bowdb_search_batch_device(db._h, self._h, batch, nnratio, int(checkOri), d_match, d_nmatches, stream))
@@ -809,6 +832,118 @@ class BowFrames:
         """the same search with compact results: d_pairs[batch][nkf][cap_pairs][2] int32 = (frame feature, keyframe feature) in frame-feature order,
         d_nmatches[batch][nkf] = counts (orbx_bowdb_search_batch_device_compact)"""
         _check(self._L.orbx_bowdb_search_batch_device_compact(db._h, self._h, batch, nnratio, int(checkOri), d_pairs, int(cap_pairs), d_nmatches, stream))
+
+
+def _bow_query(bow):
+    """(bow_id, bow_val) or dict(bow_id=, bow_val=) -> contiguous (uint32 ids, float64 values)"""
+    if isinstance(bow, dict):
+        bow = (bow["bow_id"], bow["bow_val"])
+    bid = np.ascontiguousarray(bow[0], np.uint32).reshape(-1); bval = np.ascontiguousarray(bow[1], np.float64).reshape(-1)
+    if len(bid) != len(bval):
+        raise OrbxError(-1, f"BowVector: {len(bid)} word ids, {len(bval)} values")
+    return bid, bval
+
+
+class KeyFrameDatabase:
+    """Mirror of ORB_SLAM2::KeyFrameDatabase (reference include/KeyFrameDatabase.h:42-70) over orbx_kfdb_*: the keyframes' BowVectors,
+    covisibility neighbours and relocalisation scores live in HBM.  Keyframes are named by the id `add` returns (the add sequence number).
+    A query is a host BowVector -- (bow_id, bow_val) or a dict with those keys -- or (BowFrames, index)."""
+
+    def __init__(self, nwords, device=0):
+        self._L = lib()
+        self._h = C.c_void_p()
+        _check(self._L.orbx_kfdb_create(device, int(nwords), C.byref(self._h)))
+        self.device = device
+
+    def __del__(self):
+        try:
+            h, L = getattr(self, "_h", None), _lib
+            if h and L is not None:
+                L.orbx_kfdb_destroy(h)
+            self._h = None
+        except Exception:
+            pass
+
+    def __len__(self):
+        return self._L.orbx_kfdb_size(self._h)
+
+    def next_id(self):
+        return self._L.orbx_kfdb_next_id(self._h)
+
+    def clear(self):
+        _check(self._L.orbx_kfdb_clear(self._h))
+
+    def add(self, bow, index=None, stream=None):
+        """add(host BowVector) or add(BowFrames, index): -> id"""
+        out = C.c_int(-1)
+        if isinstance(bow, BowFrames):
+            _check(self._L.orbx_kfdb_add_from_frames(self._h, bow._h, int(index), stream, C.byref(out)))
+        else:
+            bid, bval = _bow_query(bow)
+            _check(self._L.orbx_kfdb_add(self._h, _p(bid), _p(bval), len(bid), C.byref(out)))
+        return out.value
+
+    def erase(self, id):
+        _check(self._L.orbx_kfdb_erase(self._h, int(id)))
+
+    def set_covisibility(self, id, neighbours):
+        nb = np.ascontiguousarray(neighbours, np.int32).reshape(-1)
+        _check(self._L.orbx_kfdb_set_covisibility(self._h, int(id), _p(nb), len(nb)))
+
+    def reloc_scores(self):
+        out = np.zeros(self.next_id(), np.float32)
+        _check(self._L.orbx_kfdb_reloc_scores(self._h, _p(out), len(out)))
+        return out
+
+    def score(self, query, ids, index=None):
+        """ORBVocabulary::score(query, keyframe) for every id: float64, bit-exact"""
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        out = np.zeros(len(ids), np.float64)
+        if isinstance(query, BowFrames):
+            _check(self._L.orbx_kfdb_score_frame(self._h, query._h, int(index), _p(ids), len(ids), _p(out)))
+        else:
+            bid, bval = _bow_query(query)
+            _check(self._L.orbx_kfdb_score(self._h, _p(bid), _p(bval), len(bid), _p(ids), len(ids), _p(out)))
+        return out
+
+    def _detect(self, query, index, loop, connected, min_score, cap, stages):
+        n = self.next_id()
+        cap = n if cap is None else int(cap)
+        cand = np.zeros(max(cap, 1), np.int32); nc = C.c_int(0)
+        words = np.zeros(n, np.int32) if stages else None
+        score = np.zeros(n, np.float32) if stages else None
+        conn = np.ascontiguousarray(connected if connected is not None else [], np.int32).reshape(-1)
+        L = self._L
+        if isinstance(query, BowFrames):
+            if loop:
+                rc = L.orbx_kfdb_detect_loop_frame(self._h, query._h, int(index), _p(conn), len(conn), float(min_score), _p(cand), cap, C.byref(nc), _p(words), _p(score))
+            else:
+                rc = L.orbx_kfdb_detect_relocalization_frame(self._h, query._h, int(index), _p(cand), cap, C.byref(nc), _p(words), _p(score))
+        else:
+            bid, bval = _bow_query(query)
+            if loop:
+                rc = L.orbx_kfdb_detect_loop(self._h, _p(bid), _p(bval), len(bid), _p(conn), len(conn), float(min_score), _p(cand), cap, C.byref(nc), _p(words), _p(score))
+            else:
+                rc = L.orbx_kfdb_detect_relocalization(self._h, _p(bid), _p(bval), len(bid), _p(cand), cap, C.byref(nc), _p(words), _p(score))
+        if rc != 0:
+            e = OrbxError(rc, L.orbx_last_error().decode(errors="replace"))
+            e.ncand = nc.value               # ORBX_E_CAPACITY: the true count
+            raise e
+        out = [int(v) for v in cand[:nc.value]]
+        return (out, words, score) if stages else out
+
+    def DetectRelocalizationCandidates(self, F, index=None, cap=None, stages=False):
+        """-> candidate ids in the reference's order (stages=True: also words[id], score[id] of this query)"""
+        return self._detect(F, index, False, None, 0.0, cap, stages)
+
+    def DetectLoopCandidates(self, pKF, connected, minScore, index=None, cap=None, stages=False):
+        """pKF: the query keyframe's BowVector; connected: ids of pKF->GetConnectedKeyFrames()"""
+        return self._detect(pKF, index, True, connected, minScore, cap, stages)
+
+    def detect_relocalization_batch_device(self, frames, batch, d_cand, cap, d_ncand, stream=None):
+        """frames 0..batch-1 of a BowFrames as relocalisation queries, results in device memory: d_cand[batch][cap] int32, d_ncand[batch]
+        int32 (true counts); asynchronous on `stream`"""
+        _check(self._L.orbx_kfdb_detect_relocalization_batch_device(self._h, frames._h, int(batch), d_cand, int(cap), d_ncand, stream))
 
 
 class ORBmatcher:
