@@ -426,6 +426,30 @@ int orbx_bowdb_search_batch_device(orbx_bowdb *db, const orbx_bow_frames *f, int
  * solver next (src/Tracking.cc:1682-1693) -- and d_nmatches[batch][nkf] the counts (a count above cap_pairs says the list was cut). */
 int orbx_bowdb_search_batch_device_compact(orbx_bowdb *db, const orbx_bow_frames *f, int batch, float nnratio, int check_orientation,
                                            void *d_pairs, int cap_pairs, void *d_nmatches, void *stream);
+/* The search over the candidates only, as the loop of Tracking::Relocalization runs it (src/Tracking.cc:1661-1682): frame b of f against the
+ * keyframes its candidate list names, all frames in one launch, the lists read on the device.  d_cand[batch][cand_stride] (int32 ids) and
+ * d_ncand[batch] (int32 true counts: a count above cand_stride is cut to it, a negative one reads as 0) are device memory in the layout
+ * orbx_kfdb_detect_relocalization_batch_device writes with cap == cand_stride; the call is legal on the same stream directly behind it, the host
+ * never reads the lists and nothing synchronises.  d_kf_of_id (optional, device int32[n_ids]) joins an id to an index of db, -1 = not in this
+ * set; NULL = an id is the index (keyframes added to orbx_kfdb in the order orbx_bowdb_create received them).  Slot j of frame b is searched
+ * when j < min(max(d_ncand[b], 0), cand_stride) and its keyframe index lies in [0, orbx_bowdb_size(db)) (with a map: when also 0 <= id < n_ids);
+ * every id is checked before anything is indexed by it.  A searched slot receives in d_match[batch][cand_stride][cap] and
+ * d_nmatches[batch][cand_stride], at [b][j], what orbx_bowdb_search_batch_device writes at [b][kf] (entries at or beyond the frame's feature count
+ * are left alone); any other slot receives d_nmatches[b][j] = -1 and its row is left alone.  Slots are independent: a keyframe named twice
+ * is searched twice.  ORBX_E_INVALID: a NULL handle, list or output, batch outside [1, f's max_batch], another device, cand_stride < 1 or
+ * >= 2^24, batch > 65535, d_kf_of_id with n_ids < 1, feature sets too large for LDS. */
+int orbx_bowdb_search_candidates_device(orbx_bowdb *db, const orbx_bow_frames *f, int batch,
+                                        const void *d_cand, int cand_stride, const void *d_ncand,
+                                        const void *d_kf_of_id, int n_ids,
+                                        float nnratio, int check_orientation, void *d_match, void *d_nmatches, void *stream);
+/* The same with compact results, slot for slot what orbx_bowdb_search_batch_device_compact writes for the keyframe (src/Tracking.cc:1661-1682,
+ * the lists the PnP solvers of :1682-1693 read): d_pairs[batch][cand_stride][cap_pairs][2] receives the first min(count, cap_pairs) pairs of a
+ * searched slot (the rest of the list is left alone), d_nmatches[batch][cand_stride] the count, -1 for a slot that is not searched.
+ * ORBX_E_INVALID also for cap_pairs < 1. */
+int orbx_bowdb_search_candidates_device_compact(orbx_bowdb *db, const orbx_bow_frames *f, int batch,
+                                                const void *d_cand, int cand_stride, const void *d_ncand,
+                                                const void *d_kf_of_id, int n_ids,
+                                                float nnratio, int check_orientation, void *d_pairs, int cap_pairs, void *d_nmatches, void *stream);
 
 /* ---- KeyFrameDatabase: the place-recognition query in front of the relocalisation / loop-closing searches ----
  * orbx_kfdb keeps the live keyframes' BowVectors (ascending uint32 word ids, the doubles orbx_bow_transform returns) in HBM, with up to

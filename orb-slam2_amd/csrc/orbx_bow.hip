@@ -263,10 +263,13 @@ __device__ __forceinline__ void bow2_row_scan(const DevFeat &A, const DevFeat &B
                         // traffic; 6: 0.60 ms, three spilled dwords per thread (194 MB, 53 of them spill writes); 7 / 8: 0.60 / 0.59 ms with 8 / 17 spilled
                         // dwords (340 / 580 MB): the time no longer moves, the scratch traffic does
 #endif
+// The search of one pair by one 256-thread workgroup, shared by the kernels below (inlined into each: k_bow2's code is what it was when
+// this was its body).  First side sides_a[pair], second side sides_b[b_shared ? frame : pair]; the result goes to entry
+// frame * npairs_g + opair of match_out / nmatches (k_bow2: opair = pair; k_bow2_cand: the slot of the candidate list).
 template <int MODE, int OUT>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BOW2_WPE, 8))) void k_bow2(const DevFeat *__restrict__ sides_a, const DevFeat *__restrict__ sides_b,
-                                             int b_shared, float nnratio, int check_ori, int32_t *__restrict__ match_out,
-                                             int match_stride, int *__restrict__ nmatches, int xmap_npairs, int xmap_nframes)
+__device__ __forceinline__ void bow2_pair(const DevFeat *__restrict__ sides_a, const DevFeat *__restrict__ sides_b,
+                                          int b_shared, float nnratio, int check_ori, int32_t *__restrict__ match_out,
+                                          int match_stride, int *__restrict__ nmatches, int pair, int frame, int npairs_g, int opair)
 {
     __shared__ int hist[BOW_HISTO];
     __shared__ int keep3[3];
@@ -280,19 +283,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BOW2_WPE, 8
     __shared__ uint16_t choice[BOW2_ROWS];         // per first-side row of the pass: chosen column of its node or 0xFFFF
     __shared__ uint8_t row_node[BOW2_ROWS];
     __shared__ uint8_t node_dirty[2][BOW_CHUNK];
-    // Grid: (pairs, frames), or -- a keyframe set against a batch of frames -- ONE dimension in which an XCD owns whole keyframes: workgroups are
-    // dealt round-robin over the 8 XCDs in dispatch order, so workgroup L runs on XCD L % 8; XCD x takes the keyframes x, x + 8, ... and each
-    // of them with all its frames in consecutive workgroups.  A keyframe's 41 KB then come over the fabric once (its 32 uses hit the XCD's
-    // L2 while they are fresh) instead of once per few frames, and the batch's frames (1.3 MB) stay in every L2.
-    int pair, frame, npairs_g;
-    if (xmap_nframes > 0) {
-#ifndef BOW2_XG
-#define BOW2_XG 16
-#endif
-        const unsigned L = blockIdx.x, slot = L >> 3, per = (unsigned)xmap_nframes * BOW2_XG, grp = slot / per, rem = slot - grp * per;
-        frame = (int)(rem / BOW2_XG); pair = (int)((grp * BOW2_XG + rem % BOW2_XG) * 8u + (L & 7u)); npairs_g = xmap_npairs;
-        if (pair >= npairs_g) return;
-    } else { pair = blockIdx.x; frame = blockIdx.y; npairs_g = gridDim.x; }
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const DevFeat A = sides_a[pair];
     const DevFeat B = sides_b[b_shared ? frame : pair];
@@ -502,7 +492,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BOW2_WPE, 8
     }
     __threadfence_block();
     __syncthreads();
-    const long long pi = (long long)frame * npairs_g + pair;
+    const long long pi = (long long)frame * npairs_g + opair;
     histogram_filter(match, bins, nslots, check_ori, hist, keep3, &s_cnt, nmatches + pi);
     __syncthreads();
     if (OUT == 0) {
@@ -521,6 +511,57 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BOW2_WPE, 8
             __syncthreads();
         }
     }
+}
+
+template <int MODE, int OUT>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BOW2_WPE, 8))) void k_bow2(const DevFeat *__restrict__ sides_a, const DevFeat *__restrict__ sides_b,
+                                             int b_shared, float nnratio, int check_ori, int32_t *__restrict__ match_out,
+                                             int match_stride, int *__restrict__ nmatches, int xmap_npairs, int xmap_nframes)
+{
+    // Grid: (pairs, frames), or -- a keyframe set against a batch of frames -- ONE dimension in which an XCD owns whole keyframes: workgroups are
+    // dealt round-robin over the 8 XCDs in dispatch order, so workgroup L runs on XCD L % 8; XCD x takes the keyframes x, x + 8, ... and each
+    // of them with all its frames in consecutive workgroups.  A keyframe's 41 KB then come over the fabric once (its 32 uses hit the XCD's
+    // L2 while they are fresh) instead of once per few frames, and the batch's frames (1.3 MB) stay in every L2.
+    int pair, frame, npairs_g;
+    if (xmap_nframes > 0) {
+#ifndef BOW2_XG
+#define BOW2_XG 16
+#endif
+        const unsigned L = blockIdx.x, slot = L >> 3, per = (unsigned)xmap_nframes * BOW2_XG, grp = slot / per, rem = slot - grp * per;
+        frame = (int)(rem / BOW2_XG); pair = (int)((grp * BOW2_XG + rem % BOW2_XG) * 8u + (L & 7u)); npairs_g = xmap_npairs;
+        if (pair >= npairs_g) return;
+    } else { pair = blockIdx.x; frame = blockIdx.y; npairs_g = gridDim.x; }
+    bow2_pair<MODE, OUT>(sides_a, sides_b, b_shared, nnratio, check_ori, match_out, match_stride, nmatches, pair, frame, npairs_g, pair);
+}
+
+// The list form of the (KF, F) search: workgroup (j, b) searches frame b against the keyframe that slot j of the frame's candidate list names
+// (the lists orbx_kfdb_detect_relocalization_batch_device leaves in HBM; Tracking::Relocalization searches only those, src/Tracking.cc:1661-1682).
+// cand[b][cand_stride] holds ids, ncand[b] the TRUE count (it may exceed cand_stride; a negative one reads as 0), kf_of_id[n_ids] -- optional --
+// maps an id to an index of sides_a (-1: not in the set); without it an id is the index.  Every value read from the lists is checked before it
+// indexes anything: j < min(max(ncand[b], 0), cand_stride) before cand is read, 0 <= id < n_ids before kf_of_id is, 0 <= kf < nkf before sides_a
+// is.  A slot that fails any of them is dead: it reads -1 in nmatches, its row / list is not touched, and the workgroup leaves before the
+// first barrier (the condition is the same for all its threads: it depends on blockIdx and on list values only; the wave's first lane hands
+// kf to the others so that the compiler knows it too and keeps the DevFeat records in scalar registers as k_bow2 does).
+template <int OUT>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BOW2_WPE, 8))) void k_bow2_cand(const DevFeat *__restrict__ sides_a, int nkf, const DevFeat *__restrict__ sides_b,
+                                             const int32_t *__restrict__ cand, int cand_stride, const int32_t *__restrict__ ncand,
+                                             const int32_t *__restrict__ kf_of_id, int n_ids, float nnratio, int check_ori,
+                                             int32_t *__restrict__ match_out, int match_stride, int *__restrict__ nmatches)
+{
+    const int j = blockIdx.x, b = blockIdx.y;      // j < cand_stride, b < batch: the grid is exactly (cand_stride, batch)
+    const int live = min(max(ncand[b], 0), cand_stride);
+    int kf = -1;
+    if (j < live) {
+        const int id = cand[(long long)b * cand_stride + j];
+        if (!kf_of_id) kf = id;
+        else if (id >= 0 && id < n_ids) kf = kf_of_id[id];
+    }
+    kf = __builtin_amdgcn_readfirstlane(kf);
+    if (kf < 0 || kf >= nkf) {
+        if (threadIdx.x == 0) nmatches[(long long)b * cand_stride + j] = -1;
+        return;
+    }
+    bow2_pair<0, OUT>(sides_a, sides_b, 1, nnratio, check_ori, match_out, match_stride, nmatches, kf, b, cand_stride, j);
 }
 
 // 0 = choose by size, 1 = always the wave form, 2 = always the table form (explicit debug entry point, no environment lookup)
@@ -545,16 +586,22 @@ extern "C" int orbx_debug_bow_last_form(int32_t out[3])
 
 // pairs < BOW_TABLE_MIN_PAIRS: too few workgroups to fill 256 CUs, the 16-wave latency form is faster per call
 #define BOW_TABLE_MIN_PAIRS 4096
+// dynamic LDS of a workgroup: claimed[max_b] + bins[max_slots], and for the table form own[max_b] + the match row [max_slots]
+static size_t bow_lds_bytes(bool table, int max_b, int max_slots)
+{
+    const size_t base = (size_t)((max_b + 15) & ~15) + (size_t)((max_slots + 15) & ~15) + 16;
+    return table ? base + 4 * (size_t)((max_b + 3) & ~3) + 4 * (size_t)((max_slots + 3) & ~3) : base;
+}
+
 // compact = 1: d_match receives (slot, value) lists of capacity `stride` pairs per (frame, pair) instead of dense rows of `stride` ints (k_bow2 only)
 template <int MODE>
 static int bow_launch(int npairs_x, int nframes_y, int max_b, int max_slots, hipStream_t st, const DevFeat *dA, const DevFeat *dB,
                       int b_shared, float nnratio, int check_ori, int32_t *d_match, int stride, int *d_n, int compact = 0)
 {
-    const size_t base = (size_t)((max_b + 15) & ~15) + (size_t)((max_slots + 15) & ~15) + 16;
     bool table = (long long)npairs_x * nframes_y >= BOW_TABLE_MIN_PAIRS || compact;
     const int forced = g_bow_form.load(std::memory_order_relaxed); // orbx_debug_set_bow_form: the parity tests run both forms on small inputs
     if (forced && !compact) table = forced == 2;
-    const size_t lds = table ? base + 4 * (size_t)((max_b + 3) & ~3) + 4 * (size_t)((max_slots + 3) & ~3) : base;
+    const size_t lds = bow_lds_bytes(table, max_b, max_slots);
     if (lds > 120 * 1024) { orbx_set_error("feature sets too large for LDS"); return ORBX_E_INVALID; }
     g_bow_last[0].store(table ? 2 : 1, std::memory_order_relaxed); g_bow_last[1].store(0, std::memory_order_relaxed);
     g_bow_last[2].store(compact, std::memory_order_relaxed);
@@ -897,6 +944,53 @@ extern "C" int orbx_bowdb_search_batch_device_compact(orbx_bowdb *db, const orbx
     ORBX_HIP(hipSetDevice(db->device));
     return bow_launch<0>(db->nkf, batch, fr->cap, fr->cap, stream ? (hipStream_t)stream : fr->last_stream, (const DevFeat *)db->d_blob,
                          (const DevFeat *)fr->d_feats, 1, nnratio, check_orientation, (int32_t *)d_pairs, cap_pairs, (int *)d_nmatches, 1);
+}
+
+// The search over the candidates only: slot j of frame b's list against frame b, one launch of cand_stride x batch workgroups of which the
+// named ones work (k_bow2_cand).  The host reads neither list -- they may still be in flight on `stream` -- so nothing here synchronises.
+// One kernel form, the table form, for both outputs: orbx_debug_set_bow_form has nothing to choose here (at 64 live pairs the table and the
+// wave form of the all-keyframes search take 72-83 and 78-80 us, profiles/r07_reloc_candidates.txt: nothing for a second form to win), and
+// orbx_debug_bow_last_form keeps reporting the launches of bow_launch.
+static int bow_launch_cand(const char *who, orbx_bowdb *db, const orbx_bow_frames *fr, int batch, const void *d_cand, int cand_stride,
+                           const void *d_ncand, const void *d_kf_of_id, int n_ids, float nnratio, int check_ori, void *d_out, int stride,
+                           void *d_nmatches, void *stream, int compact)
+{
+    if (!db || !fr || !d_cand || !d_ncand || !d_out || !d_nmatches || batch < 1 || batch > fr->batch || fr->device != db->device ||
+        cand_stride < 1 || stride < 1 || (d_kf_of_id && n_ids < 1)) {
+        orbx_set_error("%s: invalid argument", who);
+        return ORBX_E_INVALID;
+    }
+    if (cand_stride >= (1 << 24) || batch > 65535) {      // 256 * gridDim.x must stay below 2^32, gridDim.y below 65536
+        orbx_set_error("%s: %d x %d workgroups exceed the launch limits", who, cand_stride, batch);
+        return ORBX_E_INVALID;
+    }
+    const size_t lds = bow_lds_bytes(true, fr->cap, fr->cap);
+    if (lds > 120 * 1024) { orbx_set_error("feature sets too large for LDS"); return ORBX_E_INVALID; }
+    ORBX_HIP(hipSetDevice(db->device));
+    void (*kern)(const DevFeat *, int, const DevFeat *, const int32_t *, int, const int32_t *, const int32_t *, int, float, int, int32_t *, int, int *) =
+        compact ? k_bow2_cand<1> : k_bow2_cand<0>;
+    ORBX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, dim3(cand_stride, batch), dim3(256), lds, stream ? (hipStream_t)stream : fr->last_stream, (const DevFeat *)db->d_blob,
+                       db->nkf, (const DevFeat *)fr->d_feats, (const int32_t *)d_cand, cand_stride, (const int32_t *)d_ncand,
+                       (const int32_t *)d_kf_of_id, d_kf_of_id ? n_ids : 0, nnratio, check_ori, (int32_t *)d_out, stride, (int *)d_nmatches);
+    ORBX_HIP(hipGetLastError());
+    return ORBX_OK;
+}
+
+extern "C" int orbx_bowdb_search_candidates_device(orbx_bowdb *db, const orbx_bow_frames *fr, int batch, const void *d_cand, int cand_stride,
+                                                   const void *d_ncand, const void *d_kf_of_id, int n_ids, float nnratio, int check_orientation,
+                                                   void *d_match, void *d_nmatches, void *stream)
+{
+    return bow_launch_cand("orbx_bowdb_search_candidates_device", db, fr, batch, d_cand, cand_stride, d_ncand, d_kf_of_id, n_ids, nnratio,
+                           check_orientation, d_match, fr ? fr->cap : 0, d_nmatches, stream, 0);
+}
+
+extern "C" int orbx_bowdb_search_candidates_device_compact(orbx_bowdb *db, const orbx_bow_frames *fr, int batch, const void *d_cand, int cand_stride,
+                                                           const void *d_ncand, const void *d_kf_of_id, int n_ids, float nnratio,
+                                                           int check_orientation, void *d_pairs, int cap_pairs, void *d_nmatches, void *stream)
+{
+    return bow_launch_cand("orbx_bowdb_search_candidates_device_compact", db, fr, batch, d_cand, cand_stride, d_ncand, d_kf_of_id, n_ids, nnratio,
+                           check_orientation, d_pairs, cap_pairs, d_nmatches, stream, 1);
 }
 
 // ---------------------------------------------------------------- MapPoint::ComputeDistinctiveDescriptors (f3)

@@ -202,6 +202,8 @@ def lib():
     L.orbx_bow_frames_read.argtypes = [vp, i, vp, vp, vp, ip, vp, vp, vp, ip]
     L.orbx_bowdb_search_batch_device.argtypes = [vp, vp, i, f, i, vp, vp, vp]
     L.orbx_bowdb_search_batch_device_compact.argtypes = [vp, vp, i, f, i, vp, i, vp, vp]
+    L.orbx_bowdb_search_candidates_device.argtypes = [vp, vp, i, vp, i, vp, vp, i, f, i, vp, vp, vp]
+    L.orbx_bowdb_search_candidates_device_compact.argtypes = [vp, vp, i, vp, i, vp, vp, i, f, i, vp, i, vp, vp]
     L.orbx_kfdb_create.argtypes = [i, i, C.POINTER(vp)]
     L.orbx_kfdb_destroy.argtypes = [vp]; L.orbx_kfdb_destroy.restype = None
     L.orbx_kfdb_size.argtypes = [vp]
@@ -832,6 +834,22 @@ class BowFrames:
         """the same search with compact results: d_pairs[batch][nkf][cap_pairs][2] int32 = (frame feature, keyframe feature) in frame-feature order,
         d_nmatches[batch][nkf] = counts (orbx_bowdb_search_batch_device_compact)"""
         _check(self._L.orbx_bowdb_search_batch_device_compact(db._h, self._h, batch, nnratio, int(checkOri), d_pairs, int(cap_pairs), d_nmatches, stream))
+
+    def search_candidates(self, db, batch, d_cand, cand_stride, d_ncand, d_match, d_nmatches, nnratio=0.75, checkOri=True, kf_of_id=None, n_ids=0,
+                          stream=None):
+        """frames 0..batch-1 against the keyframes their candidate lists name -- d_cand[batch][cand_stride], d_ncand[batch], device int32 as
+        KeyFrameDatabase.detect_relocalization_batch_device leaves them -- in one launch, the lists read on the device:
+        d_match[batch][cand_stride][cap], d_nmatches[batch][cand_stride] (-1 = slot not searched).  kf_of_id: optional device int32[n_ids], id ->
+        index into db (-1 = not in it); None: an id is the index (orbx_bowdb_search_candidates_device)"""
+        _check(self._L.orbx_bowdb_search_candidates_device(db._h, self._h, int(batch), d_cand, int(cand_stride), d_ncand, kf_of_id, int(n_ids), nnratio,
+                                                           int(checkOri), d_match, d_nmatches, stream))
+
+    def search_candidates_compact(self, db, batch, d_cand, cand_stride, d_ncand, d_pairs, cap_pairs, d_nmatches, nnratio=0.75, checkOri=True,
+                                  kf_of_id=None, n_ids=0, stream=None):
+        """the same with compact results: d_pairs[batch][cand_stride][cap_pairs][2] as search_compact writes them per keyframe
+        (orbx_bowdb_search_candidates_device_compact)"""
+        _check(self._L.orbx_bowdb_search_candidates_device_compact(db._h, self._h, int(batch), d_cand, int(cand_stride), d_ncand, kf_of_id, int(n_ids),
+                                                                   nnratio, int(checkOri), d_pairs, int(cap_pairs), d_nmatches, stream))
 
 
 def _bow_query(bow):

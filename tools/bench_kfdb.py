@@ -7,7 +7,10 @@ For 500 and 5000 live keyframes of ~1000 words in a vocabulary of 10^6 words, on
   4. chain (500 keyframes, 32 frames): images -> orbx_extract_batch_device -> orbx_bow_transform_batch_device -> orbx_kfdb_add_from_frames for the
      keyframes; for the query frames the same front end, then orbx_kfdb_detect_relocalization_batch_device and orbx_kf_search_by_bow_kfs_f on
      the returned candidates only -- beside orbx_bowdb_search_batch_device_compact over all keyframes on the same frames.  The candidate-only
-     matches must equal the corresponding rows of the all-keyframes search before a time is printed.
+     matches must equal the corresponding rows of the all-keyframes search before a time is printed.  A third route, timed in the same rounds:
+     orbx_kfdb_detect_relocalization_batch_device + orbx_bowdb_search_candidates_device_compact on one stream, one synchronise, no download
+     inside the clock; its lists must equal the all-keyframes rows too.
+--candidates [out] runs leg 4 alone, at 500 and at 5000 keyframes -> profiles/r07_reloc_candidates.txt.
 --trace runs a short per-call + batched sequence at 5000 keyframes and nothing else (the rocprofv3 --kernel-trace --stats pass)."""
 import os
 import struct
@@ -170,7 +173,7 @@ def chain(pkg, lines, nkf=500, B=BATCH, places=25, reps=10):
         assert ids == list(range(first, first + m))
         kfs += [featset(i, n, desc, kps, lambda k: (rng.random(k) < 0.6).astype(np.uint8)) for i in range(m)]
     for j in range(nkf):
-        mates = sorted((k for k in range(nkf) if k % places == j % places and k != j), key=lambda k: abs(k - j))
+        mates = sorted((k for k in range(j % places, nkf, places) if k != j), key=lambda k: abs(k - j))
         db.set_covisibility(j, mates[:8])
     resident = [pkg.DeviceKeyFrame(k) for k in kfs]                      # what the candidate ids are joined to
     bowdb = pkg.BowDatabase(kfs)
@@ -180,9 +183,11 @@ def chain(pkg, lines, nkf=500, B=BATCH, places=25, reps=10):
     d_pairs = torch.zeros((B, nkf, cap, 2), dtype=torch.int32, device="cuda"); d_nm = torch.zeros((B, nkf), dtype=torch.int32, device="cuda")
     ccap = 16
     d_cand = torch.zeros((B, ccap), dtype=torch.int32, device="cuda"); d_nc = torch.zeros(B, dtype=torch.int32, device="cuda")
+    d_cand3 = torch.zeros((B, ccap), dtype=torch.int32, device="cuda"); d_nc3 = torch.zeros(B, dtype=torch.int32, device="cuda")
+    d_pairs3 = torch.full((B, ccap, cap, 2), -7, dtype=torch.int32, device="cuda"); d_nm3 = torch.full((B, ccap), -9, dtype=torch.int32, device="cuda")
     matcher = pkg.ORBmatcher(0.75, True)
     torch.cuda.synchronize()
-    t_all, t_det, t_srch = [], [], []
+    t_all, t_det, t_srch, t_dev = [], [], [], []
     for rep in range(reps + 2):                                          # two warm-up rounds, the two forms alternating
         a = time.perf_counter()
         fr.search_compact(bowdb, B, d_pairs.data_ptr(), cap, d_nm.data_ptr(), 0.75, True, st)
@@ -198,19 +203,67 @@ def chain(pkg, lines, nkf=500, B=BATCH, places=25, reps=10):
             found.append((ids,) + (matcher.SearchByBoWKeyFramesFrameResident([resident[k] for k in ids], [kfs[k]["flag"] for k in ids], frames[i])
                                    if ids else (None, None)))
         d = time.perf_counter()
+        db.detect_relocalization_batch_device(fr, B, d_cand3.data_ptr(), ccap, d_nc3.data_ptr(), st)
+        fr.search_candidates_compact(bowdb, B, d_cand3.data_ptr(), ccap, d_nc3.data_ptr(), d_pairs3.data_ptr(), cap, d_nm3.data_ptr(), 0.75, True, stream=st)
+        stream.synchronize()
+        e = time.perf_counter()
         if rep >= 2:
-            t_all.append(b - a); t_det.append(c - b); t_srch.append(d - c)
+            t_all.append(b - a); t_det.append(c - b); t_srch.append(d - c); t_dev.append(e - d)
     # the candidate-only matches are the rows of the all-keyframes search
-    nm = d_nm.cpu().numpy(); pairs = d_pairs.cpu().numpy()
+    # (only the candidates' lists of the all-keyframes result come to the host: the whole of it is gigabytes at 5000 keyframes)
+    nm = d_nm.cpu().numpy()
+    sel = [(i, k) for i, (ids, _, _) in enumerate(found) for k in ids]
+    si = torch.tensor([p[0] for p in sel], dtype=torch.long, device="cuda"); sk = torch.tensor([p[1] for p in sel], dtype=torch.long, device="cuda")
+    pairs = dict(zip(sel, d_pairs[si, sk].cpu().numpy())) if sel else {}
     searched = matched = hit = 0
     for i, (ids, rows, cnt) in enumerate(found):
         hit += any(k % places == qplace[i] for k in ids)
         for j, k in enumerate(ids):
             f = np.nonzero(rows[j] >= 0)[0]
-            want = pairs[i, k, :nm[i, k]]
+            want = pairs[i, k][:nm[i, k]]
             if cnt[j] != nm[i, k] or len(f) != nm[i, k] or (want[:, 0] != f).any() or (want[:, 1] != rows[j][f]).any():
                 raise SystemExit(f"chain: frame {i}, keyframe {k}: the candidate-only search differs from the all-keyframes row ({cnt[j]} vs {nm[i, k]} matches)")
             searched += 1; matched += int(cnt[j])
+    # so are the lists of the device route, whose candidates are the downloaded route's
+    nc3 = d_nc3.cpu().numpy(); cand3 = d_cand3.cpu().numpy(); nm3 = d_nm3.cpu().numpy(); pairs3 = d_pairs3.cpu().numpy()
+    searched3 = 0
+    for i, (ids, _, _) in enumerate(found):
+        if [int(x) for x in cand3[i, :min(nc3[i], ccap)]] != ids:
+            raise SystemExit(f"chain: frame {i}: the two detect calls of a round returned different candidates")
+        if (nm3[i, len(ids):] != -1).any():
+            raise SystemExit(f"chain: frame {i}: a slot beyond the list is not marked -1")
+        for j, k in enumerate(ids):
+            if nm3[i, j] != nm[i, k] or (pairs3[i, j, :nm[i, k]] != pairs[i, k][:nm[i, k]]).any():
+                raise SystemExit(f"chain: frame {i}, slot {j}, keyframe {k}: the device list differs from the all-keyframes row ({nm3[i, j]} vs {nm[i, k]} matches)")
+            searched3 += 1
+    # the list launch alone, on the lists of the last round (launch + synchronise), compact and dense
+    d_rows3 = torch.zeros((B, ccap, cap), dtype=torch.int32, device="cuda")
+    t_list = {"compact": [], "dense": []}
+    for rep in range(reps + 2):
+        a = time.perf_counter()
+        fr.search_candidates_compact(bowdb, B, d_cand3.data_ptr(), ccap, d_nc3.data_ptr(), d_pairs3.data_ptr(), cap, d_nm3.data_ptr(), 0.75, True, stream=st)
+        stream.synchronize()
+        b = time.perf_counter()
+        fr.search_candidates(bowdb, B, d_cand3.data_ptr(), ccap, d_nc3.data_ptr(), d_rows3.data_ptr(), d_nm3.data_ptr(), 0.75, True, stream=st)
+        stream.synchronize()
+        if rep >= 2:
+            t_list["compact"].append(b - a); t_list["dense"].append(time.perf_counter() - b)
+    # the two kernel forms at about that many live pairs, by proxy: the all-keyframes entry point on two keyframes x B frames, dense rows (the
+    # wave form has no compact output and no list form)
+    small = pkg.BowDatabase(kfs[:2])
+    d_m2 = torch.zeros((B, 2, cap), dtype=torch.int32, device="cuda"); d_n2 = torch.zeros((B, 2), dtype=torch.int32, device="cuda")
+    t_form = {"table": [], "wave": []}
+    try:
+        for rep in range(reps + 2):
+            for form in ("table", "wave"):
+                pkg.orbx.debug_set_bow_form(form)
+                a = time.perf_counter()
+                fr.search(small, B, d_m2.data_ptr(), d_n2.data_ptr(), 0.75, True, st)
+                stream.synchronize()
+                if rep >= 2:
+                    t_form[form].append(time.perf_counter() - a)
+    finally:
+        pkg.orbx.debug_set_bow_form("auto")
     best_all = sum(int(nm[i].max() >= 15) for i in range(B))
     best_cand = sum(int(any(nm[i, k] >= 15 for k in ids)) for i, (ids, _, _) in enumerate(found))
     med = lambda t: float(np.median(t)) * 1e6
@@ -222,6 +275,15 @@ def chain(pkg, lines, nkf=500, B=BATCH, places=25, reps=10):
     lines.append(f"                 orbx_kf_search_by_bow_kfs_f per frame, resident keyframes  {searched:6d} (frame, keyframe) pairs searched   {med(t_srch):9.1f} us per batch")
     lines.append(f"                 together {med(t_det) + med(t_srch):9.1f} us per batch = {med(t_all) / (med(t_det) + med(t_srch)):.2f} x the all-keyframes search"
                  f" ({B * nkf / max(searched, 1):.0f} x fewer pairs)")
+    lines.append(f"candidates only, on the device: orbx_kfdb_detect_relocalization_batch_device + orbx_bowdb_search_candidates_device_compact, one stream, "
+                 f"one synchronise, nothing downloaded")
+    lines.append(f"                 {B} x {ccap} slots launched                                  {searched3:6d} (frame, keyframe) pairs searched   {med(t_dev):9.1f} us per batch"
+                 f" = {med(t_all) / med(t_dev):.2f} x the all-keyframes search, {(med(t_det) + med(t_srch)) / med(t_dev):.2f} x the download-and-call route")
+    lines.append(f"every device candidate list equals the all-keyframes list: yes ({searched3} lists, the candidates of the downloaded route)")
+    lines.append(f"the list launch alone (k_bow2_cand, {B} x {ccap} workgroups of which {searched3} work, launch + synchronise): compact lists "
+                 f"{med(t_list['compact']):.1f} us, dense rows {med(t_list['dense']):.1f} us")
+    lines.append(f"kernel forms at about that many live pairs, a proxy (orbx_bowdb_search_batch_device on 2 keyframes x {B} frames = {2 * B} workgroups, all live, "
+                 f"dense rows, launch + synchronise): table form (k_bow2) {med(t_form['table']):.1f} us, wave form (k_bow_wave) {med(t_form['wave']):.1f} us")
     lines.append(f"every candidate-only match row equals the all-keyframes row: yes ({searched} rows, {matched} matches); a keyframe of the query's own place "
                  f"among the candidates: {hit} of {B} frames; frames with a keyframe of >= 15 matches (Tracking.cc:1675): {best_cand} among the candidates, {best_all} among all")
     lines.append("(the query frame of orbx_kf_search_by_bow_kfs_f is a host feature set -- the Frame of a lost tracker lives on the host --, prepared outside the clock)")
@@ -250,6 +312,17 @@ def main():
     pkg = ge.build()
     if "--trace" in sys.argv:
         trace(pkg)
+        return
+    if "--candidates" in sys.argv:
+        out = args[0] if args else os.path.join(ROOT, "profiles", "r07_reloc_candidates.txt")
+        lines = ["# relocalisation search over the candidates only, on the device, beside the all-keyframes search and the download-and-call route "
+                 "(tools/bench_kfdb.py --candidates)", f"# device: {pkg.orbx.device_identity(0)}", ""]
+        chain(pkg, lines, nkf=500, places=25)
+        chain(pkg, lines, nkf=5000, places=250)
+        text = "\n".join(lines) + "\n"
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        open(out, "w").write(text)
+        print(text)
         return
     out = args[0] if args else os.path.join(ROOT, "profiles", "r06_kfdb.txt")
     lines = ["# KeyFrameDatabase queries: device-resident orbx_kfdb against one host core (tools/bench_kfdb.py)",
