@@ -265,7 +265,7 @@ __device__ __forceinline__ float2 dev_undistort(float2 s, const UndistortParams 
 }
 
 // ---- Frame::ComputeStereoFromRGBD (src/Frame.cc:754-774) after Tracking::GrabImageRGBD's depth conversion (src/Tracking.cc:232-233): k_rgbd_depth
-// (orbx_frame.hip) behind orbx_extract_rgbd, the pipelined RGB-D form (orbx_extract.hip) and orbx_rgbd_depth_batch_device.
+// (orbx_frame.hip) behind orbx_extract_rgbd, the pipelined RGB-D form (both orbx_hostapi.hip) and orbx_rgbd_depth_batch_device.
 struct RgbdArgs {
     UndistortParams up; int undistort;   // undistort: dist_coef[0] != 0 (src/Frame.cc:472-476)
     int depth_type, apply_scale; float scale, bf;

@@ -24,6 +24,8 @@
 #define ORBX_LAUNCH_FORM_FIELDS 9 // orbx_debug_launch_forms: pyramid regime, FAST waves + grid order, quadtree threads / tables / register mode, k_desc levels, stereo kpw / XCD grid
 #define ORBX_FAST_LIST_CAP 512 // k_fast: pretest candidates listed per round (u16 each); denser cells take several rounds
 
+static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
 // Geometry of one pyramid level for one image size (host computes, device reads).
 struct LevelGeom {
     int w, h, pitch;        // pitch in bytes of the stored level (levels >= 1)
@@ -80,13 +82,30 @@ struct ProfEvent { hipEvent_t a, b; int stage; bool owns_a; };
 struct PipeSlot {
     uint8_t *h_in, *d_in; size_t in_cap;     // both eyes, pinned host staging and device level 0
     uint8_t *h_in_dev, *h_out_dev;           // the addresses a kernel reads / writes the two pinned buffers at
-    uint8_t *h_out; size_t h_out_cap;        // pinned: [n0 n1 flag | keypoints x2 | descriptors x2 | uRight | depth]
+    uint8_t *h_out; size_t h_out_cap;        // pinned result block: orbx_result_layout(2, need)
     uint8_t *d_out;                          // one device block in the layout of h_out (a single download per frame)
     void *d_kps, *d_desc, *d_n; float *d_ur, *d_z; int out_cap;   // views into d_out
     hipEvent_t ev_h2d, ev_done, ev_d2h;      // input landed / kernels finished / results landed in h_out
     int cap, ticket, eyes; bool busy;       // eyes: 1 mono, 2 stereo, ORBX_PIPE_RGBD (one image + its depth)
     struct orbx_extractor *lane;             // the kernel lane (the handle or its shadow) that ran the slot's frame
 };
+
+// Byte layout of the block a host-pointer call's results land in (the pinned h_out of the synchronous forms; a pipeline slot's d_out and
+// h_out, always with images == 2): [counts | keypoints x images | descriptors x images | uRight | depth | xy], `need` entries per image.
+struct ResultLayout { size_t kps, desc, ur, z, xy, bytes; };   // the counts are ints at offset 0; a pipelined frame's kernel error flag is int index 2
+static inline ResultLayout orbx_result_layout(int images, int need)
+{
+    const size_t n = (size_t)need, col = align_up(4 * n, 64);
+    ResultLayout L;
+    L.kps = align_up(sizeof(int) * ((size_t)images + 1), 64);
+    L.desc = L.kps + align_up(sizeof(orbx_keypoint) * n * images, 64);
+    L.ur = L.desc + align_up(32 * n * images, 64);
+    L.z = L.ur + col;
+    // a pipeline slot always holds two images: an RGB-D frame, which extracts one, keeps its xy rows in the unused second-eye keypoint rows
+    L.xy = images == 2 ? L.kps + align_up(sizeof(orbx_keypoint) * n, 64) : L.z + col;
+    L.bytes = images == 2 ? L.z + col : L.xy + 8 * n;
+    return L;
+}
 #define ORBX_PIPE_DEPTH 4
 #define ORBX_PIPE_RGBD 3                     // PipeSlot::eyes of an RGB-D frame
 
@@ -111,7 +130,7 @@ struct orbx_extractor {
     void *d_pairs; size_t pairs_cap;       // per-pair records of k_fast2 (PairRec, orbx_extract.hip)
     int last_fast_form;                    // debug: 1 = k_fast, 2 = k_fast2 ran in the most recent extraction
     int32_t last_forms[ORBX_LAUNCH_FORM_FIELDS]; // debug: launch forms of the most recent extraction / stereo launch (orbx_debug_launch_forms)
-    int fast_pair;                         // ORBX_FAST_PAIR: -1 = k_fast2 for batches, 0 = never, 1 = always
+    int fast_pair;                         // ORBX_FAST_PAIR: 1 = k_fast2 wherever the geometry allows it, 0 (default) = never
     // workspace (sized for max_w x max_h x max_batch)
     uint8_t *d_pyr; size_t pyr_cap;        // levels >= 1, all images
     uint8_t *d_stage_in; size_t stage_in_cap; // host-API input staging (level 0)
@@ -203,6 +222,17 @@ int orbx_bow_run_legacy(int mode, int device, const orbx_featset *as, int na, co
 int orbx_bow_forced_form();
 #define ORBX_HIP(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { \
     orbx_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); return ORBX_E_HIP; } } while (0)
+
+// grows a device buffer (never shrinks it; the old contents are dropped)
+template <class T>
+static inline int ensure(T **p, size_t *cap, size_t need)
+{
+    if (need <= *cap && *p) return ORBX_OK;
+    if (*p) { ORBX_HIP(hipFree(*p)); *p = nullptr; *cap = 0; }
+    ORBX_HIP(hipMalloc((void **)p, need ? need : 16));
+    *cap = need;
+    return ORBX_OK;
+}
 
 // hipSetDevice only when the calling thread is on another device (a read of the thread's current device is cheaper than the set, and the
 // hot host paths -- a pipelined submit makes three API entries per frame -- call it every time)
