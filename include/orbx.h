@@ -353,8 +353,11 @@ typedef struct orbx_kf orbx_kf;
 int orbx_kf_create(int device, const orbx_featset *fs, orbx_kf **out);
 void orbx_kf_destroy(orbx_kf *k);
 int orbx_kf_size(const orbx_kf *k);
-/* The per-call matchers keep a small per-THREAD context per device (a stream, mapped pinned blobs, device scratch).  It is given back
- * when the thread ends; a long-lived thread that is done matching (or a pool worker between jobs) may give it back now. */
+/* Every per-call search keeps a small per-THREAD context per device: a stream plus pinned and device staging.  There are four families:
+ * the per-call matchers (SearchByBoW, SearchForTriangulation and their orbx_kf_ forms), the legacy SearchByBoW kernels (a forced form or
+ * an oversized node) with orbx_distinctive_descriptors, the projection searches with the orbx_frame_ calls, and
+ * orbx_undistort_keypoints.  All of them are given back when the thread ends; a long-lived thread that is done searching (or a pool
+ * worker between jobs) may give them back now.  The next call of the thread sets up what it needs again. */
 void orbx_thread_release(void);
 /* SearchByBoW(pKF, F): kf_flag as orbx_search_by_bow_kf_f's kf->flag; match_f[f's n] */
 int orbx_kf_search_by_bow_kf_f(const orbx_kf *kf, const uint8_t *kf_flag, const orbx_kf *f,
@@ -694,6 +697,9 @@ int orbx_debug_set_match_items(int in_memory);
 /* host phases of the calling thread's most recent per-call matcher search (orbx_match.hip), microseconds:
  * [0] prepare (node intersection, participation bytes, packing), [1] launch, [2] wait for the kernel's ticket, [3] copy-out */
 int orbx_debug_match_timing(double *out4);
+/* process-wide: the per-thread search contexts (see orbx_thread_release) that are set up right now, over all threads, families and
+ * devices.  A thread's share leaves the count when it calls orbx_thread_release or ends. */
+int orbx_debug_thread_contexts(void);
 
 #ifdef __cplusplus
 }

@@ -19,17 +19,6 @@
 #define BOW_TH_LOW 50
 #define BOW_HISTO 30
 
-// rotation bin of src/ORBmatcher.cc:253-258 (factor = 1/30 with HISTO_LENGTH = 30: upstream quirk kept)
-__device__ __forceinline__ int rot_bin(float a1, float a2)
-{
-    const float factor = 1.0f / BOW_HISTO;
-    float rot = a1 - a2;
-    if (rot < 0.0f) rot += 360.0f;
-    int bin = (int)roundf(rot * factor);
-    if (bin == BOW_HISTO) bin = 0;
-    return (unsigned)bin < BOW_HISTO ? bin : 0; // the reference asserts the range; NaN / huge angles must not index out of the histogram
-}
-
 __device__ __forceinline__ int find_node(const uint32_t *ids, int n, uint32_t key)
 {
     int lo = 0, hi = n;
@@ -629,60 +618,37 @@ static int bow_launch(int npairs_x, int nframes_y, int max_b, int max_slots, hip
 
 // ---------------------------------------------------------------- host side
 
-struct BowCtx {
-    int device = -1;
-    hipStream_t stream = nullptr;
+struct BowCtx : ThreadCtx {
     uint8_t *h_blob = nullptr; size_t h_cap = 0;   // pinned staging
     uint8_t *d_blob = nullptr; size_t d_cap = 0;
     int32_t *d_out = nullptr; size_t out_cap = 0;  // match / pairs / counts
     int32_t *h_out = nullptr; size_t h_out_cap = 0;
-};
-static thread_local BowCtx g_bow[16];
-
-static int bow_ctx(int device, BowCtx **out)
-{
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev || device >= 16) {
-        orbx_set_error("no usable HIP device %d (liborbx has no CPU fallback)", device);
-        return ORBX_E_NO_DEVICE;
+    void release()
+    {
+        if (orbx_ctx_leave(this)) {
+            if (h_blob) (void)hipHostFree(h_blob);
+            if (d_blob) (void)hipFree(d_blob);
+            if (d_out) (void)hipFree(d_out);
+            if (h_out) (void)hipHostFree(h_out);
+        }
+        h_blob = d_blob = nullptr; d_out = h_out = nullptr;
+        h_cap = d_cap = out_cap = h_out_cap = 0;
     }
-    ORBX_HIP(hipSetDevice(device));
-    BowCtx *c = &g_bow[device];
-    if (!c->stream) { ORBX_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)); c->device = device; }
-    *out = c;
-    return ORBX_OK;
-}
+    ~BowCtx() { release(); }
+};
+static thread_local BowCtx g_bow[ORBX_MAX_DEVICES];
+void orbx_bow_thread_release() { for (BowCtx &c : g_bow) c.release(); }
 
 static int bow_reserve(BowCtx *c, size_t blob, size_t out_ints)
 {
-    if (blob > c->h_cap) {
-        if (c->h_blob) ORBX_HIP(hipHostFree(c->h_blob));
-        c->h_blob = nullptr;
-        ORBX_HIP(hipHostMalloc((void **)&c->h_blob, blob * 2, hipHostMallocDefault));
-        c->h_cap = blob * 2;
-    }
-    if (blob > c->d_cap) {
-        if (c->d_blob) ORBX_HIP(hipFree(c->d_blob));
-        c->d_blob = nullptr;
-        ORBX_HIP(hipMalloc((void **)&c->d_blob, blob * 2));
-        c->d_cap = blob * 2;
-    }
-    if (out_ints > c->out_cap) {
-        if (c->d_out) ORBX_HIP(hipFree(c->d_out));
-        c->d_out = nullptr;
-        ORBX_HIP(hipMalloc((void **)&c->d_out, out_ints * 2 * sizeof(int32_t)));
-        c->out_cap = out_ints * 2;
-    }
-    if (out_ints > c->h_out_cap) {
-        if (c->h_out) ORBX_HIP(hipHostFree(c->h_out));
-        c->h_out = nullptr;
-        ORBX_HIP(hipHostMalloc((void **)&c->h_out, out_ints * 2 * sizeof(int32_t), hipHostMallocDefault));
-        c->h_out_cap = out_ints * 2;
-    }
-    return ORBX_OK;
+    const size_t out = out_ints * sizeof(int32_t);
+    int rc = ORBX_OK;
+    if (blob > c->h_cap) rc = ensure_pinned(&c->h_blob, &c->h_cap, 2 * blob);
+    if (!rc && blob > c->d_cap) rc = ensure(&c->d_blob, &c->d_cap, 2 * blob);
+    if (!rc && out > c->out_cap) rc = ensure(&c->d_out, &c->out_cap, 2 * out);
+    if (!rc && out > c->h_out_cap) rc = ensure_pinned(&c->h_out, &c->h_out_cap, 2 * out);
+    return rc;
 }
-
-static size_t a16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 int orbx_feat_validate(const orbx_featset *f, int need_geom, int need_flag)
 {
@@ -791,7 +757,7 @@ int orbx_bow_run_legacy(int mode, int device, const orbx_featset *as, int na, co
     const int stride = mode == 0 ? b->n : max_slots;
     if (mode == 0) max_slots = b->n;
     BowCtx *c;
-    int rc = bow_ctx(device, &c);
+    int rc = orbx_ctx_get(g_bow, device, &c);
     if (rc) return rc;
     const size_t out_ints = (size_t)na * (stride > 0 ? stride : 1) + na;
     if ((rc = bow_reserve(c, blob, out_ints))) return rc;
@@ -823,7 +789,8 @@ struct orbx_bowdb {
     hipStream_t stream;
     uint8_t *h_f; size_t h_f_cap;   // pinned staging of the frame side
     uint8_t *d_f; size_t d_f_cap;
-    int32_t *d_out; int32_t *h_out; size_t out_cap;
+    int32_t *d_out; size_t out_cap;
+    int32_t *h_out; size_t h_out_cap;
 };
 
 extern "C" int orbx_bowdb_create(int device, const orbx_featset *kfs, int nkf, orbx_bowdb **out)
@@ -836,7 +803,7 @@ extern "C" int orbx_bowdb_create(int device, const orbx_featset *kfs, int nkf, o
         blob += feat_bytes(&kfs[i], 0);
     }
     BowCtx *c;
-    int rc = bow_ctx(device, &c); // validates the device
+    int rc = orbx_ctx_get(g_bow, device, &c); // validates the device
     if (rc) return rc;
     orbx_bowdb *db = new orbx_bowdb();
     memset(db, 0, sizeof *db);
@@ -878,35 +845,22 @@ extern "C" int orbx_bowdb_search(orbx_bowdb *db, const orbx_featset *f, float nn
     if (!orbx_feat_validate(f, 0, 1)) { orbx_set_error("orbx_bowdb_search: malformed feature set"); return ORBX_E_INVALID; }
     ORBX_HIP(hipSetDevice(db->device));
     const size_t fb = a16(sizeof(DevFeat)) + feat_bytes(f, 0);
-    if (fb > db->h_f_cap) {
-        if (db->h_f) ORBX_HIP(hipHostFree(db->h_f));
-        if (db->d_f) ORBX_HIP(hipFree(db->d_f));
-        db->h_f = nullptr; db->d_f = nullptr;
-        ORBX_HIP(hipHostMalloc((void **)&db->h_f, fb * 2, hipHostMallocDefault));
-        ORBX_HIP(hipMalloc((void **)&db->d_f, fb * 2));
-        db->h_f_cap = db->d_f_cap = fb * 2;
-    }
+    int rc = ORBX_OK;
+    if (fb > db->h_f_cap) rc = ensure_pinned(&db->h_f, &db->h_f_cap, 2 * fb);
+    if (!rc && fb > db->d_f_cap) rc = ensure(&db->d_f, &db->d_f_cap, 2 * fb);
     const int stride = f->n > 0 ? f->n : 1;
-    const size_t out_ints = (size_t)db->nkf * stride + db->nkf;
-    if (out_ints > db->out_cap) {
-        if (db->d_out) ORBX_HIP(hipFree(db->d_out));
-        if (db->h_out) ORBX_HIP(hipHostFree(db->h_out));
-        db->d_out = nullptr; db->h_out = nullptr;
-        ORBX_HIP(hipMalloc((void **)&db->d_out, out_ints * 2 * sizeof(int32_t)));
-        ORBX_HIP(hipHostMalloc((void **)&db->h_out, out_ints * 2 * sizeof(int32_t), hipHostMallocDefault));
-        db->out_cap = out_ints * 2;
-    }
+    const size_t out_ints = (size_t)db->nkf * stride + db->nkf, out = out_ints * sizeof(int32_t);
+    if (!rc && out > db->out_cap) rc = ensure(&db->d_out, &db->out_cap, 2 * out);
+    if (!rc && out > db->h_out_cap) rc = ensure_pinned(&db->h_out, &db->h_out_cap, 2 * out);
+    if (rc) return rc;
     DevFeat *hd = (DevFeat *)db->h_f;
     size_t off = a16(sizeof(DevFeat));
     feat_pack(f, 0, db->h_f, db->d_f, &off, hd);
     ORBX_HIP(hipMemcpyAsync(db->d_f, db->h_f, off, hipMemcpyHostToDevice, db->stream));
     int32_t *d_match = db->d_out;
     int *d_n = db->d_out + (size_t)db->nkf * stride;
-    {
-        const int rc = bow_launch<0>(db->nkf, 1, f->n, f->n, db->stream, (const DevFeat *)db->d_blob, (const DevFeat *)db->d_f, 1, nnratio,
-                                     check_orientation, d_match, f->n, d_n);
-        if (rc) return rc;
-    }
+    if ((rc = bow_launch<0>(db->nkf, 1, f->n, f->n, db->stream, (const DevFeat *)db->d_blob, (const DevFeat *)db->d_f, 1, nnratio,
+                            check_orientation, d_match, f->n, d_n))) return rc;
     ORBX_HIP(hipMemcpyAsync(db->h_out, db->d_out, out_ints * sizeof(int32_t), hipMemcpyDeviceToHost, db->stream));
     ORBX_HIP(hipStreamSynchronize(db->stream));
     if (f->n) memcpy(match_f, db->h_out, sizeof(int32_t) * (size_t)db->nkf * f->n);
@@ -1046,7 +1000,7 @@ extern "C" int orbx_distinctive_descriptors(int device, const uint8_t *desc, con
         if (n > max_n) max_n = n;
     }
     BowCtx *c;
-    int rc = bow_ctx(device, &c);
+    int rc = orbx_ctx_get(g_bow, device, &c);
     if (rc) return rc;
     const size_t total = (size_t)off[npoints];
     const size_t b_desc = a16(total * 32), b_off = a16(sizeof(int32_t) * ((size_t)npoints + 1));

@@ -1,5 +1,6 @@
 // orbx_common.hip — error reporting, device query, profiling hooks, host Hamming.
 #include "orbx_internal.h"
+#include <atomic>
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -21,6 +22,55 @@ extern "C" int orbx_device_count(void)
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
     return n;
+}
+
+static int no_device(int device)
+{
+    orbx_set_error("no usable HIP device %d (liborbx has no CPU fallback)", device);
+    return ORBX_E_NO_DEVICE;
+}
+
+int orbx_check_device(int device)
+{
+    int ndev = 0;
+    return hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev ? no_device(device) : ORBX_OK;
+}
+
+// ---- per-thread contexts of the per-call searches (ThreadCtx, orbx_internal.h)
+
+static std::atomic<int> g_thread_contexts{0};   // set-up contexts of all threads: what a test watches to see them given back
+extern "C" int orbx_debug_thread_contexts(void) { return g_thread_contexts.load(std::memory_order_relaxed); }
+
+int orbx_ctx_enter(ThreadCtx *c, int device)
+{
+    if (c && c->stream) { ORBX_HIP(orbx_use_device(device)); return ORBX_OK; }   // steady state: this thread has used the device before
+    if (int rc = orbx_check_device(device)) return rc;
+    if (!c) return no_device(device);
+    ORBX_HIP(hipSetDevice(device));
+    ORBX_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    c->device = device;
+    g_thread_contexts.fetch_add(1, std::memory_order_relaxed);
+    return ORBX_OK;
+}
+
+bool orbx_ctx_leave(ThreadCtx *c)
+{
+    if (c->device < 0) return false;
+    g_thread_contexts.fetch_sub(1, std::memory_order_relaxed);   // the context is gone either way
+    int ndev = 0;
+    const bool live = hipGetDeviceCount(&ndev) == hipSuccess && c->device < ndev && hipSetDevice(c->device) == hipSuccess;   // (a runtime that is already shutting down: leave it alone)
+    if (live) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
+    c->stream = nullptr; c->device = -1;
+    return live;
+}
+
+// the calling thread's contexts of the four families on every device, now (they are also released when the thread ends)
+extern "C" void orbx_thread_release(void)
+{
+    orbx_match_thread_release();
+    orbx_bow_thread_release();
+    orbx_proj_thread_release();
+    orbx_frame_thread_release();
 }
 
 // "<pci bus id> <uuid hex> <name>" of device `device`: what an N-rank launch prints per rank so that a reader can see that every

@@ -234,6 +234,17 @@ __device__ __forceinline__ int hamming256(const uint32_t *a, const uint32_t *b)
     return d;
 }
 
+// rotation bin of src/ORBmatcher.cc:253-258 (factor = 1/30 with HISTO_LENGTH = 30: upstream quirk kept)
+__device__ __forceinline__ int rot_bin(float a1, float a2)
+{
+    const float factor = 1.0f / 30;
+    float rot = a1 - a2;
+    if (rot < 0.0f) rot += 360.0f;
+    int bin = (int)roundf(rot * factor);
+    if (bin == 30) bin = 0;
+    return (unsigned)bin < 30 ? bin : 0; // the reference asserts the range; NaN / huge angles must not index out of the histogram
+}
+
 // ---- Frame::UndistortKeyPoints (src/Frame.cc:470-515) on one point: cv::undistortPoints(mat, mat, mK, mDistCoef, cv::Mat(), mK).  Shared by
 // k_undistort (orbx_frame.hip) and the resident-frame ingest (orbx_proj.hip) so that both give the same bits (-ffp-contract=off in both).
 struct UndistortParams { double fx, fy, ifx, ify, cx, cy, k[5]; };

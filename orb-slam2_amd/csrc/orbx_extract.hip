@@ -2521,17 +2521,8 @@ int orbx_prepare_geometry(orbx_extractor *e, int w, int h)
     if ((rc = ensure(&e->d_cell_cnt, &e->cell_cnt_cap, (size_t)G.total_cells * B * 4))) return rc;
     if ((rc = ensure(&e->d_cand, &e->cand_cap, (size_t)G.cand_total * B * 4))) return rc;
     if ((rc = ensure(&e->d_cand_prim, &e->cand_prim_cap, (size_t)G.total_cells * B * ORBX_CAND_PRIM * 4))) return rc;
-    {
-        size_t need = (size_t)G.cand_total * B;
-        if (need > e->tree_cap || !e->d_tree_pts) {
-            if (e->d_tree_pts) ORBX_HIP(hipFree(e->d_tree_pts));
-            if (e->d_tree_nid) ORBX_HIP(hipFree(e->d_tree_nid));
-            e->d_tree_pts = nullptr; e->d_tree_nid = nullptr;
-            ORBX_HIP(hipMalloc((void **)&e->d_tree_pts, need * 4));
-            ORBX_HIP(hipMalloc((void **)&e->d_tree_nid, need * 2));
-            e->tree_cap = need;
-        }
-    }
+    if ((rc = ensure(&e->d_tree_pts, &e->tree_pts_cap, (size_t)G.cand_total * B * 4))) return rc;
+    if ((rc = ensure(&e->d_tree_nid, &e->tree_nid_cap, (size_t)G.cand_total * B * 2))) return rc;
     if ((rc = ensure(&e->d_lvl_kp, &e->lvl_kp_cap, (size_t)G.kp_total * B * 4))) return rc;
     if (!tree_tab_in_lds(G) && (rc = ensure(&e->d_tree_tab, &e->tree_tab_cap, align_up(tree_tab_bytes(G), 256) * e->nlevels * B))) return rc;
     e->rt_kps = nullptr;
@@ -3036,9 +3027,7 @@ int orbx_scratch(orbx_extractor *e, int slot, size_t bytes, void **out)
 {
     if (bytes > e->scratch_cap[slot] || !e->scratch[slot]) {
         { const int qrc = orbx_quiesce(e); if (qrc) return qrc; }
-        if (e->scratch[slot]) { ORBX_HIP(hipFree(e->scratch[slot])); e->scratch[slot] = nullptr; e->scratch_cap[slot] = 0; }
-        ORBX_HIP(hipMalloc(&e->scratch[slot], bytes ? bytes : 16));
-        e->scratch_cap[slot] = bytes;
+        { const int rc = ensure(&e->scratch[slot], &e->scratch_cap[slot], bytes); if (rc) return rc; }
     }
     *out = e->scratch[slot];
     return ORBX_OK;

@@ -16,8 +16,24 @@ __global__ __launch_bounds__(256) void k_undistort(const float2 *__restrict__ in
     out[i] = dev_undistort(in[i], p);   // orbx_device.h: the same arithmetic the resident-frame ingest runs (orbx_proj.hip)
 }
 
-struct FrameCtx { hipStream_t stream = nullptr; float2 *d_in = nullptr, *d_out = nullptr; float2 *h = nullptr; size_t cap = 0; };
-static thread_local FrameCtx g_frame[16];
+struct FrameCtx : ThreadCtx {
+    float2 *d_in = nullptr; size_t in_cap = 0;
+    float2 *d_out = nullptr; size_t out_cap = 0;
+    float2 *h = nullptr; size_t h_cap = 0;
+    void release()
+    {
+        if (orbx_ctx_leave(this)) {
+            if (d_in) (void)hipFree(d_in);
+            if (d_out) (void)hipFree(d_out);
+            if (h) (void)hipHostFree(h);
+        }
+        d_in = d_out = h = nullptr;
+        in_cap = out_cap = h_cap = 0;
+    }
+    ~FrameCtx() { release(); }
+};
+static thread_local FrameCtx g_frame[ORBX_MAX_DEVICES];
+void orbx_frame_thread_release() { for (FrameCtx &c : g_frame) c.release(); }
 
 extern "C" int orbx_undistort_keypoints(int device, const float *xy, int n, float fx, float fy, float cx, float cy,
                                         const float *dist_coef, int ndist, float *xy_out)
@@ -31,33 +47,21 @@ extern "C" int orbx_undistort_keypoints(int device, const float *xy, int n, floa
         if (xy_out != xy) memcpy(xy_out, xy, sizeof(float) * 2 * (size_t)n);
         return ORBX_OK;
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev || device >= 16) {
-        orbx_set_error("no usable HIP device %d (liborbx has no CPU fallback)", device);
-        return ORBX_E_NO_DEVICE;
-    }
-    ORBX_HIP(hipSetDevice(device));
-    FrameCtx *c = &g_frame[device];
-    if (!c->stream) ORBX_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    if ((size_t)n > c->cap) {
-        if (c->d_in) ORBX_HIP(hipFree(c->d_in));
-        if (c->d_out) ORBX_HIP(hipFree(c->d_out));
-        if (c->h) ORBX_HIP(hipHostFree(c->h));
-        c->d_in = c->d_out = c->h = nullptr;
-        const size_t cap = (size_t)n * 2;
-        ORBX_HIP(hipMalloc((void **)&c->d_in, sizeof(float2) * cap));
-        ORBX_HIP(hipMalloc((void **)&c->d_out, sizeof(float2) * cap));
-        ORBX_HIP(hipHostMalloc((void **)&c->h, sizeof(float2) * cap, hipHostMallocDefault));
-        c->cap = cap;
-    }
+    FrameCtx *c;
+    int rc = orbx_ctx_get(g_frame, device, &c);
+    const size_t bytes = sizeof(float2) * (size_t)n;
+    if (!rc && bytes > c->in_cap) rc = ensure(&c->d_in, &c->in_cap, 2 * bytes);
+    if (!rc && bytes > c->out_cap) rc = ensure(&c->d_out, &c->out_cap, 2 * bytes);
+    if (!rc && bytes > c->h_cap) rc = ensure_pinned(&c->h, &c->h_cap, 2 * bytes);
+    if (rc) return rc;
     const UndistortParams p = orbx_undistort_params(fx, fy, cx, cy, dist_coef, ndist);
-    memcpy(c->h, xy, sizeof(float2) * (size_t)n);
-    ORBX_HIP(hipMemcpyAsync(c->d_in, c->h, sizeof(float2) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    memcpy(c->h, xy, bytes);
+    ORBX_HIP(hipMemcpyAsync(c->d_in, c->h, bytes, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_undistort, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->d_in, c->d_out, n, p);
     ORBX_HIP(hipGetLastError());
-    ORBX_HIP(hipMemcpyAsync(c->h, c->d_out, sizeof(float2) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    ORBX_HIP(hipMemcpyAsync(c->h, c->d_out, bytes, hipMemcpyDeviceToHost, c->stream));
     ORBX_HIP(hipStreamSynchronize(c->stream));
-    memcpy(xy_out, c->h, sizeof(float2) * (size_t)n);
+    memcpy(xy_out, c->h, bytes);
     return ORBX_OK;
 }
 
@@ -138,11 +142,7 @@ extern "C" int orbx_rgbd_depth_batch_device(int device, const void *d_kps, const
     RgbdArgs a;
     int rc = orbx_rgbd_args("orbx_rgbd_depth_batch_device", p, w, h, depth_pitch, &a);
     if (rc) return rc;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-        orbx_set_error("no usable HIP device %d (liborbx has no CPU fallback)", device);
-        return ORBX_E_NO_DEVICE;
-    }
+    if ((rc = orbx_check_device(device))) return rc;
     ORBX_HIP(orbx_use_device(device));
     a.depth = (const uint8_t *)d_depth; a.depth_img_stride = (long long)depth_img_stride;
     a.kps = (const orbx_keypoint *)d_kps; a.n = (const int *)d_n; a.cap = cap;

@@ -26,15 +26,6 @@ int orbx_ensure_out_staging(orbx_extractor *e, int batch, int cap)
     return ORBX_OK;
 }
 
-static int ensure_pinned(uint8_t **p, size_t *cap, size_t need)
-{
-    if (need <= *cap && *p) return ORBX_OK;
-    if (*p) { ORBX_HIP(hipHostFree(*p)); *p = nullptr; *cap = 0; }
-    ORBX_HIP(hipHostMalloc((void **)p, need ? need : 16, hipHostMallocDefault));
-    *cap = need;
-    return ORBX_OK;
-}
-
 // What the synchronous host-pointer forms share.  begin: device, geometry, capacity check, level-0 and output staging on the device, the
 // layout of the pinned result block.  stage: rows repitched into the pinned input staging (a pageable 2-D copy is executed row by row by
 // the runtime); the caller uploads them to where its form wants them.  extract: the extraction of the staged level 0.  finish: the whole
@@ -305,29 +296,17 @@ static int pipe_slot_prepare(orbx_extractor *e, PipeSlot &s, size_t in_bytes, in
         ORBX_HIP(hipEventCreateWithFlags(&s.ev_done, hipEventDisableTiming));
         ORBX_HIP(hipEventCreateWithFlags(&s.ev_d2h, hipEventDisableTiming));
     }
-    if (in_bytes > s.in_cap) {
-        if (s.h_in) ORBX_HIP(hipHostFree(s.h_in));
-        if (s.d_in) ORBX_HIP(hipFree(s.d_in));
-        s.h_in = nullptr; s.d_in = nullptr; s.in_cap = 0;
-        ORBX_HIP(hipHostMalloc((void **)&s.h_in, in_bytes, hipHostMallocDefault));
+    int rc;
+    if (in_bytes > s.h_in_cap) {
+        if ((rc = ensure_pinned(&s.h_in, &s.h_in_cap, in_bytes))) return rc;
         ORBX_HIP(hipHostGetDevicePointer((void **)&s.h_in_dev, s.h_in, 0));
-        ORBX_HIP(hipMalloc((void **)&s.d_in, in_bytes));
-        s.in_cap = in_bytes;
     }
+    if ((rc = ensure(&s.d_in, &s.d_in_cap, in_bytes))) return rc;
     const ResultLayout L = orbx_result_layout(2, need);
-    const size_t out_bytes = L.bytes;
-    if (need > s.out_cap) {
-        if (s.d_out) ORBX_HIP(hipFree(s.d_out));
-        s.d_out = nullptr; s.out_cap = 0;
-        ORBX_HIP(hipMalloc((void **)&s.d_out, out_bytes));
-        s.out_cap = need;
-    }
-    if (out_bytes > s.h_out_cap) {
-        if (s.h_out) ORBX_HIP(hipHostFree(s.h_out));
-        s.h_out = nullptr; s.h_out_cap = 0;
-        ORBX_HIP(hipHostMalloc((void **)&s.h_out, out_bytes, hipHostMallocDefault));
+    if ((rc = ensure(&s.d_out, &s.d_out_cap, L.bytes))) return rc;
+    if (L.bytes > s.h_out_cap) {
+        if ((rc = ensure_pinned(&s.h_out, &s.h_out_cap, L.bytes))) return rc;
         ORBX_HIP(hipHostGetDevicePointer((void **)&s.h_out_dev, s.h_out, 0));
-        s.h_out_cap = out_bytes;
     }
     // the views follow `need` (the layout of this frame), not the capacity the block was allocated for
     s.d_n = s.d_out; s.d_kps = s.d_out + L.kps; s.d_desc = s.d_out + L.desc;

@@ -7,6 +7,7 @@
 #include "../../include/orbx.h"
 
 #define ORBX_MAX_LEVELS 16
+#define ORBX_MAX_DEVICES 16   // the per-thread context arrays have this size: the per-call searches refuse a device index at or beyond it
 #define ORBX_EDGE 19          // EDGE_THRESHOLD, reference src/ORBextractor.cc:74
 #define ORBX_MIN_BORDER 16    // EDGE_THRESHOLD-3, src/ORBextractor.cc:934
 #define ORBX_TILE_PITCH 80    // LDS pitch of a FAST cell tile when a cell is wider than 38 px (cell side <= 59 + 6 halo + 1): 3 rows per direct load
@@ -25,6 +26,7 @@
 #define ORBX_FAST_LIST_CAP 512 // k_fast: pretest candidates listed per round (u16 each); denser cells take several rounds
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+static inline size_t a16(size_t v) { return align_up(v, 16); }   // the sub-block alignment of every staging blob
 
 // Geometry of one pyramid level for one image size (host computes, device reads).
 struct LevelGeom {
@@ -80,11 +82,11 @@ struct ProfEvent { hipEvent_t a, b; int stage; bool owns_a; };
 
 // One frame in flight of the pipelined host-pointer stereo path (orbx_extract_stereo_submit / _wait)
 struct PipeSlot {
-    uint8_t *h_in, *d_in; size_t in_cap;     // both eyes, pinned host staging and device level 0
+    uint8_t *h_in, *d_in; size_t h_in_cap, d_in_cap;   // both eyes, pinned host staging and device level 0
     uint8_t *h_in_dev, *h_out_dev;           // the addresses a kernel reads / writes the two pinned buffers at
     uint8_t *h_out; size_t h_out_cap;        // pinned result block: orbx_result_layout(2, need)
-    uint8_t *d_out;                          // one device block in the layout of h_out (a single download per frame)
-    void *d_kps, *d_desc, *d_n; float *d_ur, *d_z; int out_cap;   // views into d_out
+    uint8_t *d_out; size_t d_out_cap;        // one device block in the layout of h_out (a single download per frame)
+    void *d_kps, *d_desc, *d_n; float *d_ur, *d_z;   // views into d_out
     hipEvent_t ev_h2d, ev_done, ev_d2h;      // input landed / kernels finished / results landed in h_out
     int cap, ticket, eyes; bool busy;       // eyes: 1 mono, 2 stereo, ORBX_PIPE_RGBD (one image + its depth)
     struct orbx_extractor *lane;             // the kernel lane (the handle or its shadow) that ran the slot's frame
@@ -137,7 +139,7 @@ struct orbx_extractor {
     int *d_cell_cnt; size_t cell_cnt_cap;
     uint32_t *d_cand; size_t cand_cap;
     uint32_t *d_cand_prim; size_t cand_prim_cap;   // [max_batch][total_cells][ORBX_CAND_PRIM]
-    uint32_t *d_tree_pts; uint16_t *d_tree_nid; size_t tree_cap; // overflow scratch of the quadtree
+    uint32_t *d_tree_pts; size_t tree_pts_cap; uint16_t *d_tree_nid; size_t tree_nid_cap; // overflow scratch of the quadtree
     unsigned char *d_tree_tab; size_t tree_tab_cap; // quadtree node tables of configurations whose tables exceed the LDS (else unused)
     int *d_lvl_cnt;                        // [max_batch][nlevels]
     uint32_t *d_lvl_kp; size_t lvl_kp_cap; // [max_batch][kp_total]
@@ -223,13 +225,26 @@ int orbx_bow_forced_form();
 #define ORBX_HIP(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { \
     orbx_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); return ORBX_E_HIP; } } while (0)
 
-// grows a device buffer (never shrinks it; the old contents are dropped)
+// grow a device / a pinned host buffer to at least `need` bytes (never shrinks it; the old contents are dropped).  On every return path,
+// failure included, *cap is at most what *p holds and *p == nullptr implies *cap == 0: a failed growth can never leave a stale
+// capacity next to a null pointer for the next, smaller request to write through.
 template <class T>
 static inline int ensure(T **p, size_t *cap, size_t need)
 {
     if (need <= *cap && *p) return ORBX_OK;
-    if (*p) { ORBX_HIP(hipFree(*p)); *p = nullptr; *cap = 0; }
-    ORBX_HIP(hipMalloc((void **)p, need ? need : 16));
+    if (*p) ORBX_HIP(hipFree(*p));
+    *p = nullptr; *cap = 0;
+    if (hipError_t e = hipMalloc((void **)p, need ? need : 16)) { *p = nullptr; orbx_set_error("hipMalloc(%zu) failed: %s", need, hipGetErrorString(e)); return ORBX_E_HIP; }
+    *cap = need;
+    return ORBX_OK;
+}
+template <class T>
+static inline int ensure_pinned(T **p, size_t *cap, size_t need, unsigned flags = hipHostMallocDefault)
+{
+    if (need <= *cap && *p) return ORBX_OK;
+    if (*p) ORBX_HIP(hipHostFree(*p));
+    *p = nullptr; *cap = 0;
+    if (hipError_t e = hipHostMalloc((void **)p, need ? need : 16, flags)) { *p = nullptr; orbx_set_error("hipHostMalloc(%zu) failed: %s", need, hipGetErrorString(e)); return ORBX_E_HIP; }
     *cap = need;
     return ORBX_OK;
 }
@@ -242,6 +257,33 @@ static inline hipError_t orbx_use_device(int device)
     if (hipGetDevice(&cur) == hipSuccess && cur == device) return hipSuccess;
     return hipSetDevice(device);
 }
+
+// ORBX_OK, or ORBX_E_NO_DEVICE with the one message every entry point gives for a device index that names no visible device
+int orbx_check_device(int device);
+
+// What a thread needs to run per-call searches on one device: its own stream.  The four families (MatchCtx orbx_match.hip, BowCtx
+// orbx_bow.hip, ProjCtx orbx_proj.hip, FrameCtx orbx_frame.hip) derive from it, add their staging buffers, and keep one thread_local array
+// [ORBX_MAX_DEVICES] each.  Each has release(): orbx_ctx_leave, then -- if that says so -- its buffers freed, then every pointer and
+// capacity reset; and a destructor calling release(), so a thread that ends gives everything back.
+struct ThreadCtx { int device = -1; hipStream_t stream = nullptr; };
+// c = the thread's slot for `device` (nullptr: device outside [0, ORBX_MAX_DEVICES)).  A set-up context only makes `device` current (no
+// device-count query in the steady state); otherwise the device is checked, made current and the non-blocking stream created.
+int orbx_ctx_enter(ThreadCtx *c, int device);
+// Synchronises and destroys the stream of a set-up context.  Returns whether the caller may free its buffers: false when the context was
+// never set up, or when the runtime is already shutting down (HIP is then left alone).
+bool orbx_ctx_leave(ThreadCtx *c);
+template <class C>
+static inline int orbx_ctx_get(C (&slots)[ORBX_MAX_DEVICES], int device, C **out)
+{
+    C *c = device >= 0 && device < ORBX_MAX_DEVICES ? &slots[device] : nullptr;
+    const int rc = orbx_ctx_enter(c, device);
+    if (rc == ORBX_OK) *out = c;
+    return rc;
+}
+void orbx_match_thread_release();   // the calling thread's contexts of one family, every device (orbx_thread_release walks the four)
+void orbx_bow_thread_release();
+void orbx_proj_thread_release();
+void orbx_frame_thread_release();
 
 // host-side exact arithmetic helpers shared by the .hip files
 static inline int orbx_cv_round(float v) { return (int)lrintf(v); }

@@ -285,8 +285,6 @@ __global__ __launch_bounds__(256) void k_kfdb_compact(const uint32_t *__restrict
 
 // ---------------------------------------------------------------- host side
 
-static size_t a16k(size_t x) { return (x + 15) & ~(size_t)15; }
-
 static int kfdb_enter(orbx_kfdb *db)
 {
     ORBX_HIP(orbx_use_device(db->device));
@@ -367,25 +365,8 @@ static int kfdb_grow_arena(orbx_kfdb *db, int n)
     return ORBX_OK;
 }
 
-static int kfdb_ws(orbx_kfdb *db, size_t bytes)
-{
-    if (bytes <= db->ws_cap) return ORBX_OK;
-    if (db->d_ws) ORBX_HIP(hipFree(db->d_ws));
-    db->d_ws = nullptr; db->ws_cap = 0;
-    ORBX_HIP(hipMalloc((void **)&db->d_ws, bytes * 2));
-    db->ws_cap = bytes * 2;
-    return ORBX_OK;
-}
-
-static int kfdb_pin(orbx_kfdb *db, size_t bytes)
-{
-    if (bytes <= db->h_cap) return ORBX_OK;
-    if (db->h_pin) ORBX_HIP(hipHostFree(db->h_pin));
-    db->h_pin = nullptr; db->h_cap = 0;
-    ORBX_HIP(hipHostMalloc((void **)&db->h_pin, bytes * 2, hipHostMallocDefault));
-    db->h_cap = bytes * 2;
-    return ORBX_OK;
-}
+static int kfdb_ws(orbx_kfdb *db, size_t bytes) { return bytes > db->ws_cap ? ensure(&db->d_ws, &db->ws_cap, 2 * bytes) : ORBX_OK; }
+static int kfdb_pin(orbx_kfdb *db, size_t bytes) { return bytes > db->h_cap ? ensure_pinned(&db->h_pin, &db->h_cap, 2 * bytes) : ORBX_OK; }
 
 static int kfdb_check_vector(const char *who, int nwords, const uint32_t *id, const double *val, int n)
 {
@@ -398,21 +379,11 @@ static int kfdb_check_vector(const char *who, int nwords, const uint32_t *id, co
     return ORBX_OK;
 }
 
-static int kfdb_no_device(int device)
-{
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-        orbx_set_error("no usable HIP device %d (liborbx has no CPU fallback)", device);
-        return ORBX_E_NO_DEVICE;
-    }
-    return ORBX_OK;
-}
-
 extern "C" int orbx_kfdb_create(int device, int nwords, orbx_kfdb **out)
 {
     if (!out || nwords < 1) { orbx_set_error("orbx_kfdb_create: invalid argument"); return ORBX_E_INVALID; }
     *out = nullptr;
-    if (int rc = kfdb_no_device(device)) return rc;
+    if (int rc = orbx_check_device(device)) return rc;
     ORBX_HIP(hipSetDevice(device));
     orbx_kfdb *db = new orbx_kfdb();
     db->device = device; db->nwords = nwords; db->stream = nullptr; db->pending = nullptr; db->has_pending = false;
@@ -588,13 +559,8 @@ static int kfdb_query(orbx_kfdb *db, const char *who, const uint32_t *qid, const
         return ORBX_OK;
     }
     if (int rc = kfdb_check_vector(who, db->nwords, qid, qval, nq)) return rc;
-    const size_t o_val = a16k(4 * (size_t)nq + 16), total = o_val + 8 * (size_t)nq + 16;
-    if (total > db->q_cap) {
-        if (db->d_q) ORBX_HIP(hipFree(db->d_q));
-        db->d_q = nullptr; db->q_cap = 0;
-        ORBX_HIP(hipMalloc((void **)&db->d_q, total * 2));
-        db->q_cap = total * 2;
-    }
+    const size_t o_val = a16(4 * (size_t)nq + 16), total = o_val + 8 * (size_t)nq + 16;
+    if (total > db->q_cap) if (int rc = ensure(&db->d_q, &db->q_cap, 2 * total)) return rc;
     if (int rc = kfdb_pin(db, total)) return rc;
     // [n | ids ...][vals ...] through the pinned block: one upload
     memcpy(db->h_pin, &nq, sizeof nq);
@@ -616,7 +582,7 @@ static KfdbWs kfdb_carve(uint8_t *base, size_t batch, size_t nids, size_t cap)
 {
     KfdbWs w;
     size_t o = 0;
-    auto take = [&](size_t bytes) { uint8_t *r = base + o; o += a16k(bytes); return r; };
+    auto take = [&](size_t bytes) { uint8_t *r = base + o; o += a16(bytes); return r; };
     const size_t m = batch * nids;
     w.maxw = (int *)take(4 * batch); w.ncand = (int *)take(4 * batch);
     w.firstkey = (unsigned long long *)take(8 * m); w.sd = (double *)take(8 * m);
@@ -665,7 +631,7 @@ static int kfdb_detect(orbx_kfdb *db, const char *who, const uint32_t *qid, cons
     if (int rc = kfdb_ws(db, w.total)) return rc;
     w = kfdb_carve(db->d_ws, 1, nids, dcap);
     // results: [maxw ncand | cand | words | si]
-    const size_t o_cand = 16, o_words = o_cand + a16k(4 * (size_t)dcap), o_si = o_words + a16k(4 * (size_t)nids), total = o_si + a16k(4 * (size_t)nids);
+    const size_t o_cand = 16, o_words = o_cand + a16(4 * (size_t)dcap), o_si = o_words + a16(4 * (size_t)nids), total = o_si + a16(4 * (size_t)nids);
     if (int rc = kfdb_pin(db, total > (size_t)nids ? total : (size_t)nids)) return rc;
     if (loop) {
         memset(db->h_pin, 0, nids);
@@ -732,7 +698,7 @@ static int kfdb_score(orbx_kfdb *db, const char *who, const uint32_t *qid, const
     KfdbQuery Q;
     if (int rc = kfdb_query(db, who, qid, qval, nq, f, index, &Q)) return rc;
     if (n == 0) return ORBX_OK;
-    const size_t o_sd = a16k(4 * (size_t)n), o_out = o_sd + a16k(8 * (size_t)n), total = o_out + a16k(8 * (size_t)n);
+    const size_t o_sd = a16(4 * (size_t)n), o_out = o_sd + a16(8 * (size_t)n), total = o_out + a16(8 * (size_t)n);
     if (int rc = kfdb_ws(db, total)) return rc;
     if (int rc = kfdb_pin(db, total)) return rc;
     memcpy(db->h_pin, ids, 4 * (size_t)n);

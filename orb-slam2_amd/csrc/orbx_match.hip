@@ -97,17 +97,6 @@ __device__ __forceinline__ const uint32_t *side_idx(const uint8_t *b, int mp) { 
 __device__ __forceinline__ const float *side_ang(const uint8_t *b, int mp) { return reinterpret_cast<const float *>(b + 36ll * mp); }
 __device__ __forceinline__ const float2 *side_xy(const uint8_t *b, int mp) { return reinterpret_cast<const float2 *>(b + 40ll * mp); }
 
-// rotation bin of src/ORBmatcher.cc:253-258 (factor = 1/30 with HISTO_LENGTH = 30: upstream quirk kept)
-__device__ __forceinline__ int m_rot_bin(float a1, float a2)
-{
-    const float factor = 1.0f / 30;
-    float rot = a1 - a2;
-    if (rot < 0.0f) rot += 360.0f;
-    int bin = (int)roundf(rot * factor);
-    if (bin == 30) bin = 0;
-    return (unsigned)bin < 30 ? bin : 0;
-}
-
 __device__ __forceinline__ void m_stage_desc(const uint32_t *src, long long p, uint32_t *dst)
 {
     const uint4 d0 = reinterpret_cast<const uint4 *>(src + 8 * p)[0], d1 = reinterpret_cast<const uint4 *>(src + 8 * p)[1];
@@ -126,7 +115,7 @@ __device__ __forceinline__ bool m_live(int cnt, unsigned long long mask, const u
 // __threadfence() per item wave (buffer_wbl2) cost 17-27 us of a 2000-item launch, profiles/r03_match_stamps.txt.
 __device__ __forceinline__ void m_record(const MArgs &g, const MItem &it, int slot, int value, float ang1, float ang2)
 {
-    const int bin = m_rot_bin(ang1, ang2);
+    const int bin = rot_bin(ang1, ang2);
     g.tmp.put(it.tmp_off + slot, (bin << 20) | value);
 }
 
@@ -538,9 +527,7 @@ __global__ __launch_bounds__(64) void k_match_v(MArgs g, const MPairV pv, const 
 
 // ---------------------------------------------------------------- host side
 
-struct MatchCtx {
-    int device = -1;
-    hipStream_t stream = nullptr;
+struct MatchCtx : ThreadCtx {
     uint8_t *h_blob = nullptr, *d_blob = nullptr; size_t blob_cap = 0;      // coherent mapped pinned memory: host view / device view
     int32_t *h_out = nullptr, *d_out = nullptr; size_t out_cap = 0;         // result block, likewise
     unsigned *h_flag = nullptr, *d_flag = nullptr;
@@ -553,24 +540,20 @@ struct MatchCtx {
     bool poisoned = false;      // a call failed after its launch: d_tmp / d_cnt may not be back at -1 / 0 (the kernels rely on that); restored before the next call
     void release()              // stream, pinned blobs and device scratch of this thread on this device
     {
-        if (device < 0) return;
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) == hipSuccess && device < ndev && hipSetDevice(device) == hipSuccess) {   // (a runtime that is already shutting down: leave it alone)
-            if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
+        if (orbx_ctx_leave(this)) {
             if (h_flag) (void)hipHostFree(h_flag);
             if (h_blob) (void)hipHostFree(h_blob);
             if (h_out) (void)hipHostFree(h_out);
             if (d_tmp) (void)hipFree(d_tmp);
             if (d_cnt) (void)hipFree(d_cnt);
         }
-        stream = nullptr; h_flag = d_flag = nullptr; h_blob = d_blob = nullptr; h_out = d_out = nullptr; d_tmp = nullptr; d_cnt = nullptr;
-        blob_cap = out_cap = tmp_cap = cnt_cap = 0; device = -1; poisoned = false;
+        h_flag = d_flag = nullptr; h_blob = d_blob = nullptr; h_out = d_out = nullptr; d_tmp = nullptr; d_cnt = nullptr;
+        blob_cap = out_cap = tmp_cap = cnt_cap = 0; poisoned = false;
     }
     ~MatchCtx() { release(); }  // a thread that called a matcher gives its resources back when it ends (thread pools, short-lived workers)
 };
-static thread_local MatchCtx g_mctx[16];
-// the calling thread's matcher resources on every device, now (they are also released when the thread ends)
-extern "C" void orbx_thread_release(void) { for (MatchCtx &c : g_mctx) c.release(); }
+static thread_local MatchCtx g_mctx[ORBX_MAX_DEVICES];
+void orbx_match_thread_release() { for (MatchCtx &c : g_mctx) c.release(); }
 // test hook: 1 = a single-pair call reads its work items from the blob like a batch does (the k_match kernels), 0 = by value (k_match_v)
 static std::atomic<int> g_items_in_memory{0};
 extern "C" int orbx_debug_set_match_items(int in_memory) { g_items_in_memory.store(in_memory ? 1 : 0, std::memory_order_relaxed); return ORBX_OK; }
@@ -581,80 +564,60 @@ extern "C" int orbx_debug_match_timing(double *out4) { if (!out4) return ORBX_E_
 
 static int mctx_get(int device, MatchCtx **out)
 {
-    MatchCtx *c = device >= 0 && device < 16 ? &g_mctx[device] : nullptr;
-    if (c && c->stream) {                 // steady state: this thread has used the device before
-        int cur = -1;
-        if (hipGetDevice(&cur) != hipSuccess || cur != device) ORBX_HIP(hipSetDevice(device));
-        if (c->poisoned) {                // an earlier call failed after its launch: scratch rows back to -1, counters to 0, before anything reads them
-            ORBX_HIP(hipStreamSynchronize(c->stream));
-            if (c->d_tmp) ORBX_HIP(hipMemset(c->d_tmp, 0xFF, c->tmp_cap * sizeof(int32_t)));
-            if (c->d_cnt) ORBX_HIP(hipMemset(c->d_cnt, 0, c->cnt_cap * sizeof(unsigned)));
-            ORBX_HIP(hipDeviceSynchronize());
-            *c->h_flag = 0; c->ticket = 0;
-            c->poisoned = false;
+    MatchCtx *c;
+    if (int rc = orbx_ctx_get(g_mctx, device, &c)) return rc;
+    if (!c->h_flag) {                     // first use: the mapped completion flag
+        unsigned *hf = nullptr;
+        ORBX_HIP(hipHostMalloc((void **)&hf, 64, hipHostMallocCoherent | hipHostMallocMapped));
+        if (hipHostGetDevicePointer((void **)&c->d_flag, hf, 0) != hipSuccess) {
+            (void)hipHostFree(hf);
+            orbx_set_error("matcher context: mapped flag could not be created on device %d", device);
+            return ORBX_E_HIP;
         }
-        *out = c;
-        return ORBX_OK;
+        *hf = 0;
+        c->h_flag = hf;
     }
-    int ndev = 0;
-    if (!c || hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) {
-        orbx_set_error("no usable HIP device %d (liborbx has no CPU fallback)", device);
-        return ORBX_E_NO_DEVICE;
+    if (c->poisoned) {                    // an earlier call failed after its launch: scratch rows back to -1, counters to 0, before anything reads them
+        ORBX_HIP(hipStreamSynchronize(c->stream));
+        if (c->d_tmp) ORBX_HIP(hipMemset(c->d_tmp, 0xFF, c->tmp_cap));
+        if (c->d_cnt) ORBX_HIP(hipMemset(c->d_cnt, 0, c->cnt_cap));
+        ORBX_HIP(hipDeviceSynchronize());
+        *c->h_flag = 0; c->ticket = 0;
+        c->poisoned = false;
     }
-    ORBX_HIP(hipSetDevice(device));
-    // the context counts as set up (c->stream != 0 is the steady-state test above) only when every piece exists
-    unsigned *hf = nullptr, *df = nullptr;
-    hipStream_t st = nullptr;
-    ORBX_HIP(hipHostMalloc((void **)&hf, 64, hipHostMallocCoherent | hipHostMallocMapped));
-    if (hipHostGetDevicePointer((void **)&df, hf, 0) != hipSuccess || hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) {
-        (void)hipHostFree(hf);
-        orbx_set_error("matcher context: stream / mapped flag could not be created on device %d", device);
-        return ORBX_E_HIP;
-    }
-    *hf = 0;
-    c->h_flag = hf; c->d_flag = df; c->device = device; c->stream = st;
     *out = c;
     return ORBX_OK;
 }
 
+// capacities in bytes; a growth waits for the stream first (the block being dropped may still be read), and allocates twice the request
 static int mctx_reserve(MatchCtx *c, size_t blob, size_t out_ints, size_t tmp_ints, size_t npairs)
 {
+    const unsigned mapped = hipHostMallocCoherent | hipHostMallocMapped;   // non-coherent pinned memory: no faster
+    const size_t out = out_ints * sizeof(int32_t), tmp = tmp_ints * sizeof(int32_t), cnt = 32 * (npairs + 1) * sizeof(unsigned);
+    int rc;
     if (blob > c->blob_cap) {
         ORBX_HIP(hipStreamSynchronize(c->stream));
-        if (c->h_blob) ORBX_HIP(hipHostFree(c->h_blob));
-        c->h_blob = nullptr; c->blob_cap = 0;
-        ORBX_HIP(hipHostMalloc((void **)&c->h_blob, blob * 2, hipHostMallocCoherent | hipHostMallocMapped));   // non-coherent pinned memory: no faster
+        if ((rc = ensure_pinned(&c->h_blob, &c->blob_cap, 2 * blob, mapped))) return rc;
         ORBX_HIP(hipHostGetDevicePointer((void **)&c->d_blob, c->h_blob, 0));
-        c->blob_cap = blob * 2;
     }
-    if (out_ints > c->out_cap) {
+    if (out > c->out_cap) {
         ORBX_HIP(hipStreamSynchronize(c->stream));
-        if (c->h_out) ORBX_HIP(hipHostFree(c->h_out));
-        c->h_out = nullptr; c->out_cap = 0;
-        ORBX_HIP(hipHostMalloc((void **)&c->h_out, out_ints * 2 * sizeof(int32_t), hipHostMallocCoherent | hipHostMallocMapped));
+        if ((rc = ensure_pinned(&c->h_out, &c->out_cap, 2 * out, mapped))) return rc;
         ORBX_HIP(hipHostGetDevicePointer((void **)&c->d_out, c->h_out, 0));
-        c->out_cap = out_ints * 2;
     }
-    if (tmp_ints > c->tmp_cap) {
+    if (tmp > c->tmp_cap) {
         ORBX_HIP(hipStreamSynchronize(c->stream));
-        if (c->d_tmp) ORBX_HIP(hipFree(c->d_tmp));
-        c->d_tmp = nullptr; c->tmp_cap = 0;
-        ORBX_HIP(hipMalloc((void **)&c->d_tmp, tmp_ints * 2 * sizeof(int32_t)));
-        ORBX_HIP(hipMemset(c->d_tmp, 0xFF, tmp_ints * 2 * sizeof(int32_t)));   // -1: every call leaves the rows it used at -1 again
-        c->tmp_cap = tmp_ints * 2;
+        if ((rc = ensure(&c->d_tmp, &c->tmp_cap, 2 * tmp))) return rc;
+        ORBX_HIP(hipMemset(c->d_tmp, 0xFF, c->tmp_cap));   // -1: every call leaves the rows it used at -1 again
     }
-    if (32 * (npairs + 1) > c->cnt_cap) {
+    if (cnt > c->cnt_cap) {
         ORBX_HIP(hipStreamSynchronize(c->stream));
-        if (c->d_cnt) ORBX_HIP(hipFree(c->d_cnt));
-        c->d_cnt = nullptr; c->cnt_cap = 0;
-        ORBX_HIP(hipMalloc((void **)&c->d_cnt, 64 * (npairs + 1) * sizeof(unsigned)));
-        ORBX_HIP(hipMemset(c->d_cnt, 0, 64 * (npairs + 1) * sizeof(unsigned)));
-        c->cnt_cap = 64 * (npairs + 1);
+        if ((rc = ensure(&c->d_cnt, &c->cnt_cap, 2 * cnt))) return rc;
+        ORBX_HIP(hipMemset(c->d_cnt, 0, c->cnt_cap));
     }
     return ORBX_OK;
 }
 
-static inline size_t m_a16(size_t v) { return (v + 15) & ~(size_t)15; }
 static inline int m_pad4(int m) { return (m + 3) & ~3; }
 
 // one side of a call as the host sees it
@@ -853,14 +816,14 @@ static int match_call(int mode, int device, HSide *sides, int nsides, const int 
     if (tmp_total >= (1ull << 31) || out_total >= (1ull << 31) || item_bound >= (1ull << 24)) { orbx_set_error("matcher call too large"); return ORBX_E_INVALID; }
     size_t off = 0;
     const size_t off_tri = off;
-    if (mode == 2 && npairs > 1) off += m_a16((size_t)npairs * sizeof(MTri));
+    if (mode == 2 && npairs > 1) off += a16((size_t)npairs * sizeof(MTri));
     for (int s = 0; s < nsides; s++) {
         HSide &S = sides[s];
         S.part_off = 0;
-        if (S.has_part) { S.part_off = off; off += m_a16((size_t)S.mp + 1); }
+        if (S.has_part) { S.part_off = off; off += a16((size_t)S.mp + 1); }
     }
     for (int s = 0; s < nsides; s++)
-        if (sides[s].pack) { sides[s].blob_off = off; off += m_a16(side_bytes(sides[s].mp, geom)); }
+        if (sides[s].pack) { sides[s].blob_off = off; off += a16(side_bytes(sides[s].mp, geom)); }
     off = (off + 127) & ~(size_t)127;
     const size_t off_items = off;
     off += item_bound * sizeof(MItem);

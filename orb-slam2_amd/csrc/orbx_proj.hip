@@ -579,47 +579,41 @@ __global__ __launch_bounds__(64) void k_init_resolve(DevFrame F, DevPoints P, Pr
 
 // ---------------------------------------------------------------- host side
 
-struct ProjCtx {
-    hipStream_t stream = nullptr;
-    uint8_t *h_blob = nullptr, *d_blob = nullptr; size_t cap = 0;
+struct ProjCtx : ThreadCtx {
+    uint8_t *h_blob = nullptr; size_t h_cap = 0;   // the staging blob, pinned
+    uint8_t *d_blob = nullptr; size_t d_cap = 0;
     uint8_t *d_work = nullptr; size_t work_cap = 0;
-    uint32_t *d_entries = nullptr; size_t ent_cap = 0;
+    uint32_t *d_entries = nullptr; size_t ent_cap = 0;   // bytes, like every capacity here
     int32_t *h_out = nullptr; size_t out_cap = 0;
     int32_t *h_n = nullptr;    // pinned: the feature count a frame created from extraction outputs reads back
-};
-static thread_local ProjCtx g_proj[16];
-
-static size_t pa16(size_t v) { return (v + 15) & ~(size_t)15; }
-
-static int proj_ctx(int device, ProjCtx **out)
-{
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev || device >= 16) {
-        orbx_set_error("no usable HIP device %d (liborbx has no CPU fallback)", device);
-        return ORBX_E_NO_DEVICE;
+    void release()
+    {
+        if (orbx_ctx_leave(this)) {
+            if (h_blob) (void)hipHostFree(h_blob);
+            if (d_blob) (void)hipFree(d_blob);
+            if (d_work) (void)hipFree(d_work);
+            if (d_entries) (void)hipFree(d_entries);
+            if (h_out) (void)hipHostFree(h_out);
+            if (h_n) (void)hipHostFree(h_n);
+        }
+        h_blob = d_blob = d_work = nullptr; d_entries = nullptr; h_out = h_n = nullptr;
+        h_cap = d_cap = work_cap = ent_cap = out_cap = 0;
     }
-    ORBX_HIP(hipSetDevice(device));
-    ProjCtx *c = &g_proj[device];
-    if (!c->stream) ORBX_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    *out = c;
-    return ORBX_OK;
-}
+    ~ProjCtx() { release(); }
+};
+static thread_local ProjCtx g_proj[ORBX_MAX_DEVICES];
+void orbx_proj_thread_release() { for (ProjCtx &c : g_proj) c.release(); }
 
 // the staging blob of one call: [frame arrays (host-pointer calls only)] [occupied] [point arrays], one upload
 static int proj_blob_reserve(ProjCtx *c, size_t blob)
 {
-    if (blob > c->cap) {
-        if (c->h_blob) ORBX_HIP(hipHostFree(c->h_blob));
-        if (c->d_blob) ORBX_HIP(hipFree(c->d_blob));
-        c->h_blob = nullptr; c->d_blob = nullptr;
-        ORBX_HIP(hipHostMalloc((void **)&c->h_blob, blob * 2, hipHostMallocDefault));
-        ORBX_HIP(hipMalloc((void **)&c->d_blob, blob * 2));
-        c->cap = blob * 2;
-    }
-    return ORBX_OK;
+    int rc = ORBX_OK;
+    if (blob > c->h_cap) rc = ensure_pinned(&c->h_blob, &c->h_cap, 2 * blob);
+    if (!rc && blob > c->d_cap) rc = ensure(&c->d_blob, &c->d_cap, 2 * blob);
+    return rc;
 }
-static size_t proj_head_bytes(size_t nc) { return 5 * pa16(4 * nc) + pa16(32 * nc); }
-static size_t proj_tail_bytes(size_t nc, size_t np) { return pa16(nc) + 6 * pa16(4 * np) + pa16(32 * np) + 2 * pa16(np); }
+static size_t proj_head_bytes(size_t nc) { return 5 * a16(4 * nc) + a16(32 * nc); }
+static size_t proj_tail_bytes(size_t nc, size_t np) { return a16(nc) + 6 * a16(4 * np) + a16(32 * np) + 2 * a16(np); }
 
 // ---- part 1 of a host-pointer search: the frame's arrays into the head of the staging blob; F addresses them where the upload of part 2
 // will put them (the grid is then built by part 2 into its work area)
@@ -629,7 +623,7 @@ static void proj_stage_frame(ProjCtx *c, const orbx_frame_feats *cur, DevFrame *
     uint8_t *h = c->h_blob;
     const uint8_t *d = c->d_blob;
     size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t r = o; o += pa16(bytes); return r; };
+    auto take = [&](size_t bytes) { const size_t r = o; o += a16(bytes); return r; };
     const size_t fx = take(4 * nc), fy = take(4 * nc), fo = take(4 * nc), fa = take(4 * nc), fu = take(4 * nc), fd = take(32 * nc);
     memcpy(h + fx, cur->x, 4 * nc); memcpy(h + fy, cur->y, 4 * nc); memcpy(h + fo, cur->octave, 4 * nc);
     if (cur->angle) memcpy(h + fa, cur->angle, 4 * nc); else memset(h + fa, 0, 4 * nc);
@@ -652,7 +646,7 @@ static int proj_search(ProjCtx *c, DevFrame F, size_t head, const int *grid_off,
     int rc = proj_blob_reserve(c, blob);
     if (rc) return rc;
     size_t o = head;
-    auto take = [&](size_t bytes) { const size_t r = o; o += pa16(bytes); return r; };
+    auto take = [&](size_t bytes) { const size_t r = o; o += a16(bytes); return r; };
     const size_t fq = take(nc);
     const size_t pu = take(4 * np), pv = take(4 * np), pa = take(4 * np), pl = take(4 * np), pg = take(4 * np), pc = take(4 * np),
                  pd = take(32 * np), pval = take(np), pobs = take(np);
@@ -679,22 +673,13 @@ static int proj_search(ProjCtx *c, DevFrame F, size_t head, const int *grid_off,
     // work: cell_off[3073] | cell_idx[nc] | beg[np] | cnt[np] | pool_used | choice_a[np] | choice_b[np] | match[nc] | out_n |
     //       pt_choice[np] | pt_dist[np]
     size_t w = 0;
-    auto wtake = [&](size_t bytes) { const size_t r = w; w += pa16(bytes); return r; };
+    auto wtake = [&](size_t bytes) { const size_t r = w; w += a16(bytes); return r; };
     const size_t w_coff = wtake(4 * (PG_CELLS + 1)), w_cidx = wtake(4 * nc), w_beg = wtake(4 * np), w_cnt = wtake(4 * np), w_used = wtake(16),
                  w_ca = wtake(4 * np), w_cb = wtake(4 * np), w_match = wtake(4 * nc), w_n = wtake(16), w_pc = wtake(4 * np),
                  w_pd = wtake(4 * np);
-    if (w > c->work_cap) {
-        if (c->d_work) ORBX_HIP(hipFree(c->d_work));
-        c->d_work = nullptr;
-        ORBX_HIP(hipMalloc((void **)&c->d_work, w * 2));
-        c->work_cap = w * 2;
-    }
-    if ((nc + 2 * np + 8) > c->out_cap) {
-        if (c->h_out) ORBX_HIP(hipHostFree(c->h_out));
-        c->h_out = nullptr;
-        ORBX_HIP(hipHostMalloc((void **)&c->h_out, sizeof(int32_t) * (nc + 2 * np + 8) * 2, hipHostMallocDefault));
-        c->out_cap = (nc + 2 * np + 8) * 2;
-    }
+    const size_t out = sizeof(int32_t) * (nc + 2 * np + 8);
+    if (w > c->work_cap && (rc = ensure(&c->d_work, &c->work_cap, 2 * w))) return rc;
+    if (out > c->out_cap && (rc = ensure_pinned(&c->h_out, &c->out_cap, 2 * out))) return rc;
     const size_t resolve_lds = pp.init_search ? (2 * sizeof(uint16_t) + sizeof(float)) * ((nc + 7) & ~(size_t)7) + 16 : sizeof(int) * (nc + 4);   // init: md, m21, the frame's angles
     if (resolve_lds > 150 * 1024 || (pp.init_search && np >= 65535)) { orbx_set_error("too many features for one search"); return ORBX_E_INVALID; }
     if (pp.init_search)
@@ -708,15 +693,12 @@ static int proj_search(ProjCtx *c, DevFrame F, size_t head, const int *grid_off,
         d_coff = (int *)(wk + w_coff); d_cidx = (int *)(wk + w_cidx);
         hipLaunchKernelGGL(k_grid_build, dim3(1), dim3(256), 0, c->stream, F, (int *)(wk + w_coff), (int *)(wk + w_cidx));
     }
-    if (!c->d_entries) { // entry pool: grown on demand, the lists and the resolve are simply repeated after an overflow
-        const size_t init = 1u << 20;
-        ORBX_HIP(hipMalloc((void **)&c->d_entries, sizeof(uint32_t) * init));
-        c->ent_cap = init;
-    }
+    // entry pool: grown on demand, the lists and the resolve are simply repeated after an overflow
+    if (!c->d_entries && (rc = ensure(&c->d_entries, &c->ent_cap, sizeof(uint32_t) << 20))) return rc;
     for (int attempt = 0; attempt < 2; attempt++) {
         ORBX_HIP(hipMemsetAsync(d_used, 0, 16, c->stream));
         hipLaunchKernelGGL(k_proj_lists, dim3((pts->n + 3) / 4), dim3(256), 0, c->stream, F, P, pp, d_coff, d_cidx, d_beg, d_cnt,
-                           c->d_entries, (int)c->ent_cap, d_used);
+                           c->d_entries, (int)(c->ent_cap / sizeof(uint32_t)), d_used);
         if (pp.init_search)
             hipLaunchKernelGGL(k_init_resolve, dim3(1), dim3(64), resolve_lds, c->stream, F, P, pp, d_beg, d_cnt, c->d_entries,
                                (int *)(wk + w_ca), (int32_t *)(wk + w_pc), (int32_t *)(wk + w_pd), (int *)(wk + w_n));
@@ -732,12 +714,9 @@ static int proj_search(ProjCtx *c, DevFrame F, size_t head, const int *grid_off,
         if (pt_dist) ORBX_HIP(hipMemcpyAsync(c->h_out + nc + 8 + np, wk + w_pd, 4 * np, hipMemcpyDeviceToHost, c->stream));
         ORBX_HIP(hipStreamSynchronize(c->stream));
         const size_t used = (size_t)(unsigned)c->h_out[nc + 1];
-        if (used <= c->ent_cap) break;
+        if (used <= c->ent_cap / sizeof(uint32_t)) break;
         if (attempt == 1) { orbx_set_error("candidate pool overflow"); return ORBX_E_CAPACITY; }
-        ORBX_HIP(hipFree(c->d_entries));
-        c->d_entries = nullptr;
-        ORBX_HIP(hipMalloc((void **)&c->d_entries, sizeof(uint32_t) * used * 2));
-        c->ent_cap = used * 2;
+        if ((rc = ensure(&c->d_entries, &c->ent_cap, sizeof(uint32_t) * used * 2))) return rc;
     }
     memcpy(match_cur, c->h_out, 4 * nc);
     *nmatches = c->h_out[nc];
@@ -774,7 +753,7 @@ static int proj_run(int device, const orbx_frame_feats *cur, const orbx_proj_poi
     for (int i = 0; i < pts->n; i++) { if (pt_choice) pt_choice[i] = -1; if (pt_dist) pt_dist[i] = 256; }
     if (cur->n == 0 || pts->n == 0) return ORBX_OK;
     ProjCtx *c;
-    int rc = proj_ctx(device, &c);
+    int rc = orbx_ctx_get(g_proj, device, &c);
     if (rc) return rc;
     const size_t head = proj_head_bytes((size_t)cur->n);
     rc = proj_blob_reserve(c, head + proj_tail_bytes((size_t)cur->n, (size_t)pts->n));
@@ -962,7 +941,7 @@ static size_t frame_layout(orbx_frame *f)
 {
     const size_t nc = (size_t)f->n;
     size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t r = o; o += pa16(bytes); return r; };
+    auto take = [&](size_t bytes) { const size_t r = o; o += a16(bytes); return r; };
     f->o_x = take(4 * nc); f->o_y = take(4 * nc); f->o_oct = take(4 * nc); f->o_ang = take(4 * nc); f->o_ur = take(4 * nc);
     f->o_desc = take(32 * nc); f->o_coff = take(4 * (PG_CELLS + 1)); f->o_cidx = take(4 * nc);
     return o;
@@ -997,7 +976,7 @@ extern "C" int orbx_frame_create(int device, const orbx_frame_feats *cur, orbx_f
     if (cur->n && (!cur->x || !cur->y || !cur->octave || !cur->u_right || !cur->desc)) { orbx_set_error("orbx_frame_create: frame arrays missing"); return ORBX_E_INVALID; }
     if (!(cur->max_x > cur->min_x) || !(cur->max_y > cur->min_y)) { orbx_set_error("orbx_frame_create: empty image bounds"); return ORBX_E_INVALID; }
     ProjCtx *c;
-    int rc = proj_ctx(device, &c);
+    int rc = orbx_ctx_get(g_proj, device, &c);
     if (rc) return rc;
     orbx_frame *f = frame_new(device, cur->n, cur->n == 0 || cur->angle ? 1 : 0, cur->min_x, cur->min_y, cur->max_x, cur->max_y);
     const size_t bytes = frame_layout(f);
@@ -1037,7 +1016,7 @@ extern "C" int orbx_frame_create_from_extraction(int device, const void *d_kps, 
     }
     if (!(max_x > min_x) || !(max_y > min_y)) { orbx_set_error("orbx_frame_create_from_extraction: empty image bounds"); return ORBX_E_INVALID; }
     ProjCtx *c;
-    int rc = proj_ctx(device, &c);
+    int rc = orbx_ctx_get(g_proj, device, &c);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (!c->h_n) ORBX_HIP(hipHostMalloc((void **)&c->h_n, 64, hipHostMallocDefault));
@@ -1126,7 +1105,7 @@ static int proj_run_resident(orbx_frame *f, const uint8_t *occupied, const orbx_
     *nmatches = 0;
     if (f->n == 0 || pts->n == 0) return ORBX_OK;
     ProjCtx *c;
-    int rc = proj_ctx(f->device, &c);
+    int rc = orbx_ctx_get(g_proj, f->device, &c);
     if (rc) return rc;
     if (f->pending) ORBX_HIP(hipStreamWaitEvent(c->stream, f->blk.ev, 0));   // the creation, ordered by its event (no device synchronisation)
     const uint8_t *d = f->blk.d;

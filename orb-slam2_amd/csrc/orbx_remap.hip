@@ -80,11 +80,7 @@ extern "C" int orbx_rectifier_create(int device, int src_w, int src_h, int dst_w
         orbx_set_error("orbx_rectifier_create: invalid argument");
         return ORBX_E_INVALID;
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-        orbx_set_error("no usable HIP device %d (liborbx has no CPU fallback)", device);
-        return ORBX_E_NO_DEVICE;
-    }
+    if (int rc = orbx_check_device(device)) return rc;
     ORBX_HIP(hipSetDevice(device));
     orbx_rectifier *r = new orbx_rectifier();
     r->device = device; r->src_w = src_w; r->src_h = src_h; r->dst_w = dst_w; r->dst_h = dst_h;

@@ -435,10 +435,7 @@ extern "C" int orbx_stereo_match_batch_device(orbx_extractor *L, int img_l0, orb
     if (need > L->st_cap || !L->d_st_dist) {
         ORBX_HIP(hipStreamSynchronize(s));
         { const int qrc = orbx_quiesce(L); if (qrc) return qrc; }
-        if (L->d_st_dist) ORBX_HIP(hipFree(L->d_st_dist));
-        L->d_st_dist = nullptr;
-        ORBX_HIP(hipMalloc((void **)&L->d_st_dist, need));
-        L->st_cap = need;
+        { const int erc = ensure(&L->d_st_dist, &L->st_cap, need); if (erc) return erc; }
     }
     StereoTabs tabs;
     tabs.reach_pk = 0;
@@ -472,10 +469,7 @@ extern "C" int orbx_stereo_match_batch_device(orbx_extractor *L, int img_l0, orb
         if (need_e > L->st_ent_cap || !L->d_st_entries) {
             ORBX_HIP(hipStreamSynchronize(s));
             { const int qrc = orbx_quiesce(L); if (qrc) return qrc; }
-            if (L->d_st_entries) ORBX_HIP(hipFree(L->d_st_entries));
-            L->d_st_entries = nullptr;
-            ORBX_HIP(hipMalloc((void **)&L->d_st_entries, need_e));
-            L->st_ent_cap = need_e;
+            if ((rc = ensure(&L->d_st_entries, &L->st_ent_cap, need_e))) return rc;
         }
         d_entries = L->d_st_entries;
     }

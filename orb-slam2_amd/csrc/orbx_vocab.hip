@@ -303,11 +303,7 @@ static int vocab_build(int device, int k, int L, int nm1, const int32_t *parent,
         return ORBX_E_INVALID;
     }
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-        orbx_set_error("no usable HIP device %d (liborbx has no CPU fallback)", device);
-        return ORBX_E_NO_DEVICE;
-    }
+    if (int rc = orbx_check_device(device)) return rc;
     const int n = nm1 + 1;
     std::vector<int> off(n + 1, 0), ids(n > 1 ? n - 1 : 1), word(n, -1);
     for (int i = 1; i < n; i++) {
@@ -425,8 +421,6 @@ extern "C" int orbx_vocab_info(const orbx_vocab *v, int *k, int *L, int *nnodes,
     return ORBX_OK;
 }
 
-static size_t a16v(size_t x) { return (x + 15) & ~(size_t)15; }
-
 extern "C" int orbx_bow_transform(orbx_vocab *v, const uint8_t *desc, int n, int levelsup,
                                   uint32_t *word_id, double *word_weight, uint32_t *node_id,
                                   uint32_t *bow_id, double *bow_val, int *nbow,
@@ -443,18 +437,12 @@ extern "C" int orbx_bow_transform(orbx_vocab *v, const uint8_t *desc, int n, int
     int npad = 64;
     while (npad < n) npad <<= 1;
     // device scratch: [desc | word u32 | weight f64 | nid u32 | bow_id | bow_val | counts | fv_node_id | fv_node_off | fv_feat]
-    const size_t o_word = a16v((size_t)n * 32), o_w = o_word + a16v(4 * (size_t)n), o_nid = o_w + a16v(8 * (size_t)n);
-    const size_t o_bid = o_nid + a16v(4 * (size_t)n), o_bval = o_bid + a16v(4 * (size_t)n), o_cnt = o_bval + a16v(8 * (size_t)n);
-    const size_t o_fid = o_cnt + 16, o_foff = o_fid + a16v(4 * (size_t)n), o_ffeat = o_foff + a16v(4 * ((size_t)n + 1));
-    const size_t total = o_ffeat + a16v(4 * (size_t)npad);
-    if (total > v->in_cap) {
-        if (v->d_in) ORBX_HIP(hipFree(v->d_in));
-        if (v->h_out) ORBX_HIP(hipHostFree(v->h_out));
-        v->d_in = nullptr; v->h_out = nullptr;
-        ORBX_HIP(hipMalloc((void **)&v->d_in, total * 2));
-        ORBX_HIP(hipHostMalloc((void **)&v->h_out, total * 2, hipHostMallocDefault));
-        v->in_cap = total * 2;
-    }
+    const size_t o_word = a16((size_t)n * 32), o_w = o_word + a16(4 * (size_t)n), o_nid = o_w + a16(8 * (size_t)n);
+    const size_t o_bid = o_nid + a16(4 * (size_t)n), o_bval = o_bid + a16(4 * (size_t)n), o_cnt = o_bval + a16(8 * (size_t)n);
+    const size_t o_fid = o_cnt + 16, o_foff = o_fid + a16(4 * (size_t)n), o_ffeat = o_foff + a16(4 * ((size_t)n + 1));
+    const size_t total = o_ffeat + a16(4 * (size_t)npad);
+    if (total > v->in_cap) if (int rc = ensure(&v->d_in, &v->in_cap, 2 * total)) return rc;
+    if (total > v->h_out_cap) if (int rc = ensure_pinned(&v->h_out, &v->h_out_cap, 2 * total)) return rc;
     uint8_t *d = v->d_in;
     ORBX_HIP(hipMemcpyAsync(d, desc, (size_t)n * 32, hipMemcpyHostToDevice, v->stream));
     hipLaunchKernelGGL(k_vocab_descend, dim3((n + 63) / 64), dim3(64), 0, v->stream, v->d_child_off, v->d_child_ids, v->d_word_id,
@@ -524,11 +512,7 @@ extern "C" int orbx_bow_frames_create(int device, int max_batch, int cap, orbx_b
 {
     if (!out || max_batch < 1 || cap < 1 || cap > 8192) { orbx_set_error("orbx_bow_frames_create: invalid argument (cap <= 8192)"); return ORBX_E_INVALID; }
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-        orbx_set_error("no usable HIP device %d (liborbx has no CPU fallback)", device);
-        return ORBX_E_NO_DEVICE;
-    }
+    if (int rc = orbx_check_device(device)) return rc;
     ORBX_HIP(hipSetDevice(device));
     orbx_bow_frames *f = new orbx_bow_frames();
     memset(f, 0, sizeof *f);
@@ -537,7 +521,7 @@ extern "C" int orbx_bow_frames_create(int device, int max_batch, int cap, orbx_b
     while (f->npad < cap) f->npad <<= 1;
     const size_t B = (size_t)max_batch, c = (size_t)cap;
     size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t r = o; o += a16v(bytes); return r; };
+    auto take = [&](size_t bytes) { const size_t r = o; o += a16(bytes); return r; };
     const size_t o_word = take(4 * B * c), o_w = take(8 * B * c), o_nid = take(4 * B * c), o_bid = take(4 * B * c), o_bval = take(8 * B * c),
                  o_cnt = take(8 * B), o_fid = take(4 * B * c), o_foff = take(4 * B * (c + 4)), o_ffeat = take(4 * B * f->npad),
                  o_ang = take(4 * B * c), o_feats = take(sizeof(DevFeat) * B), o_sd = take(32 * B * f->npad), o_sf = take(B * f->npad);
@@ -593,14 +577,9 @@ extern "C" int orbx_bow_frames_read(orbx_bow_frames *f, int index, void *stream,
     if (!f || index < 0 || index >= f->batch || !nbow || !fv_nnodes) { orbx_set_error("orbx_bow_frames_read: invalid argument"); return ORBX_E_INVALID; }
     ORBX_HIP(hipSetDevice(f->device));
     const size_t c = (size_t)f->cap;
-    const size_t o_bid = 16, o_bval = o_bid + a16v(4 * c), o_fid = o_bval + a16v(8 * c), o_foff = o_fid + a16v(4 * c),
-                 o_ffeat = o_foff + a16v(4 * (c + 4)), total = o_ffeat + a16v(4 * (size_t)f->npad);
-    if (total > f->h_cap) {
-        if (f->h_buf) ORBX_HIP(hipHostFree(f->h_buf));
-        f->h_buf = nullptr;
-        ORBX_HIP(hipHostMalloc((void **)&f->h_buf, total, hipHostMallocDefault));
-        f->h_cap = total;
-    }
+    const size_t o_bid = 16, o_bval = o_bid + a16(4 * c), o_fid = o_bval + a16(8 * c), o_foff = o_fid + a16(4 * c),
+                 o_ffeat = o_foff + a16(4 * (c + 4)), total = o_ffeat + a16(4 * (size_t)f->npad);
+    if (int rc = ensure_pinned(&f->h_buf, &f->h_cap, total)) return rc;
     hipStream_t s = stream ? (hipStream_t)stream : f->last_stream;
     uint8_t *h = f->h_buf;
     const size_t i = (size_t)index;

@@ -248,6 +248,8 @@ def lib():
     L.orbx_debug_set_bow_form.argtypes = [i]
     L.orbx_debug_set_match_items.argtypes = [i]
     L.orbx_debug_match_timing.argtypes = [vp]
+    L.orbx_thread_release.argtypes = []; L.orbx_thread_release.restype = None
+    L.orbx_debug_thread_contexts.argtypes = []; L.orbx_debug_thread_contexts.restype = i
     _lib = L
     return L
 
@@ -304,6 +306,17 @@ def debug_bow_last_form():
     out = np.zeros(3, np.int32)
     _check(lib().orbx_debug_bow_last_form(_p(out)))
     return dict(form={0: None, 1: "wave", 2: "table"}[int(out[0])], xcd_grid=bool(out[1]), compact=bool(out[2]))
+
+
+def thread_release():
+    """give back, now, what the calling thread holds for the per-call searches on every device: streams, pinned and device staging
+    (orbx_thread_release); a thread that ends does the same on its own"""
+    lib().orbx_thread_release()
+
+
+def debug_thread_contexts():
+    """set-up per-thread search contexts of the whole process (orbx_debug_thread_contexts): one per (thread, family, device) in use"""
+    return lib().orbx_debug_thread_contexts()
 
 
 def debug_set_match_items(in_memory):
