@@ -207,6 +207,18 @@ def stereo_match(oL, oR, kL, dL, kR, dR, bf, min_z):
     return ur, dp
 
 
+def fast_atan2(y, x):
+    """cv::fastAtan2 of the oracle (degrees, fp32), as np.float32"""
+    return np.float32(lib().oracle_fast_atan2(float(y), float(x)))
+
+
+def sincos(angle_rad):
+    """the build's deterministic (sin, cos) of an fp32 angle in radians, as np.float32"""
+    s, c = C.c_float(), C.c_float()
+    lib().oracle_sincos(float(angle_rad), C.byref(s), C.byref(c))
+    return np.float32(s.value), np.float32(c.value)
+
+
 def gaussian_taps(profile):
     t = np.zeros(7, np.int32)
     lib().oracle_gaussian_taps(profile, t.ctypes.data)

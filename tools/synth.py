@@ -76,6 +76,86 @@ def stereo_pair(seed, w, h, nshapes=1500, dmin=2, dmax=80):
     return _finish(rng, left), _finish(rng, right), disp
 
 
+# ----------------------------------------------------------------------------- directed images for orientation / rBRIEF
+# (tests/test_desc_model.py; 320 x 240, extracted with 8 levels at scale factor 1.2 and 500 features)
+
+_DOT3 = np.array([[150, 200, 150], [200, 255, 200], [150, 200, 150]], np.uint8)   # brighter centre: a flat 3x3 plateau has no strict FAST maximum
+
+
+def _dot_centres(w, h, pitch=40, x0=30, y0=30):
+    return [(x, y) for y in range(y0, h - 25, pitch) for x in range(x0, w - 25, pitch)]
+
+
+def _put_dot(img, x, y, big):
+    if big:
+        img[y - 1:y + 2, x - 1:x + 2] = _DOT3
+    else:
+        img[y, x] = 255
+
+
+def isolated_dots(w=320, h=240, background=40):
+    """1-pixel and 3x3 dots (alternating) on a constant background, 40 px apart: every patch of a level-0 keypoint is symmetric in
+    both axes, so m10 = m01 = 0.  -> (image, [(x, y)])"""
+    img = np.full((h, w), background, np.uint8)
+    centres = _dot_centres(w, h)
+    for i, (x, y) in enumerate(centres):
+        _put_dot(img, x, y, i % 2 == 1)
+    return img, centres
+
+
+def dots_with_bar(w=320, h=240, background=40, bar=160):
+    """the dots of isolated_dots, each with one 5 x 2 bar inside its 15-px patch, 7-8 px straight right of, below, left of or above the
+    centre and symmetric about that axis: one moment is zero, the other has either sign (orientations 0, 90, 180, 270 degrees in
+    image coordinates, y down).  -> (image, [(x, y, direction)]) with direction 0 = right, 1 = below, 2 = left, 3 = above"""
+    img, centres = isolated_dots(w, h, background)
+    out = []
+    for i, (x, y) in enumerate(centres):
+        d = (i + i // 7) % 4
+        if d == 0:
+            img[y - 2:y + 3, x + 7:x + 9] = bar
+        elif d == 1:
+            img[y + 7:y + 9, x - 2:x + 3] = bar
+        elif d == 2:
+            img[y - 2:y + 3, x - 8:x - 6] = bar
+        else:
+            img[y - 8:y - 6, x - 2:x + 3] = bar
+        out.append((x, y, d))
+    return img, out
+
+
+def border_lattice(w=320, h=240, background=40, scale_factor=1.2, levels=4):
+    """small squares (the 3x3 dot) along the four borders, phased so that for each of the first `levels` pyramid levels one of them
+    is centred on the first (19) and one on the last (size - 20) admissible keypoint column and row of that level: a keypoint there
+    has a rotated rBRIEF pattern that reaches row / column 1 of the level.  Level-l coordinate c is level-0 coordinate
+    (c + 0.5) * scale - 0.5 (bilinear resize, pixel centres); the neighbouring phases +-1 px are placed too."""
+    img = np.full((h, w), background, np.uint8)
+    s = 1.0
+    slot = 0
+    for l in range(levels):
+        lw, lh = int(round(w / s)), int(round(h / s))
+        for ph in (-1, 0, 1):
+            lo = int(round(19.5 * s - 0.5)) + ph
+            hi_x = int(round((lw - 20 + 0.5) * s - 0.5)) + ph
+            hi_y = int(round((lh - 20 + 0.5) * s - 0.5)) + ph
+            ay, ax = 40 + 14 * slot, 50 + 19 * slot                # positions along the borders: 14 / 19 px between neighbours
+            slot += 1
+            for x, y in ((lo, ay), (min(hi_x, w - 3), ay + 7), (ax, lo), (ax + 9, min(hi_y, h - 3))):
+                _put_dot(img, x, y, True)
+        s *= scale_factor
+    return img
+
+
+def block_checkerboard(seed=7, w=320, h=240, block=16, flip=0.3):
+    """0/255 checkerboard of 16-px blocks in which a seeded 30 % of the blocks are inverted: the crossing of four checkerboard blocks is
+    no FAST-9 corner (two bright and two dark arcs of four pixels), the L-corners the inverted blocks make are.  After the 7x7 blur
+    block interiors stay exactly 0 and 255 (both ends of the range), so many compared pixel pairs are equal."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    by, bx = (h + block - 1) // block, (w + block - 1) // block
+    cells = (np.add.outer(np.arange(by), np.arange(bx)) & 1).astype(np.uint8)
+    cells ^= (rng.random((by, bx)) < flip).astype(np.uint8)
+    return (np.repeat(np.repeat(cells, block, 0), block, 1)[:h, :w] * 255).astype(np.uint8)
+
+
 # ----------------------------------------------------------------------------- BoW
 
 _POPCNT = np.array([bin(i).count("1") for i in range(256)], np.uint8)
