@@ -289,3 +289,44 @@ struct RgbdArgs {
 int orbx_rgbd_args(const char *fn, const orbx_rgbd_params *p, int w, int h, size_t depth_pitch, RgbdArgs *a);
 // enqueue k_rgbd_depth for `batch` images on stream s (no host synchronisation)
 int orbx_rgbd_launch(const RgbdArgs &a, int batch, hipStream_t s);
+
+// ---- diagnostic builds (-DORBX_DIAG, tools/diag_*.py): phase stamps and wave life spans of the extraction kernels.  A kernel's file defines
+// the arrays its kernel writes (g_<kernel>_stamp; g_span_<K> for SPAN_END(K)), its stamp macro on top of STAMP_TO and the orbx_diag_* reader;
+// a normal build compiles all of it to nothing.
+#ifdef ORBX_DIAG
+#include <string.h>
+#ifdef ORBX_DIAG_SPANS_ONLY     // the summed phase stamps perturb the waves they measure (an atomic per phase): this build keeps the spans only
+                                // (and k_fast's per-wave phase log, orbx_fast.hip)
+#define STAMP_TO(arr, k) do { (void)_t_prev; } while (0)
+#else
+#define STAMP_TO(arr, k) do { const unsigned long long _t = __builtin_amdgcn_s_memtime(); \
+    if (threadIdx.x == 0) atomicAdd(&arr[((blockIdx.x * 131 + blockIdx.y) & 4095) * 8 + (k)], _t - _t_prev); _t_prev = _t; } while (0)
+#endif
+// wall-clock life of every wave of a launch (s_memrealtime, 100 MHz): (start, end) in the wave's own slot -- no atomics, nothing shared
+#define SPAN_SLOTS 16384
+#define SPAN_BEGIN() const unsigned _sp0 = (unsigned)__builtin_amdgcn_s_memrealtime()
+#define SPAN_END(K) do { if ((threadIdx.x & 63) == 0) { const unsigned _id = blockIdx.x + gridDim.x * blockIdx.y; \
+    if (_id < SPAN_SLOTS) g_span_##K[_id] = make_uint2(_sp0, (unsigned)__builtin_amdgcn_s_memrealtime()); } } while (0)
+// host readers: the phase sums over a stamp array's 4096 slots -> out[8]; one span array -> out[SPAN_SLOTS][2]
+static inline int orbx_diag_stamp_sums(const void *sym, unsigned long long *out, int reset)
+{
+    ORBX_HIP(hipDeviceSynchronize());
+    static unsigned long long h[4096 * 8];
+    ORBX_HIP(hipMemcpyFromSymbol(h, sym, sizeof h));
+    for (int k = 0; k < 8; k++) { out[k] = 0; for (int i = 0; i < 4096; i++) out[k] += h[i * 8 + k]; }
+    if (reset) { memset(h, 0, sizeof h); ORBX_HIP(hipMemcpyToSymbol(sym, h, sizeof h)); }
+    return ORBX_OK;
+}
+static inline int orbx_diag_span_read(const void *sym, unsigned *out, int reset)
+{
+    ORBX_HIP(hipMemcpyFromSymbol(out, sym, sizeof(uint2) * SPAN_SLOTS));
+    if (reset) {
+        static uint2 z[SPAN_SLOTS];
+        ORBX_HIP(hipMemcpyToSymbol(sym, z, sizeof z));
+    }
+    return ORBX_OK;
+}
+#else
+#define SPAN_BEGIN() do { } while (0)
+#define SPAN_END(K) do { } while (0)
+#endif

@@ -129,7 +129,7 @@ struct orbx_extractor {
     Geom *d_geom;        // device copy
     int16_t *d_tabs; size_t tabs_cap;      // resize tables
     CellRec *d_cells; size_t cells_cap;    // per-cell records of k_fast
-    void *d_pairs; size_t pairs_cap;       // per-pair records of k_fast2 (PairRec, orbx_extract.hip)
+    void *d_pairs; size_t pairs_cap;       // per-pair records of k_fast2 (PairRec, orbx_fast.hip)
     int last_fast_form;                    // debug: 1 = k_fast, 2 = k_fast2 ran in the most recent extraction
     int32_t last_forms[ORBX_LAUNCH_FORM_FIELDS]; // debug: launch forms of the most recent extraction / stereo launch (orbx_debug_launch_forms)
     int fast_pair;                         // ORBX_FAST_PAIR: 1 = k_fast2 wherever the geometry allows it, 0 (default) = never
@@ -289,6 +289,28 @@ void orbx_frame_thread_release();
 static inline int orbx_cv_round(float v) { return (int)lrintf(v); }
 
 int orbx_prepare_geometry(orbx_extractor *e, int w, int h);
+// The extractor's four stages, one file each (file map: orbx_extract.hip).  A plan is the stage's step of orbx_prepare_geometry: it turns the
+// level geometry into the stage's host tables and LDS sizes, and the plans run in this order (k_pyr_group's tables read the finished resize
+// tables, k_fast2's pair records the finished cells).  A launch enqueues the stage for the handle's current geometry on stream s and notes
+// the form it chose in e->last_forms.  New internal functions stay out of the library's dynamic symbol table.
+#define ORBX_LOCAL __attribute__((visibility("hidden")))
+struct PyrRef;
+ORBX_LOCAL void orbx_pyramid_plan(orbx_extractor *e, Geom &G, std::vector<int16_t> &tabs);
+ORBX_LOCAL void orbx_pyramid_launch(orbx_extractor *e, const PyrRef &pr, int batch, hipStream_t s);
+ORBX_LOCAL void orbx_fast_plan(const orbx_extractor *e, Geom &G, std::vector<CellRec> &cells, std::vector<uint8_t> &pair_bytes);
+ORBX_LOCAL void orbx_fast_launch(orbx_extractor *e, const PyrRef &pr, int batch, hipStream_t s);
+ORBX_LOCAL int orbx_tree_plan(const Geom &G, size_t *hbm_tab_bytes);
+ORBX_LOCAL int orbx_tree_commit(const Geom &G);
+ORBX_LOCAL void orbx_tree_launch(orbx_extractor *e, int batch, hipStream_t s);
+ORBX_LOCAL int orbx_desc_upload_constants(orbx_extractor *e);
+ORBX_LOCAL bool orbx_desc_rowtab_plan(const Geom &G);
+ORBX_LOCAL void orbx_desc_launch(orbx_extractor *e, const PyrRef &pr, int batch, void *d_kps, void *d_desc, void *d_n_out, int cap, hipStream_t s);
+#ifdef ORBX_DIAG    // each file's half of orbx_diag_spans
+ORBX_LOCAL int orbx_fast_diag_spans(unsigned *out, int reset);
+ORBX_LOCAL int orbx_desc_diag_spans(unsigned *out, int reset);
+#endif
+// the kernel error flag: the int behind the level counts (set by k_tree, handed on by k_desc, read and cleared by orbx_sync)
+static inline int *orbx_err_flag(const orbx_extractor *e) { return e->d_lvl_cnt + (size_t)e->max_batch * ORBX_MAX_LEVELS; }
 void orbx_prof_begin(orbx_extractor *e, int stage, hipStream_t s);
 void orbx_prof_end(orbx_extractor *e, hipStream_t s);
 int orbx_ensure_out_staging(orbx_extractor *e, int batch, int cap);

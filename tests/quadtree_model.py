@@ -1,5 +1,5 @@
 """numpy model of the data-parallel quadtree-cull formulation used by the HIP kernel
-(orb-slam2_amd/csrc/orbx_extract.hip: k_quadtree).  It exists to check, on CPU and against the
+(orb-slam2_amd/csrc/orbx_tree.hip: k_tree).  It exists to check, on CPU and against the
 sequential oracle (oracle_distribute_octtree, which follows src/ORBextractor.cc:617-915 with a
 linked list), the order algebra the kernel relies on:
 

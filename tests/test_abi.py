@@ -27,6 +27,13 @@ def test_library_exports_every_declared_symbol(pkg):
         assert hasattr(L, n), f"{n} declared in include/orbx.h but not exported by liborbx.so"
 
 
+def test_every_hip_file_is_built():
+    """a .hip file left out of HIP_SOURCES would only show as an unresolved symbol when the library loads"""
+    import __graft_entry__ as ge
+    assert len(ge.HIP_SOURCES) == len(set(ge.HIP_SOURCES))
+    assert set(ge.HIP_SOURCES) == {f for f in os.listdir(ge.CSRC) if f.endswith(".hip")}
+
+
 def test_header_is_plain_c():
     import subprocess, tempfile
     with tempfile.TemporaryDirectory() as d:

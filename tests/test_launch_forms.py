@@ -1,7 +1,8 @@
 """Parity of every launch form that batch size and image geometry select, each against the CPU oracle byte for byte.
 
-The host code picks kernel instances and grids by how many images a launch holds and by the geometry (orbx_extract.hip:
-orbx_extract_batch_device, orbx_stereo.hip: orbx_stereo_match_batch_device, orbx_bow.hip: bow_launch).  Each case below
+The host code picks kernel instances and grids by how many images a launch holds and by the geometry (the extractor's stages, each
+in its own file: orbx_pyramid_launch, orbx_fast_launch, orbx_tree_launch, orbx_desc_launch in orbx_pyramid.hip / orbx_fast.hip /
+orbx_tree.hip / orbx_desc.hip; orbx_stereo.hip: orbx_stereo_match_batch_device, orbx_bow.hip: bow_launch).  Each case below
 asserts through orbx_debug_launch_forms / orbx_debug_bow_last_form that the form it targets really ran, so a change of a
 threshold cannot leave a case silently testing something else.
 

@@ -7,7 +7,7 @@ packed-16, mul / mad, dot, cmp, cndmask, bcnt / mbcnt, bfe, lshl, any SDWA / DPP
 v_fma_f32 / v_fmac_f32 are full rate on normal operands (tools/ubench/fma_forms.hip, profiles/r03_fma_forms.txt; round 2 had timed
 them on denormals).  The cycle figures are priced at the idle-chip clock (2.4 GHz): in cycles of the loaded clock (~1.9-2.0 GHz) the two
 classes are ~2.1 and ~3.6, i.e. the guide's 2-cycle wave64 issue and its half-rate class; as TIMES per instruction they are what they are.
-Compiles orbx_extract.hip / orbx_stereo.hip to ISA (no GPU needed) and prints, per kernel, the instruction counts per class
+Compiles the extractor's stage files (orbx_pyramid.hip, orbx_fast.hip, orbx_tree.hip, orbx_desc.hip) and orbx_stereo.hip to ISA (no GPU needed) and prints, per kernel, the instruction counts per class
 and the mix-weighted cycles per VALU instruction that bench.py's roofline.issue uses (written into
 profiles/r02_sq_counters.json by tools/collect_sq.py)."""
 import json
@@ -66,7 +66,7 @@ def pretty(mangled):
 
 def main():
     res = {}
-    for src in ("orbx_extract.hip", "orbx_stereo.hip"):
+    for src in ("orbx_pyramid.hip", "orbx_fast.hip", "orbx_tree.hip", "orbx_desc.hip", "orbx_stereo.hip"):
         with tempfile.TemporaryDirectory() as d:
             out = os.path.join(d, "k.s")
             subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "-S", "--cuda-device-only",
