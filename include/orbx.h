@@ -381,7 +381,9 @@ int orbx_kf_search_for_triangulation(const orbx_kf *k1, const uint8_t *flag1, co
  * TemplatedVocabulary::loadFromTextFile builds them (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:
  * 1358-1445): parent id (0 = root), leaf flag, 32-byte descriptor, weight; children are attached
  * to their parent in id order and word ids are given to leaves in id order.  k <= 20, L <= 10 as
- * in the reference loader.  Only TF_IDF weighting with L1_NORM scoring (ORBvoc.txt) is supported. */
+ * in the reference loader.  Only TF_IDF weighting with L1_NORM scoring (ORBvoc.txt) is supported.
+ * The leaf flag must say what the tree says (isLeaf() is children.empty(), :328): a childless node
+ * without the flag, or a flagged node with children, is ORBX_E_INVALID here and in orbx_vocab_load_text. */
 typedef struct orbx_vocab orbx_vocab;
 int orbx_vocab_create(int device, int k, int L, int nnodes_minus_root, const int32_t *parent, const uint8_t *is_leaf,
                       const uint8_t *desc, const double *weight, orbx_vocab **out);

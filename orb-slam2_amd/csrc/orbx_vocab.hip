@@ -317,6 +317,13 @@ static int vocab_build(int device, int k, int L, int nm1, const int32_t *parent,
         for (int i = 1; i < n; i++) ids[cur[parent[i - 1]]++] = i; // children in id order (:1409)
     }
     if (off[1] == 0) { orbx_set_error("vocabulary root has no children"); return ORBX_E_INVALID; }
+    for (int i = 1; i < n; i++) {   // isLeaf() is children.empty() (:328), so saveToTextFile writes no other flag: a childless node without it would
+        const bool childless = off[i + 1] == off[i];    // end a descent with no word id, a flagged node with children would own a word nothing reaches
+        if (childless != (is_leaf[i - 1] != 0)) {
+            orbx_set_error("vocabulary node %d is %s but has %d children", i, is_leaf[i - 1] ? "flagged as a leaf" : "not flagged as a leaf", off[i + 1] - off[i]);
+            return ORBX_E_INVALID;
+        }
+    }
     int nwords = 0;
     for (int i = 1; i < n; i++) if (is_leaf[i - 1]) word[i] = nwords++; // :1425-1432
     std::vector<double> w(n, 0.0);

@@ -8,42 +8,7 @@ import pytest
 
 from tools import synth
 
-POP = np.array([bin(i).count("1") for i in range(256)])
-
-
-def _python_transform(k, L, parent, is_leaf, ndesc, weight, feats, levelsup):
-    n = len(parent) + 1
-    children = [[] for _ in range(n)]
-    for i, p in enumerate(parent):
-        children[p].append(i + 1)
-    word = {}
-    for i in range(1, n):
-        if is_leaf[i - 1]:
-            word[i] = len(word)
-    bow, fv = {}, {}
-    for fi, f in enumerate(feats):
-        node, level, nid = 0, 0, 0
-        while True:
-            level += 1
-            ch = children[node]
-            ds = [int(POP[f ^ ndesc[c - 1]].sum()) for c in ch]
-            node = ch[int(np.argmin(ds))]          # first minimum
-            if level == L - levelsup:
-                nid = node
-            if not children[node]:
-                break
-        w = weight[node - 1]
-        if w > 0:
-            bow[word[node]] = bow.get(word[node], 0.0) + w if word[node] in bow else w
-            fv.setdefault(nid, []).append(fi)
-    ids = sorted(bow)
-    vals = [bow[i] for i in ids]
-    norm = 0.0
-    for v in vals:
-        norm += abs(v)
-    if norm > 0:
-        vals = [v / norm for v in vals]
-    return ids, vals, {k_: fv[k_] for k_ in sorted(fv)}
+from vocab_model import python_transform as _python_transform      # the plain-Python restatement (moved to tests/vocab_model.py)
 
 
 def _data(seed, n=600):
@@ -147,6 +112,23 @@ def test_hip_vocab_edge_cases(pkg, oracle):
         pkg.ORBVocabulary(25, 2, par, leaf, nd, w)  # k > 20 (reference loader limit)
     with pytest.raises(pkg.OrbxError):
         pkg.ORBVocabulary.loadFromTextFile("/nonexistent/ORBvoc.txt")
+
+
+@pytest.mark.gpu
+def test_hip_vocab_rejects_inconsistent_leaf_flags(pkg, tmp_path):
+    """isLeaf() is children.empty() (TemplatedVocabulary.h:328), so no file DBoW2 writes has a childless node without the flag (its
+    word id would be 0xFFFFFFFF in the BowVector) or a flagged node with children"""
+    par, leaf, nd, w = synth.vocab_tree(12, 5, 2)
+    pkg.ORBVocabulary(5, 2, par, leaf, nd, w)          # consistent: accepted
+    unflagged = leaf.copy(); unflagged[-1] = 0         # a childless node not flagged
+    flagged = leaf.copy(); flagged[0] = 1              # node 1 has five children
+    for bad in (unflagged, flagged):
+        with pytest.raises(pkg.OrbxError, match="leaf"):
+            pkg.ORBVocabulary(5, 2, par, bad, nd, w)
+        path = os.path.join(tmp_path, "bad.txt")
+        synth.write_vocab_text(path, 5, 2, par, bad, nd, w)
+        with pytest.raises(pkg.OrbxError, match="leaf"):
+            pkg.ORBVocabulary.loadFromTextFile(path)
 
 
 @pytest.mark.gpu

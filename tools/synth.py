@@ -210,11 +210,14 @@ def flip_bits(rng, desc, p):
 
 
 def vocab_tree(seed, k=10, L=3, stop_frac=0.02, data=None):
-    """Seeded full k-ary vocabulary tree in DBoW2 id order (node ids assigned breadth-first, as
-    saveToTextFile / loadFromTextFile keep them): returns parent[], is_leaf[], desc[], weight[] for
-    nodes 1..N (the root is implicit).  Leaf weights are positive idf-like values, a fraction is 0
-    ("stopped" words, TemplatedVocabulary.h:1157).  Node descriptors are random, or sampled from
-    `data` descriptors (+ bit noise) so that real features spread over the tree."""
+    """Seeded FULL k-ary vocabulary tree with node ids assigned LEVEL BY LEVEL (breadth-first): returns
+    parent[], is_leaf[], desc[], weight[] for nodes 1..N (the root is implicit).  This is a valid
+    vocabulary file, but NOT the order DBoW2 gives its own trees: HKmeansStep numbers the children of
+    one node, then recurses into the first of them (TemplatedVocabulary.h:786-818), and
+    saveToTextFile / loadFromTextFile keep that order -- see vocab_tree_dbow2.  Leaf weights are
+    positive idf-like values, a fraction is 0 ("stopped" words, TemplatedVocabulary.h:1157).  Node
+    descriptors are random, or sampled from `data` descriptors (+ bit noise) so that real features
+    spread over the tree."""
     rng = np.random.Generator(np.random.PCG64(seed))
     parent, leaf = [], []
     level_nodes = [0]
@@ -233,6 +236,93 @@ def vocab_tree(seed, k=10, L=3, stop_frac=0.02, data=None):
     weight = np.where(np.array(leaf) == 1, rng.uniform(0.5, 9.0, n), 0.0)
     weight[(np.array(leaf) == 1) & (rng.random(n) < stop_frac)] = 0.0
     return np.array(parent, np.int32), np.array(leaf, np.uint8), desc, weight
+
+
+def _split_descriptors(rng, m, c, single_frac, minimum=None):
+    """m training descriptors over c clusters, none of them empty (TemplatedVocabulary.h:753); a seeded share of the clusters
+    keeps a single descriptor, the others share the rest unevenly"""
+    cnt = np.ones(c, np.int64) if minimum is None else np.asarray(minimum, np.int64).copy()
+    rest = m - int(cnt.sum())
+    assert rest >= 0, "not enough descriptors for the forced sibling groups"
+    if rest > 0:
+        grows = (rng.random(c) >= single_frac) | (cnt > 1)
+        if not grows.any():
+            grows[int(rng.integers(0, c))] = True
+        p = rng.gamma(1.0, 1.0, c) * grows
+        cnt += rng.multinomial(rest, p / p.sum())
+    return cnt
+
+
+def vocab_tree_dbow2(seed, k=10, L=6, n_feat=12000, stop_frac=0.02, noise=0.1, dup_frac=0.1, dup910_frac=0.5, single_frac=0.2,
+                     groups_l1=()):
+    """Seeded RAGGED vocabulary tree numbered and shaped as DBoW2 builds one from `n_feat` training descriptors
+    (TemplatedVocabulary::HKmeansStep, Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:642-819), without running k-means: only how many
+    descriptors each cluster holds is carried down.  Same four arrays as vocab_tree.
+
+      * a node holding m <= k descriptors gets one child per descriptor (:660-670); one holding more gets between k/2 and k (seeded;
+        k-means gives at most k, and fewer when initial centres coincide);
+      * ALL children of a node get consecutive ids first (:786-793) ...
+      * ... then each child holding more than one descriptor is expanded in turn while level < L (:796-817); a child with a single
+        descriptor stays a leaf at whatever level it is (:813).  So ids are neither level by level nor is a node's breadth-first
+        position its id, and leaves sit at every level.
+
+    Child descriptors are the parent's with `noise` bit noise (level 1: random).  A `dup_frac` share of siblings are exact copies of
+    the sibling before them, so distance ties between DIFFERENT subtrees are certain (first minimum wins, strict <, :1244); in a
+    `dup910_frac` share of the groups of more than ten children, child 10 also copies child 9 (a tie across the device's ten-child
+    trips).  `groups_l1[i]` forces the number of children of the i-th level-1 node (a test lever: sibling groups of 1, 10, 11 or 20
+    where k allows; HKmeansStep itself makes a group of one only when all centres coincide).  Weights as in vocab_tree: idf-like
+    on leaves, a `stop_frac` share 0."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    assert 2 <= k <= 20 and 1 <= L <= 10 and len(groups_l1) <= k and all(1 <= g <= k for g in groups_l1)
+    parent, desc = [], []          # nodes 1..N in id order
+    nchild = [0]                   # per node, the root included
+
+    def step(parent_id, parent_desc, m, level, forced=None):        # HKmeansStep(parent_id, descriptors, current_level), m = descriptors.size()
+        if forced is not None:
+            c = forced
+        elif m <= k:
+            c = m                                                    # :660-670
+        else:
+            c = int(rng.integers(max(1, k // 2), k + 1))
+        minimum = None
+        if level == 1 and groups_l1:
+            c = max(c, len(groups_l1))
+            minimum = np.ones(c, np.int64)
+            minimum[:len(groups_l1)] = [max(2 * g, 2) for g in groups_l1]
+        cnt = _split_descriptors(rng, m, c, single_frac, minimum)
+        if parent_desc is None:
+            d = rng.integers(0, 256, (c, 32), dtype=np.uint8)
+        else:
+            d = flip_bits(rng, np.repeat(parent_desc[None, :], c, axis=0), noise)
+        dup = rng.random(c) < dup_frac
+        for i in range(1, c):
+            if dup[i]:
+                d[i] = d[i - 1]
+        if c > 10 and rng.random() < dup910_frac:
+            d[10] = d[9]
+        first = len(parent) + 1
+        for i in range(c):                                           # create nodes: all children first (:786-793)
+            parent.append(parent_id); desc.append(d[i]); nchild.append(0)
+        nchild[parent_id] = c
+        if level < L:                                                # :796
+            for i in range(c):
+                if cnt[i] > 1:                                       # :813
+                    step(first + i, d[i], int(cnt[i]), level + 1,
+                         groups_l1[i] if level == 1 and i < len(groups_l1) else None)
+
+    step(0, None, int(n_feat), 1)                                    # create(): HKmeansStep(0, features, 1)
+    n = len(parent)
+    leaf = (np.array(nchild[1:]) == 0).astype(np.uint8)              # isLeaf() == children.empty() (:328)
+    weight = np.where(leaf == 1, rng.uniform(0.5, 9.0, n), 0.0)
+    weight[(leaf == 1) & (rng.random(n) < stop_frac)] = 0.0
+    return np.array(parent, np.int32), leaf, np.array(desc, np.uint8).reshape(n, 32), weight
+
+
+def vocab_features(seed, is_leaf, desc, n, noise=0.04):
+    """n features for a vocabulary: descriptors of seeded leaves with `noise` bit noise"""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    leaves = np.nonzero(np.asarray(is_leaf) == 1)[0]
+    return flip_bits(rng, desc[leaves[rng.integers(0, len(leaves), n)]], noise)
 
 
 def write_vocab_text(path, k, L, parent, is_leaf, desc, weight, scoring=0, weighting=0):
