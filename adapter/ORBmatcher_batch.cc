@@ -93,6 +93,101 @@ size_t KeyFrameCache::size()
     return mKFs.size();
 }
 
+// ---------------------------------------------------------------- resident keyframes of the projection searches
+
+KeyFrameFrames &KeyFrameFrames::instance()
+{
+    static KeyFrameFrames c;
+    return c;
+}
+
+KeyFrameFrames::~KeyFrameFrames() { clear(); }
+
+static void destroy_frame(const orbx_frame *f) { orbx_frame_destroy(const_cast<orbx_frame *>(f)); }
+
+// the entry of pKF if its shadow still equals the keyframe; otherwise (create, or a stale entry) a new resident copy
+FrameRef KeyFrameFrames::lookup(KeyFrame *pKF, bool create)
+{
+    const size_t n = (size_t)pKF->N;
+    const uint8_t *desc = dense_descriptors(pKF->mDescriptors, pKF->N);
+    const float bounds[4] = { (float)pKF->mnMinX, (float)pKF->mnMinY, (float)pKF->mnMaxX, (float)pKF->mnMaxY };
+    {
+        unique_lock<mutex> lock(mMutex);
+        map<const KeyFrame *, Entry>::iterator it = mKFs.find(pKF);
+        if (it == mKFs.end()) {
+            if (!create) return FrameRef();
+        } else {
+            const Entry &e = it->second;
+            if (e.device == Device() && e.n == pKF->N && memcmp(e.bounds, bounds, sizeof bounds) == 0 &&
+                (n == 0 || (memcmp(&e.keys[0], &pKF->mvKeysUn[0], n * sizeof(cv::KeyPoint)) == 0 &&
+                            memcmp(&e.u_right[0], &pKF->mvuRight[0], n * sizeof(float)) == 0 && memcmp(&e.desc[0], desc, 32 * n) == 0))) {
+                mHits++;
+                return e.frame;
+            }
+        }
+    }
+    // built outside the lock (a 1000-feature keyframe is a 53 KB upload and a grid build)
+    vector<float> x(n), y(n), angle(n);
+    vector<int32_t> octave(n);
+    for (size_t i = 0; i < n; i++) {
+        const cv::KeyPoint &kp = pKF->mvKeysUn[i];
+        x[i] = kp.pt.x; y[i] = kp.pt.y; angle[i] = kp.angle; octave[i] = kp.octave;
+    }
+    orbx_frame_feats ff;
+    memset(&ff, 0, sizeof ff);
+    ff.n = pKF->N;
+    if (n) {
+        ff.x = &x[0]; ff.y = &y[0]; ff.octave = &octave[0]; ff.angle = &angle[0]; ff.u_right = &pKF->mvuRight[0]; ff.desc = desc;
+    }
+    ff.min_x = bounds[0]; ff.min_y = bounds[1]; ff.max_x = bounds[2]; ff.max_y = bounds[3];
+    orbx_frame *f = NULL;
+    if (orbx_frame_create(Device(), &ff, &f) != ORBX_OK) throw std::runtime_error(orbx_last_error());
+    Entry e;
+    e.frame = FrameRef(f, destroy_frame);
+    e.device = Device(); e.n = pKF->N;
+    memcpy(e.bounds, bounds, sizeof bounds);
+    e.keys.assign(pKF->mvKeysUn.begin(), pKF->mvKeysUn.begin() + n);
+    e.u_right.assign(pKF->mvuRight.begin(), pKF->mvuRight.begin() + n);
+    e.desc.assign(desc, desc + 32 * n);
+    unique_lock<mutex> lock(mMutex);
+    mCreates++;
+    mKFs[pKF] = e;                            // (a copy another thread made meanwhile gives way: both hold the same content)
+    return e.frame;
+}
+
+FrameRef KeyFrameFrames::get(KeyFrame *pKF) { return lookup(pKF, true); }
+FrameRef KeyFrameFrames::find(KeyFrame *pKF) { return lookup(pKF, false); }
+
+void KeyFrameFrames::drop(const KeyFrame *pKF)
+{
+    FrameRef gone;                            // released outside the lock
+    unique_lock<mutex> lock(mMutex);
+    map<const KeyFrame *, Entry>::iterator it = mKFs.find(pKF);
+    if (it == mKFs.end()) return;
+    gone = it->second.frame;
+    mKFs.erase(it);
+}
+
+void KeyFrameFrames::clear()
+{
+    map<const KeyFrame *, Entry> gone;
+    unique_lock<mutex> lock(mMutex);
+    gone.swap(mKFs);
+}
+
+size_t KeyFrameFrames::size()
+{
+    unique_lock<mutex> lock(mMutex);
+    return mKFs.size();
+}
+
+void KeyFrameFrames::stats(int *creates, int *hits)
+{
+    unique_lock<mutex> lock(mMutex);
+    if (creates) *creates = mCreates;
+    if (hits) *hits = mHits;
+}
+
 // ---------------------------------------------------------------- per-call inputs
 
 // flag[i] = feature i holds a MapPoint that is not bad (src/ORBmatcher.cc:204-210, :605-626); the copy of the keyframe's MapPoint

@@ -8,6 +8,9 @@
 // the reference's own cv::Mat expressions (poses, depth, distance range, viewing angle, PredictScale); the window search, the level
 // gates, the chi-square gates of Fuse, the Hamming distances and the claiming order run on the device.  What changes the map --
 // Replace / AddObservation / AddMapPoint / vpReplacePoint -- is applied here, in the reference's order, from the device's answer.
+// The four searches whose target is a KeyFrame (both Fuse overloads, SearchBySim3, the Sim3 SearchByProjection) take the keyframe's
+// resident copy when it is registered with orbx_adapter::KeyFrameFrames (adapter/orbx_batch.h) and the host-pointer path otherwise;
+// orbx_adapter::FuseBatch, the first loop of LocalMapping::SearchInNeighbors as one launch, is defined at the end of this file.
 #include "ORBmatcher.h"
 
 #include <math.h>
@@ -15,14 +18,20 @@
 #include <stdexcept>
 
 #include "orbx_adapter.h"
+#include "orbx_batch.h"
 
 using namespace std;
 
 namespace ORB_SLAM2
 {
 
+using orbx_adapter::FrameRef;
 using orbx_adapter::FrameSide;
 using orbx_adapter::PointSide;
+
+// the keyframe's resident copy when it is registered with orbx_adapter::KeyFrameFrames (adapter/orbx_batch.h), else empty: the four
+// keyframe-target searches below then take the host-pointer path
+static FrameRef resident_keyframe(KeyFrame *pKF) { return orbx_adapter::KeyFrameFrames::instance().find(pKF); }
 
 // a KeyFrame's undistorted keypoints behind an orbx_frame_feats; bounds = the keyframe's image bounds (IsInImage runs on the device)
 static void keyframe_side(KeyFrame *pKF, FrameSide &s)
@@ -166,8 +175,12 @@ int ORBmatcher::SearchByProjection(KeyFrame *pKF, cv::Mat Scw, const vector<MapP
     decompose_sim3(Scw, Rcw, tcw, Ow);
     set<MapPoint *> spAlreadyFound(vpMatched.begin(), vpMatched.end());
     spAlreadyFound.erase(static_cast<MapPoint *>(NULL));
+    const FrameRef rk = resident_keyframe(pKF);
     FrameSide kf;
-    keyframe_side(pKF, kf);
+    if (!rk || orbx_adapter::kCapture)
+        keyframe_side(pKF, kf);
+    else
+        kf.occupied.assign((size_t)pKF->N, 0);
     for (size_t i = 0; i < kf.occupied.size(); i++)
         kf.occupied[i] = vpMatched[i] ? 1 : 0;                      // :386-387
     PointSide pts(vpPoints.size());
@@ -188,7 +201,10 @@ int ORBmatcher::SearchByProjection(KeyFrame *pKF, cv::Mat Scw, const vector<MapP
     vector<int32_t> match((size_t)(pKF->N > 0 ? pKF->N : 1));
     int nmatches = 0;
     ORBX_CAPTURE(kf.ff, &pts.pp);
-    if (orbx_search_by_projection_sim3(orbx_adapter::Device(), &kf.ff, &pts.pp, &pKF->mvScaleFactors[0], (int)pKF->mvScaleFactors.size(), (float)th, &match[0], &nmatches) != ORBX_OK)
+    const int rc = rk ? orbx_frame_search_by_projection_sim3(rk.get(), kf.occupied.empty() ? NULL : &kf.occupied[0], &pts.pp, &pKF->mvScaleFactors[0],
+                                                             (int)pKF->mvScaleFactors.size(), (float)th, &match[0], &nmatches)
+                      : orbx_search_by_projection_sim3(orbx_adapter::Device(), &kf.ff, &pts.pp, &pKF->mvScaleFactors[0], (int)pKF->mvScaleFactors.size(), (float)th, &match[0], &nmatches);
+    if (rc != ORBX_OK)
         throw std::runtime_error(orbx_last_error());
     for (int idx = 0; idx < pKF->N; idx++)
         if (match[idx] >= 0)
@@ -196,15 +212,13 @@ int ORBmatcher::SearchByProjection(KeyFrame *pKF, cv::Mat Scw, const vector<MapP
     return nmatches;
 }
 
-int ORBmatcher::Fuse(KeyFrame *pKF, const vector<MapPoint *> &vpMapPoints, const float th)
+// Fuse(pKF, vpMapPoints, th), the projection half (:885-949): what only the host can do, for every point that takes part
+static void fuse_project(KeyFrame *pKF, const vector<MapPoint *> &vpMapPoints, PointSide &pts, bool descriptors = true)
 {
     const cv::Mat Rcw = pKF->GetRotation();
     const cv::Mat tcw = pKF->GetTranslation();
     const float bf = pKF->mbf;
     const cv::Mat Ow = pKF->GetCameraCenter();
-    FrameSide kf;
-    keyframe_side(pKF, kf);
-    PointSide pts(vpMapPoints.size());
     for (size_t i = 0; i < vpMapPoints.size(); i++) {
         MapPoint *pMP = vpMapPoints[i];
         if (!pMP || pMP->isBad() || pMP->IsInKeyFrame(pKF))         // :889-893 (re-checked below: earlier Replace calls can change it)
@@ -218,17 +232,15 @@ int ORBmatcher::Fuse(KeyFrame *pKF, const vector<MapPoint *> &vpMapPoints, const
             continue;
         pts.level[i] = pMP->PredictScale(dist3D, pKF);
         pts.valid[i] = 1;
-        put_desc(pMP, &pts.desc[32 * i]);
+        if (descriptors)
+            put_desc(pMP, &pts.desc[32 * i]);
     }
-    const size_t np = vpMapPoints.size() ? vpMapPoints.size() : 1;
-    vector<int32_t> best(np, -1);
-    int nfound = 0;
-    ORBX_CAPTURE(kf.ff, &pts.pp);
-    if (orbx_window_best(orbx_adapter::Device(), &kf.ff, &pts.pp, &pKF->mvScaleFactors[0], &pKF->mvInvLevelSigma2[0], (int)pKF->mvScaleFactors.size(), th, 1, TH_LOW,
-                         &best[0], NULL, &nfound) != ORBX_OK)
-        throw std::runtime_error(orbx_last_error());
-    // the map surgery of :1011-1033, in the reference's order.  A point's best keypoint does not depend on the map state, but whether
-    // the point is still good and not yet in the keyframe does: an earlier Replace / AddObservation of this loop can have changed it.
+}
+
+// the map surgery of :1011-1033, in the reference's order.  A point's best keypoint does not depend on the map state, but whether
+// the point is still good and not yet in the keyframe does: an earlier Replace / AddObservation of this loop can have changed it.
+static int fuse_surgery(KeyFrame *pKF, const vector<MapPoint *> &vpMapPoints, const int32_t *best)
+{
     int nFused = 0;
     for (size_t i = 0; i < vpMapPoints.size(); i++) {
         MapPoint *pMP = vpMapPoints[i];
@@ -251,13 +263,36 @@ int ORBmatcher::Fuse(KeyFrame *pKF, const vector<MapPoint *> &vpMapPoints, const
     return nFused;
 }
 
+int ORBmatcher::Fuse(KeyFrame *pKF, const vector<MapPoint *> &vpMapPoints, const float th)
+{
+    const FrameRef rk = resident_keyframe(pKF);
+    FrameSide kf;
+    if (!rk || orbx_adapter::kCapture)
+        keyframe_side(pKF, kf);
+    PointSide pts(vpMapPoints.size());
+    fuse_project(pKF, vpMapPoints, pts);
+    const size_t np = vpMapPoints.size() ? vpMapPoints.size() : 1;
+    vector<int32_t> best(np, -1);
+    int nfound = 0;
+    ORBX_CAPTURE(kf.ff, &pts.pp);
+    const int rc = rk ? orbx_frame_window_best(rk.get(), &pts.pp, &pKF->mvScaleFactors[0], &pKF->mvInvLevelSigma2[0], (int)pKF->mvScaleFactors.size(), th, 1, TH_LOW,
+                                               &best[0], NULL, &nfound)
+                      : orbx_window_best(orbx_adapter::Device(), &kf.ff, &pts.pp, &pKF->mvScaleFactors[0], &pKF->mvInvLevelSigma2[0], (int)pKF->mvScaleFactors.size(), th, 1,
+                                         TH_LOW, &best[0], NULL, &nfound);
+    if (rc != ORBX_OK)
+        throw std::runtime_error(orbx_last_error());
+    return fuse_surgery(pKF, vpMapPoints, &best[0]);
+}
+
 int ORBmatcher::Fuse(KeyFrame *pKF, cv::Mat Scw, const vector<MapPoint *> &vpPoints, float th, vector<MapPoint *> &vpReplacePoint)
 {
     cv::Mat Rcw, tcw, Ow;
     decompose_sim3(Scw, Rcw, tcw, Ow);
     const set<MapPoint *> spAlreadyFound = pKF->GetMapPoints();
+    const FrameRef rk = resident_keyframe(pKF);
     FrameSide kf;
-    keyframe_side(pKF, kf);
+    if (!rk || orbx_adapter::kCapture)
+        keyframe_side(pKF, kf);
     PointSide pts(vpPoints.size());
     for (size_t i = 0; i < vpPoints.size(); i++) {
         MapPoint *pMP = vpPoints[i];
@@ -277,7 +312,9 @@ int ORBmatcher::Fuse(KeyFrame *pKF, cv::Mat Scw, const vector<MapPoint *> &vpPoi
     vector<int32_t> best(np, -1);
     int nfound = 0;
     ORBX_CAPTURE(kf.ff, &pts.pp);
-    if (orbx_window_best(orbx_adapter::Device(), &kf.ff, &pts.pp, &pKF->mvScaleFactors[0], NULL, (int)pKF->mvScaleFactors.size(), th, 0, TH_LOW, &best[0], NULL, &nfound) != ORBX_OK)
+    const int rc = rk ? orbx_frame_window_best(rk.get(), &pts.pp, &pKF->mvScaleFactors[0], NULL, (int)pKF->mvScaleFactors.size(), th, 0, TH_LOW, &best[0], NULL, &nfound)
+                      : orbx_window_best(orbx_adapter::Device(), &kf.ff, &pts.pp, &pKF->mvScaleFactors[0], NULL, (int)pKF->mvScaleFactors.size(), th, 0, TH_LOW, &best[0], NULL, &nfound);
+    if (rc != ORBX_OK)
         throw std::runtime_error(orbx_last_error());
     int nFused = 0;
     for (size_t i = 0; i < vpPoints.size(); i++) {                   // :1140-1157
@@ -323,9 +360,13 @@ int ORBmatcher::SearchBySim3(KeyFrame *pKF1, KeyFrame *pKF2, vector<MapPoint *> 
                 vbAlreadyMatched2[idx2] = true;
         }
     }
+    const FrameRef rk1 = resident_keyframe(pKF1), rk2 = resident_keyframe(pKF2);
+    const bool resident = rk1 && rk2;                                // both keyframes, or the host-pointer path
     FrameSide kf1, kf2;
-    keyframe_side(pKF1, kf1);
-    keyframe_side(pKF2, kf2);
+    if (!resident || orbx_adapter::kCapture) {
+        keyframe_side(pKF1, kf1);
+        keyframe_side(pKF2, kf2);
+    }
     PointSide p12((size_t)N1), p21((size_t)N2);
     for (int dir = 0; dir < 2; dir++) {
         // dir 0: KF1's points into KF2 (:1207-1262); dir 1: the mirror image (:1289-1344)
@@ -360,8 +401,11 @@ int ORBmatcher::SearchBySim3(KeyFrame *pKF1, KeyFrame *pKF2, vector<MapPoint *> 
     int nFound = 0;
     ORBX_CAPTURE(kf2.ff, &p12.pp);
     ORBX_CAPTURE2(kf1.ff, &p21.pp);
-    if (orbx_search_by_sim3(orbx_adapter::Device(), &kf1.ff, &kf2.ff, &p12.pp, &p21.pp, &pKF1->mvScaleFactors[0], &pKF2->mvScaleFactors[0], (int)pKF1->mvScaleFactors.size(), th,
-                            &m12[0], &nFound) != ORBX_OK)
+    const int rc = resident ? orbx_frame_search_by_sim3(rk1.get(), rk2.get(), &p12.pp, &p21.pp, &pKF1->mvScaleFactors[0], &pKF2->mvScaleFactors[0],
+                                                        (int)pKF1->mvScaleFactors.size(), th, &m12[0], &nFound)
+                            : orbx_search_by_sim3(orbx_adapter::Device(), &kf1.ff, &kf2.ff, &p12.pp, &p21.pp, &pKF1->mvScaleFactors[0], &pKF2->mvScaleFactors[0],
+                                                  (int)pKF1->mvScaleFactors.size(), th, &m12[0], &nFound);
+    if (rc != ORBX_OK)
         throw std::runtime_error(orbx_last_error());
     for (int i1 = 0; i1 < N1; i1++)
         if (m12[i1] >= 0)
@@ -369,4 +413,92 @@ int ORBmatcher::SearchBySim3(KeyFrame *pKF1, KeyFrame *pKF2, vector<MapPoint *> 
     return nFound;
 }
 
+// orbx_adapter::FuseBatch (adapter/orbx_batch.h): projection and surgery are the single Fuse's, the searches of all targets are one launch
+struct FuseBatchCounts { int launches, researched; FuseBatchCounts() : launches(0), researched(0) {} };
+static FuseBatchCounts &fuse_batch_counts()
+{
+    static thread_local FuseBatchCounts c;
+    return c;
+}
+
+static void fuse_batch(const vector<KeyFrame *> &vpTargetKFs, const vector<MapPoint *> &vpMapPoints, vector<int> &vnFused, float th)
+{
+    const size_t nt = vpTargetKFs.size(), np = vpMapPoints.size();
+    vnFused.assign(nt, 0);
+    if (nt == 0) return;
+    // the descriptors as they are at entry: one array, shared by the jobs of all targets (one uploaded copy)
+    vector<uint8_t> desc0(32 * (np ? np : 1), 0);
+    for (size_t i = 0; i < np; i++)
+        if (vpMapPoints[i] && !vpMapPoints[i]->isBad())
+            put_desc(vpMapPoints[i], &desc0[32 * i]);
+    vector<FrameRef> frames(nt);
+    vector<PointSide *> sides(nt, static_cast<PointSide *>(NULL));
+    vector<vector<int32_t> > best(nt, vector<int32_t>(np ? np : 1, -1));
+    vector<orbx_window_job> jobs(nt);
+    struct Sides { vector<PointSide *> &v; ~Sides() { for (size_t i = 0; i < v.size(); i++) delete v[i]; } } owner = { sides };
+    for (size_t t = 0; t < nt; t++) {
+        KeyFrame *pKF = vpTargetKFs[t];
+        frames[t] = orbx_adapter::KeyFrameFrames::instance().get(pKF);
+        sides[t] = new PointSide(np);
+        fuse_project(pKF, vpMapPoints, *sides[t], false);
+        if (np) sides[t]->pp.desc = &desc0[0];
+        orbx_window_job &jb = jobs[t];
+        memset(&jb, 0, sizeof jb);
+        jb.kf = frames[t].get(); jb.pts = &sides[t]->pp; jb.scale_factors = &pKF->mvScaleFactors[0]; jb.inv_sigma2 = &pKF->mvInvLevelSigma2[0];
+        jb.nlevels = (int)pKF->mvScaleFactors.size(); jb.th = th; jb.chi2 = 1; jb.max_dist = ORBmatcher::TH_LOW; jb.best_idx = &best[t][0];
+    }
+    if (orbx_frame_window_best_batch(&jobs[0], (int)nt) != ORBX_OK)
+        throw std::runtime_error(orbx_last_error());
+    fuse_batch_counts().launches++;
+    vector<size_t> changed;
+    for (size_t t = 0; t < nt; t++) {
+        KeyFrame *pKF = vpTargetKFs[t];
+        const PointSide &ps = *sides[t];
+        // the surgery of the targets before this one can have given a surviving point another descriptor (Replace ->
+        // ComputeDistinctiveDescriptors): such points are searched again against this target with the descriptor they have now
+        changed.clear();
+        for (size_t i = 0; t > 0 && i < np; i++) {
+            MapPoint *pMP = vpMapPoints[i];
+            if (!ps.valid[i] || pMP->isBad() || pMP->IsInKeyFrame(pKF))
+                continue;
+            const cv::Mat d = pMP->GetDescriptor();
+            if (!d.empty() && memcmp(d.data, &desc0[32 * i], 32) != 0)
+                changed.push_back(i);
+        }
+        if (!changed.empty()) {
+            PointSide again(changed.size());
+            for (size_t k = 0; k < changed.size(); k++) {
+                const size_t i = changed[k];
+                again.u[k] = ps.u[i]; again.v[k] = ps.v[i]; again.aux[k] = ps.aux[i]; again.level[k] = ps.level[i]; again.valid[k] = 1;
+                put_desc(vpMapPoints[i], &again.desc[32 * k]);
+            }
+            vector<int32_t> b(changed.size(), -1);
+            int nfound = 0;
+            if (orbx_frame_window_best(frames[t].get(), &again.pp, &pKF->mvScaleFactors[0], &pKF->mvInvLevelSigma2[0], (int)pKF->mvScaleFactors.size(), th, 1,
+                                       ORBmatcher::TH_LOW, &b[0], NULL, &nfound) != ORBX_OK)
+                throw std::runtime_error(orbx_last_error());
+            for (size_t k = 0; k < changed.size(); k++)
+                best[t][changed[k]] = b[k];
+            fuse_batch_counts().researched += (int)changed.size();
+        }
+        vnFused[t] = fuse_surgery(pKF, vpMapPoints, &best[t][0]);
+    }
+}
+
 } // namespace ORB_SLAM2
+
+namespace orbx_adapter
+{
+
+void FuseBatch(const vector<ORB_SLAM2::KeyFrame *> &vpTargetKFs, const vector<ORB_SLAM2::MapPoint *> &vpMapPoints, vector<int> &vnFused, float th)
+{
+    ORB_SLAM2::fuse_batch(vpTargetKFs, vpMapPoints, vnFused, th);
+}
+
+void FuseBatchStats(int *launches, int *researched)
+{
+    if (launches) *launches = ORB_SLAM2::fuse_batch_counts().launches;
+    if (researched) *researched = ORB_SLAM2::fuse_batch_counts().researched;
+}
+
+} // namespace orbx_adapter

@@ -545,7 +545,9 @@ typedef struct {
  * and 64x48 grid (Frame::AssignFeaturesToGrid, src/Frame.cc:261-279) never change in between.  orbx_frame keeps that
  * immutable part in HBM -- undistorted x / y, octave, angle, u_right, descriptors, bounds and the grid, built once at
  * creation -- and the searches below move only the projected points, the per-call `occupied` bytes and the results.
- * One frame is used by one thread at a time (as the extractor handles); distinct frames may be used concurrently. */
+ * One frame is used by one thread at a time (as the extractor handles); distinct frames may be used concurrently.  (The
+ * keyframe searches further down -- orbx_frame_window_best, _window_best_batch, _search_by_sim3, _search_by_projection_sim3 --
+ * only read the handle and may share one frame among threads; see there.) */
 typedef struct orbx_frame orbx_frame;
 /* from host pointers: one upload, then the grid build; synchronises.  f->occupied is ignored; f->angle may be NULL (then only
  * searches without the orientation check accept the frame).  Refused as the host-pointer searches refuse the frame: n >= 65536,
@@ -580,6 +582,49 @@ int orbx_frame_search_by_projection_map_points(orbx_frame *cur, const uint8_t *o
 int orbx_frame_search_by_projection_keyframe(orbx_frame *cur, const uint8_t *occupied, const orbx_proj_points *pts,
                                              const float *scale_factors, int nlevels, float th, int orb_dist,
                                              int check_orientation, int32_t *match_cur, int *nmatches);
+
+/* ---- resident keyframes for the projection searches of LocalMapping and LoopClosing ----------------------------------
+ * A keyframe's keypoints and descriptors never change once it exists (src/KeyFrame.cc:29-60), and the same keyframes are
+ * searched again and again (LocalMapping::SearchInNeighbors, src/LocalMapping.cc:515-599: Fuse into up to 60 / 120 neighbours
+ * per new keyframe; LoopClosing::ComputeSim3 / SearchAndFuse).  An orbx_frame made once from the keyframe (mvKeysUn, mvuRight,
+ * mDescriptors, the keyframe's image bounds) serves as the target: a call moves only the projected points and the results.
+ * Arguments, results and refusals are those of the host-pointer twins named below, with the keyframe given by handle.
+ * THREADS: unlike the three per-frame searches above, the four calls below take a const handle and only read it -- several
+ * threads may search one keyframe at the same time (LocalMapping and LoopClosing do); the staging is the calling thread's.  A
+ * frame whose creation is still pending (orbx_frame_create_from_extraction) is waited for through its event, the handle is
+ * not written.  NULL and range refusals come before any device call. */
+/* orbx_window_best on a resident keyframe: the search half of ORBmatcher::Fuse(KeyFrame*, const vector<MapPoint*>&, th)
+ * (src/ORBmatcher.cc:873-1038), of Fuse(KeyFrame*, Scw, vpPoints, th, vpReplacePoint) (:1040-1164) and of each direction of
+ * SearchBySim3 (:1218-1372).  One upload (the points), one launch, one download; nfound may be NULL. */
+int orbx_frame_window_best(const orbx_frame *kf, const orbx_proj_points *pts, const float *scale_factors,
+                           const float *inv_sigma2, int nlevels, float th, int chi2, int max_dist,
+                           int32_t *best_idx, int32_t *best_dist, int *nfound);
+/* one (keyframe, points) search of a batch: the arguments of orbx_frame_window_best */
+typedef struct {
+    const orbx_frame *kf; const orbx_proj_points *pts;
+    const float *scale_factors, *inv_sigma2;     /* [nlevels] of kf; inv_sigma2 only when chi2 != 0 */
+    int nlevels; float th; int chi2, max_dist;
+    int32_t *best_idx, *best_dist;               /* [pts->n] out; best_dist may be NULL */
+    int nfound;                                  /* out */
+} orbx_window_job;
+/* njobs searches (the loop `for each target keyframe: Fuse(pKFi, vpMapPointMatches)` of src/LocalMapping.cc:549-554, or the two
+ * directions of SearchBySim3) as ONE upload, ONE launch, ONE download; every job's results equal its single call.  A keyframe may
+ * be named by several jobs; jobs whose pts->desc is the same host array (and length) share one uploaded copy.  A job without
+ * points or whose keyframe has no features gets -1 / 256 / nfound 0; if every job is empty nothing is launched.
+ * ORBX_E_INVALID: njobs outside [1, 1024], a NULL handle / points / scale_factors / best_idx, keyframes on different devices, more
+ * than 2^20 points in all, max_dist outside [0, 256], nlevels outside [1, 16], a valid point whose level is outside [0, nlevels),
+ * missing point arrays (u, v, level, desc, valid; aux and inv_sigma2 when chi2). */
+int orbx_frame_window_best_batch(orbx_window_job *jobs, int njobs);
+/* orbx_search_by_projection_sim3 (ORBmatcher::SearchByProjection(KeyFrame*, Scw, vpPoints, vpMatched, th), src/ORBmatcher.cc:305-415)
+ * on a resident keyframe; occupied[kf n] = vpMatched[idx] != NULL passed per call (NULL: none).  Matches claim their keypoint,
+ * so this search keeps the list + resolve kernels of its twin. */
+int orbx_frame_search_by_projection_sim3(const orbx_frame *kf, const uint8_t *occupied, const orbx_proj_points *pts,
+                                         const float *scale_factors, int nlevels, float th, int32_t *match_kf, int *nmatches);
+/* orbx_search_by_sim3 (ORBmatcher::SearchBySim3, src/ORBmatcher.cc:1166-1394) on two resident keyframes: both directions
+ * (:1218-1292, :1295-1372) are two jobs of one batch launch, then the agreement check of :1375-1391 on the host. */
+int orbx_frame_search_by_sim3(const orbx_frame *kf1, const orbx_frame *kf2, const orbx_proj_points *pts12,
+                              const orbx_proj_points *pts21, const float *scale_factors1, const float *scale_factors2,
+                              int nlevels, float th, int32_t *match12, int *nfound);
 
 /* ORBmatcher::SearchByProjection(Frame &CurrentFrame, const Frame &LastFrame, th, bMono) (src/ORBmatcher.cc:1396-1553;
  * Tracking::TrackWithMotionModel).  direction: 0 none, 1 bForward, 2 bBackward (:1412-1413).  match_cur[cur->n] =

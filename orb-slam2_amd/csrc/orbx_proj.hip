@@ -577,6 +577,83 @@ __global__ __launch_bounds__(64) void k_init_resolve(DevFrame F, DevPoints P, Pr
     if (lane == 0) *out_n = nm;
 }
 
+// ---- independent points against resident keyframes (Fuse x2 :873-1164, each direction of SearchBySim3 :1218-1372): with
+// ProjParams::claims == 0 a point's answer is the first minimum of its own candidate list, so list and decision fuse into ONE kernel --
+// no pool, no atomics, no second launch -- and one launch serves many (keyframe, points) jobs.  Job j owns the workgroups
+// wg_first[j] .. wg_first[j + 1] (four points each, one wave per point, as k_proj_lists); the job table lives in device memory and is
+// found by a wave-uniform search.  The window, the level range and the column-run flattening are those of k_proj_lists; instead of
+// appending the survivors every lane keeps its smallest (dist << 16 | position in GetFeaturesInArea's traversal), dist <= 256 and
+// position < 65536 (a frame holds fewer features than that), and one wave minimum gives the reference's strict '<' (:995-999): the
+// smallest distance and, among equals, the FIRST candidate in traversal order.
+struct WinJob {
+    DevFrame F;
+    const int *cell_off, *cell_idx;
+    DevPoints P;
+    ProjParams pp;       // th, chi2, max_dist, sf[], inv_sigma2[] of the job; bounds = 2, levels [level - 1, level], claims = 0
+    int out_off;         // the job's first entry in best_idx / best_dist
+};
+
+__global__ __launch_bounds__(256) void k_window_best(const WinJob *__restrict__ jobs, const int *__restrict__ wg_first, int njobs,
+                                                     int32_t *__restrict__ best_idx, int32_t *__restrict__ best_dist)
+{
+    const int wg = blockIdx.x;
+    int lo = 0, hi = njobs;                 // the last job with wg_first[j] <= wg (jobs without workgroups are passed over)
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (wg_first[mid] <= wg) lo = mid; else hi = mid;
+    }
+    const WinJob &J = jobs[lo];
+    const int i = (wg - wg_first[lo]) * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (i >= J.P.n) return; // wave-uniform
+    unsigned key = 0xFFFFFFFFu;             // lane-local: smallest (dist << 16 | position), and the feature it belongs to
+    int key_k = -1;
+    Win w;
+    if (point_window(J.F, J.P, J.pp, i, &w)) {
+        const int ncol = w.cx1 - w.cx0 + 1;
+        int c_lo = 0, c_n = 0;
+        if (lane < ncol) {
+            const int ix = w.cx0 + lane;
+            c_lo = J.cell_off[ix * PG_ROWS + w.cy0];
+            c_n = J.cell_off[ix * PG_ROWS + w.cy1 + 1] - c_lo;
+        }
+        const int c_incl = wave_incl_scan(c_n), c_excl = c_incl - c_n;
+        const int upper = __builtin_amdgcn_readlane(c_incl, 63);
+        if (upper) {
+            uint32_t d[8];
+            const uint4 *s = reinterpret_cast<const uint4 *>(J.P.desc + (long long)i * 8);
+            const uint4 q0 = s[0], q1 = s[1];
+            d[0] = q0.x; d[1] = q0.y; d[2] = q0.z; d[3] = q0.w; d[4] = q1.x; d[5] = q1.y; d[6] = q1.z; d[7] = q1.w;
+            for (int jb = 0; jb < upper; jb += 64) {
+                const int jf = jb + lane;            // position in the flattened candidate sequence
+                int j = -1;
+                for (int q = 0; q < ncol; q++) {
+                    const int e_ = __builtin_amdgcn_readlane(c_excl, q), n_ = __builtin_amdgcn_readlane(c_n, q), l_ = __builtin_amdgcn_readlane(c_lo, q);
+                    if (jf >= e_ && jf < e_ + n_) j = l_ + (jf - e_);
+                }
+                if (jf < upper) {
+                    const int k = J.cell_idx[j];
+                    if (cand_ok(J.F, J.P, J.pp, w, i, k)) {
+                        const uint4 *t = reinterpret_cast<const uint4 *>(J.F.desc + (long long)k * 8);
+                        const uint4 v0 = t[0], v1 = t[1];
+                        const int dist = __popc(d[0] ^ v0.x) + __popc(d[1] ^ v0.y) + __popc(d[2] ^ v0.z) + __popc(d[3] ^ v0.w) +
+                                         __popc(d[4] ^ v1.x) + __popc(d[5] ^ v1.y) + __popc(d[6] ^ v1.z) + __popc(d[7] ^ v1.w);
+                        const unsigned nk = ((unsigned)dist << 16) | (unsigned)jf;
+                        if (nk < key) { key = nk; key_k = k; }   // a lane's positions ascend: '<' keeps its first minimum
+                    }
+                }
+            }
+        }
+    }
+    const unsigned best = wave_min_u32(key);
+    int out_k = -1, out_d = 256;
+    if (best != 0xFFFFFFFFu && (int)(best >> 16) <= J.pp.max_dist) {
+        const int src = (int)__builtin_ctzll(__ballot(key == best));   // positions are unique: exactly one lane holds the minimum
+        out_k = __builtin_amdgcn_readlane(key_k, src);
+        out_d = (int)(best >> 16);
+    }
+    if (lane == 0) { best_idx[J.out_off + i] = out_k; best_dist[J.out_off + i] = out_d; }
+}
+
 // ---------------------------------------------------------------- host side
 
 struct ProjCtx : ThreadCtx {
@@ -1087,9 +1164,11 @@ extern "C" void orbx_frame_destroy(orbx_frame *f)
 }
 
 // the resident twin of proj_run: the same point validation; the frame's arrays and grid come from its block, only part 2 runs
-static int proj_run_resident(orbx_frame *f, const uint8_t *occupied, const orbx_proj_points *pts, const float *sf, int nlevels,
-                             const ProjParams &pp, int32_t *match_cur, int *nmatches)
+// (the handle is only read: *synced says whether the search ran, and with it synchronised behind the frame's creation)
+static int proj_run_resident(const orbx_frame *f, const uint8_t *occupied, const orbx_proj_points *pts, const float *sf, int nlevels,
+                             const ProjParams &pp, int32_t *match_cur, int *nmatches, bool *synced)
 {
+    *synced = false;
     if (!f || !pts || !sf || !match_cur || !nmatches || nlevels < 1 || nlevels > ORBX_MAX_LEVELS || pts->n < 0 || pts->n > (1 << 20)) {
         orbx_set_error("orbx_frame_search_by_projection: invalid argument");
         return ORBX_E_INVALID;
@@ -1111,7 +1190,17 @@ static int proj_run_resident(orbx_frame *f, const uint8_t *occupied, const orbx_
     const uint8_t *d = f->blk.d;
     rc = proj_search(c, frame_dev(f), 0, (const int *)(d + f->o_coff), (const int *)(d + f->o_cidx), occupied, pts, sf, nlevels, pp,
                      match_cur, nmatches, nullptr, nullptr, nullptr);
-    if (!rc) f->pending = false;   // this search synchronised behind the creation
+    if (!rc) *synced = true;
+    return rc;
+}
+
+// the per-frame searches: one thread at a time on a frame, so the search that synchronised behind the creation may say so in the handle
+static int proj_run_resident_own(orbx_frame *f, const uint8_t *occupied, const orbx_proj_points *pts, const float *sf, int nlevels,
+                                 const ProjParams &pp, int32_t *match_cur, int *nmatches)
+{
+    bool synced;
+    const int rc = proj_run_resident(f, occupied, pts, sf, nlevels, pp, match_cur, nmatches, &synced);
+    if (synced) f->pending = false;
     return rc;
 }
 
@@ -1120,19 +1209,194 @@ extern "C" int orbx_frame_search_by_projection_last_frame(orbx_frame *cur, const
                                                           int check_orientation, int32_t *match_cur, int *nmatches)
 {
     if (direction < 0 || direction > 2) { orbx_set_error("direction must be 0 (none), 1 (forward) or 2 (backward)"); return ORBX_E_INVALID; }
-    return proj_run_resident(cur, occupied, pts, scale_factors, nlevels, params_last_frame(th, direction, mbf, check_orientation), match_cur, nmatches);
+    return proj_run_resident_own(cur, occupied, pts, scale_factors, nlevels, params_last_frame(th, direction, mbf, check_orientation), match_cur, nmatches);
 }
 
 extern "C" int orbx_frame_search_by_projection_map_points(orbx_frame *cur, const uint8_t *occupied, const orbx_proj_points *pts,
                                                           const float *scale_factors, int nlevels, float th, float nnratio,
                                                           int32_t *match_cur, int *nmatches)
 {
-    return proj_run_resident(cur, occupied, pts, scale_factors, nlevels, params_map_points(th, nnratio), match_cur, nmatches);
+    return proj_run_resident_own(cur, occupied, pts, scale_factors, nlevels, params_map_points(th, nnratio), match_cur, nmatches);
 }
 
 extern "C" int orbx_frame_search_by_projection_keyframe(orbx_frame *cur, const uint8_t *occupied, const orbx_proj_points *pts,
                                                         const float *scale_factors, int nlevels, float th, int orb_dist,
                                                         int check_orientation, int32_t *match_cur, int *nmatches)
 {
-    return proj_run_resident(cur, occupied, pts, scale_factors, nlevels, params_keyframe(th, orb_dist, check_orientation), match_cur, nmatches);
+    return proj_run_resident_own(cur, occupied, pts, scale_factors, nlevels, params_keyframe(th, orb_dist, check_orientation), match_cur, nmatches);
+}
+
+// ---------------------------------------------------------------- resident keyframes: Fuse, SearchBySim3, Sim3 SearchByProjection
+// A keyframe's keypoints and descriptors never change (src/KeyFrame.cc:29-60): an orbx_frame serves as the keyframe.  These calls only
+// read the handle, so LocalMapping and LoopClosing may search one keyframe at the same time; the staging is the calling thread's ProjCtx.
+
+extern "C" int orbx_frame_search_by_projection_sim3(const orbx_frame *kf, const uint8_t *occupied, const orbx_proj_points *pts,
+                                                    const float *scale_factors, int nlevels, float th, int32_t *match_kf, int *nmatches)
+{
+    ProjParams pp;
+    memset(&pp, 0, sizeof pp);
+    pp.bounds = 2; pp.lo_off = -1; pp.hi_off = 0; pp.max_dist = 50; pp.claims = 2;   // as orbx_search_by_projection_sim3
+    pp.th = th;
+    bool synced;
+    return proj_run_resident(kf, occupied, pts, scale_factors, nlevels, pp, match_kf, nmatches, &synced);
+}
+
+// the refusals of one job, before any device call and without reading the handle
+static int window_job_check(const orbx_window_job &jb, int j)
+{
+    if (!jb.kf || !jb.pts || !jb.scale_factors || !jb.best_idx || jb.nlevels < 1 || jb.nlevels > ORBX_MAX_LEVELS || jb.pts->n < 0 ||
+        jb.pts->n > (1 << 20) || jb.max_dist < 0 || jb.max_dist > 256) {
+        orbx_set_error("orbx_frame_window_best: job %d: invalid argument", j);
+        return ORBX_E_INVALID;
+    }
+    const orbx_proj_points *p = jb.pts;
+    if (p->n && (!p->u || !p->v || !p->level || !p->desc || !p->valid || (jb.chi2 && !p->aux))) { orbx_set_error("job %d: point arrays missing", j); return ORBX_E_INVALID; }
+    if (jb.chi2 && !jb.inv_sigma2) { orbx_set_error("job %d: inv_sigma2 missing", j); return ORBX_E_INVALID; }
+    for (int i = 0; i < p->n; i++)
+        if (p->valid[i] && (p->level[i] < 0 || p->level[i] >= jb.nlevels)) { orbx_set_error("job %d, point %d: level %d out of range", j, i, p->level[i]); return ORBX_E_INVALID; }
+    return ORBX_OK;
+}
+
+extern "C" int orbx_frame_window_best_batch(orbx_window_job *jobs, int njobs)
+{
+    if (!jobs || njobs < 1 || njobs > 1024) { orbx_set_error("orbx_frame_window_best_batch: 1 to 1024 jobs"); return ORBX_E_INVALID; }
+    size_t total_in = 0;
+    for (int j = 0; j < njobs; j++) {
+        const int rc = window_job_check(jobs[j], j);
+        if (rc) return rc;
+        total_in += (size_t)jobs[j].pts->n;
+    }
+    if (total_in > ((size_t)1 << 20)) { orbx_set_error("orbx_frame_window_best_batch: more than 2^20 points in one call"); return ORBX_E_INVALID; }
+    const int device = jobs[0].kf->device;
+    for (int j = 1; j < njobs; j++)
+        if (jobs[j].kf->device != device) { orbx_set_error("orbx_frame_window_best_batch: the keyframes live on different devices"); return ORBX_E_INVALID; }
+    // jobs with work, their workgroups and output offsets; the points' staging: u v level valid [aux] per job, descriptors once per
+    // distinct host array (the jobs of one FuseBatch share the map points' descriptors)
+    std::vector<int> wg_first((size_t)njobs + 1, 0);
+    std::vector<size_t> o_desc((size_t)njobs, 0);
+    size_t blob = a16(sizeof(WinJob) * (size_t)njobs);
+    const size_t o_wg = blob;
+    blob += a16(sizeof(int) * ((size_t)njobs + 1));
+    size_t total = 0;
+    for (int j = 0; j < njobs; j++) {
+        orbx_window_job &jb = jobs[j];
+        jb.nfound = 0;
+        const size_t np = (size_t)jb.pts->n;
+        for (size_t i = 0; i < np; i++) { jb.best_idx[i] = -1; if (jb.best_dist) jb.best_dist[i] = 256; }
+        const bool work = np && jb.kf->n;
+        wg_first[j + 1] = wg_first[j] + (work ? (int)((np + 3) / 4) : 0);
+        if (!work) continue;
+        total += np;
+        int same = -1;
+        for (int q = 0; q < j && same < 0; q++)
+            if (o_desc[q] && jobs[q].pts->desc == jb.pts->desc && jobs[q].pts->n == jb.pts->n) same = q;
+        if (same >= 0) o_desc[j] = o_desc[same];
+        else { o_desc[j] = blob; blob += a16(32 * np); }
+    }
+    if (total == 0) return ORBX_OK;
+    ProjCtx *c;
+    int rc = orbx_ctx_get(g_proj, device, &c);
+    if (rc) return rc;
+    const size_t o_pts = blob;
+    for (int j = 0; j < njobs; j++)
+        if (wg_first[j + 1] > wg_first[j]) { const size_t np = (size_t)jobs[j].pts->n; blob += 3 * a16(4 * np) + a16(np) + (jobs[j].chi2 ? a16(4 * np) : 0); }
+    if ((rc = proj_blob_reserve(c, blob))) return rc;
+    const size_t out = 2 * sizeof(int32_t) * total;
+    if (out > c->work_cap && (rc = ensure(&c->d_work, &c->work_cap, 2 * out))) return rc;
+    if (out > c->out_cap && (rc = ensure_pinned(&c->h_out, &c->out_cap, 2 * out))) return rc;
+    uint8_t *h = c->h_blob;
+    const uint8_t *d = c->d_blob;
+    WinJob *wj = reinterpret_cast<WinJob *>(h);
+    memcpy(h + o_wg, wg_first.data(), sizeof(int) * ((size_t)njobs + 1));
+    size_t o = o_pts, off = 0;
+    bool pending = false;
+    for (int j = 0; j < njobs; j++) {
+        const orbx_window_job &jb = jobs[j];
+        WinJob &W = wj[j];
+        memset(&W, 0, sizeof W);
+        if (wg_first[j + 1] == wg_first[j]) continue;   // no workgroup reads the record
+        const orbx_frame *f = jb.kf;
+        const orbx_proj_points *p = jb.pts;
+        const size_t np = (size_t)p->n;
+        auto take = [&](size_t bytes) { const size_t r = o; o += a16(bytes); return r; };
+        const size_t pu = take(4 * np), pv = take(4 * np), pl = take(4 * np), pval = take(np), pa = jb.chi2 ? take(4 * np) : 0;
+        memcpy(h + pu, p->u, 4 * np); memcpy(h + pv, p->v, 4 * np); memcpy(h + pl, p->level, 4 * np); memcpy(h + pval, p->valid, np);
+        if (jb.chi2) memcpy(h + pa, p->aux, 4 * np);
+        bool first = true;
+        for (int q = 0; q < j; q++) if (o_desc[q] == o_desc[j]) first = false;
+        if (first) memcpy(h + o_desc[j], p->desc, 32 * np);
+        W.F = frame_dev(f);
+        W.cell_off = (const int *)(f->blk.d + f->o_coff); W.cell_idx = (const int *)(f->blk.d + f->o_cidx);
+        W.P.n = p->n; W.P.u = (const float *)(d + pu); W.P.v = (const float *)(d + pv); W.P.level = (const int32_t *)(d + pl);
+        W.P.valid = d + pval; W.P.aux = jb.chi2 ? (const float *)(d + pa) : nullptr; W.P.desc = (const uint32_t *)(d + o_desc[j]);
+        W.pp.bounds = 2; W.pp.lo_off = -1; W.pp.hi_off = 0; W.pp.max_dist = jb.max_dist; W.pp.chi2 = jb.chi2 ? 1 : 0; W.pp.th = jb.th;
+        for (int i = 0; i < ORBX_MAX_LEVELS; i++) {
+            W.pp.sf[i] = i < jb.nlevels ? jb.scale_factors[i] : 0.f;
+            W.pp.inv_sigma2[i] = (jb.chi2 && i < jb.nlevels) ? jb.inv_sigma2[i] : 0.f;
+        }
+        W.out_off = (int)off;
+        off += np;
+        pending = pending || f->pending;
+    }
+    if (pending)   // a keyframe made from extraction buffers whose creation may still run: ordered by its event, the handle is not written
+        for (int j = 0; j < njobs; j++)
+            if (wg_first[j + 1] > wg_first[j] && jobs[j].kf->pending) ORBX_HIP(hipStreamWaitEvent(c->stream, jobs[j].kf->blk.ev, 0));
+    int32_t *d_idx = (int32_t *)c->d_work, *d_dist = d_idx + total;
+    ORBX_HIP(hipMemcpyAsync(c->d_blob, h, blob, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_window_best, dim3(wg_first[njobs]), dim3(256), 0, c->stream, (const WinJob *)d, (const int *)(d + o_wg), njobs, d_idx, d_dist);
+    ORBX_HIP(hipGetLastError());
+    ORBX_HIP(hipMemcpyAsync(c->h_out, c->d_work, out, hipMemcpyDeviceToHost, c->stream));
+    ORBX_HIP(hipStreamSynchronize(c->stream));
+    off = 0;
+    for (int j = 0; j < njobs; j++) {
+        orbx_window_job &jb = jobs[j];
+        if (wg_first[j + 1] == wg_first[j]) continue;
+        const size_t np = (size_t)jb.pts->n;
+        memcpy(jb.best_idx, c->h_out + off, 4 * np);
+        if (jb.best_dist) memcpy(jb.best_dist, c->h_out + total + off, 4 * np);
+        int nf = 0;
+        for (size_t i = 0; i < np; i++) nf += jb.best_idx[i] >= 0;
+        jb.nfound = nf;
+        off += np;
+    }
+    return ORBX_OK;
+}
+
+extern "C" int orbx_frame_window_best(const orbx_frame *kf, const orbx_proj_points *pts, const float *scale_factors,
+                                      const float *inv_sigma2, int nlevels, float th, int chi2, int max_dist, int32_t *best_idx,
+                                      int32_t *best_dist, int *nfound)
+{
+    orbx_window_job jb;
+    memset(&jb, 0, sizeof jb);
+    jb.kf = kf; jb.pts = pts; jb.scale_factors = scale_factors; jb.inv_sigma2 = inv_sigma2; jb.nlevels = nlevels; jb.th = th;
+    jb.chi2 = chi2; jb.max_dist = max_dist; jb.best_idx = best_idx; jb.best_dist = best_dist;
+    const int rc = orbx_frame_window_best_batch(&jb, 1);
+    if (!rc && nfound) *nfound = jb.nfound;
+    return rc;
+}
+
+extern "C" int orbx_frame_search_by_sim3(const orbx_frame *kf1, const orbx_frame *kf2, const orbx_proj_points *pts12,
+                                         const orbx_proj_points *pts21, const float *scale_factors1, const float *scale_factors2,
+                                         int nlevels, float th, int32_t *match12, int *nfound)
+{
+    if (!kf1 || !kf2 || !pts12 || !pts21 || !match12 || !nfound || pts12->n != kf1->n || pts21->n != kf2->n) {
+        orbx_set_error("orbx_frame_search_by_sim3: invalid argument (one projected point per keypoint on each side)");
+        return ORBX_E_INVALID;
+    }
+    std::vector<int32_t> m1((size_t)pts12->n + 1), m2((size_t)pts21->n + 1);
+    orbx_window_job jb[2];
+    memset(jb, 0, sizeof jb);
+    jb[0].kf = kf2; jb[0].pts = pts12; jb[0].scale_factors = scale_factors2; jb[0].best_idx = m1.data();   // :1218-1292
+    jb[1].kf = kf1; jb[1].pts = pts21; jb[1].scale_factors = scale_factors1; jb[1].best_idx = m2.data();   // :1295-1372
+    for (int j = 0; j < 2; j++) { jb[j].nlevels = nlevels; jb[j].th = th; jb[j].max_dist = 100; }
+    const int rc = orbx_frame_window_best_batch(jb, 2);
+    if (rc) return rc;
+    int found = 0;
+    for (int i1 = 0; i1 < pts12->n; i1++) { // the agreement check, :1375-1391
+        const int idx2 = m1[i1];
+        match12[i1] = -1;
+        if (idx2 >= 0 && m2[idx2] == i1) { match12[i1] = idx2; found++; }
+    }
+    *nfound = found;
+    return ORBX_OK;
 }

@@ -107,6 +107,13 @@ class ProjPoints(C.Structure):
                 ("angle", C.c_void_p), ("view_cos", C.c_void_p), ("desc", C.c_void_p), ("valid", C.c_void_p), ("has_obs", C.c_void_p)]
 
 
+class WindowJob(C.Structure):
+    """orbx_window_job (include/orbx.h)"""
+    _fields_ = [("kf", C.c_void_p), ("pts", C.POINTER(ProjPoints)), ("scale_factors", C.c_void_p), ("inv_sigma2", C.c_void_p),
+                ("nlevels", C.c_int), ("th", C.c_float), ("chi2", C.c_int), ("max_dist", C.c_int), ("best_idx", C.c_void_p),
+                ("best_dist", C.c_void_p), ("nfound", C.c_int)]
+
+
 _lib = None
 
 
@@ -196,6 +203,10 @@ def lib():
     L.orbx_frame_search_by_projection_last_frame.argtypes = [vp, vp, C.POINTER(ProjPoints), vp, i, f, i, f, i, vp, ip]
     L.orbx_frame_search_by_projection_map_points.argtypes = [vp, vp, C.POINTER(ProjPoints), vp, i, f, f, vp, ip]
     L.orbx_frame_search_by_projection_keyframe.argtypes = [vp, vp, C.POINTER(ProjPoints), vp, i, f, i, i, vp, ip]
+    L.orbx_frame_window_best.argtypes = [vp, C.POINTER(ProjPoints), vp, vp, i, f, i, i, vp, vp, ip]
+    L.orbx_frame_window_best_batch.argtypes = [C.POINTER(WindowJob), i]
+    L.orbx_frame_search_by_projection_sim3.argtypes = [vp, vp, C.POINTER(ProjPoints), vp, i, f, vp, ip]
+    L.orbx_frame_search_by_sim3.argtypes = [vp, vp, C.POINTER(ProjPoints), C.POINTER(ProjPoints), vp, vp, i, f, vp, ip]
     L.orbx_bow_frames_create.argtypes = [i, i, i, C.POINTER(vp)]
     L.orbx_bow_frames_destroy.argtypes = [vp]; L.orbx_bow_frames_destroy.restype = None
     L.orbx_bow_transform_batch_device.argtypes = [vp, vp, vp, vp, vp, i, i, vp]
@@ -1190,6 +1201,54 @@ class ORBmatcher:
         _check(lib().orbx_window_best(self.device, C.byref(a), C.byref(b), _p(sf), None if sg is None else _p(sg), len(sf), th,
                                       0 if sg is None else 1, int(max_dist), _p(bi), _p(bd), C.byref(n)))
         return bi, bd, n.value
+
+    # ---- the keyframe searches on resident keyframes (DeviceFrame as the keyframe): only the points travel per call; safe from several
+    # threads on one DeviceFrame (ctypes releases the GIL during the call)
+    def FuseResident(self, kf, vpMapPoints, scaleFactors, invLevelSigma2=None, th=3.0, max_dist=50):
+        """Fuse's search half on a DeviceFrame (orbx_frame_window_best) -> (best_idx, best_dist, nfound)"""
+        b, kb = self._points(vpMapPoints)
+        sf = np.ascontiguousarray(scaleFactors, np.float32)
+        sg = None if invLevelSigma2 is None else np.ascontiguousarray(invLevelSigma2, np.float32)
+        bi = np.full(b.n, -1, np.int32); bd = np.full(b.n, 256, np.int32); n = C.c_int()
+        _check(lib().orbx_frame_window_best(kf._h, C.byref(b), _p(sf), None if sg is None else _p(sg), len(sf), th, 0 if sg is None else 1,
+                                            int(max_dist), _p(bi), _p(bd), C.byref(n)))
+        return bi, bd, n.value
+
+    def FuseResidentBatch(self, jobs):
+        """jobs: dicts with kf (DeviceFrame), points, scaleFactors and optionally invLevelSigma2 (given: the chi2-gated variant), th (3.0),
+        max_dist (50) -- one upload, one launch, one download (orbx_frame_window_best_batch) -> [(best_idx, best_dist, nfound), ...]"""
+        arr = (WindowJob * max(len(jobs), 1))()
+        keep, outs = [], []
+        for j, jb in enumerate(jobs):
+            b, kb = self._points(jb["points"])
+            sf = np.ascontiguousarray(jb["scaleFactors"], np.float32)
+            sg = None if jb.get("invLevelSigma2") is None else np.ascontiguousarray(jb["invLevelSigma2"], np.float32)
+            bi = np.full(b.n, -1, np.int32); bd = np.full(b.n, 256, np.int32)
+            keep.append((b, kb, sf, sg, jb["kf"]))
+            w = arr[j]
+            w.kf = jb["kf"]._h.value; w.pts = C.pointer(b); w.scale_factors = sf.ctypes.data; w.inv_sigma2 = None if sg is None else sg.ctypes.data
+            w.nlevels = len(sf); w.th = float(jb.get("th", 3.0)); w.chi2 = 0 if sg is None else 1; w.max_dist = int(jb.get("max_dist", 50))
+            w.best_idx = bi.ctypes.data; w.best_dist = bd.ctypes.data
+            outs.append((bi, bd))
+        _check(lib().orbx_frame_window_best_batch(arr, len(jobs)))
+        return [(bi, bd, arr[j].nfound) for j, (bi, bd) in enumerate(outs)]
+
+    def SearchByProjectionSim3Resident(self, kf, occupied, vpPoints, scaleFactors, th):
+        """SearchByProjectionSim3 on a DeviceFrame, occupied (vpMatched[idx] != NULL) per call -> (match_kf, nmatches)"""
+        oc = _occupied_for(occupied, kf, "SearchByProjectionSim3Resident")
+        b, kb = self._points(vpPoints)
+        sf = np.ascontiguousarray(scaleFactors, np.float32)
+        out = np.full(kf.n, -1, np.int32); n = C.c_int()
+        _check(lib().orbx_frame_search_by_projection_sim3(kf._h, None if oc is None else _p(oc), C.byref(b), _p(sf), len(sf), th, _p(out), C.byref(n)))
+        return out, n.value
+
+    def SearchBySim3Resident(self, kf1, kf2, pts12, pts21, scaleFactors1, scaleFactors2, th):
+        """SearchBySim3 on two DeviceFrames: both directions in one launch -> (match12, nFound)"""
+        p, kp = self._points(pts12); q, kq = self._points(pts21)
+        s1 = np.ascontiguousarray(scaleFactors1, np.float32); s2 = np.ascontiguousarray(scaleFactors2, np.float32)
+        out = np.full(kf1.n, -1, np.int32); n = C.c_int()
+        _check(lib().orbx_frame_search_by_sim3(kf1._h, kf2._h, C.byref(p), C.byref(q), _p(s1), _p(s2), len(s1), th, _p(out), C.byref(n)))
+        return out, n.value
 
     def SearchForInitialization(self, F1, F2, vbPrevMatched, windowSize=100):
         """SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, windowSize), src/ORBmatcher.cc:430-556
