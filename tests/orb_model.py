@@ -2,6 +2,7 @@
 oracle/orb_oracle.c: the intensity-centroid angle (src/ORBextractor.cc:83-111), the steered BRIEF descriptor
 (src/ORBextractor.cc:116-157) and Frame::ComputeStereoMatches (src/Frame.cc:577-751).  They pin the oracle stages ic_angle,
 orb_descriptor and oracle_stereo_match -- and through them the kernels k_desc and k_stereo / k_stereo_prep / stereo_cut -- bit for bit.
+The stages before them (pyramid, per-cell FAST, quadtree, records, blur) are pinned in the same way by tests/front_model.py.
 
 Two helpers are taken from the oracle on purpose, because each has a known-answer test of its own (test_oracle_known_answers.py):
 oracle_py.fast_atan2 (the polynomial of cv::fastAtan2) and oracle_py.sincos (the build's deterministic sin / cos).  The models pin
@@ -90,7 +91,9 @@ def rbrief_model(blurred_level, x, y, angle_deg, pattern):
 
 def extract_tail_model(oracle_handle, kps):
     """angle and descriptor of every keypoint the oracle returned, recomputed from the oracle's own level pixels (orientation,
-    src/ORBextractor.cc:538-546) and blurred levels (descriptors, :1302-1325); pyramid and blur have known-answer tests of their own.
+    src/ORBextractor.cc:538-546) and blurred levels (descriptors, :1302-1325).  Those levels are no longer taken on trust:
+    front_model.py restates the pyramid and the blur, tests/test_front_model.py holds the oracle's levels to it pixel for pixel, and
+    front_model.extract_model runs ic_angle_model and rbrief_model on the model's own levels, keypoints included.
     -> (angles f32[n], desc u8[n,32], info) with info = level coordinates and the number of compared pairs with equal pixels"""
     pattern = load_pattern()
     umax = umax_model()

@@ -136,16 +136,18 @@ def test_gaussian_taps_both_opencv_profiles(oracle, pkg):
 
 
 def test_blur_reflect101(oracle):
+    """the oracle's 7x7 blur against the numpy blur of front_model, both tap profiles"""
+    import front_model
     rng = np.random.default_rng(3)
     img = rng.integers(0, 256, (24, 30), dtype=np.uint8)
     out = np.zeros_like(img)
     oracle.lib().oracle_gaussian_blur7(img.ctypes.data, 30, 24, 30, out.ctypes.data, 30)
-    pad = np.pad(img.astype(np.int64), 3, mode="reflect")   # numpy 'reflect' == BORDER_REFLECT_101
-    taps = np.array([18, 34, 49, 55, 49, 34, 18], np.int64)
-    rows = sum(taps[k] * pad[:, k:k + 30] for k in range(7))
-    full = sum(taps[k] * rows[k:k + 24, :] for k in range(7))
-    exp = np.minimum((full + (1 << 15)) >> 16, 255)
+    assert front_model.gaussian_taps(0).tolist() == [18, 34, 49, 55, 49, 34, 18] and front_model.gaussian_taps(1).tolist() == [18, 34, 48, 56, 48, 34, 18]
+    exp = front_model.blur7_model(img, 0)
     assert (out == exp).all()
+    for profile in (0, 1):
+        oracle.lib().oracle_gaussian_blur7_profile(img.ctypes.data, 30, 24, 30, out.ctypes.data, 30, profile)
+        assert (out == front_model.blur7_model(img, profile)).all()
 
 
 def test_resize_constant_and_bounds(oracle):
@@ -230,7 +232,10 @@ def test_fast_score_matches_definition(oracle):
 
 
 def test_candidates_order_and_nms(oracle):
-    """candidates come cell-row-major then row-major inside a cell; each is a strict 3x3 maximum of its cell"""
+    """candidates come cell-row-major then row-major inside a cell; each is a strict 3x3 maximum of its cell's own score buffer: the
+    list is the one front_model.cell_candidates_model keeps, which suppresses per cell (tests/test_front_model.py asserts that this
+    differs from a suppression over the whole level on this kind of scene)"""
+    import front_model
     img = synth.image(6, 400, 300)
     o = oracle.Oracle(500)
     o.extract(img)
@@ -244,12 +249,13 @@ def test_candidates_order_and_nms(oracle):
     assert (np.diff(key) > 0).all()
     # coordinates are relative to (16,16) and lie in the FAST-detectable area
     assert x.min() >= 3 and y.min() >= 3 and x.max() <= width - 4 and y.max() <= height - 4
+    mx, my, mr, ev = front_model.cell_candidates_model(img, 20, 7)
+    assert (x == mx).all() and (y == my).all() and (r == mr).all()
+    assert len(ev["border_kept"]) > 20        # kept although a neighbour across the cell boundary scores at least as much
 
 
-def test_quadtree_model_matches_sequential_oracle(oracle):
-    """the data-parallel formulation used by the HIP kernel == the sequential list algorithm"""
-    from quadtree_model import quadtree_model
-    L = oracle.lib()
+def quadtree_random_sets():
+    """120 seeded point sets (a few are skipped: a box higher than wide has no root) -> (trial, W, H, xs, ys, responses, N)"""
     rng = np.random.default_rng(7)
     for trial in range(120):
         W = int(rng.integers(40, 1300)); H = int(rng.integers(40, 500))
@@ -265,11 +271,22 @@ def test_quadtree_model_matches_sequential_oracle(oracle):
         p = np.unique(np.stack([ys, xs], 1), axis=0)
         ys, xs = np.ascontiguousarray(p[:, 0], np.int32), np.ascontiguousarray(p[:, 1], np.int32)
         r = np.ascontiguousarray(rng.integers(7, 40 if trial % 3 else 255, len(xs)), np.int32)
+        yield trial, W, H, xs, ys, r, N
+
+
+def test_quadtree_model_matches_sequential_oracle(oracle):
+    """the data-parallel formulation used by the HIP kernel == the sequential list algorithm"""
+    from quadtree_model import quadtree_model
+    L = oracle.lib()
+    ran = 0
+    for trial, W, H, xs, ys, r, N in quadtree_random_sets():
         out = np.zeros(len(xs) + 1, np.int32)
         cnt = L.oracle_distribute_octtree(xs.ctypes.data, ys.ctypes.data, r.ctypes.data, len(xs), 16, 16 + W, 16, 16 + H, N, out.ctypes.data, len(out))
         model = quadtree_model(xs, ys, r, 16, 16 + W, 16, 16 + H, N)
         assert cnt == len(model) and (out[:cnt] == model).all(), trial
         assert cnt <= max(N + 2, 4 * max(round(W / H), 1)) or cnt == len(xs)   # SURVEY.md A.4 output bound
+        ran += 1
+    assert ran > 100
 
 
 def test_extract_output_invariants(oracle):

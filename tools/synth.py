@@ -156,6 +156,86 @@ def block_checkerboard(seed=7, w=320, h=240, block=16, flip=0.3):
     return (np.repeat(np.repeat(cells, block, 0), block, 1)[:h, :w] * 255).astype(np.uint8)
 
 
+# ----------------------------------------------------------------------------- directed images for the cell grid of per-cell FAST
+# (tests/test_front_model.py; 320 x 240 with 8 levels at scale factor 1.2 unless said otherwise)
+
+def cell_lattice(size):
+    """first detectable column (or row) of every FAST cell of a level `size` pixels wide (or high), src/ORBextractor.cc:934-976:
+    cell j detects in [19 + j * cell, 19 + (j + 1) * cell) -> (starts, cell)"""
+    extent = size - 32
+    n = int(extent / 30)
+    cell = -(-extent // n)
+    return [19 + j * cell for j in range(n)], cell
+
+
+def tie_bars(w=320, h=240, background=40):
+    """pairs of adjacent single pixels of 255 on a flat background: both pixels of a pair have the same FAST score (214), so each
+    suppresses the other and neither is kept, at either threshold.  Level-0 cells are 32 x 35 px from (19, 19).
+      cell (row 1, column 1): the pair (60, 60) (61, 60) and the single pixel (70, 70) = background + 12 (score 11): empty at
+        iniThFAST = 20 only after suppression, so the cell runs again at minThFAST = 7 and gives exactly the candidate (54, 54, 11);
+      cell (1, 3): a horizontal pair alone: empty in both passes;
+      cell (1, 5): a vertical and a diagonal pair.
+    -> (image, dict of the pixel positions)"""
+    img = np.full((h, w), background, np.uint8)
+    pairs = dict(horizontal_with_weak=((60, 60), (61, 60)), horizontal=((125, 65), (126, 65)), vertical=((185, 60), (185, 61)),
+                 diagonal=((200, 75), (201, 76)))
+    for a, b in pairs.values():
+        img[a[1], a[0]] = 255; img[b[1], b[0]] = 255
+    weak = (70, 70)
+    img[weak[1], weak[0]] = background + 12
+    return img, dict(pairs=pairs, weak=weak)
+
+
+def straddling_corners(w=320, h=240, background=40, weak=150, strong=255, scale_factor=1.2):
+    """pairs of adjacent single pixels of unequal value (FAST scores weak - background - 1 and strong - background - 1).  Inside one
+    cell the weaker pixel is suppressed.  Where a cell boundary runs between the two, each cell scores only its own pixel (the other
+    lies outside its detectable area, where the score buffer is 0) and BOTH are kept.
+      level 0 (y < 70): pairs across a vertical boundary (weaker left, weaker right), a horizontal one (weaker above, weaker below)
+        and a cell corner (both diagonals), and the same three kinds inside a cell;
+      level 1 (y >= 90): the same kinds at the level-0 position (c + 0.5) * scale_factor - 0.5 of level-1 boundaries c, each at
+        the three phases -1, 0, +1 px (the resize spreads a pixel over two, so which phase puts the maximum just across the
+        boundary is left to the phases).
+    -> (image, dict: level-0 pixel positions 'across' [(weak, strong)] and 'inside' [(weak, strong)])"""
+    img = np.full((h, w), background, np.uint8)
+
+    def put(pw, ps):
+        img[pw[1], pw[0]] = weak; img[ps[1], ps[0]] = strong
+        return pw, ps
+    xs0, _ = cell_lattice(w); ys0, _ = cell_lattice(h)
+    bx = [x - 1 for x in xs0[1:]]; by = [y - 1 for y in ys0[1:]]          # last detectable column / row of cells 0, 1, ...
+    across = [put((bx[1], 30), (bx[1] + 1, 30)), put((bx[2] + 1, 30), (bx[2], 30)),                     # vertical boundary
+              put((30, by[0]), (30, by[0] + 1)), put((100, by[0] + 1), (100, by[0])),                   # horizontal boundary
+              put((bx[0], by[0]), (bx[0] + 1, by[0] + 1)), put((bx[3] + 1, by[0]), (bx[3], by[0] + 1))]  # cell corner
+    x_in = xs0[5]
+    inside = [put((x_in + 6, 30), (x_in + 7, 30)), put((x_in + 21, 30), (x_in + 21, 31)), put((x_in + 11, 42), (x_in + 12, 43))]
+    # level 1
+    lw, lh = int(np.rint(np.float32(w) / np.float32(scale_factor))), int(np.rint(np.float32(h) / np.float32(scale_factor)))
+    xs1, _ = cell_lattice(lw); ys1, _ = cell_lattice(lh)
+    bx1 = [int(np.floor((x - 1 + 0.5) * scale_factor)) for x in xs1[1:]]  # level-0 position of the last column of level-1 cells 0, 1, ...
+    by1 = [int(np.floor((y - 1 + 0.5) * scale_factor)) for y in ys1[1:]]
+    for ph in (-1, 0, 1):
+        put((bx1[1] + ph, 124 + 12 * ph), (bx1[1] + ph + 1, 124 + 12 * ph))
+        put((165 + 10 * ph, by1[1] + ph), (165 + 10 * ph, by1[1] + ph + 1))
+    corners = [(bx1[3], by1[2]), (bx1[4], by1[2]), (bx1[5], by1[2]), (bx1[3], by1[3]), (bx1[4], by1[3]), (bx1[5], by1[3]),
+               (bx1[0], by1[2]), (bx1[0], by1[3]), (bx1[2], by1[3])]
+    for (cx, cy), (px, py) in zip(corners, [(a, b) for a in (-1, 0, 1) for b in (-1, 0, 1)]):
+        put((cx + px, cy + py), (cx + px + 1, cy + py + 1))
+    return img, dict(across=across, inside=inside)
+
+
+def one_cell_fallback(seed=31, w=320, h=240, cells=((1, 1), (1, 4), (1, 7), (4, 1), (4, 4), (4, 7))):
+    """a textured scene in which the whole FAST window (detectable area + 3 px) of isolated level-0 cells (row, column) is replaced
+    by its own low-contrast copy, contrast between minThFAST = 7 and iniThFAST = 20: such a cell finds nothing at 20 and runs again
+    at 7, while its 8 neighbours, textured, do not.  -> (image, cells)"""
+    img = image(seed, w, h)
+    low = (100 + (img.astype(np.int32) - 100) // 8).astype(np.uint8)
+    xs, cw = cell_lattice(w); ys, ch = cell_lattice(h)
+    for i, j in cells:
+        x0, y0 = xs[j] - 3, ys[i] - 3
+        img[y0:y0 + ch + 6, x0:x0 + cw + 6] = low[y0:y0 + ch + 6, x0:x0 + cw + 6]
+    return img, cells
+
+
 # ----------------------------------------------------------------------------- BoW
 
 _POPCNT = np.array([bin(i).count("1") for i in range(256)], np.uint8)
