@@ -456,6 +456,43 @@ int orbx_bowdb_search_candidates_device_compact(orbx_bowdb *db, const orbx_bow_f
                                                 const void *d_kf_of_id, int n_ids,
                                                 float nnratio, int check_orientation, void *d_pairs, int cap_pairs, void *d_nmatches, void *stream);
 
+/* ---- a live orbx_bowdb: keyframes enter, leave and change their map-point flags while the set is searched ----
+ * The set of orbx_bowdb_create is immutable: a map that gains or culls a keyframe (LocalMapping::ProcessNewKeyFrame, src/LocalMapping.cc:147-193;
+ * KeyFrame::SetBadFlag, src/KeyFrame.cc:489), or whose map points are created and culled (src/LocalMapping.cc:195, :237), had to rebuild it from
+ * every keyframe's host feature set.  A live set holds max_kf slots of `cap` features (1 <= cap <= 8192) in one device allocation made here;
+ * nothing grows afterwards.  A keyframe is named by the caller's id in [0, max_ids) -- the id orbx_kfdb_add_from_frames returned, say -- and
+ * takes the lowest free slot; orbx_bowdb_size is the number of slots ever used, and the all-keyframes searches report slot i at index i (an
+ * empty slot as a keyframe without features: count 0).  Every search entry point above accepts a live set unchanged, except that the candidate
+ * searches join ids to slots through the set's own map: d_kf_of_id must be NULL (an explicit map with a live set is ORBX_E_INVALID).
+ * Streams: every call that enqueues work on the set -- the searches included -- first makes its stream wait for the previous such call when
+ * that went to another stream, so a slot is never rewritten under a search in flight elsewhere; no call needs a host synchronisation between.
+ * Refusals come before any device work and leave the set unchanged.  ORBX_E_INVALID: a NULL argument, a set of orbx_bowdb_create, frames of
+ * another device or cap, an index outside the frames' batch, an id outside [0, max_ids), an id already in the set (add), an id not in the set
+ * (erase, set_flags, read_keyframe), a feature set with more than cap features or nodes.  ORBX_E_CAPACITY: no free slot.  An erased id may be
+ * added again. */
+int orbx_bowdb_create_live(int device, int max_kf, int cap, int max_ids, orbx_bowdb **out);
+/* Keyframe `id` from slot `index` of f (orbx_bow_transform_batch_device's output), device to device, asynchronous on `stream` (NULL: the stream
+ * of f's last transform); the counts are read on the device.  Replaces the download, feat_pack and upload of orbx_bowdb_create for the
+ * keyframe.  d_flag = device uint8[cap], != 0 <=> feature i holds a non-bad MapPoint (src/ORBmatcher.cc:205-210); NULL = every feature does. */
+int orbx_bowdb_add_from_frames(orbx_bowdb *db, int id, const orbx_bow_frames *f, int index, const void *d_flag, void *stream);
+/* The same from a host feature set, validated as orbx_bowdb_create validates it, kf->n and kf->nnodes <= cap.  Synchronises `stream`
+ * (NULL: the set's own). */
+int orbx_bowdb_add(orbx_bowdb *db, int id, const orbx_featset *kf, void *stream);
+/* KeyFrameDatabase::erase (src/KeyFrameDatabase.cc:48-68) for the searched set: asynchronous, the slot is free for the next add. */
+int orbx_bowdb_erase(orbx_bowdb *db, int id, void *stream);
+/* New map-point flags for n distinct live keyframes in ONE launch: flags[i] = host uint8[that keyframe's feature count].  The searched form is
+ * rebuilt on the device from the resident descriptors (replaces the rebuild of the set).  Synchronises `stream`. */
+int orbx_bowdb_set_flags(orbx_bowdb *db, const int32_t *ids, int n, const uint8_t *const *flags, void *stream);
+int orbx_bowdb_live_count(const orbx_bowdb *db);                                /* keyframes in the set (a negative code on error) */
+/* id_of_slot[nslots >= orbx_bowdb_size(db)] = the id behind each slot, -1 = empty: the join orbx_bowdb_create's caller keeps by hand
+ * (ORBX_E_CAPACITY: nslots too small). */
+int orbx_bowdb_ids(const orbx_bowdb *db, int32_t *id_of_slot, int nslots);
+/* Tests and debugging: the searched form of keyframe `id` as the kernels see it, through its device record.  node_id[nnodes],
+ * node_off[nnodes + 1], feat / sdesc[32 x] / sflag over the filtered list of node_off[nnodes] entries, flag / angle / desc[32 x] over n; every
+ * array has room for cap entries (node_off cap + 1).  NULL arguments are skipped.  Synchronises. */
+int orbx_bowdb_read_keyframe(orbx_bowdb *db, int id, int *n, int *nnodes, uint32_t *node_id, int32_t *node_off,
+                             uint32_t *feat, uint8_t *flag, float *angle, uint8_t *desc, uint8_t *sdesc, uint8_t *sflag);
+
 /* ---- KeyFrameDatabase: the place-recognition query in front of the relocalisation / loop-closing searches ----
  * orbx_kfdb keeps the live keyframes' BowVectors (ascending uint32 word ids, the doubles orbx_bow_transform returns) in HBM, with up to
  * 10 covisibility neighbours and one persistent relocalisation score per keyframe; the host needs the vectors no more after add.

@@ -11,7 +11,10 @@
 // wave min-reductions for best / second best.  Rotation histogram + ComputeThreeMaxima run once
 // per pair in LDS.
 #include "orbx_device.h"
+#include <algorithm>
 #include <atomic>
+#include <mutex>
+#include <set>
 #include <stdlib.h>
 #include <string.h>
 #include <vector>
@@ -791,6 +794,92 @@ struct orbx_bowdb {
     uint8_t *d_f; size_t d_f_cap;
     int32_t *d_out; size_t out_cap;
     int32_t *h_out; size_t h_out_cap;
+    struct BowdbLive *live;   // nullptr: the immutable set of orbx_bowdb_create
+};
+
+// ---- the live set (orbx_bowdb_create_live): max_kf slots of fixed size in ONE allocation made at creation; nothing grows afterwards.
+// A slot keeps the keyframe's immutable master -- descriptors, angles, node ids, the unfiltered node_off / feat -- and behind it the searched
+// form that feat_pack(..., drop_unflagged = true) builds for the immutable set: flag[n], node_off / feat of the flagged features only (order
+// kept, a node without survivor an empty range), sdesc in filtered list order, sflag = 1.  k_bowdb_pack derives the second from the first and
+// the flags, so new flags cost one launch and no descriptor crosses PCIe again.  The search kernels read the slots' DevFeat records as they
+// read the immutable set's; a slot without keyframe has n = nnodes = 0.
+struct BowSlotLayout {       // byte offsets inside a slot, each a multiple of 16
+    size_t hdr, desc, angle, node_id, off_all, feat_all, flag;     // master: hdr = int[4] (n, nnodes, 0, 0); flag ends what a host add uploads
+    size_t node_off, feat, sdesc, sflag;                            // searched form
+    size_t upload, stride;
+};
+
+// one job of k_bowdb_pack
+struct BowPackJob {
+    int slot, id;
+    int empty;               // 1: erase -- the record becomes n = nnodes = 0 and kf_of_id[id] = -1
+    int flag_ones;           // 1: every feature is flagged (flag is not read)
+    const DevFeat *src;      // the DevFeat of an orbx_bow_frames slot to copy the master from, or nullptr: the slot's master is in place
+    const uint8_t *flag;     // device uint8[>= n]; may be the slot's own flag array (a host add uploads it there)
+};
+
+struct BowdbLive {
+    int max_kf, cap, npad, max_ids;
+    int nslots, nlive;                   // high-water mark of the slots ever used; live keyframes
+    BowSlotLayout lay;
+    uint8_t *d_slots;                    // views into orbx_bowdb::d_blob: DevFeat[max_kf] | slots | kf_of_id | jobs | flag staging
+    int32_t *d_kf_of_id;
+    BowPackJob *d_jobs;
+    uint8_t *d_flags;                    // [max_kf][a16(cap)] flags of one set_flags call
+    uint8_t *h_stage; size_t h_stage_bytes;   // pinned: one slot (host add, read_keyframe) or the jobs and flags of one set_flags call
+    std::vector<int32_t> kf_of_id;       // host mirror, -1 = not live
+    std::vector<int32_t> id_of_slot;     // -1 = empty
+    std::vector<int32_t> n_of_slot;      // feature count of the slot's keyframe, -1 = known to the device only (add_from_frames)
+    std::set<int> free_slots;            // below nslots, lowest first
+    hipEvent_t ev; hipStream_t ev_stream; bool ev_set;   // the most recent work that touched the slots, and the stream it went to
+    std::mutex mu;
+};
+
+static BowSlotLayout bow_slot_layout(int cap, int npad)
+{
+    const size_t c = (size_t)cap, p = (size_t)npad;
+    BowSlotLayout L;
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t r = o; o += a16(bytes); return r; };
+    L.hdr = take(16); L.desc = take(32 * c); L.angle = take(4 * c); L.node_id = take(4 * c); L.off_all = take(4 * (c + 4));
+    L.feat_all = take(4 * p); L.flag = take(c);
+    L.upload = o;
+    L.node_off = take(4 * (c + 4)); L.feat = take(4 * p); L.sdesc = take(32 * p); L.sflag = take(p);
+    // an odd number of 256-byte lines: consecutive slots never start on the same HBM channel as a power-of-two stride would make them
+    size_t lines = (o + 255) / 256;
+    if (!(lines & 1)) lines++;
+    L.stride = lines * 256;
+    return L;
+}
+
+static inline hipStream_t bowdb_stream(const orbx_bowdb *db, const orbx_bow_frames *fr, void *stream)
+{
+    return stream ? (hipStream_t)stream : (fr ? fr->last_stream : db->stream);
+}
+// Ordering across streams (live sets only): work that touches the slots waits for the previous such work when that went to another stream,
+// and leaves the event behind for the next.  A slot is then never rewritten under a search still running elsewhere.
+static int bowdb_order_before(orbx_bowdb *db, hipStream_t s)
+{
+    BowdbLive *L = db->live;
+    if (L && L->ev_set && L->ev_stream != s) ORBX_HIP(hipStreamWaitEvent(s, L->ev, 0));
+    return ORBX_OK;
+}
+static int bowdb_order_after(orbx_bowdb *db, hipStream_t s)
+{
+    BowdbLive *L = db->live;
+    if (!L) return ORBX_OK;
+    ORBX_HIP(hipEventRecord(L->ev, s));
+    L->ev_stream = s; L->ev_set = true;
+    return ORBX_OK;
+}
+static inline int bowdb_nkf(const orbx_bowdb *db) { return db->live ? db->live->nslots : db->nkf; }
+// calls on one live set serialise inside it (its slot table, free list and event are host state); an immutable set has nothing to guard
+struct BowdbLock {
+    std::mutex *m;
+    explicit BowdbLock(const orbx_bowdb *db) : m(db->live ? &db->live->mu : nullptr) { if (m) m->lock(); }
+    ~BowdbLock() { if (m) m->unlock(); }
+    BowdbLock(const BowdbLock &) = delete;
+    BowdbLock &operator=(const BowdbLock &) = delete;
 };
 
 extern "C" int orbx_bowdb_create(int device, const orbx_featset *kfs, int nkf, orbx_bowdb **out)
@@ -823,7 +912,7 @@ extern "C" int orbx_bowdb_create(int device, const orbx_featset *kfs, int nkf, o
     return ORBX_OK;
 }
 
-extern "C" int orbx_bowdb_size(const orbx_bowdb *db) { return db ? db->nkf : ORBX_E_INVALID; }
+extern "C" int orbx_bowdb_size(const orbx_bowdb *db) { return db ? bowdb_nkf(db) : ORBX_E_INVALID; }
 
 extern "C" void orbx_bowdb_destroy(orbx_bowdb *db)
 {
@@ -835,6 +924,11 @@ extern "C" void orbx_bowdb_destroy(orbx_bowdb *db)
     if (db->h_f) hipHostFree(db->h_f);
     if (db->d_out) hipFree(db->d_out);
     if (db->h_out) hipHostFree(db->h_out);
+    if (db->live) {
+        if (db->live->ev) hipEventDestroy(db->live->ev);
+        if (db->live->h_stage) hipHostFree(db->live->h_stage);
+        delete db->live;
+    }
     delete db;
 }
 
@@ -843,13 +937,16 @@ extern "C" int orbx_bowdb_search(orbx_bowdb *db, const orbx_featset *f, float nn
 {
     if (!db || !f || !match_f || !nmatches) { orbx_set_error("orbx_bowdb_search: null argument"); return ORBX_E_INVALID; }
     if (!orbx_feat_validate(f, 0, 1)) { orbx_set_error("orbx_bowdb_search: malformed feature set"); return ORBX_E_INVALID; }
+    BowdbLock guard(db);
     ORBX_HIP(hipSetDevice(db->device));
+    const int nkf = bowdb_nkf(db);
+    if (nkf == 0) return ORBX_OK;           // a live set no keyframe has entered yet: nothing to write
     const size_t fb = a16(sizeof(DevFeat)) + feat_bytes(f, 0);
     int rc = ORBX_OK;
     if (fb > db->h_f_cap) rc = ensure_pinned(&db->h_f, &db->h_f_cap, 2 * fb);
     if (!rc && fb > db->d_f_cap) rc = ensure(&db->d_f, &db->d_f_cap, 2 * fb);
     const int stride = f->n > 0 ? f->n : 1;
-    const size_t out_ints = (size_t)db->nkf * stride + db->nkf, out = out_ints * sizeof(int32_t);
+    const size_t out_ints = (size_t)nkf * stride + nkf, out = out_ints * sizeof(int32_t);
     if (!rc && out > db->out_cap) rc = ensure(&db->d_out, &db->out_cap, 2 * out);
     if (!rc && out > db->h_out_cap) rc = ensure_pinned(&db->h_out, &db->h_out_cap, 2 * out);
     if (rc) return rc;
@@ -858,13 +955,15 @@ extern "C" int orbx_bowdb_search(orbx_bowdb *db, const orbx_featset *f, float nn
     feat_pack(f, 0, db->h_f, db->d_f, &off, hd);
     ORBX_HIP(hipMemcpyAsync(db->d_f, db->h_f, off, hipMemcpyHostToDevice, db->stream));
     int32_t *d_match = db->d_out;
-    int *d_n = db->d_out + (size_t)db->nkf * stride;
-    if ((rc = bow_launch<0>(db->nkf, 1, f->n, f->n, db->stream, (const DevFeat *)db->d_blob, (const DevFeat *)db->d_f, 1, nnratio,
+    int *d_n = db->d_out + (size_t)nkf * stride;
+    if ((rc = bowdb_order_before(db, db->stream))) return rc;
+    if ((rc = bow_launch<0>(nkf, 1, f->n, f->n, db->stream, (const DevFeat *)db->d_blob, (const DevFeat *)db->d_f, 1, nnratio,
                             check_orientation, d_match, f->n, d_n))) return rc;
+    if ((rc = bowdb_order_after(db, db->stream))) return rc;
     ORBX_HIP(hipMemcpyAsync(db->h_out, db->d_out, out_ints * sizeof(int32_t), hipMemcpyDeviceToHost, db->stream));
     ORBX_HIP(hipStreamSynchronize(db->stream));
-    if (f->n) memcpy(match_f, db->h_out, sizeof(int32_t) * (size_t)db->nkf * f->n);
-    memcpy(nmatches, db->h_out + (size_t)db->nkf * stride, sizeof(int) * db->nkf);
+    if (f->n) memcpy(match_f, db->h_out, sizeof(int32_t) * (size_t)nkf * f->n);
+    memcpy(nmatches, db->h_out + (size_t)nkf * stride, sizeof(int) * nkf);
     return ORBX_OK;
 }
 
@@ -877,11 +976,16 @@ extern "C" int orbx_bowdb_search_batch_device(orbx_bowdb *db, const orbx_bow_fra
         orbx_set_error("orbx_bowdb_search_batch_device: invalid argument");
         return ORBX_E_INVALID;
     }
+    BowdbLock guard(db);
     ORBX_HIP(hipSetDevice(db->device));
-    const int rc = bow_launch<0>(db->nkf, batch, fr->cap, fr->cap, stream ? (hipStream_t)stream : fr->last_stream, (const DevFeat *)db->d_blob,
+    const int nkf = bowdb_nkf(db);
+    if (nkf == 0) return ORBX_OK;           // a live set no keyframe has entered yet: nothing to write
+    hipStream_t s = bowdb_stream(db, fr, stream);
+    if (int rc = bowdb_order_before(db, s)) return rc;
+    const int rc = bow_launch<0>(nkf, batch, fr->cap, fr->cap, s, (const DevFeat *)db->d_blob,
                                  (const DevFeat *)fr->d_feats, 1, nnratio, check_orientation, (int32_t *)d_match, fr->cap, (int *)d_nmatches);
     if (rc) return rc;
-    return ORBX_OK;
+    return bowdb_order_after(db, s);
 }
 
 // The same search with the result in the form its consumer reads: Tracking::Relocalization hands every candidate's matches to a PnP solver
@@ -895,9 +999,15 @@ extern "C" int orbx_bowdb_search_batch_device_compact(orbx_bowdb *db, const orbx
         orbx_set_error("orbx_bowdb_search_batch_device_compact: invalid argument");
         return ORBX_E_INVALID;
     }
+    BowdbLock guard(db);
     ORBX_HIP(hipSetDevice(db->device));
-    return bow_launch<0>(db->nkf, batch, fr->cap, fr->cap, stream ? (hipStream_t)stream : fr->last_stream, (const DevFeat *)db->d_blob,
-                         (const DevFeat *)fr->d_feats, 1, nnratio, check_orientation, (int32_t *)d_pairs, cap_pairs, (int *)d_nmatches, 1);
+    const int nkf = bowdb_nkf(db);
+    if (nkf == 0) return ORBX_OK;
+    hipStream_t s = bowdb_stream(db, fr, stream);
+    if (int rc = bowdb_order_before(db, s)) return rc;
+    if (int rc = bow_launch<0>(nkf, batch, fr->cap, fr->cap, s, (const DevFeat *)db->d_blob,
+                               (const DevFeat *)fr->d_feats, 1, nnratio, check_orientation, (int32_t *)d_pairs, cap_pairs, (int *)d_nmatches, 1)) return rc;
+    return bowdb_order_after(db, s);
 }
 
 // The search over the candidates only: slot j of frame b's list against frame b, one launch of cand_stride x batch workgroups of which the
@@ -918,17 +1028,24 @@ static int bow_launch_cand(const char *who, orbx_bowdb *db, const orbx_bow_frame
         orbx_set_error("%s: %d x %d workgroups exceed the launch limits", who, cand_stride, batch);
         return ORBX_E_INVALID;
     }
+    BowdbLock guard(db);
+    if (db->live) {      // a live set joins ids to slots through its own map
+        if (d_kf_of_id) { orbx_set_error("%s: a live database looks ids up in its own map, d_kf_of_id must be NULL", who); return ORBX_E_INVALID; }
+        d_kf_of_id = db->live->d_kf_of_id; n_ids = db->live->max_ids;
+    }
     const size_t lds = bow_lds_bytes(true, fr->cap, fr->cap);
     if (lds > 120 * 1024) { orbx_set_error("feature sets too large for LDS"); return ORBX_E_INVALID; }
     ORBX_HIP(hipSetDevice(db->device));
+    hipStream_t s = bowdb_stream(db, fr, stream);
+    if (int rc = bowdb_order_before(db, s)) return rc;
     void (*kern)(const DevFeat *, int, const DevFeat *, const int32_t *, int, const int32_t *, const int32_t *, int, float, int, int32_t *, int, int *) =
         compact ? k_bow2_cand<1> : k_bow2_cand<0>;
     ORBX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(cand_stride, batch), dim3(256), lds, stream ? (hipStream_t)stream : fr->last_stream, (const DevFeat *)db->d_blob,
-                       db->nkf, (const DevFeat *)fr->d_feats, (const int32_t *)d_cand, cand_stride, (const int32_t *)d_ncand,
+    hipLaunchKernelGGL(kern, dim3(cand_stride, batch), dim3(256), lds, s, (const DevFeat *)db->d_blob,
+                       bowdb_nkf(db), (const DevFeat *)fr->d_feats, (const int32_t *)d_cand, cand_stride, (const int32_t *)d_ncand,
                        (const int32_t *)d_kf_of_id, d_kf_of_id ? n_ids : 0, nnratio, check_ori, (int32_t *)d_out, stride, (int *)d_nmatches);
     ORBX_HIP(hipGetLastError());
-    return ORBX_OK;
+    return bowdb_order_after(db, s);
 }
 
 extern "C" int orbx_bowdb_search_candidates_device(orbx_bowdb *db, const orbx_bow_frames *fr, int batch, const void *d_cand, int cand_stride,
@@ -945,6 +1062,375 @@ extern "C" int orbx_bowdb_search_candidates_device_compact(orbx_bowdb *db, const
 {
     return bow_launch_cand("orbx_bowdb_search_candidates_device_compact", db, fr, batch, d_cand, cand_stride, d_ncand, d_kf_of_id, n_ids, nnratio,
                            check_orientation, d_pairs, cap_pairs, d_nmatches, stream, 1);
+}
+
+// ---------------------------------------------------------------- the live set: k_bowdb_pack and its entry points
+// One 256-thread workgroup per job, one launch for any number of jobs (a single job travels in the kernel arguments, so that an add or an
+// erase uploads nothing).  A job (1) copies the keyframe's master from a DevFeat of an orbx_bow_frames, read entirely here -- its counts
+// too, so nothing synchronises -- (2) takes keep[k] = flag[feat_all[k]] per list position, (3) scans keep exclusively in LDS
+// (lds_excl_scan, orbx_device.h: m <= cap <= 8192 positions, 32 per thread at most), (4) writes feat / sdesc / sflag at the scanned
+// positions, (5) sets node_off[i] to the scan value at the node's first position and node_off[nnodes] to the total, and (6) writes the slot's
+// DevFeat record and kf_of_id[id].  The filtered list keeps its order by construction, so there are no atomics.  Every count and index that
+// comes out of device memory is clamped or tested against n / cap before it addresses anything.
+#define BOWDB_MAX_CAP 8192
+__global__ __launch_bounds__(256) void k_bowdb_pack(BowPackJob one, const BowPackJob *jobs, uint8_t *slots, BowSlotLayout lay,
+                                                    DevFeat *recs, int32_t *kf_of_id, int max_ids, int cap)
+{
+    __shared__ int pos[BOWDB_MAX_CAP];
+    __shared__ int s_w[4];
+    const int tid = threadIdx.x;
+    const BowPackJob job = jobs ? jobs[blockIdx.x] : one;
+    uint8_t *base = slots + (size_t)job.slot * lay.stride;
+    int *hdr = reinterpret_cast<int *>(base + lay.hdr);
+    uint32_t *m_desc = reinterpret_cast<uint32_t *>(base + lay.desc);
+    float *m_angle = reinterpret_cast<float *>(base + lay.angle);
+    uint32_t *m_node_id = reinterpret_cast<uint32_t *>(base + lay.node_id);
+    int32_t *m_off_all = reinterpret_cast<int32_t *>(base + lay.off_all);
+    uint32_t *m_feat_all = reinterpret_cast<uint32_t *>(base + lay.feat_all);
+    uint8_t *s_flag = base + lay.flag;
+    int32_t *s_node_off = reinterpret_cast<int32_t *>(base + lay.node_off);
+    uint32_t *s_feat = reinterpret_cast<uint32_t *>(base + lay.feat);
+    uint32_t *s_sdesc = reinterpret_cast<uint32_t *>(base + lay.sdesc);
+    uint8_t *s_sflag = base + lay.sflag;
+    DevFeat rec;
+    rec.n = 0; rec.nnodes = 0;
+    rec.desc = m_desc; rec.node_id = m_node_id; rec.node_off = s_node_off; rec.feat = s_feat; rec.flag = s_flag; rec.angle = m_angle;
+    rec.x = rec.y = rec.u_right = nullptr; rec.octave = nullptr;
+    rec.sdesc = s_sdesc; rec.sflag = s_sflag;
+    if (job.empty) {
+        if (tid == 0) {
+            hdr[0] = 0; hdr[1] = 0;
+            recs[job.slot] = rec;
+            if (job.id >= 0 && job.id < max_ids) kf_of_id[job.id] = -1;
+        }
+        return;
+    }
+    // ---- the master: where this job reads it, and (with a source) its copy into the slot
+    int n, nn;
+    const uint32_t *r_desc = m_desc, *r_feat_all = m_feat_all;
+    const int32_t *r_off_all = m_off_all;
+    if (job.src) {
+        const DevFeat S = *job.src;
+        n = min(max(S.n, 0), cap); nn = min(max(S.nnodes, 0), cap);
+        r_desc = S.desc; r_feat_all = S.feat; r_off_all = S.node_off;
+        const uint4 *src4 = reinterpret_cast<const uint4 *>(S.desc);
+        uint4 *dst4 = reinterpret_cast<uint4 *>(m_desc);
+        for (int i = tid; i < 2 * n; i += 256) dst4[i] = src4[i];
+        for (int i = tid; i < n; i += 256) m_angle[i] = S.angle[i];
+        for (int i = tid; i < nn; i += 256) m_node_id[i] = S.node_id[i];
+        for (int i = tid; i <= nn; i += 256) m_off_all[i] = nn ? S.node_off[i] : 0;
+        if (tid == 0) { hdr[0] = n; hdr[1] = nn; }
+    } else {
+        n = min(max(hdr[0], 0), cap); nn = min(max(hdr[1], 0), cap);
+    }
+    const int m = nn ? min(max(r_off_all[nn], 0), n) : 0;      // list positions: a FeatureVector names a feature at most once, so m <= n
+    // ---- keep per list position (and the master's list, and the flags, into the slot)
+    for (int k = tid; k < m; k += 256) {
+        const uint32_t idx = r_feat_all[k];
+        if (job.src) m_feat_all[k] = idx;
+        pos[k] = idx < (uint32_t)n && (job.flag_ones || job.flag[idx] != 0) ? 1 : 0;
+    }
+    for (int i = tid; i < n; i += 256) s_flag[i] = job.flag_ones ? (uint8_t)1 : job.flag[i];
+    __syncthreads();
+    const int total = lds_excl_scan(pos, m, s_w);
+    // ---- the filtered list: feature, flag and descriptor at the scanned position, two 16-byte halves of a descriptor by two threads
+    for (int i = tid; i < 2 * m; i += 256) {
+        const int k = i >> 1, p = pos[k];
+        if ((k + 1 < m ? pos[k + 1] : total) == p) continue;     // not kept
+        const uint32_t idx = r_feat_all[k];                      // < n: tested when keep was taken
+        if (!(i & 1)) { s_feat[p] = idx; s_sflag[p] = 1; }
+        reinterpret_cast<uint4 *>(s_sdesc)[2 * (long long)p + (i & 1)] = reinterpret_cast<const uint4 *>(r_desc)[2 * (long long)idx + (i & 1)];
+    }
+    for (int i = tid; i <= nn; i += 256) {
+        const int o = i < nn ? min(max(r_off_all[i], 0), m) : m;
+        s_node_off[i] = o < m ? pos[o] : total;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        rec.n = n; rec.nnodes = nn;
+        recs[job.slot] = rec;
+        if (job.id >= 0 && job.id < max_ids) kf_of_id[job.id] = job.slot;
+    }
+}
+
+static void bowdb_pack_launch(orbx_bowdb *db, const BowPackJob &one, const BowPackJob *d_jobs, int njobs, hipStream_t s)
+{
+    BowdbLive *L = db->live;
+    hipLaunchKernelGGL(k_bowdb_pack, dim3(njobs), dim3(256), 0, s, one, d_jobs, L->d_slots, L->lay, (DevFeat *)db->d_blob, L->d_kf_of_id,
+                       L->max_ids, L->cap);
+}
+
+// A set that keyframes enter and leave while it is searched: replaces rebuilding the whole set with orbx_bowdb_create (every keyframe's
+// descriptors and FeatureVector through feat_pack and over PCIe again) whenever the map of Tracking::Relocalization's candidates
+// (src/Tracking.cc:1661-1682) gains or culls a keyframe.
+extern "C" int orbx_bowdb_create_live(int device, int max_kf, int cap, int max_ids, orbx_bowdb **out)
+{
+    if (!out || max_kf < 1 || cap < 1 || cap > BOWDB_MAX_CAP || max_ids < 1 || max_kf >= (1 << 24)) {
+        orbx_set_error("orbx_bowdb_create_live: invalid argument (max_kf >= 1, 1 <= cap <= 8192, max_ids >= 1)");
+        return ORBX_E_INVALID;
+    }
+    *out = nullptr;
+    BowCtx *c;
+    int rc = orbx_ctx_get(g_bow, device, &c); // validates the device
+    if (rc) return rc;
+    orbx_bowdb *db = new orbx_bowdb();
+    memset(db, 0, sizeof *db);
+    db->device = device; db->max_n = cap;
+    BowdbLive *L = db->live = new BowdbLive();
+    L->max_kf = max_kf; L->cap = cap; L->max_ids = max_ids; L->nslots = L->nlive = 0;
+    L->npad = 64;
+    while (L->npad < cap) L->npad <<= 1;     // as orbx_bow_frames pads its lists
+    L->lay = bow_slot_layout(cap, L->npad);
+    L->h_stage = nullptr; L->ev = nullptr; L->ev_stream = nullptr; L->ev_set = false;
+    const size_t o_slots = align_up(sizeof(DevFeat) * (size_t)max_kf, 256), o_map = o_slots + L->lay.stride * (size_t)max_kf,
+                 o_jobs = o_map + a16(4 * (size_t)max_ids), o_flags = o_jobs + a16(sizeof(BowPackJob) * (size_t)max_kf),
+                 total = o_flags + a16((size_t)cap) * (size_t)max_kf;
+    L->h_stage_bytes = std::max(L->lay.stride + a16(sizeof(DevFeat)), total - o_jobs);
+    hipError_t e1 = hipMalloc((void **)&db->d_blob, total);      // the one device allocation of the set's life
+    hipError_t e2 = hipStreamCreateWithFlags(&db->stream, hipStreamNonBlocking);
+    hipError_t e3 = hipEventCreateWithFlags(&L->ev, hipEventDisableTiming);
+    hipError_t e4 = hipHostMalloc((void **)&L->h_stage, L->h_stage_bytes, hipHostMallocDefault);
+    if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || e4 != hipSuccess) {
+        if (e1 != hipSuccess) db->d_blob = nullptr;
+        if (e2 != hipSuccess) db->stream = nullptr;
+        if (e3 != hipSuccess) L->ev = nullptr;
+        if (e4 != hipSuccess) L->h_stage = nullptr;
+        orbx_set_error("orbx_bowdb_create_live: HIP allocation of %zu bytes failed", total);
+        orbx_bowdb_destroy(db);
+        return ORBX_E_HIP;
+    }
+    L->d_slots = db->d_blob + o_slots; L->d_kf_of_id = (int32_t *)(db->d_blob + o_map);
+    L->d_jobs = (BowPackJob *)(db->d_blob + o_jobs); L->d_flags = db->d_blob + o_flags;
+    // every record n = nnodes = 0 (a slot without keyframe), every id -1
+    if (hipMemsetAsync(db->d_blob, 0, o_slots, db->stream) != hipSuccess ||
+        hipMemsetAsync(L->d_kf_of_id, 0xFF, 4 * (size_t)max_ids, db->stream) != hipSuccess || hipStreamSynchronize(db->stream) != hipSuccess) {
+        orbx_set_error("orbx_bowdb_create_live: initialisation failed");
+        orbx_bowdb_destroy(db);
+        return ORBX_E_HIP;
+    }
+    L->kf_of_id.assign((size_t)max_ids, -1);
+    L->id_of_slot.assign((size_t)max_kf, -1);
+    L->n_of_slot.assign((size_t)max_kf, -1);
+    *out = db;
+    return ORBX_OK;
+}
+
+// the slot the next add takes (lowest free one first, then the high-water mark), or -1; takes nothing yet
+static int bowdb_peek_slot(const BowdbLive *L)
+{
+    if (!L->free_slots.empty()) return *L->free_slots.begin();
+    return L->nslots < L->max_kf ? L->nslots : -1;
+}
+static void bowdb_take_slot(BowdbLive *L, int slot, int id, int n)
+{
+    if (slot == L->nslots) L->nslots++; else L->free_slots.erase(slot);
+    L->kf_of_id[id] = slot; L->id_of_slot[slot] = id; L->n_of_slot[slot] = n; L->nlive++;
+}
+
+// the refusals every add shares: ORBX_E_INVALID / ORBX_E_CAPACITY, or ORBX_OK with the slot
+static int bowdb_add_check(const char *who, orbx_bowdb *db, int id, int *slot)
+{
+    BowdbLive *L = db->live;
+    if (id < 0 || id >= L->max_ids) { orbx_set_error("%s: id %d outside [0, %d)", who, id, L->max_ids); return ORBX_E_INVALID; }
+    if (L->kf_of_id[id] >= 0) { orbx_set_error("%s: id %d is already in the set", who, id); return ORBX_E_INVALID; }
+    *slot = bowdb_peek_slot(L);
+    if (*slot < 0) { orbx_set_error("%s: all %d slots hold a keyframe", who, L->max_kf); return ORBX_E_CAPACITY; }
+    return ORBX_OK;
+}
+
+// Replaces, for one keyframe, the host route of orbx_bowdb_create (descriptors and FeatureVector of an extracted frame down to the host,
+// feat_pack, up again): the frame's slot of orbx_bow_transform_batch_device becomes keyframe `id` device to device -- the step behind
+// orbx_kfdb_add_from_frames when Tracking / LocalMapping insert a keyframe (LocalMapping::ProcessNewKeyFrame, src/LocalMapping.cc:147-193).
+extern "C" int orbx_bowdb_add_from_frames(orbx_bowdb *db, int id, const orbx_bow_frames *f, int index, const void *d_flag, void *stream)
+{
+    if (!db || !f || !db->live || f->device != db->device || f->cap != db->live->cap || index < 0 || index >= f->batch) {
+        orbx_set_error("orbx_bowdb_add_from_frames: invalid argument (a live database, frames of its device and cap, an index of the batch)");
+        return ORBX_E_INVALID;
+    }
+    BowdbLive *L = db->live;
+    std::lock_guard<std::mutex> g(L->mu);
+    int slot;
+    if (int rc = bowdb_add_check("orbx_bowdb_add_from_frames", db, id, &slot)) return rc;
+    ORBX_HIP(hipSetDevice(db->device));
+    hipStream_t s = bowdb_stream(db, f, stream);
+    if (int rc = bowdb_order_before(db, s)) return rc;
+    BowPackJob job;
+    job.slot = slot; job.id = id; job.empty = 0; job.flag_ones = d_flag ? 0 : 1;
+    job.src = f->d_feats + index; job.flag = (const uint8_t *)d_flag;
+    bowdb_pack_launch(db, job, nullptr, 1, s);
+    ORBX_HIP(hipGetLastError());
+    bowdb_take_slot(L, slot, id, -1);
+    return bowdb_order_after(db, s);
+}
+
+// The same from a host feature set: what orbx_bowdb_create does for every keyframe of a set, for one (src/ORBmatcher.cc:171-303 reads it).
+extern "C" int orbx_bowdb_add(orbx_bowdb *db, int id, const orbx_featset *kf, void *stream)
+{
+    if (!db || !kf || !db->live) { orbx_set_error("orbx_bowdb_add: invalid argument (a live database and a feature set)"); return ORBX_E_INVALID; }
+    BowdbLive *L = db->live;
+    if (!orbx_feat_validate(kf, 0, 1)) { orbx_set_error("orbx_bowdb_add: malformed feature set"); return ORBX_E_INVALID; }
+    if (kf->n > L->cap || kf->nnodes > L->cap) {
+        orbx_set_error("orbx_bowdb_add: %d features / %d nodes exceed the slots' capacity %d", kf->n, kf->nnodes, L->cap);
+        return ORBX_E_INVALID;
+    }
+    std::lock_guard<std::mutex> g(L->mu);
+    int slot;
+    if (int rc = bowdb_add_check("orbx_bowdb_add", db, id, &slot)) return rc;
+    ORBX_HIP(hipSetDevice(db->device));
+    hipStream_t s = bowdb_stream(db, nullptr, stream);
+    // the master and the flags in the slot's own layout, one upload
+    uint8_t *h = L->h_stage;
+    const size_t n = (size_t)kf->n, nn = (size_t)kf->nnodes, m = nn ? (size_t)kf->node_off[nn] : 0;
+    memset(h, 0, L->lay.upload);
+    int *hdr = (int *)(h + L->lay.hdr);
+    hdr[0] = kf->n; hdr[1] = kf->nnodes;
+    if (n) { memcpy(h + L->lay.desc, kf->desc, 32 * n); memcpy(h + L->lay.angle, kf->angle, 4 * n); memcpy(h + L->lay.flag, kf->flag, n); }
+    if (nn) { memcpy(h + L->lay.node_id, kf->node_id, 4 * nn); memcpy(h + L->lay.off_all, kf->node_off, 4 * (nn + 1)); }
+    if (m) memcpy(h + L->lay.feat_all, kf->feat, 4 * m);
+    uint8_t *d_slot = L->d_slots + (size_t)slot * L->lay.stride;
+    if (int rc = bowdb_order_before(db, s)) return rc;
+    ORBX_HIP(hipMemcpyAsync(d_slot, h, L->lay.upload, hipMemcpyHostToDevice, s));
+    BowPackJob job;
+    job.slot = slot; job.id = id; job.empty = 0; job.flag_ones = 0; job.src = nullptr; job.flag = d_slot + L->lay.flag;
+    bowdb_pack_launch(db, job, nullptr, 1, s);
+    ORBX_HIP(hipGetLastError());
+    bowdb_take_slot(L, slot, id, kf->n);
+    if (int rc = bowdb_order_after(db, s)) return rc;
+    ORBX_HIP(hipStreamSynchronize(s));       // the staging block is free for the next call
+    return ORBX_OK;
+}
+
+// KeyFrameDatabase::erase's counterpart for the searched set (src/KeyFrameDatabase.cc:48-68, a keyframe culled by KeyFrame::SetBadFlag, src/KeyFrame.cc:489): replaces the rebuild without it.
+extern "C" int orbx_bowdb_erase(orbx_bowdb *db, int id, void *stream)
+{
+    if (!db || !db->live) { orbx_set_error("orbx_bowdb_erase: invalid argument (a live database)"); return ORBX_E_INVALID; }
+    BowdbLive *L = db->live;
+    std::lock_guard<std::mutex> g(L->mu);
+    if (id < 0 || id >= L->max_ids || L->kf_of_id[id] < 0) { orbx_set_error("orbx_bowdb_erase: id %d is not in the set", id); return ORBX_E_INVALID; }
+    ORBX_HIP(hipSetDevice(db->device));
+    hipStream_t s = bowdb_stream(db, nullptr, stream);
+    if (int rc = bowdb_order_before(db, s)) return rc;
+    const int slot = L->kf_of_id[id];
+    BowPackJob job;
+    job.slot = slot; job.id = id; job.empty = 1; job.flag_ones = 1; job.src = nullptr; job.flag = nullptr;
+    bowdb_pack_launch(db, job, nullptr, 1, s);
+    ORBX_HIP(hipGetLastError());
+    L->kf_of_id[id] = -1; L->id_of_slot[slot] = -1; L->n_of_slot[slot] = -1; L->nlive--;
+    L->free_slots.insert(slot);
+    return bowdb_order_after(db, s);
+}
+
+// the feature count of a slot whose keyframe came from frames: read from the slot's header once (synchronises s), then remembered
+static int bowdb_slot_n(orbx_bowdb *db, int slot, hipStream_t s, int *n)
+{
+    BowdbLive *L = db->live;
+    if (L->n_of_slot[slot] < 0) {
+        int *hdr = (int *)L->h_stage;
+        ORBX_HIP(hipMemcpyAsync(hdr, L->d_slots + (size_t)slot * L->lay.stride + L->lay.hdr, 16, hipMemcpyDeviceToHost, s));
+        ORBX_HIP(hipStreamSynchronize(s));
+        L->n_of_slot[slot] = std::min(std::max(hdr[0], 0), L->cap);
+    }
+    *n = L->n_of_slot[slot];
+    return ORBX_OK;
+}
+
+// Map points created, culled or fused change which features hold one (LocalMapping::MapPointCulling / CreateNewMapPoints / SearchInNeighbors, src/LocalMapping.cc:195, :237, :515): the new flags of n keyframes, the
+// searched forms rebuilt from the resident masters in one launch.  Replaces the rebuild of the whole set for a change of flags.
+extern "C" int orbx_bowdb_set_flags(orbx_bowdb *db, const int32_t *ids, int n, const uint8_t *const *flags, void *stream)
+{
+    if (!db || !db->live || n < 0 || (n && (!ids || !flags))) { orbx_set_error("orbx_bowdb_set_flags: invalid argument (a live database, n ids and flag arrays)"); return ORBX_E_INVALID; }
+    BowdbLive *L = db->live;
+    std::lock_guard<std::mutex> g(L->mu);
+    if (n > L->nlive) { orbx_set_error("orbx_bowdb_set_flags: %d ids, %d keyframes in the set", n, L->nlive); return ORBX_E_INVALID; }
+    for (int i = 0; i < n; i++) {
+        if (ids[i] < 0 || ids[i] >= L->max_ids || L->kf_of_id[ids[i]] < 0) { orbx_set_error("orbx_bowdb_set_flags: id %d is not in the set", ids[i]); return ORBX_E_INVALID; }
+        if (!flags[i]) { orbx_set_error("orbx_bowdb_set_flags: no flags for id %d", ids[i]); return ORBX_E_INVALID; }
+        for (int j = 0; j < i; j++)
+            if (ids[j] == ids[i]) { orbx_set_error("orbx_bowdb_set_flags: id %d named twice", ids[i]); return ORBX_E_INVALID; }
+    }
+    if (n == 0) return ORBX_OK;
+    ORBX_HIP(hipSetDevice(db->device));
+    hipStream_t s = bowdb_stream(db, nullptr, stream);
+    if (int rc = bowdb_order_before(db, s)) return rc;
+    std::vector<int> cnt((size_t)n);
+    for (int i = 0; i < n; i++)
+        if (int rc = bowdb_slot_n(db, L->kf_of_id[ids[i]], s, &cnt[i])) return rc;
+    // jobs and flags in one pinned block, in the layout of the device block behind d_jobs: one upload, one launch
+    const size_t fstride = a16((size_t)L->cap), o_flags = (size_t)((uint8_t *)L->d_flags - (uint8_t *)L->d_jobs);
+    BowPackJob *hj = (BowPackJob *)L->h_stage;
+    for (int i = 0; i < n; i++) {
+        hj[i].slot = L->kf_of_id[ids[i]]; hj[i].id = ids[i]; hj[i].empty = 0; hj[i].flag_ones = 0; hj[i].src = nullptr;
+        hj[i].flag = L->d_flags + fstride * (size_t)i;
+        if (cnt[i]) memcpy(L->h_stage + o_flags + fstride * (size_t)i, flags[i], (size_t)cnt[i]);
+    }
+    ORBX_HIP(hipMemcpyAsync(L->d_jobs, L->h_stage, o_flags + fstride * (size_t)n, hipMemcpyHostToDevice, s));
+    bowdb_pack_launch(db, hj[0], L->d_jobs, n, s);
+    ORBX_HIP(hipGetLastError());
+    if (int rc = bowdb_order_after(db, s)) return rc;
+    ORBX_HIP(hipStreamSynchronize(s));
+    return ORBX_OK;
+}
+
+extern "C" int orbx_bowdb_live_count(const orbx_bowdb *db)
+{
+    if (!db || !db->live) { orbx_set_error("orbx_bowdb_live_count: invalid argument (a live database)"); return ORBX_E_INVALID; }
+    std::lock_guard<std::mutex> g(db->live->mu);
+    return db->live->nlive;
+}
+
+// id_of_slot[i] = the id behind slot i < orbx_bowdb_size(db), the index the all-keyframes searches report it under (replaces the
+// d_kf_of_id join a caller of orbx_bowdb_create keeps by hand); entries at or beyond the size read -1
+extern "C" int orbx_bowdb_ids(const orbx_bowdb *db, int32_t *id_of_slot, int nslots)
+{
+    if (!db || !db->live || !id_of_slot || nslots < 0) { orbx_set_error("orbx_bowdb_ids: invalid argument (a live database, an array)"); return ORBX_E_INVALID; }
+    BowdbLive *L = db->live;
+    std::lock_guard<std::mutex> g(L->mu);
+    if (nslots < L->nslots) { orbx_set_error("orbx_bowdb_ids: %d entries, the set has %d slots", nslots, L->nslots); return ORBX_E_CAPACITY; }
+    for (int i = 0; i < nslots; i++) id_of_slot[i] = i < L->nslots ? L->id_of_slot[i] : -1;
+    return ORBX_OK;
+}
+
+// the searched form of a keyframe through its DevFeat record, as k_bow2 / k_bow2_cand reach it (tests; replaces nothing of the reference)
+extern "C" int orbx_bowdb_read_keyframe(orbx_bowdb *db, int id, int *n, int *nnodes, uint32_t *node_id, int32_t *node_off,
+                                        uint32_t *feat, uint8_t *flag, float *angle, uint8_t *desc, uint8_t *sdesc, uint8_t *sflag)
+{
+    if (!db || !db->live) { orbx_set_error("orbx_bowdb_read_keyframe: invalid argument (a live database)"); return ORBX_E_INVALID; }
+    BowdbLive *L = db->live;
+    std::lock_guard<std::mutex> g(L->mu);
+    if (id < 0 || id >= L->max_ids || L->kf_of_id[id] < 0) { orbx_set_error("orbx_bowdb_read_keyframe: id %d is not in the set", id); return ORBX_E_INVALID; }
+    ORBX_HIP(hipSetDevice(db->device));
+    if (int rc = bowdb_order_before(db, db->stream)) return rc;
+    const int slot = L->kf_of_id[id];
+    const uint8_t *d_slot = L->d_slots + (size_t)slot * L->lay.stride;
+    uint8_t *h = L->h_stage;
+    const bool arrays = node_id || node_off || feat || flag || angle || desc || sdesc || sflag;
+    ORBX_HIP(hipMemcpyAsync(h, (const DevFeat *)db->d_blob + slot, sizeof(DevFeat), hipMemcpyDeviceToHost, db->stream));
+    if (arrays) ORBX_HIP(hipMemcpyAsync(h + a16(sizeof(DevFeat)), d_slot, L->lay.stride, hipMemcpyDeviceToHost, db->stream));
+    if (int rc = bowdb_order_after(db, db->stream)) return rc;
+    ORBX_HIP(hipStreamSynchronize(db->stream));
+    const DevFeat rec = *(const DevFeat *)h;
+    const uint8_t *hs = h + a16(sizeof(DevFeat));
+    const size_t rn = (size_t)std::min(std::max(rec.n, 0), L->cap), rnn = (size_t)std::min(std::max(rec.nnodes, 0), L->cap);
+    if (n) *n = (int)rn;
+    if (nnodes) *nnodes = (int)rnn;
+    if (!arrays) return ORBX_OK;
+    // every array through the pointer the record holds; one that leaves the slot would be a bug of k_bowdb_pack
+    auto at = [&](const void *p, size_t bytes) -> const uint8_t * {
+        const uint8_t *q = (const uint8_t *)p;
+        return q >= d_slot && bytes <= L->lay.stride && (size_t)(q - d_slot) <= L->lay.stride - bytes ? hs + (q - d_slot) : nullptr;
+    };
+    const int32_t *h_off = (const int32_t *)at(rec.node_off, 4 * (rnn + 1));
+    const size_t mf = h_off ? (size_t)std::min(std::max(h_off[rnn], 0), (int)rn) : 0;
+    struct { void *dst; const void *src; size_t bytes; } parts[] = {
+        { node_id, rec.node_id, 4 * rnn }, { node_off, rec.node_off, 4 * (rnn + 1) }, { feat, rec.feat, 4 * mf }, { flag, rec.flag, rn },
+        { angle, rec.angle, 4 * rn }, { desc, rec.desc, 32 * rn }, { sdesc, rec.sdesc, 32 * mf }, { sflag, rec.sflag, mf } };
+    for (const auto &p : parts) {
+        if (!p.dst) continue;
+        const uint8_t *q = at(p.src, p.bytes);
+        if (!q) { orbx_set_error("orbx_bowdb_read_keyframe: the record of id %d points outside its slot", id); return ORBX_E_HIP; }
+        memcpy(p.dst, q, p.bytes);
+    }
+    return ORBX_OK;
 }
 
 // ---------------------------------------------------------------- MapPoint::ComputeDistinctiveDescriptors (f3)

@@ -215,6 +215,14 @@ def lib():
     L.orbx_bowdb_search_batch_device_compact.argtypes = [vp, vp, i, f, i, vp, i, vp, vp]
     L.orbx_bowdb_search_candidates_device.argtypes = [vp, vp, i, vp, i, vp, vp, i, f, i, vp, vp, vp]
     L.orbx_bowdb_search_candidates_device_compact.argtypes = [vp, vp, i, vp, i, vp, vp, i, f, i, vp, i, vp, vp]
+    L.orbx_bowdb_create_live.argtypes = [i, i, i, i, C.POINTER(vp)]
+    L.orbx_bowdb_add_from_frames.argtypes = [vp, i, vp, i, vp, vp]
+    L.orbx_bowdb_add.argtypes = [vp, i, FS, vp]
+    L.orbx_bowdb_erase.argtypes = [vp, i, vp]
+    L.orbx_bowdb_set_flags.argtypes = [vp, vp, i, C.POINTER(vp), vp]
+    L.orbx_bowdb_live_count.argtypes = [vp]
+    L.orbx_bowdb_ids.argtypes = [vp, vp, i]
+    L.orbx_bowdb_read_keyframe.argtypes = [vp, i, ip, ip, vp, vp, vp, vp, vp, vp, vp, vp]
     L.orbx_kfdb_create.argtypes = [i, i, C.POINTER(vp)]
     L.orbx_kfdb_destroy.argtypes = [vp]; L.orbx_kfdb_destroy.restype = None
     L.orbx_kfdb_size.argtypes = [vp]
@@ -813,9 +821,81 @@ class BowDatabase:
 
     def search(self, F, nnratio=0.75, checkOri=True):
         b, kb = make_featset(F)
-        out = np.full((self.nkf, b.n), -1, np.int32); n = np.zeros(self.nkf, np.int32)
+        nkf = self._L.orbx_bowdb_size(self._h)
+        out = np.full((nkf, b.n), -1, np.int32); n = np.zeros(nkf, np.int32)
         _check(self._L.orbx_bowdb_search(self._h, C.byref(b), nnratio, int(checkOri), _p(out), _p(n)))
         return out, n
+
+    # ---- the live set (orbx_bowdb_create_live): keyframes enter, leave and change flags while it is searched
+    @classmethod
+    def live(cls, max_kf, cap, max_ids, device=0):
+        """an empty set of max_kf slots of `cap` features for ids in [0, max_ids); BowFrames.search* take it as they take an immutable one
+        (the candidate searches with kf_of_id=None: the set keeps the id map itself)"""
+        self = cls.__new__(cls)
+        self._L = lib()
+        self._h = C.c_void_p()
+        _check(self._L.orbx_bowdb_create_live(device, int(max_kf), int(cap), int(max_ids), C.byref(self._h)))
+        self.max_kf, self.cap, self.max_ids, self.device = int(max_kf), int(cap), int(max_ids), device
+        return self
+
+    def size(self):
+        """keyframes (an immutable set) or slots ever used (a live one): the rows the all-keyframes searches write (orbx_bowdb_size)"""
+        return self._L.orbx_bowdb_size(self._h)
+
+    def add_from_frames(self, id, frames, index, d_flag=None, stream=None):
+        """keyframe `id` from slot `index` of a BowFrames, device to device and asynchronous; d_flag = device uint8[cap] or None (all set)"""
+        _check(self._L.orbx_bowdb_add_from_frames(self._h, int(id), frames._h, int(index), d_flag, stream))
+
+    def add(self, id, keyframe, stream=None):
+        """keyframe `id` from a host feature set (the dict BowDatabase(...) takes)"""
+        b, kb = make_featset(keyframe)
+        _check(self._L.orbx_bowdb_add(self._h, int(id), C.byref(b), stream))
+
+    def erase(self, id, stream=None):
+        _check(self._L.orbx_bowdb_erase(self._h, int(id), stream))
+
+    def set_flags(self, ids, flags, stream=None):
+        """new map-point flags (uint8 per feature) for the live keyframes `ids`, one launch.  The mirror first asks the set for each
+        keyframe's feature count (a small synchronising read per keyframe) to refuse an array of another length; a caller that cannot
+        afford that calls orbx_bowdb_set_flags itself, as tools/bench_live_bowdb.py does"""
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        if len(flags) != len(ids):
+            raise OrbxError(-1, f"set_flags: {len(ids)} ids, {len(flags)} flag arrays")
+        keep = [np.ascontiguousarray(f, np.uint8).reshape(-1) for f in flags]
+        for k, a in zip(ids, keep):           # the C entry reads as many bytes as the keyframe has features
+            n = C.c_int(-1)
+            _check(self._L.orbx_bowdb_read_keyframe(self._h, int(k), C.byref(n), None, None, None, None, None, None, None, None, None))
+            if len(a) != n.value:
+                raise OrbxError(-1, f"set_flags: {len(a)} flags for keyframe {int(k)} of {n.value} features")
+        ptrs = (C.c_void_p * max(len(keep), 1))(*[a.ctypes.data for a in keep])
+        _check(self._L.orbx_bowdb_set_flags(self._h, _p(ids), len(ids), ptrs, stream))
+
+    def live_count(self):
+        rc = self._L.orbx_bowdb_live_count(self._h)
+        if rc < 0:
+            _check(rc)
+        return rc
+
+    def ids(self):
+        """the id behind every slot, -1 = empty (int32[size()])"""
+        out = np.full(self.size(), -1, np.int32)
+        _check(self._L.orbx_bowdb_ids(self._h, _p(out), len(out)))
+        return out
+
+    def read_keyframe(self, id):
+        """the searched form of keyframe `id` as the kernels see it: dict(n, nnodes, node_id, node_off, feat, flag, angle, desc, sdesc, sflag),
+        the filtered arrays cut to the filtered length"""
+        cap = self.cap
+        n, nn = C.c_int(), C.c_int()
+        node_id = np.zeros(cap, np.uint32); node_off = np.zeros(cap + 1, np.int32); feat = np.zeros(cap, np.uint32)
+        flag = np.zeros(cap, np.uint8); angle = np.zeros(cap, np.float32); desc = np.zeros((cap, 32), np.uint8)
+        sdesc = np.zeros((cap, 32), np.uint8); sflag = np.zeros(cap, np.uint8)
+        _check(self._L.orbx_bowdb_read_keyframe(self._h, int(id), C.byref(n), C.byref(nn), _p(node_id), _p(node_off), _p(feat), _p(flag),
+                                                _p(angle), _p(desc), _p(sdesc), _p(sflag)))
+        n, nn = n.value, nn.value
+        m = int(node_off[nn])
+        return dict(n=n, nnodes=nn, node_id=node_id[:nn].copy(), node_off=node_off[:nn + 1].copy(), feat=feat[:m].copy(), flag=flag[:n].copy(),
+                    angle=angle[:n].copy(), desc=desc[:n].copy(), sdesc=sdesc[:m].copy(), sflag=sflag[:m].copy())
 
 
 class BowFrames:
