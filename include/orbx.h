@@ -83,6 +83,11 @@ void orbx_extractor_destroy(orbx_extractor *e);
 #define ORBX_CV_PROFILE_3_4_2 ORBX_CV_TAPS_256
 int orbx_extractor_set_cv_profile(orbx_extractor *e, int profile);
 int orbx_gaussian_taps(int profile, int taps[7]);
+/* inspection: the constant operand of the descriptor kernel's matrix-core row pass for a tap profile.  The row pass is the banded product
+ * R[43 x 37] = Raw[43 x 43] . G, G[k][c] = taps[k - c] for 0 <= k - c <= 6; `out` (3 * 64 * 16 bytes) receives G cut into three column
+ * tiles of 16 in the lane layout of the 16x16x64 int8 matrix instruction: byte j of lane l of tile t is G[16 (l / 16) + j][16 t + l % 16],
+ * zero for k >= 43 and c >= 37.  *acc0 = 128 * sum(taps), where the accumulators start: the kernel multiplies pixel - 128. */
+int orbx_desc_rowpass_matrix(int profile, uint8_t *out, int *acc0);
 
 /* Tuning, no effect on results: extractions of at most `max_images` images per launch build the pyramid (ComputePyramid,
  * src/ORBextractor.cc:1347-1370) with two launches that each produce several levels (a single frame's time is its chain of dependent
@@ -759,12 +764,13 @@ int orbx_debug_level_counts(orbx_extractor *e, int image_index, int32_t *counts 
 int orbx_debug_fast_form(const orbx_extractor *e);
 /* which form each size- and geometry-dependent launch of the handle took: the most recent extraction, and the most recent
  * stereo launch with `e` as the left handle (launches of `e` itself: the pipelined forms run on internal lanes).  Writes the
- * first min(n, 9) fields and returns 9 (the field count):
+ * first min(n, 10) fields and returns 10 (the field count):
  *   [0] pyramid regime: 2 = grouped launches, 1 = per level for the big levels + grouped small ones, 0 = one launch per level
  *   [1] FAST waves per cell (1 .. 4; 0 = k_fast2)     [2] FAST grid order: 1 = image-major, 0 = cell-major
  *   [3] quadtree threads (1024, 256)   [4] node tables in LDS (1) or HBM (0)   [5] register point form (1 / 0)
  *   [6] k_desc level template (8, 16)
  *   [7] stereo keypoints per wave (1, 4; 0 = no stereo launch yet)   [8] stereo XCD-owned pair grid (1 / 0)
+ *   [9] k_desc row pass: 2 = matrix cores, 1 = vector ALUs (ORBX_DESC_VALU_ROWPASS=1 when the handle was created)
  * All 0 before the first launch. */
 int orbx_debug_launch_forms(const orbx_extractor *e, int32_t *out, int n);
 /* test hook: the SearchByBoW kernels exist in a latency form (one 16-wave workgroup per pair) and a throughput form

@@ -11,6 +11,7 @@
 
 __constant__ uint32_t c_pat4[256];        // x0 | y0<<8 | x1<<16 | y1<<24, signed bytes (src/ORBextractor.cc:160-418, data)
 __constant__ uint4 c_omask[64];           // IC_Angle: per lane (row, half) the byte mask of its 16-pixel window inside the circular patch
+__constant__ uint4 c_rowB[2][3][64];      // row pass on the matrix cores: per tap profile and column tile the lane's B fragment (orbx_desc_rowpass_matrix)
 
 #ifdef ORBX_DIAG
 __device__ unsigned long long g_desc_stamp[4096 * 8]; // diagnostic build only: summed phase cycles of k_desc, 4096 slots
@@ -27,6 +28,11 @@ __device__ uint2 g_span_1[SPAN_SLOTS];                // SPAN_END(1): slot 1 of 
 // applied to the patch only (never materialising the blurred level; its row pass on the whole patch, its
 // column pass only at the 512 steered sample positions), and the 256 pairs are compared with one ballot
 // per 64 pairs (computeOrbDescriptor, :116-157).
+// The row pass is the exact integer banded product R[43 x 37] = Raw[43 x 43] . G[43 x 37].  MF = true (the default) computes it on the
+// matrix cores: nine v_mfma_i32_16x16x64_i8 (three row tiles x three column tiles, one K step of 64 >= 43 each) on the pixels biased to
+// signed bytes (p - 128, one XOR per dword) against the constant banded tap matrix, with 128 * sum(g) as the accumulator's start, so that
+// the int32 result is sum(g * p) itself.  MF = false keeps the row pass on the vector ALUs (v_dot4_u32_u8 against shifted tap words);
+// ORBX_DESC_VALU_ROWPASS=1, read when the extractor is created, selects it.  Both forms write the same u16 values and share everything else.
 // Launch constants of k_desc by value (kernel-argument segment, scalar loads that depend on nothing): the level of a slot is
 // found by comparing against kp_off[] in registers, and only then one dependent fetch (the level's record) remains before the
 // patch address is known.  Fetching them through the Geom pointer was a chain of dependent scalar loads at the start of every
@@ -35,6 +41,7 @@ struct DescLevel { int w, h, pitch, kp_off; long long pyr_off; float scale; int 
 struct DescArgs {
     int nlevels, kp_total;
     unsigned gauss;                   // taps g0 | g1 << 8 | g2 << 16 | g3 << 24 of the handle's 7-tap kernel (symmetric; orbx_gaussian_taps)
+    int rowb, acc0;                   // matrix-core row pass: which c_rowB table (the tap profile), and 128 * sum(g), where its accumulators start
     int kp_off[ORBX_MAX_LEVELS];      // first staging slot of level i; INT_MAX for i >= nlevels
     DescLevel lv[ORBX_MAX_LEVELS];
 };
@@ -122,8 +129,8 @@ __device__ __forceinline__ void desc_rowtab(const DescArgs &da, const int *__res
 #undef FOR_KEYPOINTS
 }
 
-template <int NL>
-__global__ __launch_bounds__(64) void k_desc(const DescArgs da, PyrRef pr, const int *__restrict__ lvl_cnt,
+template <int NL, bool MF>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(64))) void k_desc(const DescArgs da, PyrRef pr, const int *__restrict__ lvl_cnt,
                                              const uint32_t *__restrict__ lvl_kp, orbx_keypoint *__restrict__ out_kps,
                                              uint8_t *__restrict__ out_desc, int *__restrict__ out_n, int cap, int nimg, const RowTabArgs rt,
                                              const int *__restrict__ err_flag, int *__restrict__ flag_out)
@@ -131,12 +138,19 @@ __global__ __launch_bounds__(64) void k_desc(const DescArgs da, PyrRef pr, const
     // LDS pitches: raw bytes (11 dwords per row), row-pass u16 (column-major, 43 rows per column, 37 columns).  1908 + 3188 bytes
     // round to 5120 = 160 KB / 32: the CU holds its maximum of 32 waves (the kernel is latency bound: with 5600 bytes, 29 waves
     // per CU, it ran 3 % slower; every KB more costs 7 %)
-    constexpr int RP = 44, HR = 43;
-    constexpr int RAW_BYTES = 43 * RP + 16;              // 1908
-    __shared__ __align__(16) uint8_t desc_smem[RAW_BYTES + (37 * HR + 3) * 2];
+    // Matrix-core form: 12 dwords per raw row (every A fragment is an aligned 16-byte read; bytes 44..47 of a row are never staged and
+    // only ever meet zero taps) and 44 rows per hb column (a lane's four vertically adjacent results are one aligned 8-byte store).
+    // The fragment reads of the third row tile run to row 47 + 16 bytes = byte 2320.  The raw patch is dead once the fragments
+    // are in registers, so hb (37 * 88 = 3256 bytes) lies OVER it: 2320 + 3256 would not fit the 5120.  The array keeps the vector form's
+    // size (the row-table wave needs it).
+    constexpr int RP = MF ? 48 : 44, HR = MF ? 44 : 43;
+    constexpr int RAW_BYTES = 43 * 44 + 16;              // 1908 (vector form)
+    constexpr int SMEM_BYTES = RAW_BYTES + (37 * 43 + 3) * 2;    // 5096
+    __shared__ __align__(16) uint8_t desc_smem[SMEM_BYTES];
     uint8_t *raw = desc_smem;
-    uint16_t *hb = reinterpret_cast<uint16_t *>(desc_smem + RAW_BYTES);   // + the zero-tap row "43" of the last column, read as part of a dword
+    uint16_t *hb = reinterpret_cast<uint16_t *>(desc_smem + (MF ? 0 : RAW_BYTES));   // vector form: + the zero-tap row "43" of the last column, read as part of a dword
     static_assert(RAW_BYTES % 4 == 0 && sizeof(desc_smem) >= 16 * ORBX_MAX_LEVELS + 2 * (ORBX_ROWTAB_MAX_ROWS + 4) * sizeof(int), "row table workspace");
+    static_assert(!MF || (47 * RP + 64 <= SMEM_BYTES && 37 * HR * 2 <= SMEM_BYTES && RP % 16 == 0 && (HR * 2) % 8 == 0), "matrix-core row pass: fragment reads and hb inside the array, aligned");
     // Workgroups are dealt round-robin over the 8 XCDs (linear id % 8, speed only): XCD x walks the images x, x + 8, x + 16, ...
     // one after the other, so the patches its waves fetch at any time come from one or two images (1.4 MB of pyramid each)
     // instead of from every image in flight on the chip: the per-XCD L2 (4 MB) then holds them
@@ -176,6 +190,11 @@ __global__ __launch_bounds__(64) void k_desc(const DescArgs da, PyrRef pr, const
 #pragma unroll
     for (int jj = 0; jj < 4; jj++) pat4[jj] = c_pat4[lane + 64 * jj];
     const uint4 omask = c_omask[lane];
+    uint4 rowB[3] = {};     // (matrix-core form) the lane's B fragments of the three column tiles
+    if constexpr (MF) {
+#pragma unroll
+        for (int nt = 0; nt < 3; nt++) rowB[nt] = c_rowB[da.rowb][nt][lane];
+    }
     int off = 0, total = 0;
 #pragma unroll
     for (int i = 0; i < NL; i++) { const int c = lc[i]; off += i < l ? c : 0; total += c; }
@@ -198,15 +217,17 @@ __global__ __launch_bounds__(64) void k_desc(const DescArgs da, PyrRef pr, const
     // so the realignment shifts below are immediates and the row pass reads three dwords per item instead of four)
     constexpr int xo = 0;
     const int x0a = x - 21;
-    if (x >= 21 && x + 21 < L.w && y >= 21 && y + 21 < L.h && x0a + RP <= pitch) {
+    if (x >= 21 && x + 21 < L.w && y >= 21 && y + 21 < L.h && x0a + 44 <= pitch) {
         const uint8_t *src = img + (long long)(y - 21) * pitch + x0a;
         // nine direct loads (global_load_lds_dword: any byte alignment, no VGPR round trip, no ds_write), all in flight together.
         // Lane = (row lane/11, dword lane%11) of a 5-row band (55 lanes), band k covers rows 5k..5k+4 and lands at raw + 220 k + 4 lane:
-        // row-major with the 44-byte pitch.
+        // row-major with the 44-byte pitch.  (Matrix-core form: 12 dwords per row, 60 lanes, 240 bytes per band; the twelfth dword of a
+        // row is not loaded -- it only meets zero taps, and loading it would push keypoints near the right edge of the pitch to the slow path.)
         // scalar band base + one 32-bit lane offset: the bands advance on the scalar unit (a 64-bit vector multiply-add per load otherwise)
-        const int lr = lane / 11, lc = lane - lr * 11;
+        constexpr int DW = RP / 4;
+        const int lr = lane / DW, lc = lane - lr * DW;
         const unsigned voff = (unsigned)(lr * pitch + 4 * lc);
-        if (lane < 55) {
+        if (lane < 5 * DW && lc < 11) {
 #pragma unroll
             for (int k = 0; k < 8; k++, src += 5 * (long long)pitch)
                 __builtin_amdgcn_global_load_lds(reinterpret_cast<const uint32_t *>(src + voff), reinterpret_cast<uint32_t *>(raw + 5 * RP * k), 4, 0, 0);
@@ -257,9 +278,41 @@ __global__ __launch_bounds__(64) void k_desc(const DescArgs da, PyrRef pr, const
     const float factor_pi = (float)(3.14159265358979323846 / 180.f);
     float sn, cs;
     dev_sincos(angle * factor_pi, &sn, &cs);
-    // ---- row pass: 4 outputs per item from 3 aligned dwords.  Output k needs bytes k .. k + 6: instead of shifting the data
-    // (v_alignbyte) the TAPS are shifted -- ten constant tap words, v_dot4_u32_u8 against each dword an output touches
     const unsigned g0 = da.gauss & 0xFFu, g1 = (da.gauss >> 8) & 0xFFu, g2 = (da.gauss >> 16) & 0xFFu, g3 = da.gauss >> 24;   // symmetric: g4 = g2, g5 = g1, g6 = g0
+    if constexpr (MF) {
+        // ---- row pass on the matrix cores.  Row tile mt, column tile nt: D[16 x 16] = A_mt[16 x 64] . B_nt[64 x 16] + acc0.
+        // A fragment: lane = (row l % 16 of the tile, K block l / 16) holds 16 consecutive bytes of its raw row (one aligned ds_read_b128),
+        // biased to signed.  Byte j of K block q is column 16 q + j in both A and B, so the product does not depend on the order in which
+        // the instruction walks K.  Columns 43..63 (the next raw row's first bytes for q = 3, never-staged bytes 44..47) and rows 43..47
+        // (beyond the patch, inside the array) are arbitrary bytes: the former meet zero taps, the latter's results are padding or dropped.
+        typedef int i32x4 __attribute__((ext_vector_type(4)));
+        const int r16 = lane & 15, q = lane >> 4;
+        const uint4 *ap = reinterpret_cast<const uint4 *>(raw + r16 * RP + 16 * q);
+        i32x4 A[3];
+#pragma unroll
+        for (int mt = 0; mt < 3; mt++) {
+            const uint4 t = ap[mt * RP];     // 16 rows of RP bytes, in uint4s
+            A[mt] = i32x4{ (int)(t.x ^ 0x80808080u), (int)(t.y ^ 0x80808080u), (int)(t.z ^ 0x80808080u), (int)(t.w ^ 0x80808080u) };
+        }
+        // hb overlays the raw patch: every fragment is in registers before the first result is written (one wave per workgroup)
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        // D layout: lane = (column l % 16 of the tile, rows 4 (l / 16) .. + 3): four vertically adjacent u16 of one hb column, one
+        // aligned 8-byte store.  Rows >= 44 and columns >= 37 are not written (row 43 is the padding row that only meets the zero tap)
+        const i32x4 C0 = { da.acc0, da.acc0, da.acc0, da.acc0 };
+        uint8_t *wp = reinterpret_cast<uint8_t *>(hb) + r16 * (HR * 2) + q * 8;
+#pragma unroll
+        for (int mt = 0; mt < 3; mt++) {
+#pragma unroll
+            for (int nt = 0; nt < 3; nt++) {
+                const i32x4 Bf = { (int)rowB[nt].x, (int)rowB[nt].y, (int)rowB[nt].z, (int)rowB[nt].w };
+                const i32x4 D = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[mt], Bf, C0, 0, 0, 0);
+                if ((mt < 2 || q < 3) && (nt < 2 || r16 < 5))     // results of real rows are <= 65535
+                    *reinterpret_cast<uint2 *>(wp + nt * 16 * (HR * 2) + mt * 32) = make_uint2(__builtin_amdgcn_perm((unsigned)D.y, (unsigned)D.x, 0x05040100u), __builtin_amdgcn_perm((unsigned)D.w, (unsigned)D.z, 0x05040100u));   // low halves: D.x | D.y << 16
+            }
+        }
+    } else {
+    // ---- row pass on the vector ALUs: 4 outputs per item from 3 aligned dwords.  Output k needs bytes k .. k + 6: instead of shifting the data
+    // (v_alignbyte) the TAPS are shifted -- ten constant tap words, v_dot4_u32_u8 against each dword an output touches
     const unsigned TA0 = g0 | g1 << 8 | g2 << 16 | g3 << 24, TB0 = g2 | g1 << 8 | g0 << 16;
     const unsigned TA1 = g0 << 8 | g1 << 16 | g2 << 24, TB1 = g3 | g2 << 8 | g1 << 16 | g0 << 24;
     const unsigned TA2 = g0 << 16 | g1 << 24, TB2 = g2 | g3 << 8 | g2 << 16 | g1 << 24, TC2 = g0;
@@ -287,6 +340,7 @@ __global__ __launch_bounds__(64) void k_desc(const DescArgs da, PyrRef pr, const
                 }
             }
         }
+    }
     }
     __syncthreads();
     DSTAMP(2);
@@ -363,6 +417,12 @@ int orbx_desc_upload_constants(orbx_extractor *e)
         pat[i] = (uint32_t)(uint8_t)ORB_PAT_X0[i] | ((uint32_t)(uint8_t)ORB_PAT_Y0[i] << 8) | ((uint32_t)(uint8_t)ORB_PAT_X1[i] << 16) |
                  ((uint32_t)(uint8_t)ORB_PAT_Y1[i] << 24);
     ORBX_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_pat4), pat, sizeof pat));
+    {   // the banded tap matrices of the matrix-core row pass, one per tap profile (a launch names its profile's table: DescArgs::rowb)
+        uint8_t rb[2][3 * 64 * 16];
+        int acc0;
+        for (int prof = 0; prof < 2; prof++) { const int rc = orbx_desc_rowpass_matrix(prof, rb[prof], &acc0); if (rc) return rc; }
+        ORBX_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_rowB), rb, sizeof rb));
+    }
     {   // k_desc's orientation lanes: lane = (row v = lane/2 - 15, half = lane & 1); the left half covers u = -16..-1 and
         // keeps u >= -umax[|v|], the right half covers u = 0..15 and keeps u <= umax[|v|] (src/ORBextractor.cc:91-108)
         uint8_t m[64][16];
@@ -411,6 +471,27 @@ extern "C" int orbx_gaussian_taps(int profile, int taps[7])
     return ORBX_OK;
 }
 
+// The constant operand of k_desc's matrix-core row pass for a tap profile: R[43 x 37] = Raw[43 x 43] . G with G[k][c] = g[k - c] for
+// 0 <= k - c <= 6, else 0, cut into three column tiles of 16 and laid out as the B fragments of v_mfma_i32_16x16x64_i8: byte j of lane l
+// of tile nt is G[16 (l / 16) + j][16 nt + l % 16], zero for k >= 43 and c >= 37.  *acc0 = 128 * sum(g): the kernel feeds p - 128.
+extern "C" int orbx_desc_rowpass_matrix(int profile, uint8_t *out, int *acc0)
+{
+    int taps[7];
+    const int rc = orbx_gaussian_taps(profile, taps);
+    if (rc) return rc;
+    if (!out || !acc0) { orbx_set_error("orbx_desc_rowpass_matrix: null argument"); return ORBX_E_INVALID; }
+    int sum = 0;
+    for (int i = 0; i < 7; i++) sum += taps[i];
+    *acc0 = 128 * sum;
+    for (int nt = 0; nt < 3; nt++)
+        for (int l = 0; l < 64; l++)
+            for (int j = 0; j < 16; j++) {
+                const int k = 16 * (l / 16) + j, c = 16 * nt + l % 16, d = k - c;
+                out[(nt * 64 + l) * 16 + j] = (uint8_t)(k < 43 && c < 37 && d >= 0 && d <= 6 ? taps[d] : 0);
+            }
+    return ORBX_OK;
+}
+
 extern "C" int orbx_extractor_set_cv_profile(orbx_extractor *e, int profile)
 {
     if (!e) { orbx_set_error("null extractor"); return ORBX_E_INVALID; }
@@ -432,6 +513,7 @@ void orbx_desc_launch(orbx_extractor *e, const PyrRef &pr, int batch, void *d_kp
     memset(&da, 0, sizeof da);
     da.nlevels = G.nlevels; da.kp_total = G.kp_total;
     da.gauss = (unsigned)e->gauss[0] | (unsigned)e->gauss[1] << 8 | (unsigned)e->gauss[2] << 16 | (unsigned)e->gauss[3] << 24;
+    da.rowb = e->cv_profile == ORBX_CV_PROFILE_3_4_2; da.acc0 = 128 * (2 * (e->gauss[0] + e->gauss[1] + e->gauss[2]) + e->gauss[3]);
     for (int i = 0; i < ORBX_MAX_LEVELS; i++) {
         da.kp_off[i] = i < G.nlevels ? G.lv[i].kp_off : INT_MAX;
         if (i < G.nlevels) {
@@ -448,6 +530,9 @@ void orbx_desc_launch(orbx_extractor *e, const PyrRef &pr, int batch, void *d_kp
         e->rt_kps = d_kps; e->rt_cap = cap; e->rt_batch = batch;
     }
     e->last_forms[6] = G.nlevels <= 8 ? 8 : ORBX_MAX_LEVELS;    // orbx_debug_launch_forms
-    hipLaunchKernelGGL((G.nlevels <= 8 ? k_desc<8> : k_desc<ORBX_MAX_LEVELS>), dim3((batch < 8 ? batch : 8) * (G.kp_total + rt.on), (batch + 7) / 8), dim3(64), 0, s, da, pr, e->d_lvl_cnt, e->d_lvl_kp,
+    e->last_forms[9] = e->desc_valu_rowpass ? 1 : 2;
+    const auto kern = e->desc_valu_rowpass ? (G.nlevels <= 8 ? k_desc<8, false> : k_desc<ORBX_MAX_LEVELS, false>)
+                                           : (G.nlevels <= 8 ? k_desc<8, true> : k_desc<ORBX_MAX_LEVELS, true>);
+    hipLaunchKernelGGL(kern, dim3((batch < 8 ? batch : 8) * (G.kp_total + rt.on), (batch + 7) / 8), dim3(64), 0, s, da, pr, e->d_lvl_cnt, e->d_lvl_kp,
                        (orbx_keypoint *)d_kps, (uint8_t *)d_desc, (int *)d_n_out, cap, batch, rt, (const int *)orbx_err_flag(e), e->flag_out);
 }

@@ -175,6 +175,8 @@ extern "C" int orbx_extractor_create(orbx_extractor **out, int nfeatures, float 
         // and latency, and a pair wave's 7.8 KB of LDS leaves 21 waves per CU against 28)
         const char *fp = getenv("ORBX_FAST_PAIR");
         e->fast_pair = fp && *fp == '1' ? 1 : 0;
+        const char *dv = getenv("ORBX_DESC_VALU_ROWPASS");  // tests / A-B: k_desc's older row pass (v_dot4_u32_u8) instead of the matrix cores; same results
+        e->desc_valu_rowpass = dv && *dv == '1' ? 1 : 0;
     }
     // src/ORBextractor.cc:436-461
     e->sf[0] = 1.0f; e->sig2[0] = 1.0f;

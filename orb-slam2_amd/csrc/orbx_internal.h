@@ -22,7 +22,7 @@
 #ifndef ORBX_TREE_OVER_PTS
 #define ORBX_TREE_OVER_PTS 1024 // register form: points of a level beyond the register capacity that an LDS overflow array takes
 #endif
-#define ORBX_LAUNCH_FORM_FIELDS 9 // orbx_debug_launch_forms: pyramid regime, FAST waves + grid order, quadtree threads / tables / register mode, k_desc levels, stereo kpw / XCD grid
+#define ORBX_LAUNCH_FORM_FIELDS 10 // orbx_debug_launch_forms: pyramid regime, FAST waves + grid order, quadtree threads / tables / register mode, k_desc levels, stereo kpw / XCD grid, k_desc row pass
 #define ORBX_FAST_LIST_CAP 512 // k_fast: pretest candidates listed per round (u16 each); denser cells take several rounds
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -133,6 +133,7 @@ struct orbx_extractor {
     int last_fast_form;                    // debug: 1 = k_fast, 2 = k_fast2 ran in the most recent extraction
     int32_t last_forms[ORBX_LAUNCH_FORM_FIELDS]; // debug: launch forms of the most recent extraction / stereo launch (orbx_debug_launch_forms)
     int fast_pair;                         // ORBX_FAST_PAIR: 1 = k_fast2 wherever the geometry allows it, 0 (default) = never
+    int desc_valu_rowpass;                 // ORBX_DESC_VALU_ROWPASS: 1 = k_desc's row pass on the vector ALUs, 0 (default) = on the matrix cores
     // workspace (sized for max_w x max_h x max_batch)
     uint8_t *d_pyr; size_t pyr_cap;        // levels >= 1, all images
     uint8_t *d_stage_in; size_t stage_in_cap; // host-API input staging (level 0)

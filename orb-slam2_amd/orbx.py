@@ -139,6 +139,7 @@ def lib():
     L.orbx_extractor_set_cv_profile.argtypes = [vp, i]
     L.orbx_extractor_set_pyramid_group_limit.argtypes = [vp, i]
     L.orbx_gaussian_taps.argtypes = [i, vp]
+    L.orbx_desc_rowpass_matrix.argtypes = [i, vp, ip]
     L.orbx_extractor_destroy.argtypes = [vp]
     L.orbx_extractor_destroy.restype = None
     L.orbx_get_levels.argtypes = [vp]
@@ -314,6 +315,14 @@ def gaussian_taps(profile):
     return t
 
 
+def desc_rowpass_matrix(profile):
+    """(B, acc0) of k_desc's matrix-core row pass: B[tile, lane, j] uint8 in the instruction's lane layout (orbx_desc_rowpass_matrix)"""
+    b = np.zeros((3, 64, 16), np.uint8)
+    acc0 = C.c_int(0)
+    _check(lib().orbx_desc_rowpass_matrix(profile, _p(b), C.byref(acc0)))
+    return b, acc0.value
+
+
 def debug_set_bow_form(form):
     """test hook: "auto" / "wave" / "table" form of the SearchByBoW kernels (orbx_debug_set_bow_form)"""
     _check(lib().orbx_debug_set_bow_form({"auto": 0, "wave": 1, "table": 2}[form]))
@@ -414,7 +423,7 @@ class ORBextractor:
         return self._L.orbx_debug_fast_form(self._h)
 
     LAUNCH_FORM_FIELDS = ("pyramid_regime", "fast_waves", "fast_image_major", "tree_threads", "tree_tab_lds", "tree_reg",
-                          "desc_levels", "stereo_kpw", "stereo_xcd_grid")
+                          "desc_levels", "stereo_kpw", "stereo_xcd_grid", "desc_rowpass")
 
     def debug_launch_forms(self):
         """the form each size- and geometry-dependent launch took in the most recent extraction and in the most recent stereo
