@@ -51,15 +51,9 @@ __device__ void histogram_filter(int32_t *match, const uint8_t *bins, int nslots
             if (bins[i] != 255) atomicAdd(&hist[bins[i]], 1);
         __syncthreads();
         if (tid == 0) {
-            int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;
-            for (int i = 0; i < BOW_HISTO; i++) {
-                const int s = hist[i];
-                if (s > max1) { max3 = max2; max2 = max1; max1 = s; i3 = i2; i2 = i1; i1 = i; }
-                else if (s > max2) { max3 = max2; max2 = s; i3 = i2; i2 = i; }
-                else if (s > max3) { max3 = s; i3 = i; }
-            }
-            if ((float)max2 < 0.1f * (float)max1) { i2 = -1; i3 = -1; }
-            else if ((float)max3 < 0.1f * (float)max1) { i3 = -1; }
+            static_assert(BOW_HISTO == 30, "three_maxima scans the 30 bins of rot_bin");
+            int i1, i2, i3;
+            three_maxima(hist, &i1, &i2, &i3);
             keep3[0] = i1; keep3[1] = i2; keep3[2] = i3;
         }
         __syncthreads();

@@ -245,6 +245,22 @@ __device__ __forceinline__ int rot_bin(float a1, float a2)
     return (unsigned)bin < 30 ? bin : 0; // the reference asserts the range; NaN / huge angles must not index out of the histogram
 }
 
+// ComputeThreeMaxima (src/ORBmatcher.cc:1687-1728) on the 30 per-bin counts, as the reference scans them: strict comparisons, so among
+// equal counts the lowest bin ranks first; a bin the 0.1f tests drop (or that never was) reads -1.  One thread.
+__device__ __forceinline__ void three_maxima(const int *hist, int *i1, int *i2, int *i3)
+{
+    int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
+    for (int i = 0; i < 30; i++) {
+        const int s = hist[i];
+        if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
+        else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
+        else if (s > max3) { max3 = s; ind3 = i; }
+    }
+    if ((float)max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
+    else if ((float)max3 < 0.1f * (float)max1) { ind3 = -1; }
+    *i1 = ind1; *i2 = ind2; *i3 = ind3;   // written once: the scan itself stays in registers
+}
+
 // ---- Frame::UndistortKeyPoints (src/Frame.cc:470-515) on one point: cv::undistortPoints(mat, mat, mK, mDistCoef, cv::Mat(), mK).  Shared by
 // k_undistort (orbx_frame.hip) and the resident-frame ingest (orbx_proj.hip) so that both give the same bits (-ffp-contract=off in both).
 struct UndistortParams { double fx, fy, ifx, ify, cx, cy, k[5]; };

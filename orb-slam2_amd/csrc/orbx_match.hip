@@ -141,6 +141,7 @@ __device__ void m_finalize(const MArgs &g, const MItem &it, int lane, unsigned *
         __syncthreads();
         // the sequential scan of the reference keeps, with strict comparisons, the three largest bins in the order (count
         // descending, bin ascending) among bins with count > 0: three wave maxima of count << 8 | (255 - bin)
+        // (three_maxima() in orbx_device.h is the serial statement of the same rule)
         const unsigned hv = lane < 30 ? s_hist[lane] : 0u;
         unsigned key = hv ? (hv << 8) | (255u - (unsigned)lane) : 0u;
         const unsigned m1 = wave_max_u32(key);

@@ -1,8 +1,25 @@
-// orbx_proj.hip — the two per-frame projection-guided matchers of ORB-SLAM2's tracking thread
-// (SURVEY.md 8f row f1):
-//   ORBmatcher::SearchByProjection(Frame&, const Frame&, th, bMono)        reference src/ORBmatcher.cc:1396-1553
-//   ORBmatcher::SearchByProjection(Frame&, const vector<MapPoint*>&, th)   reference src/ORBmatcher.cc:48-129
+// orbx_proj.hip — the projection-guided searches of ORB-SLAM2, seven in all, reference src/ORBmatcher.cc:
+//   SearchByProjection(Frame&, const Frame&, th, bMono)                 :1396-1553   last frame
+//   SearchByProjection(Frame&, const vector<MapPoint*>&, th)            :48-129      local map points
+//   SearchByProjection(Frame&, KeyFrame*, sAlreadyFound, th, ORBdist)   :1555-1685   relocalisation
+//   SearchByProjection(KeyFrame*, Scw, vpPoints, vpMatched, th)         :305-415     loop closing
+//   Fuse x2 (search half) and each direction of SearchBySim3            :873-1164, :1218-1372   ("window best": independent points)
+//   SearchBySim3                                                        :1166-1394
+//   SearchForInitialization                                             :430-556
 // with Frame::AssignFeaturesToGrid / PosInGrid / GetFeaturesInArea (src/Frame.cc:261-279, :386-457).
+//
+// In file order:
+//   device   DevFrame, DevPoints, ProjParams (one parameter block describes every search)
+//            the grid build: grid_build_body, k_grid_build
+//            the frame ingest from extraction buffers: k_frame_ingest, k_frame_ingest_grid
+//            a point's window and candidate test: point_window, cand_ok; the window walk both per-point kernels share: window_walk
+//            k_proj_lists (candidate lists), k_proj_resolve (claim fixpoint + rotation filter), k_init_resolve (SearchForInitialization)
+//            k_window_best (independent points against resident keyframes, many jobs per launch)
+//   host     ProjCtx (per-thread staging); frame_layout, dev_frame (one layout of a frame's arrays); proj_stage_frame, points_stage;
+//            proj_search (upload, grid, lists, resolve, download); points_check, proj_run; the parameter blocks params_*; sim3_agree
+//            the host-pointer entry points of the seven searches
+//            the frame pool and the orbx_frame handle (create, create_from_extraction, read, destroy)
+//            the searches on a resident current frame; the searches on resident keyframes (orbx_frame_window_best_batch and its users)
 //
 // The reference walks the map points sequentially and lets every accepted match claim its feature
 // (later points skip features whose holder has Observations() > 0), so the result depends on the order.
@@ -263,11 +280,60 @@ __device__ __forceinline__ bool cand_ok(const DevFrame &F, const DevPoints &P, c
     return true;
 }
 
-// Candidate list of every point, one wave per point.  For a fixed grid column ix the cells (ix, cy0..cy1) are
-// consecutive in the CSR, so the window is a handful of contiguous index ranges whose concatenation is exactly
-// GetFeaturesInArea's traversal order (ix, iy, position in cell): lanes stride over a range, test the candidate and
-// compute the Hamming distance, and a ballot keeps the order when the survivors are appended
-// (entry = feature | dist<<16 | octave<<25).  The wave reserves the window's total range length in the pool with
+// ---- the window walk of one point by one wave, shared by k_proj_lists and k_window_best.  For a fixed grid column ix the cells
+// (ix, cy0..cy1) are consecutive in the CSR (cells are stored column by column), so the window is a handful of contiguous index runs
+// whose concatenation is exactly GetFeaturesInArea's traversal order (ix, iy, position in cell).  Lane q fetches the run of column
+// cx0 + q (the grid has 64 columns), a wave prefix sum flattens the runs, and the candidates are then taken 64 at a time ACROSS columns
+// -- in the order the column-by-column walk had (the order decides every tie downstream).  That walk was four dependent memory round
+// trips per column; this is four per point.
+// Returns upper, the window's total run length (wave-uniform).  admit(upper) is asked once, when upper > 0, whether the walk takes place
+// (k_proj_lists reserves its pool space there).  visit(ok, jf, k, dist) is then called once per 64-candidate chunk on ALL lanes (a
+// visitor may ballot): jf = the lane's position in the flattened candidate sequence, ok = the position exists and the candidate passed
+// cand_ok; then k is the feature and dist its Hamming distance to the point's descriptor (loaded once, before the chunks).
+template <typename Admit, typename Visit>
+__device__ __forceinline__ int window_walk(const DevFrame &F, const int *__restrict__ cell_off, const int *__restrict__ cell_idx,
+                                           const DevPoints &P, const ProjParams &pp, const Win &w, int i, int lane, Admit admit, Visit visit)
+{
+    const int ncol = w.cx1 - w.cx0 + 1;
+    int c_lo = 0, c_n = 0;
+    if (lane < ncol) {
+        const int ix = w.cx0 + lane;
+        c_lo = cell_off[ix * PG_ROWS + w.cy0];
+        c_n = cell_off[ix * PG_ROWS + w.cy1 + 1] - c_lo;
+    }
+    const int c_incl = wave_incl_scan(c_n), c_excl = c_incl - c_n;
+    const int upper = __builtin_amdgcn_readlane(c_incl, 63);
+    if (!upper || !admit(upper)) return upper;
+    uint32_t d[8];
+    const uint4 *s = reinterpret_cast<const uint4 *>(P.desc + (long long)i * 8);
+    const uint4 q0 = s[0], q1 = s[1];
+    d[0] = q0.x; d[1] = q0.y; d[2] = q0.z; d[3] = q0.w; d[4] = q1.x; d[5] = q1.y; d[6] = q1.z; d[7] = q1.w;
+    for (int jb = 0; jb < upper; jb += 64) {
+        const int jf = jb + lane;            // position in the flattened candidate sequence
+        int j = -1;
+        for (int q = 0; q < ncol; q++) {     // which column's run holds it (a handful of columns; their runs ride in lanes 0 .. ncol - 1)
+            const int e_ = __builtin_amdgcn_readlane(c_excl, q), n_ = __builtin_amdgcn_readlane(c_n, q), l_ = __builtin_amdgcn_readlane(c_lo, q);
+            if (jf >= e_ && jf < e_ + n_) j = l_ + (jf - e_);
+        }
+        bool ok = false;
+        int k = -1, dist = 0;
+        if (jf < upper) {
+            k = cell_idx[j];
+            if (cand_ok(F, P, pp, w, i, k)) {
+                ok = true;
+                const uint4 *t = reinterpret_cast<const uint4 *>(F.desc + (long long)k * 8);
+                const uint4 v0 = t[0], v1 = t[1];
+                const uint32_t e[8] = { v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w };
+                dist = hamming256(d, e);
+            }
+        }
+        visit(ok, jf, k, dist);
+    }
+    return upper;
+}
+
+// Candidate list of every point, one wave per point: the survivors of the window walk are appended behind a ballot, which keeps
+// the walk's order (entry = feature | dist<<16 | octave<<25).  The wave reserves the window's total run length in the pool with
 // one atomicAdd (an upper bound of its list); beg[i] / cnt[i] locate the list.  If the pool overflows the host
 // grows it and repeats the call (pool_used = entries needed).
 __global__ __launch_bounds__(256) void k_proj_lists(DevFrame F, DevPoints P, ProjParams pp, const int *__restrict__ cell_off,
@@ -279,57 +345,18 @@ __global__ __launch_bounds__(256) void k_proj_lists(DevFrame F, DevPoints P, Pro
     Win w;
     int n = 0, base = 0;
     if (point_window(F, P, pp, i, &w)) {
-        // The window's cells are, per grid column, one contiguous run of the CSR (cells are stored column by column): lane q fetches the run of
-        // column cx0 + q (the grid has 64 columns), a wave prefix sum flattens the runs, and the candidates are then taken 64 at a time ACROSS
-        // columns -- in the order the column-by-column walk had (the list order decides ties downstream).  That walk was four dependent memory
-        // round trips per column; this is four per point.
-        const int ncol = w.cx1 - w.cx0 + 1;
-        int c_lo = 0, c_n = 0;
-        if (lane < ncol) {
-            const int ix = w.cx0 + lane;
-            c_lo = cell_off[ix * PG_ROWS + w.cy0];
-            c_n = cell_off[ix * PG_ROWS + w.cy1 + 1] - c_lo;
-        }
-        const int c_incl = wave_incl_scan(c_n), c_excl = c_incl - c_n;
-        const int upper = __builtin_amdgcn_readlane(c_incl, 63);
-        if (upper) {
-            if (lane == 0) base = atomicAdd(pool_used, upper);
-            base = __builtin_amdgcn_readfirstlane(base);
-        }
-        if (upper && base + upper <= pool_cap) {
-            uint32_t d[8];
-            const uint4 *s = reinterpret_cast<const uint4 *>(P.desc + (long long)i * 8);
-            const uint4 q0 = s[0], q1 = s[1];
-            d[0] = q0.x; d[1] = q0.y; d[2] = q0.z; d[3] = q0.w; d[4] = q1.x; d[5] = q1.y; d[6] = q1.z; d[7] = q1.w;
-            {
-                for (int jb = 0; jb < upper; jb += 64) {
-                    const int jf = jb + lane;            // position in the flattened candidate sequence
-                    int j = -1;
-                    for (int q = 0; q < ncol; q++) {     // which column's run holds it (a handful of columns; their runs ride in lanes 0 .. ncol - 1)
-                        const int e_ = __builtin_amdgcn_readlane(c_excl, q), n_ = __builtin_amdgcn_readlane(c_n, q), l_ = __builtin_amdgcn_readlane(c_lo, q);
-                        if (jf >= e_ && jf < e_ + n_) j = l_ + (jf - e_);
-                    }
-                    bool ok = false;
-                    uint32_t en = 0;
-                    if (jf < upper) {
-                        const int k = cell_idx[j];
-                        if (cand_ok(F, P, pp, w, i, k)) {
-                            ok = true;
-                            const uint4 *t = reinterpret_cast<const uint4 *>(F.desc + (long long)k * 8);
-                            const uint4 v0 = t[0], v1 = t[1];
-                            const int dist = __popc(d[0] ^ v0.x) + __popc(d[1] ^ v0.y) + __popc(d[2] ^ v0.z) + __popc(d[3] ^ v0.w) +
-                                             __popc(d[4] ^ v1.x) + __popc(d[5] ^ v1.y) + __popc(d[6] ^ v1.z) + __popc(d[7] ^ v1.w);
-                            en = (uint32_t)k | ((uint32_t)dist << 16) | ((uint32_t)(F.octave[k] & 31) << 25);
-                        }
-                    }
-                    const unsigned long long m = __ballot(ok);
-                    if (ok) entries[base + n + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0))] = en;
-                    n += __popcll(m);
-                }
-            }
-        } else if (upper) {
-            n = 0; // overflow: the host repeats the call with a larger pool
-        }
+        window_walk(F, cell_off, cell_idx, P, pp, w, i, lane,
+            [&](int upper) {
+                if (lane == 0) base = atomicAdd(pool_used, upper);
+                base = __builtin_amdgcn_readfirstlane(base);
+                return base + upper <= pool_cap;   // overflow: no entry is written, the host repeats the call with a larger pool
+            },
+            [&](bool ok, int, int k, int dist) {
+                const unsigned long long m = __ballot(ok);
+                if (ok) entries[base + n + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0))] =
+                    (uint32_t)k | ((uint32_t)dist << 16) | ((uint32_t)(F.octave[k] & 31) << 25);
+                n += __popcll(m);
+            });
     }
     if (lane == 0) { beg[i] = base; cnt[i] = n; }
 }
@@ -412,11 +439,7 @@ __global__ __launch_bounds__(1024) void k_proj_resolve(DevFrame F, DevPoints P, 
         atomicMax(&match[f], i);
         local++;
         if (pp.check_ori) {
-            float rot = P.angle[i] - F.angle[f];               // :1493-1500
-            if (rot < 0.0f) rot += 360.0f;
-            int bin = (int)roundf(rot * (1.0f / 30));
-            if (bin == 30) bin = 0;
-            bin = (unsigned)bin < 30u ? bin : 0;
+            const int bin = rot_bin(P.angle[i], F.angle[f]);   // :1493-1500
             atomicAdd(&hist[bin], 1);
             nxt[i] = bin;
         }
@@ -425,16 +448,9 @@ __global__ __launch_bounds__(1024) void k_proj_resolve(DevFrame F, DevPoints P, 
     __threadfence_block();
     __syncthreads();
     if (pp.check_ori) {
-        if (tid == 0) { // ComputeThreeMaxima (:1687-1728)
-            int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;
-            for (int i = 0; i < 30; i++) {
-                const int s = hist[i];
-                if (s > max1) { max3 = max2; max2 = max1; max1 = s; i3 = i2; i2 = i1; i1 = i; }
-                else if (s > max2) { max3 = max2; max2 = s; i3 = i2; i2 = i; }
-                else if (s > max3) { max3 = s; i3 = i; }
-            }
-            if ((float)max2 < 0.1f * (float)max1) { i2 = -1; i3 = -1; }
-            else if ((float)max3 < 0.1f * (float)max1) { i3 = -1; }
+        if (tid == 0) {
+            int i1, i2, i3;
+            three_maxima(hist, &i1, &i2, &i3);
             keep3[0] = i1; keep3[1] = i2; keep3[2] = i3;
         }
         __syncthreads();
@@ -533,11 +549,7 @@ __global__ __launch_bounds__(64) void k_init_resolve(DevFrame F, DevPoints P, Pr
                     pt_choice[i1] = f; pt_dist[i1] = bd;
                     m21[f] = (uint16_t)(i1 + 1); md[f] = (uint16_t)bd;
                     if (pp.check_ori) {
-                        float rot = __uint_as_float((unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(my_ang), j)) - fang[f];   // :501-509
-                        if (rot < 0.0f) rot += 360.0f;
-                        int bin = (int)roundf(rot * (1.0f / 30));
-                        if (bin == 30) bin = 0;
-                        bin = (unsigned)bin < 30u ? bin : 0;
+                        const int bin = rot_bin(__uint_as_float((unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(my_ang), j)), fang[f]);   // :501-509
                         hist[bin]++; bins[i1] = bin;
                     }
                 }
@@ -553,17 +565,7 @@ __global__ __launch_bounds__(64) void k_init_resolve(DevFrame F, DevPoints P, Pr
     __syncthreads();
     // nmatches = matches still standing (every steal removed one, :492), then the orientation filter (:514-541)
     int i1k = -1, i2k = -1, i3k = -1;
-    if (pp.check_ori) {
-        int max1 = 0, max2 = 0, max3 = 0;
-        for (int i = 0; i < 30; i++) {
-            const int sv = hist[i];
-            if (sv > max1) { max3 = max2; max2 = max1; max1 = sv; i3k = i2k; i2k = i1k; i1k = i; }
-            else if (sv > max2) { max3 = max2; max2 = sv; i3k = i2k; i2k = i; }
-            else if (sv > max3) { max3 = sv; i3k = i; }
-        }
-        if ((float)max2 < 0.1f * (float)max1) { i2k = -1; i3k = -1; }
-        else if ((float)max3 < 0.1f * (float)max1) { i3k = -1; }
-    }
+    if (pp.check_ori) three_maxima(hist, &i1k, &i2k, &i3k);
     int local = 0;
     for (int i = lane; i < P.n; i += 64) {
         if (pt_choice[i] < 0) continue;
@@ -581,7 +583,7 @@ __global__ __launch_bounds__(64) void k_init_resolve(DevFrame F, DevPoints P, Pr
 // ProjParams::claims == 0 a point's answer is the first minimum of its own candidate list, so list and decision fuse into ONE kernel --
 // no pool, no atomics, no second launch -- and one launch serves many (keyframe, points) jobs.  Job j owns the workgroups
 // wg_first[j] .. wg_first[j + 1] (four points each, one wave per point, as k_proj_lists); the job table lives in device memory and is
-// found by a wave-uniform search.  The window, the level range and the column-run flattening are those of k_proj_lists; instead of
+// found by a wave-uniform search.  The window, the level range and the walk (window_walk) are those of k_proj_lists; instead of
 // appending the survivors every lane keeps its smallest (dist << 16 | position in GetFeaturesInArea's traversal), dist <= 256 and
 // position < 65536 (a frame holds fewer features than that), and one wave minimum gives the reference's strict '<' (:995-999): the
 // smallest distance and, among equals, the FIRST candidate in traversal order.
@@ -609,40 +611,11 @@ __global__ __launch_bounds__(256) void k_window_best(const WinJob *__restrict__ 
     int key_k = -1;
     Win w;
     if (point_window(J.F, J.P, J.pp, i, &w)) {
-        const int ncol = w.cx1 - w.cx0 + 1;
-        int c_lo = 0, c_n = 0;
-        if (lane < ncol) {
-            const int ix = w.cx0 + lane;
-            c_lo = J.cell_off[ix * PG_ROWS + w.cy0];
-            c_n = J.cell_off[ix * PG_ROWS + w.cy1 + 1] - c_lo;
-        }
-        const int c_incl = wave_incl_scan(c_n), c_excl = c_incl - c_n;
-        const int upper = __builtin_amdgcn_readlane(c_incl, 63);
-        if (upper) {
-            uint32_t d[8];
-            const uint4 *s = reinterpret_cast<const uint4 *>(J.P.desc + (long long)i * 8);
-            const uint4 q0 = s[0], q1 = s[1];
-            d[0] = q0.x; d[1] = q0.y; d[2] = q0.z; d[3] = q0.w; d[4] = q1.x; d[5] = q1.y; d[6] = q1.z; d[7] = q1.w;
-            for (int jb = 0; jb < upper; jb += 64) {
-                const int jf = jb + lane;            // position in the flattened candidate sequence
-                int j = -1;
-                for (int q = 0; q < ncol; q++) {
-                    const int e_ = __builtin_amdgcn_readlane(c_excl, q), n_ = __builtin_amdgcn_readlane(c_n, q), l_ = __builtin_amdgcn_readlane(c_lo, q);
-                    if (jf >= e_ && jf < e_ + n_) j = l_ + (jf - e_);
-                }
-                if (jf < upper) {
-                    const int k = J.cell_idx[j];
-                    if (cand_ok(J.F, J.P, J.pp, w, i, k)) {
-                        const uint4 *t = reinterpret_cast<const uint4 *>(J.F.desc + (long long)k * 8);
-                        const uint4 v0 = t[0], v1 = t[1];
-                        const int dist = __popc(d[0] ^ v0.x) + __popc(d[1] ^ v0.y) + __popc(d[2] ^ v0.z) + __popc(d[3] ^ v0.w) +
-                                         __popc(d[4] ^ v1.x) + __popc(d[5] ^ v1.y) + __popc(d[6] ^ v1.z) + __popc(d[7] ^ v1.w);
-                        const unsigned nk = ((unsigned)dist << 16) | (unsigned)jf;
-                        if (nk < key) { key = nk; key_k = k; }   // a lane's positions ascend: '<' keeps its first minimum
-                    }
-                }
-            }
-        }
+        window_walk(J.F, J.cell_off, J.cell_idx, J.P, J.pp, w, i, lane, [](int) { return true; },
+            [&](bool ok, int jf, int k, int dist) {
+                const unsigned nk = ((unsigned)dist << 16) | (unsigned)jf;
+                if (ok && nk < key) { key = nk; key_k = k; }   // a lane's positions ascend: '<' keeps its first minimum
+            });
     }
     const unsigned best = wave_min_u32(key);
     int out_k = -1, out_d = 256;
@@ -689,27 +662,77 @@ static int proj_blob_reserve(ProjCtx *c, size_t blob)
     if (!rc && blob > c->d_cap) rc = ensure(&c->d_blob, &c->d_cap, 2 * blob);
     return rc;
 }
-static size_t proj_head_bytes(size_t nc) { return 5 * a16(4 * nc) + a16(32 * nc); }
-static size_t proj_tail_bytes(size_t nc, size_t np) { return a16(nc) + 6 * a16(4 * np) + a16(32 * np) + 2 * a16(np); }
+// ---- the arrays of a frame, as they lie in a resident frame's block and, up to o_coff, at the head of a host-pointer call's staging
+// blob: x[n] y[n] octave[n] angle[n] u_right[n] desc[n][32] | cell_off[3073] cell_idx[n]
+struct FrameLayout { size_t o_x, o_y, o_oct, o_ang, o_ur, o_desc, o_coff, o_cidx, bytes; };
 
-// ---- part 1 of a host-pointer search: the frame's arrays into the head of the staging blob; F addresses them where the upload of part 2
-// will put them (the grid is then built by part 2 into its work area)
-static void proj_stage_frame(ProjCtx *c, const orbx_frame_feats *cur, DevFrame *F)
+static FrameLayout frame_layout(size_t nc)
 {
-    const size_t nc = (size_t)cur->n;
-    uint8_t *h = c->h_blob;
-    const uint8_t *d = c->d_blob;
+    FrameLayout L;
     size_t o = 0;
     auto take = [&](size_t bytes) { const size_t r = o; o += a16(bytes); return r; };
-    const size_t fx = take(4 * nc), fy = take(4 * nc), fo = take(4 * nc), fa = take(4 * nc), fu = take(4 * nc), fd = take(32 * nc);
-    memcpy(h + fx, cur->x, 4 * nc); memcpy(h + fy, cur->y, 4 * nc); memcpy(h + fo, cur->octave, 4 * nc);
-    if (cur->angle) memcpy(h + fa, cur->angle, 4 * nc); else memset(h + fa, 0, 4 * nc);
-    memcpy(h + fu, cur->u_right, 4 * nc); memcpy(h + fd, cur->desc, 32 * nc);
-    F->n = cur->n; F->x = (const float *)(d + fx); F->y = (const float *)(d + fy); F->octave = (const int32_t *)(d + fo);
-    F->angle = (const float *)(d + fa); F->u_right = (const float *)(d + fu); F->desc = (const uint32_t *)(d + fd);
-    F->min_x = cur->min_x; F->min_y = cur->min_y; F->max_x = cur->max_x; F->max_y = cur->max_y;
-    F->inv_w = (float)PG_COLS / (cur->max_x - cur->min_x);  // src/Frame.cc:164-165
-    F->inv_h = (float)PG_ROWS / (cur->max_y - cur->min_y);
+    L.o_x = take(4 * nc); L.o_y = take(4 * nc); L.o_oct = take(4 * nc); L.o_ang = take(4 * nc); L.o_ur = take(4 * nc);
+    L.o_desc = take(32 * nc); L.o_coff = take(4 * (PG_CELLS + 1)); L.o_cidx = take(4 * nc);
+    L.bytes = o;
+    return L;
+}
+
+// the DevFrame of n features laid out by L behind `base` (a device address), image bounds b = min_x, min_y, max_x, max_y; occupied is
+// the search's to set
+static DevFrame dev_frame(const uint8_t *base, const FrameLayout &L, int n, const float b[4])
+{
+    DevFrame F;
+    F.n = n; F.x = (const float *)(base + L.o_x); F.y = (const float *)(base + L.o_y); F.octave = (const int32_t *)(base + L.o_oct);
+    F.angle = (const float *)(base + L.o_ang); F.u_right = (const float *)(base + L.o_ur); F.desc = (const uint32_t *)(base + L.o_desc);
+    F.occupied = nullptr;
+    F.min_x = b[0]; F.min_y = b[1]; F.max_x = b[2]; F.max_y = b[3];
+    F.inv_w = (float)PG_COLS / (b[2] - b[0]);  // src/Frame.cc:164-165
+    F.inv_h = (float)PG_ROWS / (b[3] - b[1]);
+    return F;
+}
+
+static size_t proj_tail_bytes(size_t nc, size_t np) { return a16(nc) + 6 * a16(4 * np) + a16(32 * np) + 2 * a16(np); }
+
+// ---- part 1 of a host-pointer search: the frame's arrays into the head of the staging blob (frame_layout(n).o_coff bytes); the DevFrame
+// addresses them where the upload of part 2 will put them (the grid is then built by part 2 into its work area)
+static DevFrame proj_stage_frame(ProjCtx *c, const orbx_frame_feats *cur)
+{
+    const size_t nc = (size_t)cur->n;
+    const FrameLayout L = frame_layout(nc);
+    uint8_t *h = c->h_blob;
+    memcpy(h + L.o_x, cur->x, 4 * nc); memcpy(h + L.o_y, cur->y, 4 * nc); memcpy(h + L.o_oct, cur->octave, 4 * nc);
+    if (cur->angle) memcpy(h + L.o_ang, cur->angle, 4 * nc); else memset(h + L.o_ang, 0, 4 * nc);
+    memcpy(h + L.o_ur, cur->u_right, 4 * nc); memcpy(h + L.o_desc, cur->desc, 32 * nc);
+    const float b[4] = { cur->min_x, cur->min_y, cur->max_x, cur->max_y };
+    return dev_frame(c->d_blob, L, cur->n, b);
+}
+
+// ---- the arrays of a point set into a staging blob at *o (advanced; sub-blocks in the order of DevPoints): u v level valid always, of
+// the others those that `want` names.  A wanted array the caller left NULL reads 0 (has_obs: 1).  The DevPoints addresses them behind
+// `d`, where the upload will put them; an array not wanted is NULL there.
+enum { PT_AUX = 1, PT_ANGLE = 2, PT_VIEW_COS = 4, PT_DESC = 8, PT_HAS_OBS = 16, PT_ALL = 31 };
+
+static DevPoints points_stage(uint8_t *h, const uint8_t *d, size_t *o, const orbx_proj_points *p, unsigned want)
+{
+    const size_t np = (size_t)p->n;
+    auto put = [&](bool wanted, const void *src, size_t bytes, int absent) -> const uint8_t * {
+        if (!wanted) return nullptr;
+        const size_t at = *o;
+        *o += a16(bytes);
+        if (src) memcpy(h + at, src, bytes); else memset(h + at, absent, bytes);
+        return d + at;
+    };
+    DevPoints P;
+    P.n = p->n;
+    P.u = (const float *)put(true, p->u, 4 * np, 0); P.v = (const float *)put(true, p->v, 4 * np, 0);
+    P.aux = (const float *)put(want & PT_AUX, p->aux, 4 * np, 0);
+    P.level = (const int32_t *)put(true, p->level, 4 * np, 0);
+    P.angle = (const float *)put(want & PT_ANGLE, p->angle, 4 * np, 0);
+    P.view_cos = (const float *)put(want & PT_VIEW_COS, p->view_cos, 4 * np, 0);
+    P.desc = (const uint32_t *)put(want & PT_DESC, p->desc, 32 * np, 0);
+    P.valid = put(true, p->valid, np, 0);
+    P.has_obs = put(want & PT_HAS_OBS, p->has_obs, np, 1);
+    return P;
 }
 
 // ---- part 2: occupied + points staged behind `head` bytes, one upload of the whole blob, the grid build when the frame is not resident
@@ -722,26 +745,13 @@ static int proj_search(ProjCtx *c, DevFrame F, size_t head, const int *grid_off,
     const size_t blob = head + proj_tail_bytes(nc, np);
     int rc = proj_blob_reserve(c, blob);
     if (rc) return rc;
-    size_t o = head;
-    auto take = [&](size_t bytes) { const size_t r = o; o += a16(bytes); return r; };
-    const size_t fq = take(nc);
-    const size_t pu = take(4 * np), pv = take(4 * np), pa = take(4 * np), pl = take(4 * np), pg = take(4 * np), pc = take(4 * np),
-                 pd = take(32 * np), pval = take(np), pobs = take(np);
     uint8_t *h = c->h_blob;
-    if (occupied) memcpy(h + fq, occupied, nc); else memset(h + fq, 0, nc);
-    memcpy(h + pu, pts->u, 4 * np); memcpy(h + pv, pts->v, 4 * np); memcpy(h + pl, pts->level, 4 * np);
-    if (pts->aux) memcpy(h + pa, pts->aux, 4 * np); else memset(h + pa, 0, 4 * np);
-    if (pts->angle) memcpy(h + pg, pts->angle, 4 * np); else memset(h + pg, 0, 4 * np);
-    if (pts->view_cos) memcpy(h + pc, pts->view_cos, 4 * np); else memset(h + pc, 0, 4 * np);
-    memcpy(h + pd, pts->desc, 32 * np); memcpy(h + pval, pts->valid, np);
-    if (pts->has_obs) memcpy(h + pobs, pts->has_obs, np); else memset(h + pobs, 1, np);
-    ORBX_HIP(hipMemcpyAsync(c->d_blob, h, blob, hipMemcpyHostToDevice, c->stream));
     const uint8_t *d = c->d_blob;
-    F.occupied = d + fq;
-    DevPoints P;
-    P.n = pts->n; P.u = (const float *)(d + pu); P.v = (const float *)(d + pv); P.aux = (const float *)(d + pa);
-    P.level = (const int32_t *)(d + pl); P.angle = (const float *)(d + pg); P.view_cos = (const float *)(d + pc);
-    P.desc = (const uint32_t *)(d + pd); P.valid = d + pval; P.has_obs = d + pobs;
+    size_t o = head + a16(nc);
+    if (occupied) memcpy(h + head, occupied, nc); else memset(h + head, 0, nc);
+    F.occupied = d + head;
+    const DevPoints P = points_stage(h, d, &o, pts, PT_ALL);
+    ORBX_HIP(hipMemcpyAsync(c->d_blob, h, blob, hipMemcpyHostToDevice, c->stream));
     ProjParams pp = pp_in;
     for (int i = 0; i < ORBX_MAX_LEVELS; i++) {
         pp.sf[i] = i < nlevels ? sf[i] : 0.f;
@@ -802,6 +812,21 @@ static int proj_search(ProjCtx *c, DevFrame F, size_t head, const int *grid_off,
     return ORBX_OK;
 }
 
+// the refusals of a point set against a parameter block, for every search: its size (worded as `who`'s invalid argument), the arrays the
+// block makes the kernels read, the level of every valid point.  job >= 0: the set belongs to that job of a batch.
+static int points_check(const orbx_proj_points *p, const ProjParams &pp, int nlevels, const char *who, int job)
+{
+    char pre[32] = "", pre_pt[32] = "";
+    auto name_job = [&] { if (job >= 0) { snprintf(pre, sizeof pre, "job %d: ", job); snprintf(pre_pt, sizeof pre_pt, "job %d, ", job); } };   // on a refusal only
+    if (!p || p->n < 0 || p->n > (1 << 20)) { name_job(); orbx_set_error("%s: %sinvalid argument", who, pre); return ORBX_E_INVALID; }
+    const bool need_aux = pp.need_pos_aux || pp.ur_mode || pp.chi2;
+    if (p->n && (!p->u || !p->v || !p->level || !p->desc || !p->valid || (need_aux && !p->aux) || (pp.claims == 1 && !p->has_obs) ||
+                 (pp.check_ori && !p->angle) || (pp.radius_mode == 1 && !p->view_cos))) { name_job(); orbx_set_error("%spoint arrays missing", pre); return ORBX_E_INVALID; }
+    for (int i = 0; i < p->n; i++)
+        if (p->valid[i] && (p->level[i] < 0 || p->level[i] >= nlevels)) { name_job(); orbx_set_error("%spoint %d: level %d out of range", pre_pt, i, p->level[i]); return ORBX_E_INVALID; }
+    return ORBX_OK;
+}
+
 static int proj_run(int device, const orbx_frame_feats *cur, const orbx_proj_points *pts, const float *sf, int nlevels,
                     const ProjParams &pp_in, int32_t *match_cur, int *nmatches, const float *inv_sigma2 = nullptr,
                     int32_t *pt_choice = nullptr, int32_t *pt_dist = nullptr)
@@ -810,33 +835,27 @@ static int proj_run(int device, const orbx_frame_feats *cur, const orbx_proj_poi
     std::vector<int32_t> mc_dummy;
     if (!nmatches) nmatches = &nm_dummy;
     if (!match_cur && cur && cur->n >= 0) { mc_dummy.resize((size_t)cur->n + 1); match_cur = mc_dummy.data(); }
-    if (!cur || !pts || !sf || !match_cur || !nmatches || nlevels < 1 || nlevels > ORBX_MAX_LEVELS || cur->n < 0 || pts->n < 0 ||
-        cur->n >= 65536 || pts->n > (1 << 20)) {
+    if (!cur || !pts || !sf || !match_cur || !nmatches || nlevels < 1 || nlevels > ORBX_MAX_LEVELS || cur->n < 0 || cur->n >= 65536) {
         orbx_set_error("search_by_projection: invalid argument");
         return ORBX_E_INVALID;
     }
-    const bool need_aux = pp_in.need_pos_aux || pp_in.ur_mode || pp_in.chi2;
     if (cur->n && (!cur->x || !cur->y || !cur->octave || !cur->u_right || !cur->desc || (pp_in.check_ori && !cur->angle) ||
                    (pp_in.claims && !cur->occupied))) { orbx_set_error("frame arrays missing"); return ORBX_E_INVALID; }
-    if (pts->n && (!pts->u || !pts->v || !pts->level || !pts->desc || !pts->valid || (need_aux && !pts->aux) ||
-                   (pp_in.claims == 1 && !pts->has_obs) || (pp_in.check_ori && !pts->angle) ||
-                   (pp_in.radius_mode == 1 && !pts->view_cos))) { orbx_set_error("point arrays missing"); return ORBX_E_INVALID; }
+    int rc = points_check(pts, pp_in, nlevels, "search_by_projection", -1);
+    if (rc) return rc;
     if (pp_in.chi2 && !inv_sigma2) { orbx_set_error("inv_sigma2 missing"); return ORBX_E_INVALID; }
     if (!(cur->max_x > cur->min_x) || !(cur->max_y > cur->min_y)) { orbx_set_error("empty image bounds"); return ORBX_E_INVALID; }
-    for (int i = 0; i < pts->n; i++)
-        if (pts->valid[i] && (pts->level[i] < 0 || pts->level[i] >= nlevels)) { orbx_set_error("point %d: level %d out of range", i, pts->level[i]); return ORBX_E_INVALID; }
     for (int i = 0; i < cur->n; i++) match_cur[i] = -1;
     *nmatches = 0;
     for (int i = 0; i < pts->n; i++) { if (pt_choice) pt_choice[i] = -1; if (pt_dist) pt_dist[i] = 256; }
     if (cur->n == 0 || pts->n == 0) return ORBX_OK;
     ProjCtx *c;
-    int rc = orbx_ctx_get(g_proj, device, &c);
+    rc = orbx_ctx_get(g_proj, device, &c);
     if (rc) return rc;
-    const size_t head = proj_head_bytes((size_t)cur->n);
+    const size_t head = frame_layout((size_t)cur->n).o_coff;
     rc = proj_blob_reserve(c, head + proj_tail_bytes((size_t)cur->n, (size_t)pts->n));
     if (rc) return rc;
-    DevFrame F;
-    proj_stage_frame(c, cur, &F);                                                  // part 1
+    const DevFrame F = proj_stage_frame(c, cur);                                   // part 1
     return proj_search(c, F, head, nullptr, nullptr, cur->occupied, pts, sf, nlevels, pp_in, match_cur, nmatches, inv_sigma2,
                        pt_choice, pt_dist);                                        // part 2
 }
@@ -868,6 +887,35 @@ static ProjParams params_keyframe(float th, int orb_dist, int check_orientation)
     return pp;
 }
 
+static ProjParams params_sim3(float th)   // SearchByProjection(KeyFrame, Scw, ...), :305-415
+{
+    ProjParams pp;
+    memset(&pp, 0, sizeof pp);
+    pp.bounds = 2; pp.lo_off = -1; pp.hi_off = 0; pp.max_dist = 50; pp.claims = 2;
+    pp.th = th;
+    return pp;
+}
+static ProjParams params_window(float th, int chi2, int max_dist)   // Fuse x2 and each direction of SearchBySim3: independent points
+{
+    ProjParams pp;
+    memset(&pp, 0, sizeof pp);
+    pp.bounds = 2; pp.lo_off = -1; pp.hi_off = 0; pp.max_dist = max_dist; pp.chi2 = chi2 ? 1 : 0; pp.claims = 0;
+    pp.th = th;
+    return pp;
+}
+
+// the agreement check of SearchBySim3 (:1375-1391) on the two directions' best candidates
+static int sim3_agree(const int32_t *m1, const int32_t *m2, int n1, int32_t *match12)
+{
+    int found = 0;
+    for (int i1 = 0; i1 < n1; i1++) {
+        const int idx2 = m1[i1];
+        match12[i1] = -1;
+        if (idx2 >= 0 && m2[idx2] == i1) { match12[i1] = idx2; found++; }
+    }
+    return found;
+}
+
 extern "C" int orbx_search_by_projection_last_frame(int device, const orbx_frame_feats *cur, const orbx_proj_points *pts,
                                                     const float *scale_factors, int nlevels, float th, int direction, float mbf,
                                                     int check_orientation, int32_t *match_cur, int *nmatches)
@@ -893,11 +941,7 @@ extern "C" int orbx_search_by_projection_keyframe(int device, const orbx_frame_f
 extern "C" int orbx_search_by_projection_sim3(int device, const orbx_frame_feats *kf, const orbx_proj_points *pts,
                                               const float *scale_factors, int nlevels, float th, int32_t *match_kf, int *nmatches)
 {
-    ProjParams pp;
-    memset(&pp, 0, sizeof pp);
-    pp.bounds = 2; pp.lo_off = -1; pp.hi_off = 0; pp.max_dist = 50; pp.claims = 2;
-    pp.th = th;
-    return proj_run(device, kf, pts, scale_factors, nlevels, pp, match_kf, nmatches);
+    return proj_run(device, kf, pts, scale_factors, nlevels, params_sim3(th), match_kf, nmatches);
 }
 
 extern "C" int orbx_window_best(int device, const orbx_frame_feats *kf, const orbx_proj_points *pts, const float *scale_factors,
@@ -905,11 +949,7 @@ extern "C" int orbx_window_best(int device, const orbx_frame_feats *kf, const or
                                 int32_t *best_dist, int *nfound)
 {
     if (!best_idx || max_dist < 0 || max_dist > 256) { orbx_set_error("orbx_window_best: invalid argument"); return ORBX_E_INVALID; }
-    ProjParams pp;
-    memset(&pp, 0, sizeof pp);
-    pp.bounds = 2; pp.lo_off = -1; pp.hi_off = 0; pp.max_dist = max_dist; pp.chi2 = chi2 ? 1 : 0; pp.claims = 0;
-    pp.th = th;
-    return proj_run(device, kf, pts, scale_factors, nlevels, pp, nullptr, nfound, inv_sigma2, best_idx, best_dist);
+    return proj_run(device, kf, pts, scale_factors, nlevels, params_window(th, chi2, max_dist), nullptr, nfound, inv_sigma2, best_idx, best_dist);
 }
 
 extern "C" int orbx_search_for_initialization(int device, const orbx_frame_feats *f1, const orbx_frame_feats *f2,
@@ -955,13 +995,7 @@ extern "C" int orbx_search_by_sim3(int device, const orbx_frame_feats *kf1, cons
     if (rc) return rc;
     rc = orbx_window_best(device, kf1, pts21, scale_factors1, nullptr, nlevels, th, 0, 100, m2.data(), nullptr, &n2);     // :1295-1372
     if (rc) return rc;
-    int found = 0;
-    for (int i1 = 0; i1 < pts12->n; i1++) { // the agreement check, :1375-1391
-        const int idx2 = m1[i1];
-        match12[i1] = -1;
-        if (idx2 >= 0 && m2[idx2] == i1) { match12[i1] = idx2; found++; }
-    }
-    *nfound = found;
+    *nfound = sim3_agree(m1.data(), m2.data(), pts12->n, match12);
     return ORBX_OK;
 }
 
@@ -1006,42 +1040,21 @@ static void frame_block_put(int device, FrameBlock b)
     hipFree(b.d);
 }
 
-struct orbx_frame {
+struct orbx_frame : FrameLayout {   // the block's layout: frame_layout(n)
     int device, n, has_angle;
-    float min_x, min_y, max_x, max_y;
+    float bounds[4];   // min_x, min_y, max_x, max_y
     FrameBlock blk;
-    size_t o_x, o_y, o_oct, o_ang, o_ur, o_desc, o_coff, o_cidx;
     bool pending;   // the creation may still be running: the first search waits for blk.ev on its own stream
 };
 
-static size_t frame_layout(orbx_frame *f)
-{
-    const size_t nc = (size_t)f->n;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t r = o; o += a16(bytes); return r; };
-    f->o_x = take(4 * nc); f->o_y = take(4 * nc); f->o_oct = take(4 * nc); f->o_ang = take(4 * nc); f->o_ur = take(4 * nc);
-    f->o_desc = take(32 * nc); f->o_coff = take(4 * (PG_CELLS + 1)); f->o_cidx = take(4 * nc);
-    return o;
-}
-
-static DevFrame frame_dev(const orbx_frame *f)
-{
-    const uint8_t *d = f->blk.d;
-    DevFrame F;
-    F.n = f->n; F.x = (const float *)(d + f->o_x); F.y = (const float *)(d + f->o_y); F.octave = (const int32_t *)(d + f->o_oct);
-    F.angle = (const float *)(d + f->o_ang); F.u_right = (const float *)(d + f->o_ur); F.desc = (const uint32_t *)(d + f->o_desc);
-    F.occupied = nullptr;
-    F.min_x = f->min_x; F.min_y = f->min_y; F.max_x = f->max_x; F.max_y = f->max_y;
-    F.inv_w = (float)PG_COLS / (f->max_x - f->min_x);  // src/Frame.cc:164-165, as part 1 of the host-pointer calls
-    F.inv_h = (float)PG_ROWS / (f->max_y - f->min_y);
-    return F;
-}
+static DevFrame frame_dev(const orbx_frame *f) { return dev_frame(f->blk.d, *f, f->n, f->bounds); }
 
 static orbx_frame *frame_new(int device, int n, int has_angle, float min_x, float min_y, float max_x, float max_y)
 {
     orbx_frame *f = new orbx_frame();
+    static_cast<FrameLayout &>(*f) = frame_layout((size_t)n);
     f->device = device; f->n = n; f->has_angle = has_angle;
-    f->min_x = min_x; f->min_y = min_y; f->max_x = max_x; f->max_y = max_y;
+    f->bounds[0] = min_x; f->bounds[1] = min_y; f->bounds[2] = max_x; f->bounds[3] = max_y;
     f->pending = false;
     return f;
 }
@@ -1056,16 +1069,14 @@ extern "C" int orbx_frame_create(int device, const orbx_frame_feats *cur, orbx_f
     int rc = orbx_ctx_get(g_proj, device, &c);
     if (rc) return rc;
     orbx_frame *f = frame_new(device, cur->n, cur->n == 0 || cur->angle ? 1 : 0, cur->min_x, cur->min_y, cur->max_x, cur->max_y);
-    const size_t bytes = frame_layout(f);
-    rc = frame_block_get(device, bytes, &f->blk);
+    rc = frame_block_get(device, f->bytes, &f->blk);
     if (rc) { delete f; return rc; }
-    // the frame arrays of the block are laid out as the head of a host-pointer call's staging blob: part 1 stages them, one upload
+    // the frame arrays of the block are the head of a host-pointer call's staging blob (one frame_layout): part 1 stages them, one upload
     rc = proj_blob_reserve(c, f->o_coff);
     if (!rc) {
         const DevFrame F = frame_dev(f);
         if (cur->n) {
-            DevFrame Fs;
-            proj_stage_frame(c, cur, &Fs);
+            proj_stage_frame(c, cur);
             if (hipMemcpyAsync(f->blk.d, c->h_blob, f->o_coff, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = ORBX_E_HIP;
         }
         if (!rc) hipLaunchKernelGGL(k_grid_build, dim3(1), dim3(256), 0, c->stream, F, (int *)(f->blk.d + f->o_coff), (int *)(f->blk.d + f->o_cidx));
@@ -1105,8 +1116,7 @@ extern "C" int orbx_frame_create_from_extraction(int device, const void *d_kps, 
         return ORBX_E_INVALID;
     }
     orbx_frame *f = frame_new(device, n, 1, min_x, min_y, max_x, max_y);
-    const size_t bytes = frame_layout(f);
-    rc = frame_block_get(device, bytes, &f->blk);
+    rc = frame_block_get(device, f->bytes, &f->blk);
     if (rc) { delete f; return rc; }
     FrameIngest in;
     memset(&in, 0, sizeof in);
@@ -1169,22 +1179,18 @@ static int proj_run_resident(const orbx_frame *f, const uint8_t *occupied, const
                              const ProjParams &pp, int32_t *match_cur, int *nmatches, bool *synced)
 {
     *synced = false;
-    if (!f || !pts || !sf || !match_cur || !nmatches || nlevels < 1 || nlevels > ORBX_MAX_LEVELS || pts->n < 0 || pts->n > (1 << 20)) {
+    if (!f || !pts || !sf || !match_cur || !nmatches || nlevels < 1 || nlevels > ORBX_MAX_LEVELS) {
         orbx_set_error("orbx_frame_search_by_projection: invalid argument");
         return ORBX_E_INVALID;
     }
-    const bool need_aux = pp.need_pos_aux || pp.ur_mode || pp.chi2;
     if (pp.check_ori && !f->has_angle) { orbx_set_error("orbx_frame_search_by_projection: the frame was created without angles"); return ORBX_E_INVALID; }
-    if (pts->n && (!pts->u || !pts->v || !pts->level || !pts->desc || !pts->valid || (need_aux && !pts->aux) ||
-                   (pp.claims == 1 && !pts->has_obs) || (pp.check_ori && !pts->angle) ||
-                   (pp.radius_mode == 1 && !pts->view_cos))) { orbx_set_error("point arrays missing"); return ORBX_E_INVALID; }
-    for (int i = 0; i < pts->n; i++)
-        if (pts->valid[i] && (pts->level[i] < 0 || pts->level[i] >= nlevels)) { orbx_set_error("point %d: level %d out of range", i, pts->level[i]); return ORBX_E_INVALID; }
+    int rc = points_check(pts, pp, nlevels, "orbx_frame_search_by_projection", -1);
+    if (rc) return rc;
     for (int i = 0; i < f->n; i++) match_cur[i] = -1;
     *nmatches = 0;
     if (f->n == 0 || pts->n == 0) return ORBX_OK;
     ProjCtx *c;
-    int rc = orbx_ctx_get(g_proj, f->device, &c);
+    rc = orbx_ctx_get(g_proj, f->device, &c);
     if (rc) return rc;
     if (f->pending) ORBX_HIP(hipStreamWaitEvent(c->stream, f->blk.ev, 0));   // the creation, ordered by its event (no device synchronisation)
     const uint8_t *d = f->blk.d;
@@ -1233,27 +1239,21 @@ extern "C" int orbx_frame_search_by_projection_keyframe(orbx_frame *cur, const u
 extern "C" int orbx_frame_search_by_projection_sim3(const orbx_frame *kf, const uint8_t *occupied, const orbx_proj_points *pts,
                                                     const float *scale_factors, int nlevels, float th, int32_t *match_kf, int *nmatches)
 {
-    ProjParams pp;
-    memset(&pp, 0, sizeof pp);
-    pp.bounds = 2; pp.lo_off = -1; pp.hi_off = 0; pp.max_dist = 50; pp.claims = 2;   // as orbx_search_by_projection_sim3
-    pp.th = th;
     bool synced;
-    return proj_run_resident(kf, occupied, pts, scale_factors, nlevels, pp, match_kf, nmatches, &synced);
+    return proj_run_resident(kf, occupied, pts, scale_factors, nlevels, params_sim3(th), match_kf, nmatches, &synced);
 }
 
 // the refusals of one job, before any device call and without reading the handle
 static int window_job_check(const orbx_window_job &jb, int j)
 {
-    if (!jb.kf || !jb.pts || !jb.scale_factors || !jb.best_idx || jb.nlevels < 1 || jb.nlevels > ORBX_MAX_LEVELS || jb.pts->n < 0 ||
-        jb.pts->n > (1 << 20) || jb.max_dist < 0 || jb.max_dist > 256) {
+    if (!jb.kf || !jb.pts || !jb.scale_factors || !jb.best_idx || jb.nlevels < 1 || jb.nlevels > ORBX_MAX_LEVELS || jb.max_dist < 0 ||
+        jb.max_dist > 256) {
         orbx_set_error("orbx_frame_window_best: job %d: invalid argument", j);
         return ORBX_E_INVALID;
     }
-    const orbx_proj_points *p = jb.pts;
-    if (p->n && (!p->u || !p->v || !p->level || !p->desc || !p->valid || (jb.chi2 && !p->aux))) { orbx_set_error("job %d: point arrays missing", j); return ORBX_E_INVALID; }
+    const int rc = points_check(jb.pts, params_window(jb.th, jb.chi2, jb.max_dist), jb.nlevels, "orbx_frame_window_best", j);
+    if (rc) return rc;
     if (jb.chi2 && !jb.inv_sigma2) { orbx_set_error("job %d: inv_sigma2 missing", j); return ORBX_E_INVALID; }
-    for (int i = 0; i < p->n; i++)
-        if (p->valid[i] && (p->level[i] < 0 || p->level[i] >= jb.nlevels)) { orbx_set_error("job %d, point %d: level %d out of range", j, i, p->level[i]); return ORBX_E_INVALID; }
     return ORBX_OK;
 }
 
@@ -1270,7 +1270,7 @@ extern "C" int orbx_frame_window_best_batch(orbx_window_job *jobs, int njobs)
     const int device = jobs[0].kf->device;
     for (int j = 1; j < njobs; j++)
         if (jobs[j].kf->device != device) { orbx_set_error("orbx_frame_window_best_batch: the keyframes live on different devices"); return ORBX_E_INVALID; }
-    // jobs with work, their workgroups and output offsets; the points' staging: u v level valid [aux] per job, descriptors once per
+    // jobs with work, their workgroups and output offsets; the points' staging: u v [aux] level valid per job (points_stage), descriptors once per
     // distinct host array (the jobs of one FuseBatch share the map points' descriptors)
     std::vector<int> wg_first((size_t)njobs + 1, 0);
     std::vector<size_t> o_desc((size_t)njobs, 0);
@@ -1318,18 +1318,14 @@ extern "C" int orbx_frame_window_best_batch(orbx_window_job *jobs, int njobs)
         const orbx_frame *f = jb.kf;
         const orbx_proj_points *p = jb.pts;
         const size_t np = (size_t)p->n;
-        auto take = [&](size_t bytes) { const size_t r = o; o += a16(bytes); return r; };
-        const size_t pu = take(4 * np), pv = take(4 * np), pl = take(4 * np), pval = take(np), pa = jb.chi2 ? take(4 * np) : 0;
-        memcpy(h + pu, p->u, 4 * np); memcpy(h + pv, p->v, 4 * np); memcpy(h + pl, p->level, 4 * np); memcpy(h + pval, p->valid, np);
-        if (jb.chi2) memcpy(h + pa, p->aux, 4 * np);
+        W.P = points_stage(h, d, &o, p, jb.chi2 ? PT_AUX : 0);
         bool first = true;
         for (int q = 0; q < j; q++) if (o_desc[q] == o_desc[j]) first = false;
         if (first) memcpy(h + o_desc[j], p->desc, 32 * np);
         W.F = frame_dev(f);
         W.cell_off = (const int *)(f->blk.d + f->o_coff); W.cell_idx = (const int *)(f->blk.d + f->o_cidx);
-        W.P.n = p->n; W.P.u = (const float *)(d + pu); W.P.v = (const float *)(d + pv); W.P.level = (const int32_t *)(d + pl);
-        W.P.valid = d + pval; W.P.aux = jb.chi2 ? (const float *)(d + pa) : nullptr; W.P.desc = (const uint32_t *)(d + o_desc[j]);
-        W.pp.bounds = 2; W.pp.lo_off = -1; W.pp.hi_off = 0; W.pp.max_dist = jb.max_dist; W.pp.chi2 = jb.chi2 ? 1 : 0; W.pp.th = jb.th;
+        W.P.desc = (const uint32_t *)(d + o_desc[j]);
+        W.pp = params_window(jb.th, jb.chi2, jb.max_dist);
         for (int i = 0; i < ORBX_MAX_LEVELS; i++) {
             W.pp.sf[i] = i < jb.nlevels ? jb.scale_factors[i] : 0.f;
             W.pp.inv_sigma2[i] = (jb.chi2 && i < jb.nlevels) ? jb.inv_sigma2[i] : 0.f;
@@ -1391,12 +1387,6 @@ extern "C" int orbx_frame_search_by_sim3(const orbx_frame *kf1, const orbx_frame
     for (int j = 0; j < 2; j++) { jb[j].nlevels = nlevels; jb[j].th = th; jb[j].max_dist = 100; }
     const int rc = orbx_frame_window_best_batch(jb, 2);
     if (rc) return rc;
-    int found = 0;
-    for (int i1 = 0; i1 < pts12->n; i1++) { // the agreement check, :1375-1391
-        const int idx2 = m1[i1];
-        match12[i1] = -1;
-        if (idx2 >= 0 && m2[idx2] == i1) { match12[i1] = idx2; found++; }
-    }
-    *nfound = found;
+    *nfound = sim3_agree(m1.data(), m2.data(), pts12->n, match12);
     return ORBX_OK;
 }
