@@ -668,6 +668,72 @@ int orbx_frame_search_by_sim3(const orbx_frame *kf1, const orbx_frame *kf2, cons
                               const orbx_proj_points *pts21, const float *scale_factors1, const float *scale_factors2,
                               int nlevels, float th, int32_t *match12, int *nfound);
 
+/* ---- resident map points: Frame::isInFrustum and Tracking::SearchLocalPoints from a pose -----------------------------
+ * Tracking::SearchLocalPoints (src/Tracking.cc:1403-1466) runs on every tracked frame: Frame::isInFrustum (src/Frame.cc:310-380) on
+ * each of the 2 000 - 8 000 local map points, then ORBmatcher::SearchByProjection(F, vpLocalMapPoints, th).  A map point's
+ * position, normal, distance range and descriptor change rarely, and then one point at a time; the pose changes every frame and
+ * is 15 floats.  orbx_mappoints keeps the points in HBM, a slot per point, and the searches below move a pose, one int32 slot
+ * and one flag byte per local point, `occupied`, and the results.
+ * The table has a fixed capacity and ONE device allocation made at creation; nothing grows: 64 bytes per slot, plus the staging of
+ * one upload (68 bytes for each of min(capacity, 65536) records, and a pinned host buffer of that size).  THREADS: _set serialises against
+ * every other call on the table; _frustum, _read and orbx_frame_search_local_points only read it and may run from several
+ * threads at once.  A _set on one stream and a search on another are ordered through an event the table keeps (no device
+ * synchronisation), and a slot is never rewritten under a search in flight. */
+typedef struct orbx_mappoints orbx_mappoints;
+/* ORBX_E_INVALID: out == NULL, capacity outside [1, 2^24] */
+int orbx_mappoints_create(int device, int capacity, orbx_mappoints **out);
+void orbx_mappoints_destroy(orbx_mappoints *m);
+int orbx_mappoints_capacity(const orbx_mappoints *m);                          /* a negative code on error */
+/* Writes n slots: geom[n][8] = X Y Z mfMinDistance nx ny nz mfMaxDistance (mWorldPos, mNormalVector and the RAW distances, not
+ * GetMinDistanceInvariance's 0.8 / GetMaxDistanceInvariance's 1.2 products), desc[n][32] = mDescriptor.  Either array may be
+ * NULL to leave that half of every named slot as it is (UpdateNormalAndDepth and bundle adjustment change only geom,
+ * ComputeDistinctiveDescriptors only desc), provided each named slot has been given that half before.  A slot is "set" once it
+ * has been given both halves; the host keeps that bitmap.  One upload -- packed by n: 4 + 32 bytes per record for one half, 4 + 64 for both, whatever the
+ * capacity -- and one scatter kernel per 65536 records (a frame's changes are one of each), enqueued on `stream` (NULL: the
+ * calling thread's own stream); the call does not wait for them -- later calls on the table are ordered behind them.
+ * Refusals come before any device work and leave the table unchanged.  ORBX_E_CAPACITY: a slot >= capacity.  ORBX_E_INVALID: a
+ * negative slot, a slot named twice in one call, both arrays NULL, a half left out that the slot never had. */
+int orbx_mappoints_set(orbx_mappoints *m, const int32_t *slots, int n, const float *geom, const uint8_t *desc, void *stream);
+/* tests and debugging: geom[n][8] / desc[n][32] of the named slots (NULL arguments are skipped; a half never given reads 0) */
+int orbx_mappoints_read(const orbx_mappoints *m, const int32_t *slots, int n, float *geom, uint8_t *desc);
+/* Frame::isInFrustum for points slots[0..n) of the table.  pose = Rcw[9] (row major) tcw[3] Ow[3]; cam = fx fy cx cy mbf mnMinX
+ * mnMinY mnMaxX mnMaxY; log_scale_factor = mfLogScaleFactor, nlevels = mnScaleLevels.  eligible[i] == 0 (the caller's isBad() /
+ * mnLastFrameSeen tests, src/Tracking.cc:1437-1440) gives in_view[i] = 0 without touching the table: its slot may be anything.
+ * An eligible point whose slot is out of range or not set is refused, ORBX_E_INVALID, before any launch.  Outputs (in_view is
+ * required, the others may be NULL): in_view = mbTrackInView, u / v / xr = mTrackProjX / Y / XR, level = mnTrackScaleLevel,
+ * view_cos = mTrackViewCos; a point not in view reads 0 in all of them.
+ * The arithmetic is fixed, in this order, in float unless a step says double, every operation rounded on its own (no fused
+ * multiply-add), division and square root correctly rounded:
+ *   1. Pc_k = ((R[k][0]*X + R[k][1]*Y) + R[k][2]*Z) + t[k]; out if Pc_z < 0
+ *   2. invz = 1.0f / Pc_z; u = (fx*Pc_x)*invz + cx; v = (fy*Pc_y)*invz + cy; out if u < mnMinX, u > mnMaxX, v < mnMinY or
+ *      v > mnMaxY (the bounds are inclusive), and out if u or v is not finite (a defined deviation: the reference would carry
+ *      a NaN into GetFeaturesInArea, whose float-to-int conversion is undefined)
+ *   3. PO = P - Ow per component; dist = (float)sqrt(((double)POx*POx + (double)POy*POy) + (double)POz*POz) (cv::norm
+ *      accumulates CV_32F in double); out if dist < 0.8f*dmin or dist > 1.2f*dmax
+ *   4. view_cos = (float)((((double)POx*nx + (double)POy*ny) + (double)POz*nz) / (double)dist) (Mat::dot in double); out if it
+ *      is not finite or < view_cos_limit
+ *   5. ratio = dmax / dist; level = clamp(ceilf(logf(ratio) / log_scale_factor), 0, nlevels - 1) with the C library's logf:
+ *      the device evaluates no logarithm.  At call time the host finds, for k = 0 .. nlevels - 2, the smallest positive float
+ *      r_k with ceilf(logf(r_k) / log_scale_factor) > k (bisection over float bit patterns, cached per (log_scale_factor,
+ *      nlevels)), and the device counts the r_k <= ratio.  (A NaN ratio, from a NaN dmax, counts 0.)
+ *   6. xr = u - mbf*invz
+ * Against OpenCV's own cv::Mat arithmetic this restatement is unpinned. */
+int orbx_mappoints_frustum(const orbx_mappoints *m, const int32_t *slots, const uint8_t *eligible, int n, const float *pose,
+                           const float *cam, float view_cos_limit, float log_scale_factor, int nlevels, uint8_t *in_view,
+                           float *u, float *v, float *xr, int32_t *level, float *view_cos);
+/* The second loop of Tracking::SearchLocalPoints and its matcher call (src/Tracking.cc:1433-1463) in one call on a resident
+ * frame: orbx_mappoints_frustum, then orbx_frame_search_by_projection_map_points on its outputs -- bit for bit that pair of
+ * calls, without the points crossing PCIe.  flags[i] bit 0 = eligible, bit 1 = Observations() > 0 (orbx_proj_points::has_obs).
+ * One upload (slots, flags, occupied), three launches (the frustum kernel, which writes the dense point set with each in-view
+ * point's descriptor copied out of the table, then the list and resolve kernels of the map-point search), one group of
+ * downloads behind one synchronisation: match_cur[cur n] (an index into slots[] / flags[], -1 none), *nmatches, in_view[n]
+ * (for IncreaseVisible() and nToMatch).  n == 0 or a frame without features: ORBX_OK, no launch, match_cur = -1, in_view = 0.
+ * Refusals as orbx_mappoints_frustum and the map-point search; also a frame and a table on different devices. */
+int orbx_frame_search_local_points(orbx_frame *cur, const uint8_t *occupied, const orbx_mappoints *m, const int32_t *slots,
+                                   const uint8_t *flags, int n, const float *pose, const float *cam, float view_cos_limit,
+                                   float log_scale_factor, const float *scale_factors, int nlevels, float th, float nnratio,
+                                   int32_t *match_cur, int *nmatches, uint8_t *in_view);
+
 /* ORBmatcher::SearchByProjection(Frame &CurrentFrame, const Frame &LastFrame, th, bMono) (src/ORBmatcher.cc:1396-1553;
  * Tracking::TrackWithMotionModel).  direction: 0 none, 1 bForward, 2 bBackward (:1412-1413).  match_cur[cur->n] =
  * index of the point each current feature finally holds (-1 none); *nmatches = the reference's return value

@@ -15,11 +15,13 @@
 //            a point's window and candidate test: point_window, cand_ok; the window walk both per-point kernels share: window_walk
 //            k_proj_lists (candidate lists), k_proj_resolve (claim fixpoint + rotation filter), k_init_resolve (SearchForInitialization)
 //            k_window_best (independent points against resident keyframes, many jobs per launch)
+//            the resident map-point table: k_mappoints_scatter (orbx_mappoints_set), k_frustum (Frame::isInFrustum from a pose)
 //   host     ProjCtx (per-thread staging); frame_layout, dev_frame (one layout of a frame's arrays); proj_stage_frame, points_stage;
 //            proj_search (upload, grid, lists, resolve, download); points_check, proj_run; the parameter blocks params_*; sim3_agree
 //            the host-pointer entry points of the seven searches
 //            the frame pool and the orbx_frame handle (create, create_from_extraction, read, destroy)
 //            the searches on a resident current frame; the searches on resident keyframes (orbx_frame_window_best_batch and its users)
+//            the resident map points (orbx_mappoints: create, set, read, frustum) and orbx_frame_search_local_points
 //
 // The reference walks the map points sequentially and lets every accepted match claim its feature
 // (later points skip features whose holder has Observations() > 0), so the result depends on the order.
@@ -31,7 +33,10 @@
 // per link of the longest conflict chain).  Projections (u, v, 1/z) come from the adaptor, which has the
 // poses: restating cv::gemm's accumulation is not needed.
 #include "orbx_device.h"
+#include <algorithm>
+#include <math.h>
 #include <mutex>
+#include <shared_mutex>
 #include <string.h>
 #include <vector>
 
@@ -627,6 +632,77 @@ __global__ __launch_bounds__(256) void k_window_best(const WinJob *__restrict__ 
     if (lane == 0) { best_idx[J.out_off + i] = out_k; best_dist[J.out_off + i] = out_d; }
 }
 
+// ---- resident map points (include/orbx.h: orbx_mappoints).  The table is geom[capacity] (32 B: X Y Z dmin | nx ny nz dmax) and
+// desc[capacity] (32 B); a slot is a map point.  orbx_mappoints_set uploads the changed records densely and this kernel scatters them: four
+// threads per point, one 16-byte move each (q = 0, 1: the geometry halves, 2, 3: the descriptor halves; a half not given is NULL).
+__global__ __launch_bounds__(256) void k_mappoints_scatter(const int32_t *__restrict__ slots, const uint4 *__restrict__ geom_in,
+                                                           const uint4 *__restrict__ desc_in, int n, uint4 *__restrict__ geom,
+                                                           uint4 *__restrict__ desc)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x, i = t >> 2, q = t & 3;
+    if (i >= n) return;
+    const long long s = slots[i];   // in [0, capacity): checked on the host
+    if (q < 2) { if (geom_in) geom[2 * s + q] = geom_in[2 * (long long)i + q]; }
+    else if (desc_in) desc[2 * s + (q - 2)] = desc_in[2 * (long long)i + (q - 2)];
+}
+
+// ---- Frame::isInFrustum (src/Frame.cc:310-380) from a pose, one thread per point; the arithmetic is the contract stated in include/orbx.h
+// (float unless a step says double, no contraction, correctly rounded division and square root).  The scale level is NOT a logarithm here:
+// thr[k] is the smallest float r with ceilf(logf(r) / mfLogScaleFactor) > k, found on the host with the C library's logf, and the level is
+// the number of thresholds at or below dmax / dist -- no device logf equals the host's bit for bit.
+struct FrustumArgs {
+    float R[9], t[3], Ow[3];
+    float fx, fy, cx, cy, mbf, min_x, min_y, max_x, max_y;
+    float view_cos_limit;
+    int nlevels;
+    float thr[ORBX_MAX_LEVELS - 1];   // [nlevels - 1] used
+};
+// what k_frustum writes: the arrays of a dense DevPoints (aux = xr, valid = in_view).  has_obs / desc are NULL for orbx_mappoints_frustum.
+struct FrustumOut {
+    float *u, *v, *xr, *view_cos;
+    int32_t *level;
+    uint8_t *in_view, *has_obs;
+    uint4 *desc;
+};
+
+__global__ __launch_bounds__(256) void k_frustum(const float4 *__restrict__ geom, const uint4 *__restrict__ tdesc,
+                                                 const int32_t *__restrict__ slots, const uint8_t *__restrict__ flags, int n, FrustumArgs A,
+                                                 FrustumOut o)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const unsigned fl = flags[i];   // bit 0: eligible, bit 1: Observations() > 0
+    float u = 0.f, v = 0.f, xr = 0.f, vc = 0.f;
+    int level = 0;
+    bool in = false;
+    long long s = 0;
+    if (fl & 1) do {
+        s = slots[i];               // in [0, capacity) and set: checked on the host
+        const float4 g0 = geom[2 * s], g1 = geom[2 * s + 1];
+        const float X = g0.x, Y = g0.y, Z = g0.z, dmin = g0.w, nx = g1.x, ny = g1.y, nz = g1.z, dmax = g1.w;
+        const float pcx = ((A.R[0] * X + A.R[1] * Y) + A.R[2] * Z) + A.t[0];
+        const float pcy = ((A.R[3] * X + A.R[4] * Y) + A.R[5] * Z) + A.t[1];
+        const float pcz = ((A.R[6] * X + A.R[7] * Y) + A.R[8] * Z) + A.t[2];
+        if (pcz < 0.0f) break;
+        const float invz = 1.0f / pcz;
+        const float pu = (A.fx * pcx) * invz + A.cx, pv = (A.fy * pcy) * invz + A.cy;
+        if (pu < A.min_x || pu > A.max_x || pv < A.min_y || pv > A.max_y) break;
+        if (!isfinite(pu) || !isfinite(pv)) break;                                        // (a NaN passes every comparison above)
+        const float pox = X - A.Ow[0], poy = Y - A.Ow[1], poz = Z - A.Ow[2];
+        const float dist = (float)__dsqrt_rn(((double)pox * pox + (double)poy * poy) + (double)poz * poz);   // cv::norm: double accumulation
+        if (dist < 0.8f * dmin || dist > 1.2f * dmax) break;
+        const float c = (float)((((double)pox * nx + (double)poy * ny) + (double)poz * nz) / (double)dist);   // Mat::dot in double
+        if (!isfinite(c) || c < A.view_cos_limit) break;
+        const float ratio = dmax / dist;                                                  // MapPoint::PredictScale
+        int l = 0;
+        for (int k = 0; k < A.nlevels - 1; k++) l += A.thr[k] <= ratio ? 1 : 0;
+        u = pu; v = pv; xr = pu - A.mbf * invz; vc = c; level = l; in = true;
+    } while (0);
+    o.u[i] = u; o.v[i] = v; o.xr[i] = xr; o.view_cos[i] = vc; o.level[i] = level; o.in_view[i] = in ? 1 : 0;
+    if (o.has_obs) o.has_obs[i] = (fl >> 1) & 1;
+    if (o.desc && in) { o.desc[2 * (long long)i] = tdesc[2 * s]; o.desc[2 * (long long)i + 1] = tdesc[2 * s + 1]; }
+}
+
 // ---------------------------------------------------------------- host side
 
 struct ProjCtx : ThreadCtx {
@@ -735,14 +811,46 @@ static DevPoints points_stage(uint8_t *h, const uint8_t *d, size_t *o, const orb
     return P;
 }
 
+// ---- the resident map-point table (include/orbx.h: orbx_mappoints).  ONE device allocation made at creation: geom[capacity][8] |
+// desc[capacity][32] | the staging of one upload of orbx_mappoints_set, MP_STAGE_RECORDS records at most (a larger set goes in several
+// uploads); nothing grows.  An upload is packed by its own record count, slots[k] | geom[k][8] | desc[k][32] with a half not given left
+// out, so what crosses PCIe is 4 + 32 or 4 + 64 bytes per record sent, whatever the capacity.
+// Host state: which halves every slot has been given, and the event of the most recent _set.  A _set holds `mu` exclusively while it
+// enqueues, a search holds it shared until its stream has drained: a slot is never rewritten under a search in flight, and a search on
+// another stream than the _set's waits for the event, not for the device.
+#define MP_STAGE_RECORDS 65536
+struct orbx_mappoints {
+    int device, capacity;
+    uint8_t *d_blob;
+    float4 *d_geom; uint4 *d_desc;
+    uint8_t *d_stage, *h_stage;          // h_stage: pinned, as large as d_stage
+    int stage_records; size_t st_bytes;  // records one upload holds; bytes of the staging
+    std::vector<uint8_t> have;           // bit 0: geom given, bit 1: desc given; 3 = set
+    std::vector<uint32_t> stamp; uint32_t gen;   // duplicate slots of one _set
+    mutable hipEvent_t ev; mutable hipStream_t ev_stream; mutable bool ev_set;
+    mutable std::shared_timed_mutex mu;
+};
+
+// the points of orbx_frame_search_local_points: slots of a resident table, in view or not by k_frustum -- nothing but the slot and a flag
+// byte per point is staged, the dense DevPoints is written on the device (into the work area)
+struct LocalPts {
+    const orbx_mappoints *m;
+    const int32_t *slots;
+    const uint8_t *flags;
+    int n;
+    FrustumArgs A;
+    uint8_t *in_view;   // [n] out
+};
+
 // ---- part 2: occupied + points staged behind `head` bytes, one upload of the whole blob, the grid build when the frame is not resident
-// (grid == NULL), lists, resolve, download.  F.occupied is set here (it points into the blob).
+// (grid == NULL), lists, resolve, download.  F.occupied is set here (it points into the blob).  lp != NULL: the points are lp's (pts is
+// NULL) and k_frustum runs in front of the lists.
 static int proj_search(ProjCtx *c, DevFrame F, size_t head, const int *grid_off, const int *grid_idx, const uint8_t *occupied,
                        const orbx_proj_points *pts, const float *sf, int nlevels, const ProjParams &pp_in, int32_t *match_cur,
-                       int *nmatches, const float *inv_sigma2, int32_t *pt_choice, int32_t *pt_dist)
+                       int *nmatches, const float *inv_sigma2, int32_t *pt_choice, int32_t *pt_dist, const LocalPts *lp = nullptr)
 {
-    const size_t nc = (size_t)F.n, np = (size_t)pts->n;
-    const size_t blob = head + proj_tail_bytes(nc, np);
+    const size_t nc = (size_t)F.n, np = (size_t)(lp ? lp->n : pts->n);
+    const size_t blob = head + (lp ? a16(nc) + a16(4 * np) + a16(np) : proj_tail_bytes(nc, np));
     int rc = proj_blob_reserve(c, blob);
     if (rc) return rc;
     uint8_t *h = c->h_blob;
@@ -750,7 +858,16 @@ static int proj_search(ProjCtx *c, DevFrame F, size_t head, const int *grid_off,
     size_t o = head + a16(nc);
     if (occupied) memcpy(h + head, occupied, nc); else memset(h + head, 0, nc);
     F.occupied = d + head;
-    const DevPoints P = points_stage(h, d, &o, pts, PT_ALL);
+    DevPoints P;
+    size_t o_slots = 0, o_flags = 0;
+    if (lp) {
+        o_slots = o; o += a16(4 * np); o_flags = o; o += a16(np);
+        memcpy(h + o_slots, lp->slots, 4 * np); memcpy(h + o_flags, lp->flags, np);
+        memset(&P, 0, sizeof P);
+        P.n = lp->n;            // its arrays: in the work area, below
+    } else {
+        P = points_stage(h, d, &o, pts, PT_ALL);
+    }
     ORBX_HIP(hipMemcpyAsync(c->d_blob, h, blob, hipMemcpyHostToDevice, c->stream));
     ProjParams pp = pp_in;
     for (int i = 0; i < ORBX_MAX_LEVELS; i++) {
@@ -758,13 +875,21 @@ static int proj_search(ProjCtx *c, DevFrame F, size_t head, const int *grid_off,
         pp.inv_sigma2[i] = (inv_sigma2 && i < nlevels) ? inv_sigma2[i] : 0.f;
     }
     // work: cell_off[3073] | cell_idx[nc] | beg[np] | cnt[np] | pool_used | choice_a[np] | choice_b[np] | match[nc] | out_n |
-    //       pt_choice[np] | pt_dist[np]
+    //       pt_choice[np] | pt_dist[np] | (lp: valid[np] u v aux level view_cos has_obs desc of the DevPoints k_frustum writes)
     size_t w = 0;
     auto wtake = [&](size_t bytes) { const size_t r = w; w += a16(bytes); return r; };
     const size_t w_coff = wtake(4 * (PG_CELLS + 1)), w_cidx = wtake(4 * nc), w_beg = wtake(4 * np), w_cnt = wtake(4 * np), w_used = wtake(16),
                  w_ca = wtake(4 * np), w_cb = wtake(4 * np), w_match = wtake(4 * nc), w_n = wtake(16), w_pc = wtake(4 * np),
                  w_pd = wtake(4 * np);
-    const size_t out = sizeof(int32_t) * (nc + 2 * np + 8);
+    FrustumOut fo;
+    memset(&fo, 0, sizeof fo);
+    size_t w_valid = 0, w_lp[7] = { 0 };
+    if (lp) {
+        w_valid = wtake(np);
+        for (int q = 0; q < 5; q++) w_lp[q] = wtake(4 * np);
+        w_lp[5] = wtake(np); w_lp[6] = wtake(32 * np);
+    }
+    const size_t out = sizeof(int32_t) * (nc + 2 * np + 8) + (lp ? a16(np) : 0);
     if (w > c->work_cap && (rc = ensure(&c->d_work, &c->work_cap, 2 * w))) return rc;
     if (out > c->out_cap && (rc = ensure_pinned(&c->h_out, &c->out_cap, 2 * out))) return rc;
     const size_t resolve_lds = pp.init_search ? (2 * sizeof(uint16_t) + sizeof(float)) * ((nc + 7) & ~(size_t)7) + 16 : sizeof(int) * (nc + 4);   // init: md, m21, the frame's angles
@@ -775,6 +900,14 @@ static int proj_search(ProjCtx *c, DevFrame F, size_t head, const int *grid_off,
         ORBX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_proj_resolve), hipFuncAttributeMaxDynamicSharedMemorySize, (int)resolve_lds));
     uint8_t *wk = c->d_work;
     int *d_beg = (int *)(wk + w_beg), *d_cnt = (int *)(wk + w_cnt), *d_used = (int *)(wk + w_used);
+    if (lp) {
+        fo.in_view = wk + w_valid; fo.u = (float *)(wk + w_lp[0]); fo.v = (float *)(wk + w_lp[1]); fo.xr = (float *)(wk + w_lp[2]);
+        fo.level = (int32_t *)(wk + w_lp[3]); fo.view_cos = (float *)(wk + w_lp[4]); fo.has_obs = wk + w_lp[5]; fo.desc = (uint4 *)(wk + w_lp[6]);
+        P.u = fo.u; P.v = fo.v; P.aux = fo.xr; P.level = fo.level; P.view_cos = fo.view_cos; P.valid = fo.in_view; P.has_obs = fo.has_obs;
+        P.desc = (const uint32_t *)fo.desc;
+        hipLaunchKernelGGL(k_frustum, dim3((lp->n + 255) / 256), dim3(256), 0, c->stream, lp->m->d_geom, lp->m->d_desc,
+                           (const int32_t *)(d + o_slots), d + o_flags, lp->n, lp->A, fo);
+    }
     const int *d_coff = grid_off, *d_cidx = grid_idx;
     if (!grid_off) {   // a host-pointer frame: Frame::AssignFeaturesToGrid, once per call
         d_coff = (int *)(wk + w_coff); d_cidx = (int *)(wk + w_cidx);
@@ -784,7 +917,7 @@ static int proj_search(ProjCtx *c, DevFrame F, size_t head, const int *grid_off,
     if (!c->d_entries && (rc = ensure(&c->d_entries, &c->ent_cap, sizeof(uint32_t) << 20))) return rc;
     for (int attempt = 0; attempt < 2; attempt++) {
         ORBX_HIP(hipMemsetAsync(d_used, 0, 16, c->stream));
-        hipLaunchKernelGGL(k_proj_lists, dim3((pts->n + 3) / 4), dim3(256), 0, c->stream, F, P, pp, d_coff, d_cidx, d_beg, d_cnt,
+        hipLaunchKernelGGL(k_proj_lists, dim3((P.n + 3) / 4), dim3(256), 0, c->stream, F, P, pp, d_coff, d_cidx, d_beg, d_cnt,
                            c->d_entries, (int)(c->ent_cap / sizeof(uint32_t)), d_used);
         if (pp.init_search)
             hipLaunchKernelGGL(k_init_resolve, dim3(1), dim3(64), resolve_lds, c->stream, F, P, pp, d_beg, d_cnt, c->d_entries,
@@ -799,6 +932,7 @@ static int proj_search(ProjCtx *c, DevFrame F, size_t head, const int *grid_off,
         ORBX_HIP(hipMemcpyAsync(c->h_out + nc + 1, d_used, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         if (pt_choice) ORBX_HIP(hipMemcpyAsync(c->h_out + nc + 8, wk + w_pc, 4 * np, hipMemcpyDeviceToHost, c->stream));
         if (pt_dist) ORBX_HIP(hipMemcpyAsync(c->h_out + nc + 8 + np, wk + w_pd, 4 * np, hipMemcpyDeviceToHost, c->stream));
+        if (lp && attempt == 0) ORBX_HIP(hipMemcpyAsync(c->h_out + nc + 8 + 2 * np, wk + w_valid, np, hipMemcpyDeviceToHost, c->stream));
         ORBX_HIP(hipStreamSynchronize(c->stream));
         const size_t used = (size_t)(unsigned)c->h_out[nc + 1];
         if (used <= c->ent_cap / sizeof(uint32_t)) break;
@@ -809,6 +943,7 @@ static int proj_search(ProjCtx *c, DevFrame F, size_t head, const int *grid_off,
     *nmatches = c->h_out[nc];
     if (pt_choice) memcpy(pt_choice, c->h_out + nc + 8, 4 * np);
     if (pt_dist) memcpy(pt_dist, c->h_out + nc + 8 + np, 4 * np);
+    if (lp) memcpy(lp->in_view, c->h_out + nc + 8 + 2 * np, np);
     return ORBX_OK;
 }
 
@@ -1389,4 +1524,251 @@ extern "C" int orbx_frame_search_by_sim3(const orbx_frame *kf1, const orbx_frame
     if (rc) return rc;
     *nfound = sim3_agree(m1.data(), m2.data(), pts12->n, match12);
     return ORBX_OK;
+}
+
+// ---------------------------------------------------------------- resident map points (include/orbx.h: orbx_mappoints)
+
+extern "C" int orbx_mappoints_create(int device, int capacity, orbx_mappoints **out)
+{
+    if (!out || capacity < 1 || capacity > (1 << 24)) { orbx_set_error("orbx_mappoints_create: invalid argument (1 <= capacity <= 2^24)"); return ORBX_E_INVALID; }
+    *out = nullptr;
+    ProjCtx *c;
+    int rc = orbx_ctx_get(g_proj, device, &c);
+    if (rc) return rc;
+    const size_t cap = (size_t)capacity;
+    orbx_mappoints *m = new orbx_mappoints();
+    m->device = device; m->capacity = capacity;
+    m->stage_records = capacity < MP_STAGE_RECORDS ? capacity : MP_STAGE_RECORDS;
+    m->st_bytes = a16(4 * (size_t)m->stage_records) + 64 * (size_t)m->stage_records;
+    const size_t table = 64 * cap, total = table + m->st_bytes;
+    m->d_blob = nullptr; m->h_stage = nullptr; m->ev = nullptr; m->ev_stream = nullptr; m->ev_set = false; m->gen = 0;
+    const hipError_t e1 = hipMalloc((void **)&m->d_blob, total);
+    const hipError_t e2 = e1 == hipSuccess ? hipHostMalloc((void **)&m->h_stage, m->st_bytes, hipHostMallocDefault) : e1;
+    const hipError_t e3 = e2 == hipSuccess ? hipEventCreateWithFlags(&m->ev, hipEventDisableTiming) : e2;
+    const hipError_t e4 = e3 == hipSuccess ? hipMemset(m->d_blob, 0, table) : e3;   // a half never given reads 0
+    if (e4 != hipSuccess) {
+        orbx_set_error("orbx_mappoints_create: HIP allocation of %zu bytes failed: %s", total, hipGetErrorString(e4));
+        if (m->ev) hipEventDestroy(m->ev);
+        if (m->h_stage) hipHostFree(m->h_stage);
+        if (m->d_blob) hipFree(m->d_blob);
+        delete m;
+        return ORBX_E_HIP;
+    }
+    m->d_geom = (float4 *)m->d_blob; m->d_desc = (uint4 *)(m->d_blob + 32 * cap); m->d_stage = m->d_blob + table;
+    m->have.assign(cap, 0); m->stamp.assign(cap, 0);
+    *out = m;
+    return ORBX_OK;
+}
+
+extern "C" void orbx_mappoints_destroy(orbx_mappoints *m)
+{
+    if (!m) return;
+    if (orbx_use_device(m->device) == hipSuccess) {
+        if (m->ev_set) hipEventSynchronize(m->ev);
+        hipEventDestroy(m->ev);
+        hipHostFree(m->h_stage);
+        hipFree(m->d_blob);
+    }
+    delete m;
+}
+
+extern "C" int orbx_mappoints_capacity(const orbx_mappoints *m) { return m ? m->capacity : ORBX_E_INVALID; }
+
+extern "C" int orbx_mappoints_set(orbx_mappoints *m, const int32_t *slots, int n, const float *geom, const uint8_t *desc, void *stream)
+{
+    if (!m || n < 0 || (n && (!slots || (!geom && !desc)))) { orbx_set_error("orbx_mappoints_set: invalid argument (a table, n slots, geom and / or desc)"); return ORBX_E_INVALID; }
+    if (n == 0) return ORBX_OK;
+    std::unique_lock<std::shared_timed_mutex> lk(m->mu);
+    // refusals first: the table and its bitmap stay as they were
+    if (++m->gen == 0) { std::fill(m->stamp.begin(), m->stamp.end(), 0u); m->gen = 1; }
+    const unsigned give = (geom ? 1u : 0u) | (desc ? 2u : 0u);
+    for (int i = 0; i < n; i++) {
+        const int s = slots[i];
+        if (s < 0) { orbx_set_error("orbx_mappoints_set: entry %d: negative slot %d", i, s); return ORBX_E_INVALID; }
+        if (s >= m->capacity) { orbx_set_error("orbx_mappoints_set: entry %d: slot %d, capacity %d", i, s, m->capacity); return ORBX_E_CAPACITY; }
+        if (m->stamp[s] == m->gen) { orbx_set_error("orbx_mappoints_set: slot %d named twice", s); return ORBX_E_INVALID; }
+        m->stamp[s] = m->gen;
+        if ((m->have[s] | give) != 3) { orbx_set_error("orbx_mappoints_set: slot %d has never been given its %s", s, geom ? "descriptor" : "geometry"); return ORBX_E_INVALID; }
+    }
+    ProjCtx *c;
+    int rc = orbx_ctx_get(g_proj, m->device, &c);
+    if (rc) return rc;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    // one upload and one scatter launch per MP_STAGE_RECORDS records (a frame's changes are one), each packed by its own count
+    for (int first = 0; first < n; first += m->stage_records) {
+        const int k = n - first < m->stage_records ? n - first : m->stage_records;
+        const size_t kk = (size_t)k, o_geom = a16(4 * kk), o_desc = o_geom + (geom ? 32 * kk : 0), bytes = o_desc + (desc ? 32 * kk : 0);
+        if (m->ev_set) ORBX_HIP(hipEventSynchronize(m->ev));   // the previous upload has read the staging
+        memcpy(m->h_stage, slots + first, 4 * kk);
+        if (geom) memcpy(m->h_stage + o_geom, geom + 8 * (size_t)first, 32 * kk);
+        if (desc) memcpy(m->h_stage + o_desc, desc + 32 * (size_t)first, 32 * kk);
+        ORBX_HIP(hipMemcpyAsync(m->d_stage, m->h_stage, bytes, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_mappoints_scatter, dim3((4 * k + 255) / 256), dim3(256), 0, st, (const int32_t *)m->d_stage,
+                           geom ? (const uint4 *)(m->d_stage + o_geom) : nullptr, desc ? (const uint4 *)(m->d_stage + o_desc) : nullptr, k,
+                           (uint4 *)m->d_geom, m->d_desc);
+        ORBX_HIP(hipGetLastError());
+        ORBX_HIP(hipEventRecord(m->ev, st));
+        m->ev_stream = st; m->ev_set = true;
+        for (int i = first; i < first + k; i++) m->have[slots[i]] |= (uint8_t)give;   // what has been enqueued is in the table for every later call
+    }
+    return ORBX_OK;
+}
+
+extern "C" int orbx_mappoints_read(const orbx_mappoints *m, const int32_t *slots, int n, float *geom, uint8_t *desc)
+{
+    if (!m || n < 0 || (n && !slots)) { orbx_set_error("orbx_mappoints_read: invalid argument"); return ORBX_E_INVALID; }
+    for (int i = 0; i < n; i++)
+        if (slots[i] < 0 || slots[i] >= m->capacity) { orbx_set_error("orbx_mappoints_read: entry %d: slot %d outside [0, %d)", i, slots[i], m->capacity); return ORBX_E_INVALID; }
+    if (n == 0) return ORBX_OK;
+    std::shared_lock<std::shared_timed_mutex> lk(m->mu);
+    ORBX_HIP(orbx_use_device(m->device));
+    if (m->ev_set) ORBX_HIP(hipEventSynchronize(m->ev));
+    // one copy per run of consecutive ascending slots and half: proportional to n, not to the capacity
+    for (int i = 0; i < n;) {
+        int j = i + 1;
+        while (j < n && slots[j] == slots[j - 1] + 1) j++;
+        const size_t run = 32 * (size_t)(j - i), src = 32 * (size_t)slots[i], dst = 32 * (size_t)i;
+        if (geom) ORBX_HIP(hipMemcpy((uint8_t *)geom + dst, (const uint8_t *)m->d_geom + src, run, hipMemcpyDeviceToHost));
+        if (desc) ORBX_HIP(hipMemcpy(desc + dst, (const uint8_t *)m->d_desc + src, run, hipMemcpyDeviceToHost));
+        i = j;
+    }
+    return ORBX_OK;
+}
+
+// the smallest positive float r with ceilf(logf(r) / lsf) > k: bisection over float bit patterns (the predicate is monotone in r; it is
+// false at 0, where logf is -inf, and true at +inf)
+static float level_threshold(float lsf, int k)
+{
+    uint32_t lo = 0, hi = 0x7F800000u;
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        float r;
+        memcpy(&r, &mid, 4);
+        if (ceilf(logf(r) / lsf) > (float)k) hi = mid; else lo = mid;
+    }
+    float r;
+    memcpy(&r, &hi, 4);
+    return r;
+}
+
+struct LevelThr { float lsf; int nlevels; float thr[ORBX_MAX_LEVELS - 1]; };
+static std::mutex g_thr_mu;
+static std::vector<LevelThr> g_thr;   // one entry per (log_scale_factor, nlevels) seen: a SLAM system has one or two
+
+static void level_thresholds(float lsf, int nlevels, float *thr)
+{
+    std::lock_guard<std::mutex> lk(g_thr_mu);
+    for (const LevelThr &t : g_thr)
+        if (memcmp(&t.lsf, &lsf, 4) == 0 && t.nlevels == nlevels) { memcpy(thr, t.thr, sizeof t.thr); return; }
+    LevelThr t;
+    memset(&t, 0, sizeof t);
+    t.lsf = lsf; t.nlevels = nlevels;
+    for (int k = 0; k < nlevels - 1; k++) t.thr[k] = level_threshold(lsf, k);
+    if (g_thr.size() >= 64) g_thr.clear();
+    g_thr.push_back(t);
+    memcpy(thr, t.thr, sizeof t.thr);
+}
+
+// the refusals of a frustum call, before any launch, and its kernel arguments.  bit0: which bit pattern of flags[i] makes point i eligible
+// (orbx_mappoints_frustum: any non-zero byte; the fused search: bit 0)
+static int frustum_args(const char *who, const orbx_mappoints *m, const int32_t *slots, const uint8_t *flags, int n, bool any_bit,
+                        const float *pose, const float *cam, float view_cos_limit, float lsf, int nlevels, FrustumArgs *A)
+{
+    if (!m || n < 0 || n > (1 << 20) || (n && (!slots || !flags)) || !pose || !cam || nlevels < 1 || nlevels > ORBX_MAX_LEVELS ||
+        !(lsf > 0.f) || !isfinite(lsf)) {
+        orbx_set_error("%s: invalid argument (a table, n <= 2^20 slots and flags, pose, cam, 1 <= nlevels <= %d, log_scale_factor > 0)", who, ORBX_MAX_LEVELS);
+        return ORBX_E_INVALID;
+    }
+    for (int i = 0; i < n; i++) {
+        if (!(any_bit ? flags[i] != 0 : (flags[i] & 1) != 0)) continue;   // not eligible: the slot is never looked at
+        const int s = slots[i];
+        if (s < 0 || s >= m->capacity) { orbx_set_error("%s: point %d: slot %d outside [0, %d)", who, i, s, m->capacity); return ORBX_E_INVALID; }
+        if (m->have[s] != 3) { orbx_set_error("%s: point %d: slot %d is not set", who, i, s); return ORBX_E_INVALID; }
+    }
+    memset(A, 0, sizeof *A);
+    memcpy(A->R, pose, 9 * sizeof(float)); memcpy(A->t, pose + 9, 3 * sizeof(float)); memcpy(A->Ow, pose + 12, 3 * sizeof(float));
+    A->fx = cam[0]; A->fy = cam[1]; A->cx = cam[2]; A->cy = cam[3]; A->mbf = cam[4];
+    A->min_x = cam[5]; A->min_y = cam[6]; A->max_x = cam[7]; A->max_y = cam[8];
+    A->view_cos_limit = view_cos_limit; A->nlevels = nlevels;
+    level_thresholds(lsf, nlevels, A->thr);
+    return ORBX_OK;
+}
+
+// a search's stream behind the table's most recent _set (the caller holds m->mu shared)
+static int mappoints_order_before(const orbx_mappoints *m, hipStream_t s)
+{
+    if (m->ev_set && m->ev_stream != s) ORBX_HIP(hipStreamWaitEvent(s, m->ev, 0));
+    return ORBX_OK;
+}
+
+extern "C" int orbx_mappoints_frustum(const orbx_mappoints *m, const int32_t *slots, const uint8_t *eligible, int n, const float *pose,
+                                      const float *cam, float view_cos_limit, float log_scale_factor, int nlevels, uint8_t *in_view,
+                                      float *u, float *v, float *xr, int32_t *level, float *view_cos)
+{
+    if (n > 0 && !in_view) { orbx_set_error("orbx_mappoints_frustum: in_view missing"); return ORBX_E_INVALID; }
+    if (!m) { orbx_set_error("orbx_mappoints_frustum: null table"); return ORBX_E_INVALID; }
+    std::shared_lock<std::shared_timed_mutex> lk(m->mu);
+    FrustumArgs A;
+    int rc = frustum_args("orbx_mappoints_frustum", m, slots, eligible, n, true, pose, cam, view_cos_limit, log_scale_factor, nlevels, &A);
+    if (rc) return rc;
+    if (n == 0) return ORBX_OK;
+    ProjCtx *c;
+    if ((rc = orbx_ctx_get(g_proj, m->device, &c))) return rc;
+    const size_t np = (size_t)n, col = a16(4 * np);
+    const size_t blob = col + a16(np), out = 5 * col + a16(np);   // up: slots | flags   down: u v xr view_cos level | in_view
+    if ((rc = proj_blob_reserve(c, blob))) return rc;
+    if (out > c->work_cap && (rc = ensure(&c->d_work, &c->work_cap, 2 * out))) return rc;
+    if (out > c->out_cap && (rc = ensure_pinned(&c->h_out, &c->out_cap, 2 * out))) return rc;
+    memcpy(c->h_blob, slots, 4 * np);
+    for (size_t i = 0; i < np; i++) c->h_blob[col + i] = eligible[i] ? 1 : 0;
+    if ((rc = mappoints_order_before(m, c->stream))) return rc;
+    ORBX_HIP(hipMemcpyAsync(c->d_blob, c->h_blob, blob, hipMemcpyHostToDevice, c->stream));
+    uint8_t *wk = c->d_work;
+    FrustumOut fo;
+    memset(&fo, 0, sizeof fo);
+    fo.u = (float *)wk; fo.v = (float *)(wk + col); fo.xr = (float *)(wk + 2 * col); fo.view_cos = (float *)(wk + 3 * col);
+    fo.level = (int32_t *)(wk + 4 * col); fo.in_view = wk + 5 * col;
+    hipLaunchKernelGGL(k_frustum, dim3((n + 255) / 256), dim3(256), 0, c->stream, m->d_geom, m->d_desc, (const int32_t *)c->d_blob,
+                       c->d_blob + col, n, A, fo);
+    ORBX_HIP(hipGetLastError());
+    ORBX_HIP(hipMemcpyAsync(c->h_out, wk, out, hipMemcpyDeviceToHost, c->stream));
+    ORBX_HIP(hipStreamSynchronize(c->stream));
+    const uint8_t *ho = (const uint8_t *)c->h_out;
+    if (u) memcpy(u, ho, 4 * np);
+    if (v) memcpy(v, ho + col, 4 * np);
+    if (xr) memcpy(xr, ho + 2 * col, 4 * np);
+    if (view_cos) memcpy(view_cos, ho + 3 * col, 4 * np);
+    if (level) memcpy(level, ho + 4 * col, 4 * np);
+    memcpy(in_view, ho + 5 * col, np);
+    return ORBX_OK;
+}
+
+extern "C" int orbx_frame_search_local_points(orbx_frame *cur, const uint8_t *occupied, const orbx_mappoints *m, const int32_t *slots,
+                                              const uint8_t *flags, int n, const float *pose, const float *cam, float view_cos_limit,
+                                              float log_scale_factor, const float *scale_factors, int nlevels, float th, float nnratio,
+                                              int32_t *match_cur, int *nmatches, uint8_t *in_view)
+{
+    if (!cur || !m || !scale_factors || !match_cur || !nmatches || (n > 0 && !in_view)) {
+        orbx_set_error("orbx_frame_search_local_points: invalid argument");
+        return ORBX_E_INVALID;
+    }
+    if (cur->device != m->device) { orbx_set_error("orbx_frame_search_local_points: the frame and the table live on different devices"); return ORBX_E_INVALID; }
+    std::shared_lock<std::shared_timed_mutex> lk(m->mu);
+    LocalPts lp;
+    int rc = frustum_args("orbx_frame_search_local_points", m, slots, flags, n, false, pose, cam, view_cos_limit, log_scale_factor, nlevels, &lp.A);
+    if (rc) return rc;
+    for (int i = 0; i < cur->n; i++) match_cur[i] = -1;
+    *nmatches = 0;
+    if (n) memset(in_view, 0, (size_t)n);
+    if (cur->n == 0 || n == 0) return ORBX_OK;
+    lp.m = m; lp.slots = slots; lp.flags = flags; lp.n = n; lp.in_view = in_view;
+    ProjCtx *c;
+    if ((rc = orbx_ctx_get(g_proj, cur->device, &c))) return rc;
+    if (cur->pending) ORBX_HIP(hipStreamWaitEvent(c->stream, cur->blk.ev, 0));
+    if ((rc = mappoints_order_before(m, c->stream))) return rc;
+    const uint8_t *d = cur->blk.d;
+    rc = proj_search(c, frame_dev(cur), 0, (const int *)(d + cur->o_coff), (const int *)(d + cur->o_cidx), occupied, nullptr, scale_factors,
+                     nlevels, params_map_points(th, nnratio), match_cur, nmatches, nullptr, nullptr, nullptr, &lp);
+    if (!rc) cur->pending = false;
+    return rc;
 }

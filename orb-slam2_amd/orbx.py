@@ -208,6 +208,13 @@ def lib():
     L.orbx_frame_window_best_batch.argtypes = [C.POINTER(WindowJob), i]
     L.orbx_frame_search_by_projection_sim3.argtypes = [vp, vp, C.POINTER(ProjPoints), vp, i, f, vp, ip]
     L.orbx_frame_search_by_sim3.argtypes = [vp, vp, C.POINTER(ProjPoints), C.POINTER(ProjPoints), vp, vp, i, f, vp, ip]
+    L.orbx_mappoints_create.argtypes = [i, i, C.POINTER(vp)]
+    L.orbx_mappoints_destroy.argtypes = [vp]; L.orbx_mappoints_destroy.restype = None
+    L.orbx_mappoints_capacity.argtypes = [vp]
+    L.orbx_mappoints_set.argtypes = [vp, vp, i, vp, vp, vp]
+    L.orbx_mappoints_read.argtypes = [vp, vp, i, vp, vp]
+    L.orbx_mappoints_frustum.argtypes = [vp, vp, vp, i, vp, vp, f, f, i, vp, vp, vp, vp, vp, vp]
+    L.orbx_frame_search_local_points.argtypes = [vp, vp, vp, vp, vp, i, vp, vp, f, f, vp, i, f, f, vp, ip, vp]
     L.orbx_bow_frames_create.argtypes = [i, i, i, C.POINTER(vp)]
     L.orbx_bow_frames_destroy.argtypes = [vp]; L.orbx_bow_frames_destroy.restype = None
     L.orbx_bow_transform_batch_device.argtypes = [vp, vp, vp, vp, vp, i, i, vp]
@@ -791,6 +798,23 @@ class DeviceFrame:
         _check(lib().orbx_frame_read(self._h, _p(x), _p(y), _p(o), _p(a), _p(u), _p(d)))
         return dict(x=x, y=y, octave=o, angle=a, u_right=u, desc=d)
 
+    def search_local_points(self, occupied, points, slots, flags, pose, cam, view_cos_limit, log_scale_factor, scaleFactors, th=1.0,
+                            nnratio=0.8):
+        """Tracking::SearchLocalPoints' second loop and matcher call on slots of a MapPoints table: flags bit 0 = eligible, bit 1 =
+        Observations() > 0 -> (match_cur, nmatches, in_view)"""
+        oc = _occupied_for(occupied, self, "DeviceFrame.search_local_points")
+        sl = MapPoints._slots(slots)
+        fl = np.ascontiguousarray(flags, np.uint8)
+        if fl.shape != sl.shape:
+            raise OrbxError(-1, f"DeviceFrame.search_local_points: {len(sl)} slots, {fl.size} flag bytes")
+        po, ca = _pose_cam(pose, cam, "DeviceFrame.search_local_points")
+        sf = np.ascontiguousarray(scaleFactors, np.float32)
+        out = np.full(self.n, -1, np.int32); n = C.c_int(); iv = np.zeros(len(sl), np.uint8)
+        _check(lib().orbx_frame_search_local_points(self._h, None if oc is None else _p(oc), points._h, _p(sl), _p(fl), len(sl), _p(po), _p(ca),
+                                                    float(view_cos_limit), float(log_scale_factor), _p(sf), len(sf), float(th), float(nnratio),
+                                                    _p(out), C.byref(n), _p(iv)))
+        return out, n.value, iv
+
     def __del__(self):
         try:
             h, L = getattr(self, "_h", None), _lib
@@ -799,6 +823,72 @@ class DeviceFrame:
             self._h = None
         except Exception:
             pass
+
+
+class MapPoints:
+    """orbx_mappoints: the map points' position, normal, distance range and descriptor resident in HBM, a slot per point, in a table of
+    fixed capacity.  frustum() is Frame::isInFrustum from a pose; DeviceFrame.search_local_points fuses it with the map-point search."""
+
+    def __init__(self, capacity, device=0):
+        h = C.c_void_p()
+        _check(lib().orbx_mappoints_create(device, int(capacity), C.byref(h)))
+        self._h, self.device = h, device
+        self.capacity = lib().orbx_mappoints_capacity(h)
+
+    def __del__(self):
+        try:
+            h, L = getattr(self, "_h", None), _lib
+            if h and L is not None:
+                L.orbx_mappoints_destroy(h)
+            self._h = None
+        except Exception:
+            pass
+
+    @staticmethod
+    def _slots(slots):
+        sl = np.ascontiguousarray(slots, np.int32)
+        if sl.ndim != 1:
+            raise OrbxError(-1, "MapPoints: slots must be one-dimensional")
+        return sl
+
+    def set(self, slots, geom=None, desc=None, stream=None):
+        """geom[n][8] = X Y Z mfMinDistance nx ny nz mfMaxDistance, desc[n][32]; either may be None to leave that half as it is"""
+        sl = self._slots(slots)
+        g = None if geom is None else np.ascontiguousarray(geom, np.float32)
+        d = None if desc is None else np.ascontiguousarray(desc, np.uint8)
+        if (g is not None and g.shape != (len(sl), 8)) or (d is not None and d.shape != (len(sl), 32)):
+            raise OrbxError(-1, f"MapPoints.set: {len(sl)} slots need geom [{len(sl)}][8] and desc [{len(sl)}][32]")
+        _check(lib().orbx_mappoints_set(self._h, _p(sl), len(sl), None if g is None else _p(g), None if d is None else _p(d), stream))
+
+    def read(self, slots):
+        """-> (geom[n][8], desc[n][32]) of the named slots"""
+        sl = self._slots(slots)
+        g = np.zeros((len(sl), 8), np.float32); d = np.zeros((len(sl), 32), np.uint8)
+        _check(lib().orbx_mappoints_read(self._h, _p(sl), len(sl), _p(g), _p(d)))
+        return g, d
+
+    def frustum(self, slots, eligible, pose, cam, view_cos_limit, log_scale_factor, nlevels):
+        """Frame::isInFrustum of the named slots; pose = Rcw[9] tcw[3] Ow[3], cam = fx fy cx cy mbf mnMinX mnMinY mnMaxX mnMaxY
+        -> dict(in_view, u, v, xr, level, view_cos)"""
+        sl = self._slots(slots)
+        el = np.ascontiguousarray(eligible, np.uint8)
+        if el.shape != sl.shape:
+            raise OrbxError(-1, f"MapPoints.frustum: {len(sl)} slots, {el.size} eligible bytes")
+        po, ca = _pose_cam(pose, cam, "MapPoints.frustum")
+        n = len(sl)
+        o = dict(in_view=np.zeros(n, np.uint8), u=np.zeros(n, np.float32), v=np.zeros(n, np.float32), xr=np.zeros(n, np.float32),
+                 level=np.zeros(n, np.int32), view_cos=np.zeros(n, np.float32))
+        _check(lib().orbx_mappoints_frustum(self._h, _p(sl), _p(el), n, _p(po), _p(ca), float(view_cos_limit), float(log_scale_factor),
+                                            int(nlevels), _p(o["in_view"]), _p(o["u"]), _p(o["v"]), _p(o["xr"]), _p(o["level"]),
+                                            _p(o["view_cos"])))
+        return o
+
+
+def _pose_cam(pose, cam, who):
+    po = np.ascontiguousarray(pose, np.float32).reshape(-1); ca = np.ascontiguousarray(cam, np.float32).reshape(-1)
+    if len(po) != 15 or len(ca) != 9:
+        raise OrbxError(-1, f"{who}: pose is Rcw[9] tcw[3] Ow[3], cam is fx fy cx cy mbf mnMinX mnMinY mnMaxX mnMaxY")
+    return po, ca
 
 
 def _occupied_for(occupied, frame, who):
