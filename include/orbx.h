@@ -734,6 +734,88 @@ int orbx_frame_search_local_points(orbx_frame *cur, const uint8_t *occupied, con
                                    float log_scale_factor, const float *scale_factors, int nlevels, float th, float nnratio,
                                    int32_t *match_cur, int *nmatches, uint8_t *in_view);
 
+/* ---- Optimizer::PoseOptimization: motion-only pose optimisation (src/Optimizer.cc:286-513) ---------------------------
+ * The one per-frame step of Tracking that g2o solved on a host core (TrackWithMotionModel, TrackReferenceKeyFrame, TrackLocalMap;
+ * Relocalization up to three times per candidate, src/Tracking.cc:1730-1800): one 6-DoF vertex, one unary edge per feature that
+ * holds a map point.  The whole function -- four rounds of at most ten Levenberg iterations with at most ten damping trials each,
+ * and the inlier / outlier classification between the rounds -- is ONE kernel launch, one workgroup per job.  Only this function:
+ * the bundle adjustments, OptimizeSim3 and the essential graph stay with g2o.
+ * The arithmetic, in double unless a step says float, every operation rounded on its own (no fused multiply-add):
+ *   edges    feature i with has_point[i] is a monocular edge (src/Optimizer.cc:335-377) if u_right[i] < 0, else a stereo edge
+ *            (:378-416).  Measurement, Xw, cam and inv_sigma2 are floats widened to double; information = inv_sigma2[i] * I.
+ *   start    Converter::toSE3Quat(mTcw): the float rotation block goes to a quaternion (Eigen's Quaternion(Matrix3)), w >= 0,
+ *            normalised -- it is never used as a matrix.  EVERY round restarts from this pose (:437).
+ *   error    measurement - projection of Pc = q * Xw + t.  Monocular: (Pc.x / Pc.z) * fx + cx, likewise y.  Stereo: invz =
+ *            (double)(float)(1.0 / Pc.z) (types_six_dof_expmap.cpp:300 keeps it in a float), u = (Pc.x * invz) * fx + cx, v
+ *            likewise, third row u - mbf * invz.  chi2 = sum_r e_r * (inv_sigma2 * e_r).
+ *   Jacobian types_six_dof_expmap.cpp:266-288 / :335-364, with the double 1.0 / Pc.z also for the stereo edge.
+ *   Huber    delta = (float)sqrt(5.991) / (float)sqrt(7.815), robust_kernel_impl.cpp:78-91; b -= rho1 * A^T (w e),
+ *            H += A^T (rho1 w) A (base_unary_edge.hpp:56-66).  The active robust chi2 sums rho0, or chi2 in the fourth round.
+ *   system   21 + 6 + 1 sums over the active edges.  The summation order is a fixed function of (n, thread index): results are
+ *            bit-reproducible from run to run and do not depend on the other jobs of a launch.  No atomics.
+ *   solve    (H + lambda I) x = b by LDL^T without pivoting; a pivot <= 0 makes the trial's chi2 DBL_MAX (linear_solver_dense.h).
+ *   update   pose = SE3Quat::exp(x) * pose, x[0..2] rotation, x[3..5] translation, with the theta < 1e-5 branch of se3quat.h:237
+ *            and the quaternion re-normalised after the product.
+ *   Levenberg optimization_algorithm_levenberg.cpp:61-189: lambda = 1e-5 * max |H_jj| at iteration 0 of every round; rho = (cur -
+ *            temp) / (sum_j x_j (lambda x_j + b_j) + 1e-3); accept on rho > 0 && isfinite(temp) with lambda *= clamp(1 - (2 rho -
+ *            1)^3, 1/3, 2/3), else lambda *= ni, ni *= 2; at most 10 trials; the iteration loop ends on 10 trials, on rho == 0 or
+ *            when (iniChi - currentChi) * 1e3 < iniChi held three times in a row.
+ *   rounds   after a round (:441-502) an edge flagged outlier gets a fresh error at the round's final pose, an active edge keeps
+ *            the error of the LAST EVALUATED TRIAL -- after a rejected last trial that is the rejected pose (g2o's pop() restores
+ *            the vertex, not the edge errors).  outlier = (float)chi2 > 5.991f (monocular) / 7.815f (stereo); outliers leave the next
+ *            round's system; after the third round the Huber kernels go; with fewer than 10 edges (all, not only active ones)
+ *            there is one round only.
+ *   result   Converter::toCvMat(SE3Quat): the quaternion to a rotation matrix, [R | t] cast to float, last row 0 0 0 1.
+ * Fewer than 3 correspondences (:423-424): the return value is 0, Tcw_out is Tcw bit for bit, the flags are 0.
+ * Outside the contract: a correspondence whose projection is not finite at a pose the solver visits (Pc.z == 0, NaN inputs).  A
+ * finite point behind the camera is inside it (it projects mirrored, as in the reference, and normally ends as an outlier).
+ * Against g2o's own arithmetic (Eigen's LDLT pivots, its product evaluation order) this restatement is unpinned: DESIGN.md. */
+typedef struct {
+    int n;                     /* Frame::N, 0 .. 65535 */
+    const float *x, *y;        /* mvKeysUn[i].pt */
+    const float *u_right;      /* mvuRight[i] */
+    const float *inv_sigma2;   /* mvInvLevelSigma2[mvKeysUn[i].octave] */
+    const float *Xw;           /* [n][3] pMP->GetWorldPos(); read only where has_point[i] */
+    const uint8_t *has_point;  /* mvpMapPoints[i] != NULL */
+} orbx_pose_obs;
+typedef struct {
+    int n_corr;                /* nInitialCorrespondences */
+    int rounds;                /* rounds run: 0 (fewer than 3 correspondences), 1 (fewer than 10) or 4 */
+    int n_bad[4];              /* nBad after each round */
+    int iterations[4];         /* Levenberg iterations of each round */
+    double chi2[4];            /* the active robust chi2 each round ended with */
+    double pose[12];           /* the final [R | t], row major, in double: Tcw_out is exactly its float cast */
+} orbx_pose_report;
+/* cam = fx fy cx cy mbf; Tcw / Tcw_out = 16 floats, row major (may alias).  outlier[n] = mvbOutlier, written only where
+ * has_point[i]; *n_inliers = the reference's return value, nInitialCorrespondences - nBad; report may be NULL.  One upload, one
+ * launch, one download.  ORBX_E_INVALID before any device work: NULL obs / cam / Tcw / Tcw_out / n_inliers, n outside [0, 65535],
+ * with n > 0 a NULL array of obs or NULL outlier. */
+int orbx_pose_optimize(int device, const orbx_pose_obs *obs, const float *cam, const float *Tcw, float *Tcw_out, uint8_t *outlier,
+                       int *n_inliers, orbx_pose_report *report);
+/* one job of a batch: the arguments of orbx_pose_optimize */
+typedef struct {
+    const orbx_pose_obs *obs; const float *cam, *Tcw;
+    float *Tcw_out; uint8_t *outlier;
+    int n_inliers;                               /* out */
+    orbx_pose_report *report;                    /* out, may be NULL */
+} orbx_pose_job;
+/* njobs optimisations (Relocalization's candidates; a server tracking many streams) as ONE upload, ONE launch of njobs
+ * workgroups, ONE download; every job's results are byte-equal to its single call.  ORBX_E_INVALID: njobs outside [1, 1024], any
+ * refusal of the single call in any job; ORBX_E_CAPACITY: more than 2^22 features in all. */
+int orbx_pose_optimize_batch(int device, orbx_pose_job *jobs, int njobs);
+/* On a resident frame and a resident map-point table: slot_of_feature[cur n] names each feature's point (-1: none); positions,
+ * octaves and u_right are read from the frame, Xw from the table (geom[0..2]), inv_sigma2 = inv_level_sigma2[octave].  Up go n
+ * int32 slots and the pose, back come n flag bytes and the pose; results are byte-equal to orbx_pose_optimize on the same
+ * values.  The call is ordered behind a pending orbx_mappoints_set or frame creation through the events the handles keep; both
+ * handles are only read (several threads may optimise on one frame and one table).  ORBX_E_INVALID before any device work: the
+ * refusals of orbx_pose_optimize; a slot >= capacity or < -1, or not set; a frame and a table on different devices; nlevels
+ * outside [1, 16]; a feature with a point whose octave is outside [0, nlevels).  (The octaves of a frame made by
+ * orbx_frame_create_from_extraction exist on the device only: for such a frame the kernel makes that last check before it
+ * optimises, writes nothing, and the call returns ORBX_E_INVALID after its one launch.) */
+int orbx_frame_pose_optimize(const orbx_frame *cur, const orbx_mappoints *m, const int32_t *slot_of_feature,
+                             const float *inv_level_sigma2, int nlevels, const float *cam, const float *Tcw, float *Tcw_out,
+                             uint8_t *outlier, int *n_inliers, orbx_pose_report *report);
+
 /* ORBmatcher::SearchByProjection(Frame &CurrentFrame, const Frame &LastFrame, th, bMono) (src/ORBmatcher.cc:1396-1553;
  * Tracking::TrackWithMotionModel).  direction: 0 none, 1 bForward, 2 bBackward (:1412-1413).  match_cur[cur->n] =
  * index of the point each current feature finally holds (-1 none); *nmatches = the reference's return value

@@ -310,6 +310,22 @@ ORBX_LOCAL void orbx_desc_launch(orbx_extractor *e, const PyrRef &pr, int batch,
 ORBX_LOCAL int orbx_fast_diag_spans(unsigned *out, int reset);
 ORBX_LOCAL int orbx_desc_diag_spans(unsigned *out, int reset);
 #endif
+// orbx_pose.hip: one job of k_pose_opt (Optimizer::PoseOptimization).  Every pointer is a device address.  The host-pointer calls give
+// inv_sigma2 / Xw / has_point and leave octave / geom / slot NULL; the resident call gives octave (with lvl_isig), the table's geom and
+// slot (a feature has a point where slot >= 0) and leaves the other three NULL.  outlier[n] is the kernel's per-edge state and its output.
+struct PoseJob {
+    int n, nlevels;      // nlevels: entries of lvl_isig (resident form)
+    const float *x, *y, *u_right;
+    const float *inv_sigma2; const int32_t *octave;
+    const float *Xw; const float4 *geom; const int32_t *slot;
+    const uint8_t *has_point;
+    uint8_t *outlier;
+    float lvl_isig[ORBX_MAX_LEVELS];
+    float cam[5];        // fx fy cx cy mbf
+    float Tcw[16];
+};
+struct PoseOut { double pose[12], chi2[4]; float Tcw[16]; int32_t n_corr, rounds, n_bad[4], iterations[4], n_inliers, bad_octave; };
+ORBX_LOCAL void orbx_pose_launch(const PoseJob *d_jobs, PoseOut *d_out, int njobs, hipStream_t s);
 // the kernel error flag: the int behind the level counts (set by k_tree, handed on by k_desc, read and cleared by orbx_sync)
 static inline int *orbx_err_flag(const orbx_extractor *e) { return e->d_lvl_cnt + (size_t)e->max_batch * ORBX_MAX_LEVELS; }
 void orbx_prof_begin(orbx_extractor *e, int stage, hipStream_t s);

@@ -1,0 +1,426 @@
+// orbx_pose.hip — k_pose_opt: Optimizer::PoseOptimization (reference src/Optimizer.cc:286-513) in one launch.
+// One workgroup of 256 threads per job.  The pose (a unit quaternion and a translation, as g2o's SE3Quat keeps it) and every scalar of the
+// Levenberg loop live in registers of EVERY thread: each thread runs the 6x6 solve, the exponential and the bookkeeping redundantly on
+// values that are bit-identical across the workgroup (they come out of block_sum, which hands every thread the same sums), so the loop
+// trip counts are uniform and nothing but the partial sums crosses the LDS.  The observations are strided over the threads; a
+// linearisation reduces 28 doubles (21 of H's upper triangle, 6 of b, the robust chi2), a trial one.
+// The reduction order is a fixed function of (n, thread index): per thread ascending i, then the xor butterfly across the wave (both
+// partners add the same two numbers, so all 64 lanes hold the same bits), then ((w0 + w1) + (w2 + w3)) over the four waves.  No atomics:
+// a job's result does not depend on the run or on the other jobs of the launch.
+// Per-edge state is one byte, the outlier flag in the job's output array; the error an active edge "keeps" between rounds (the one of the
+// last evaluated trial, base of the classification at :441-502) is recomputed from that trial's pose, which gives the same bits.
+// The arithmetic is restated in include/orbx.h (orbx_pose_optimize) and, in numpy, in tests/pose_model.py; the host side of the three
+// calls is in orbx_proj.hip, beside the handles it reads.
+#include "orbx_internal.h"
+#include <float.h>
+
+namespace {
+
+struct Pose { double qx, qy, qz, qw, tx, ty, tz; };
+struct Edge { double mx, my, mr, X, Y, Z, w; bool stereo; };
+struct Cam { double fx, fy, cx, cy, bf; };
+
+__device__ __forceinline__ bool edge_present(const PoseJob &J, int i) { return J.slot ? J.slot[i] >= 0 : J.has_point[i] != 0; }
+
+__device__ __forceinline__ Edge edge_load(const PoseJob &J, int i)
+{
+    Edge e;
+    e.mx = (double)J.x[i]; e.my = (double)J.y[i];
+    const float ur = J.u_right[i];
+    e.stereo = !(ur < 0.f);   // src/Optimizer.cc:335
+    e.mr = (double)ur;
+    e.w = (double)(J.inv_sigma2 ? J.inv_sigma2[i] : J.lvl_isig[J.octave[i]]);
+    if (J.slot) {
+        const float4 g = J.geom[2 * (long long)J.slot[i]];
+        e.X = (double)g.x; e.Y = (double)g.y; e.Z = (double)g.z;
+    } else {
+        e.X = (double)J.Xw[3 * (long long)i]; e.Y = (double)J.Xw[3 * (long long)i + 1]; e.Z = (double)J.Xw[3 * (long long)i + 2];
+    }
+    return e;
+}
+
+// Eigen's Quaternion * vector: uv = 2 (q.vec x v); v + w uv + q.vec x uv; then + t (SE3Quat::map)
+__device__ __forceinline__ void pose_map(const Pose &P, const Edge &e, double &x, double &y, double &z)
+{
+    const double ux = 2.0 * (P.qy * e.Z - P.qz * e.Y), uy = 2.0 * (P.qz * e.X - P.qx * e.Z), uz = 2.0 * (P.qx * e.Y - P.qy * e.X);
+    x = ((e.X + P.qw * ux) + (P.qy * uz - P.qz * uy)) + P.tx;
+    y = ((e.Y + P.qw * uy) + (P.qz * ux - P.qx * uz)) + P.ty;
+    z = ((e.Z + P.qw * uz) + (P.qx * uy - P.qy * ux)) + P.tz;
+}
+
+// error = measurement - projection (types_six_dof_expmap.h computeError); returns chi2 = e . (w e)
+__device__ __forceinline__ double edge_error(const Edge &e, const Cam &K, double x, double y, double z, double err[3])
+{
+    if (e.stereo) {
+        const double invz = (double)(float)(1.0 / z);   // types_six_dof_expmap.cpp:300: `const float invz = 1.0f/trans_xyz[2]`
+        const double u = (x * invz) * K.fx + K.cx, v = (y * invz) * K.fy + K.cy;
+        err[0] = e.mx - u; err[1] = e.my - v; err[2] = e.mr - (u - K.bf * invz);
+        return (err[0] * (e.w * err[0]) + err[1] * (e.w * err[1])) + err[2] * (e.w * err[2]);
+    }
+    err[0] = e.mx - ((x / z) * K.fx + K.cx); err[1] = e.my - ((y / z) * K.fy + K.cy); err[2] = 0.0;
+    return err[0] * (e.w * err[0]) + err[1] * (e.w * err[1]);
+}
+
+__device__ __forceinline__ double edge_chi2(const PoseJob &J, int i, const Pose &P, const Cam &K, bool *stereo)
+{
+    const Edge e = edge_load(J, i);
+    double x, y, z, err[3];
+    pose_map(P, e, x, y, z);
+    *stereo = e.stereo;
+    return edge_error(e, K, x, y, z, err);
+}
+
+// robust_kernel_impl.cpp:78-91 (rho[2] is never used: base_edge.h:96-102)
+__device__ __forceinline__ void huber(double e, double delta, double &rho0, double &rho1)
+{
+    const double dsqr = delta * delta;
+    if (e <= dsqr) { rho0 = e; rho1 = 1.0; return; }
+    const double sqrte = sqrt(e);
+    rho0 = 2.0 * sqrte * delta - dsqr;
+    rho1 = delta / sqrte;
+}
+
+__device__ __forceinline__ double wave_sum(double v)
+{
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+
+template <int K>
+__device__ __forceinline__ void block_sum(double (&a)[K], double *red)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < K; k++) a[k] = wave_sum(a[k]);
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < K; k++) red[wave * K + k] = a[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < K; k++) a[k] = (red[k] + red[K + k]) + (red[2 * K + k] + red[3 * K + k]);
+    __syncthreads();
+}
+
+// Eigen's Quaternion(Matrix3): m row-major
+__device__ __forceinline__ void quat_from_matrix(const double m[9], double &qx, double &qy, double &qz, double &qw)
+{
+    double t = (m[0] + m[4]) + m[8];
+    if (t > 0.0) {
+        t = sqrt(t + 1.0);
+        qw = 0.5 * t;
+        t = 0.5 / t;
+        qx = (m[7] - m[5]) * t; qy = (m[2] - m[6]) * t; qz = (m[3] - m[1]) * t;
+        return;
+    }
+    // i = the largest diagonal entry, j = i + 1, k = i + 2 (mod 3); the three cases written out (no indexed register arrays)
+    int i = 0;
+    if (m[4] > m[0]) i = 1;
+    if (m[8] > (i ? m[4] : m[0])) i = 2;
+    if (i == 0) {
+        t = sqrt(((m[0] - m[4]) - m[8]) + 1.0);
+        qx = 0.5 * t; t = 0.5 / t;
+        qw = (m[7] - m[5]) * t; qy = (m[3] + m[1]) * t; qz = (m[6] + m[2]) * t;
+    } else if (i == 1) {
+        t = sqrt(((m[4] - m[8]) - m[0]) + 1.0);
+        qy = 0.5 * t; t = 0.5 / t;
+        qw = (m[2] - m[6]) * t; qz = (m[7] + m[5]) * t; qx = (m[1] + m[3]) * t;
+    } else {
+        t = sqrt(((m[8] - m[0]) - m[4]) + 1.0);
+        qz = 0.5 * t; t = 0.5 / t;
+        qw = (m[3] - m[1]) * t; qx = (m[2] + m[6]) * t; qy = (m[5] + m[7]) * t;
+    }
+}
+
+// SE3Quat::normalizeRotation
+__device__ __forceinline__ void quat_normalize(double &qx, double &qy, double &qz, double &qw)
+{
+    if (qw < 0.0) { qx = -qx; qy = -qy; qz = -qz; qw = -qw; }
+    const double n = sqrt(((qx * qx + qy * qy) + qz * qz) + qw * qw);
+    qx /= n; qy /= n; qz /= n; qw /= n;
+}
+
+__device__ __forceinline__ void quat_to_matrix(const Pose &P, double R[9])
+{
+    const double tx = 2.0 * P.qx, ty = 2.0 * P.qy, tz = 2.0 * P.qz;
+    const double twx = tx * P.qw, twy = ty * P.qw, twz = tz * P.qw, txx = tx * P.qx, txy = ty * P.qx, txz = tz * P.qx;
+    const double tyy = ty * P.qy, tyz = tz * P.qy, tzz = tz * P.qz;
+    R[0] = 1.0 - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy;
+    R[3] = txy + twz; R[4] = 1.0 - (txx + tzz); R[5] = tyz - twx;
+    R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1.0 - (txx + tyy);
+}
+
+// VertexSE3Expmap::oplusImpl: SE3Quat::exp(x) * P (se3quat.h:223-257, :104-110); x[0..2] rotation, x[3..5] translation
+__device__ __forceinline__ Pose pose_update(const Pose &P, const double x[6])
+{
+    const double o0 = x[0], o1 = x[1], o2 = x[2];
+    const double theta = sqrt((o0 * o0 + o1 * o1) + o2 * o2);
+    const double O[9] = { 0.0, -o2, o1, o2, 0.0, -o0, -o1, o0, 0.0 };
+    double O2[9], R[9], V[9];
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+        for (int c = 0; c < 3; c++) O2[3 * r + c] = (O[3 * r] * O[c] + O[3 * r + 1] * O[3 + c]) + O[3 * r + 2] * O[6 + c];
+    if (theta < 0.00001) {
+#pragma unroll
+        for (int k = 0; k < 9; k++) { R[k] = ((k % 4 == 0 ? 1.0 : 0.0) + O[k]) + O2[k]; V[k] = R[k]; }
+    } else {
+        const double s = sin(theta), c = cos(theta);
+        const double a = s / theta, b = (1.0 - c) / (theta * theta), cc = (theta - s) / ((theta * theta) * theta);
+#pragma unroll
+        for (int k = 0; k < 9; k++) {
+            const double id = k % 4 == 0 ? 1.0 : 0.0;
+            R[k] = (id + a * O[k]) + b * O2[k];
+            V[k] = (id + b * O[k]) + cc * O2[k];
+        }
+    }
+    Pose E;
+    quat_from_matrix(R, E.qx, E.qy, E.qz, E.qw);
+    quat_normalize(E.qx, E.qy, E.qz, E.qw);
+    E.tx = (V[0] * x[3] + V[1] * x[4]) + V[2] * x[5];
+    E.ty = (V[3] * x[3] + V[4] * x[4]) + V[5] * x[5];
+    E.tz = (V[6] * x[3] + V[7] * x[4]) + V[8] * x[5];
+    // E * P: t = E.t + E.q * P.t ; q = E.q * P.q, normalised
+    Pose N;
+    {
+        const double ux = 2.0 * (E.qy * P.tz - E.qz * P.ty), uy = 2.0 * (E.qz * P.tx - E.qx * P.tz), uz = 2.0 * (E.qx * P.ty - E.qy * P.tx);
+        N.tx = E.tx + ((P.tx + E.qw * ux) + (E.qy * uz - E.qz * uy));
+        N.ty = E.ty + ((P.ty + E.qw * uy) + (E.qz * ux - E.qx * uz));
+        N.tz = E.tz + ((P.tz + E.qw * uz) + (E.qx * uy - E.qy * ux));
+    }
+    N.qw = ((E.qw * P.qw - E.qx * P.qx) - E.qy * P.qy) - E.qz * P.qz;
+    N.qx = ((E.qw * P.qx + E.qx * P.qw) + E.qy * P.qz) - E.qz * P.qy;
+    N.qy = ((E.qw * P.qy + E.qy * P.qw) + E.qz * P.qx) - E.qx * P.qz;
+    N.qz = ((E.qw * P.qz + E.qz * P.qw) + E.qx * P.qy) - E.qy * P.qx;
+    quat_normalize(N.qx, N.qy, N.qz, N.qw);
+    return N;
+}
+
+// (H + lambda I) x = b by LDL^T without pivoting; H's upper triangle in row order (00 01 .. 05 11 12 ..).  false (x untouched) unless
+// every pivot is > 0 (linear_solver_dense.h:104-112)
+__device__ __forceinline__ bool solve6(const double *Hu, const double *b, double lambda, double x[6])
+{
+    double A[6][6], L[6][6], d[6];
+    int k = 0;
+#pragma unroll
+    for (int r = 0; r < 6; r++)
+#pragma unroll
+        for (int c = r; c < 6; c++) { A[r][c] = A[c][r] = Hu[k++]; }
+#pragma unroll
+    for (int r = 0; r < 6; r++) A[r][r] += lambda;
+#pragma unroll
+    for (int j = 0; j < 6; j++) {
+        double dj = A[j][j];
+#pragma unroll
+        for (int m = 0; m < j; m++) dj -= (L[j][m] * L[j][m]) * d[m];
+        if (!(dj > 0.0)) return false;
+        d[j] = dj;
+#pragma unroll
+        for (int i = j + 1; i < 6; i++) {
+            double v = A[i][j];
+#pragma unroll
+            for (int m = 0; m < j; m++) v -= (L[i][m] * L[j][m]) * d[m];
+            L[i][j] = v / dj;
+        }
+    }
+    double y[6];
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+        double v = b[i];
+#pragma unroll
+        for (int m = 0; m < i; m++) v -= L[i][m] * y[m];
+        y[i] = v;
+    }
+#pragma unroll
+    for (int i = 0; i < 6; i++) y[i] = y[i] / d[i];
+#pragma unroll
+    for (int i = 5; i >= 0; i--) {
+        double v = y[i];
+#pragma unroll
+        for (int m = i + 1; m < 6; m++) v -= L[m][i] * x[m];
+        x[i] = v;
+    }
+    return true;
+}
+
+__global__ __launch_bounds__(256) void k_pose_opt(const PoseJob *__restrict__ jobs, PoseOut *__restrict__ outs)
+{
+    __shared__ double red[4 * 28];
+    const PoseJob &J = jobs[blockIdx.x];
+    PoseOut &out = outs[blockIdx.x];
+    const int tid = threadIdx.x, n = J.n;
+    const Cam K = { (double)J.cam[0], (double)J.cam[1], (double)J.cam[2], (double)J.cam[3], (double)J.cam[4] };
+    const double delta_mono = (double)(float)sqrt(5.991), delta_stereo = (double)(float)sqrt(7.815);   // src/Optimizer.cc:322-323
+
+    double cnt[2] = { 0.0, 0.0 };   // correspondences; those whose octave names no level (resident form)
+    for (int i = tid; i < n; i += 256)
+        if (edge_present(J, i)) {
+            cnt[0] += 1.0; J.outlier[i] = 0;
+            if (J.octave && (unsigned)J.octave[i] >= (unsigned)J.nlevels) cnt[1] += 1.0;
+        }
+    block_sum(cnt, red);
+    const int n_corr = (int)cnt[0];
+    if (cnt[1] != 0.0) {   // refused: the host reports it, nothing else is written
+        if (tid == 0) out.bad_octave = 1;
+        return;
+    }
+
+    Pose start;
+    {
+        double m[9];
+#pragma unroll
+        for (int r = 0; r < 3; r++)
+#pragma unroll
+            for (int c = 0; c < 3; c++) m[3 * r + c] = (double)J.Tcw[4 * r + c];
+        quat_from_matrix(m, start.qx, start.qy, start.qz, start.qw);   // Converter::toSE3Quat: SE3Quat(R, t)
+        quat_normalize(start.qx, start.qy, start.qz, start.qw);
+        start.tx = (double)J.Tcw[3]; start.ty = (double)J.Tcw[7]; start.tz = (double)J.Tcw[11];
+    }
+
+    if (n_corr < 3) {   // :423-424: nothing is optimised, SetPose is not called
+        if (tid == 0) {
+            for (int r = 0; r < 3; r++)
+                for (int c = 0; c < 4; c++) out.pose[4 * r + c] = (double)J.Tcw[4 * r + c];
+            for (int k = 0; k < 16; k++) out.Tcw[k] = J.Tcw[k];
+            for (int k = 0; k < 4; k++) { out.chi2[k] = 0.0; out.n_bad[k] = 0; out.iterations[k] = 0; }
+            out.n_corr = n_corr; out.rounds = 0; out.n_inliers = 0; out.bad_octave = 0;
+        }
+        return;
+    }
+
+    Pose P = start;
+    int rounds = 0, n_bad = 0;
+    double x[6] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };   // the solver's x: a failed factorisation leaves the previous solution in it
+    for (int it = 0; it < 4; it++) {
+        const bool robust = it < 3;   // :468-469, :497-498: the kernels go after the third round
+        P = start;                    // :437
+        Pose Ptrial = start;
+        double lambda = 0.0, ni = 2.0, cur_chi = 0.0;
+        int stop_bad = 0, iters = 0;
+        for (int iter = 0; iter < 10; iter++) {
+            // computeActiveErrors + buildSystem at P
+            double acc[28];
+#pragma unroll
+            for (int k = 0; k < 28; k++) acc[k] = 0.0;
+            for (int i = tid; i < n; i += 256) {
+                if (!edge_present(J, i) || J.outlier[i]) continue;
+                const Edge e = edge_load(J, i);
+                double X, Y, Z, err[3];
+                pose_map(P, e, X, Y, Z);
+                const double chi = edge_error(e, K, X, Y, Z, err);
+                double rho0 = chi, rho1 = 1.0;
+                if (robust) huber(chi, e.stereo ? delta_stereo : delta_mono, rho0, rho1);
+                acc[27] += rho0;
+                const double invz = 1.0 / Z, invz_2 = invz * invz;   // types_six_dof_expmap.cpp:266-288, :335-364
+                double A[3][6];
+                A[0][0] = X * Y * invz_2 * K.fx; A[0][1] = -(1.0 + (X * X * invz_2)) * K.fx; A[0][2] = Y * invz * K.fx;
+                A[0][3] = -invz * K.fx; A[0][4] = 0.0; A[0][5] = X * invz_2 * K.fx;
+                A[1][0] = (1.0 + Y * Y * invz_2) * K.fy; A[1][1] = -X * Y * invz_2 * K.fy; A[1][2] = -X * invz * K.fy;
+                A[1][3] = 0.0; A[1][4] = -invz * K.fy; A[1][5] = Y * invz_2 * K.fy;
+                A[2][0] = A[0][0] - K.bf * Y * invz_2; A[2][1] = A[0][1] + K.bf * X * invz_2; A[2][2] = A[0][2];
+                A[2][3] = A[0][3]; A[2][4] = 0.0; A[2][5] = A[0][5] - K.bf * invz_2;
+                const double rw = rho1 * e.w, we0 = e.w * err[0], we1 = e.w * err[1], we2 = e.w * err[2];
+                int k = 0;
+                if (e.stereo) {
+#pragma unroll
+                    for (int r = 0; r < 6; r++) {
+#pragma unroll
+                        for (int c = r; c < 6; c++, k++) acc[k] += ((A[0][r] * rw) * A[0][c] + (A[1][r] * rw) * A[1][c]) + (A[2][r] * rw) * A[2][c];
+                        acc[21 + r] -= rho1 * ((A[0][r] * we0 + A[1][r] * we1) + A[2][r] * we2);
+                    }
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 6; r++) {
+#pragma unroll
+                        for (int c = r; c < 6; c++, k++) acc[k] += (A[0][r] * rw) * A[0][c] + (A[1][r] * rw) * A[1][c];
+                        acc[21 + r] -= rho1 * (A[0][r] * we0 + A[1][r] * we1);
+                    }
+                }
+            }
+            block_sum(acc, red);
+            cur_chi = acc[27];
+            const double ini_chi = cur_chi;
+            if (iter == 0) {   // optimization_algorithm_levenberg.cpp:93-97, :166-180
+                double md = 0.0;
+                const int diag[6] = { 0, 6, 11, 15, 18, 20 };
+#pragma unroll
+                for (int k = 0; k < 6; k++) md = fmax(fabs(acc[diag[k]]), md);
+                lambda = 1e-5 * md; ni = 2.0; stop_bad = 0;
+            }
+            double rho = 0.0;
+            int qmax = 0;
+            do {
+                const Pose backup = P;
+                const bool ok = solve6(acc, acc + 21, lambda, x);
+                P = pose_update(P, x);
+                Ptrial = P;
+                double tc[1] = { 0.0 };
+                for (int i = tid; i < n; i += 256) {
+                    if (!edge_present(J, i) || J.outlier[i]) continue;
+                    bool st;
+                    const double chi = edge_chi2(J, i, P, K, &st);
+                    double rho0 = chi, rho1 = 1.0;
+                    if (robust) huber(chi, st ? delta_stereo : delta_mono, rho0, rho1);
+                    tc[0] += rho0;
+                }
+                block_sum(tc, red);
+                const double temp_chi = ok ? tc[0] : DBL_MAX;
+                double scale = 0.0;
+#pragma unroll
+                for (int j = 0; j < 6; j++) scale += x[j] * (lambda * x[j] + acc[21 + j]);
+                scale += 1e-3;
+                rho = (cur_chi - temp_chi) / scale;
+                if (rho > 0.0 && isfinite(temp_chi)) {
+                    const double t = 2.0 * rho - 1.0;
+                    double alpha = 1.0 - (t * t) * t;
+                    alpha = fmin(alpha, 2.0 / 3.0);
+                    lambda *= fmax(1.0 / 3.0, alpha);
+                    ni = 2.0;
+                    cur_chi = temp_chi;
+                } else {
+                    lambda *= ni; ni *= 2.0;
+                    P = backup;   // pop(): the vertex goes back, the edges keep the errors of the rejected pose
+                }
+                qmax++;
+            } while (rho < 0.0 && qmax < 10);
+            iters++;
+            if (qmax == 10 || rho == 0.0) break;
+            if ((ini_chi - cur_chi) * 1e3 < ini_chi) stop_bad++; else stop_bad = 0;
+            if (stop_bad >= 3) break;
+        }
+        // :441-502: an outlier gets a fresh error at the round's pose, an active edge keeps the error of the last evaluated trial
+        double bad[1] = { 0.0 };
+        for (int i = tid; i < n; i += 256) {
+            if (!edge_present(J, i)) continue;
+            bool st;
+            const double chi = edge_chi2(J, i, J.outlier[i] ? P : Ptrial, K, &st);
+            const bool o = (float)chi > (st ? 7.815f : 5.991f);
+            J.outlier[i] = o ? 1 : 0;
+            if (o) bad[0] += 1.0;
+        }
+        block_sum(bad, red);
+        n_bad = (int)bad[0];
+        rounds = it + 1;
+        if (tid == 0) { out.chi2[it] = cur_chi; out.n_bad[it] = n_bad; out.iterations[it] = iters; }
+        if (n_corr < 10) break;   // :501: optimizer.edges().size(), all edges
+    }
+    if (tid == 0) {
+        for (int k = rounds; k < 4; k++) { out.chi2[k] = 0.0; out.n_bad[k] = 0; out.iterations[k] = 0; }
+        double R[9];
+        quat_to_matrix(P, R);
+        const double t[3] = { P.tx, P.ty, P.tz };
+        for (int r = 0; r < 3; r++) {
+            for (int c = 0; c < 3; c++) { out.pose[4 * r + c] = R[3 * r + c]; out.Tcw[4 * r + c] = (float)R[3 * r + c]; }
+            out.pose[4 * r + 3] = t[r]; out.Tcw[4 * r + 3] = (float)t[r];
+        }
+        out.Tcw[12] = 0.f; out.Tcw[13] = 0.f; out.Tcw[14] = 0.f; out.Tcw[15] = 1.f;
+        out.n_corr = n_corr; out.rounds = rounds; out.n_inliers = n_corr - n_bad; out.bad_octave = 0;
+    }
+}
+
+}   // namespace
+
+void orbx_pose_launch(const PoseJob *d_jobs, PoseOut *d_out, int njobs, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_pose_opt, dim3(njobs), dim3(256), 0, s, d_jobs, d_out);
+}

@@ -114,6 +114,24 @@ class WindowJob(C.Structure):
                 ("best_dist", C.c_void_p), ("nfound", C.c_int)]
 
 
+class PoseObs(C.Structure):
+    """orbx_pose_obs (include/orbx.h)"""
+    _fields_ = [("n", C.c_int), ("x", C.c_void_p), ("y", C.c_void_p), ("u_right", C.c_void_p), ("inv_sigma2", C.c_void_p),
+                ("Xw", C.c_void_p), ("has_point", C.c_void_p)]
+
+
+class PoseReport(C.Structure):
+    """orbx_pose_report (include/orbx.h)"""
+    _fields_ = [("n_corr", C.c_int), ("rounds", C.c_int), ("n_bad", C.c_int * 4), ("iterations", C.c_int * 4),
+                ("chi2", C.c_double * 4), ("pose", C.c_double * 12)]
+
+
+class PoseJob(C.Structure):
+    """orbx_pose_job (include/orbx.h)"""
+    _fields_ = [("obs", C.POINTER(PoseObs)), ("cam", C.c_void_p), ("Tcw", C.c_void_p), ("Tcw_out", C.c_void_p),
+                ("outlier", C.c_void_p), ("n_inliers", C.c_int), ("report", C.POINTER(PoseReport))]
+
+
 _lib = None
 
 
@@ -215,6 +233,9 @@ def lib():
     L.orbx_mappoints_read.argtypes = [vp, vp, i, vp, vp]
     L.orbx_mappoints_frustum.argtypes = [vp, vp, vp, i, vp, vp, f, f, i, vp, vp, vp, vp, vp, vp]
     L.orbx_frame_search_local_points.argtypes = [vp, vp, vp, vp, vp, i, vp, vp, f, f, vp, i, f, f, vp, ip, vp]
+    L.orbx_pose_optimize.argtypes = [i, C.POINTER(PoseObs), vp, vp, vp, vp, ip, C.POINTER(PoseReport)]
+    L.orbx_pose_optimize_batch.argtypes = [i, C.POINTER(PoseJob), i]
+    L.orbx_frame_pose_optimize.argtypes = [vp, vp, vp, vp, i, vp, vp, vp, vp, ip, C.POINTER(PoseReport)]
     L.orbx_bow_frames_create.argtypes = [i, i, i, C.POINTER(vp)]
     L.orbx_bow_frames_destroy.argtypes = [vp]; L.orbx_bow_frames_destroy.restype = None
     L.orbx_bow_transform_batch_device.argtypes = [vp, vp, vp, vp, vp, i, i, vp]
@@ -815,6 +836,19 @@ class DeviceFrame:
                                                     _p(out), C.byref(n), _p(iv)))
         return out, n.value, iv
 
+    def pose_optimize(self, points, slot_of_feature, invLevelSigma2, cam, Tcw):
+        """Optimizer::PoseOptimization on this frame and a MapPoints table: slot_of_feature[n] names each feature's point (-1: none)
+        -> dict as pose_optimize (outlier is 0 where a feature has no point)"""
+        sl = MapPoints._slots(slot_of_feature)
+        if len(sl) != self.n:
+            raise OrbxError(-1, f"DeviceFrame.pose_optimize: {len(sl)} slots, the frame has {self.n} features")
+        isig = np.ascontiguousarray(invLevelSigma2, np.float32).reshape(-1)
+        ca, tc = _pose_inputs(cam, Tcw, "DeviceFrame.pose_optimize")
+        out = np.zeros(16, np.float32); fl = np.zeros(self.n, np.uint8); ni = C.c_int(); rep = PoseReport()
+        _check(lib().orbx_frame_pose_optimize(self._h, points._h, _p(sl), _p(isig), len(isig), _p(ca), _p(tc), _p(out), _p(fl), C.byref(ni),
+                                              C.byref(rep)))
+        return _pose_result(out, fl, ni.value, rep)
+
     def __del__(self):
         try:
             h, L = getattr(self, "_h", None), _lib
@@ -882,6 +916,56 @@ class MapPoints:
                                             int(nlevels), _p(o["in_view"]), _p(o["u"]), _p(o["v"]), _p(o["xr"]), _p(o["level"]),
                                             _p(o["view_cos"])))
         return o
+
+
+def _pose_inputs(cam, Tcw, who):
+    ca = np.ascontiguousarray(cam, np.float32).reshape(-1); tc = np.ascontiguousarray(Tcw, np.float32).reshape(-1)
+    if len(ca) != 5 or len(tc) != 16:
+        raise OrbxError(-1, f"{who}: cam is fx fy cx cy mbf, Tcw is 4 x 4")
+    return ca, tc
+
+
+def _pose_result(Tcw_out, outlier, n_inliers, rep):
+    return dict(Tcw=Tcw_out.reshape(4, 4), outlier=outlier, n_inliers=n_inliers, n_corr=rep.n_corr, rounds=rep.rounds,
+                n_bad=np.array(rep.n_bad[:], np.int32), iterations=np.array(rep.iterations[:], np.int32),
+                chi2=np.array(rep.chi2[:], np.float64), pose=np.array(rep.pose[:], np.float64).reshape(3, 4))
+
+
+def _pose_obs(obs, who):
+    """obs = dict(x, y, u_right, inv_sigma2, Xw[n][3], has_point) -> (PoseObs, the arrays it points into)"""
+    keep = [np.ascontiguousarray(obs[k], np.float32) for k in ("x", "y", "u_right", "inv_sigma2")]
+    n = len(keep[0])
+    keep.append(np.ascontiguousarray(obs["Xw"], np.float32).reshape(-1, 3))
+    keep.append(np.ascontiguousarray(obs["has_point"], np.uint8))
+    if any(a.ndim != 1 or len(a) != n for a in keep[:4]) or keep[4].shape != (n, 3) or keep[5].shape != (n,):
+        raise OrbxError(-1, f"{who}: x, y, u_right, inv_sigma2, has_point need n entries, Xw [n][3]")
+    return PoseObs(n, *[_p(a) for a in keep]), keep
+
+
+def pose_optimize(obs, cam, Tcw, device=0):
+    """Optimizer::PoseOptimization (orbx_pose_optimize): obs = dict(x, y, u_right, inv_sigma2, Xw, has_point), cam = fx fy cx cy mbf,
+    Tcw 4 x 4 -> dict(Tcw, outlier, n_inliers, n_corr, rounds, n_bad, iterations, chi2, pose)"""
+    po, keep = _pose_obs(obs, "pose_optimize")
+    ca, tc = _pose_inputs(cam, Tcw, "pose_optimize")
+    out = np.zeros(16, np.float32); fl = np.zeros(po.n, np.uint8); ni = C.c_int(); rep = PoseReport()
+    _check(lib().orbx_pose_optimize(device, C.byref(po), _p(ca), _p(tc), _p(out), _p(fl), C.byref(ni), C.byref(rep)))
+    return _pose_result(out, fl, ni.value, rep)
+
+
+def pose_optimize_batch(jobs, device=0):
+    """orbx_pose_optimize_batch: jobs = [(obs, cam, Tcw), ...] in one upload, one launch, one download -> [dict as pose_optimize]"""
+    nj = len(jobs)
+    arr = (PoseJob * max(nj, 1))()
+    keep = []
+    for j, (obs, cam, Tcw) in enumerate(jobs):
+        po, k = _pose_obs(obs, "pose_optimize_batch")
+        ca, tc = _pose_inputs(cam, Tcw, "pose_optimize_batch")
+        out = np.zeros(16, np.float32); fl = np.zeros(po.n, np.uint8); rep = PoseReport()
+        keep.append((po, k, ca, tc, out, fl, rep))
+        arr[j].obs = C.pointer(po); arr[j].cam = _p(ca); arr[j].Tcw = _p(tc); arr[j].Tcw_out = _p(out); arr[j].outlier = _p(fl)
+        arr[j].report = C.pointer(rep)
+    _check(lib().orbx_pose_optimize_batch(device, arr, nj))
+    return [_pose_result(k[4], k[5], arr[j].n_inliers, k[6]) for j, k in enumerate(keep)]
 
 
 def _pose_cam(pose, cam, who):
