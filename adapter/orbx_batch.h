@@ -129,6 +129,10 @@ void FuseBatchStats(int *launches, int *researched);
 
 // src/LocalMapping.cc:241-309 as one call: vF12[i] = ComputeF12(pKF1, vpKF2[i]) (3x3 CV_32F), vvMatchedPairs[i] = what
 // matcher.SearchForTriangulation(pKF1, vpKF2[i], vF12[i], vMatchedIndices, bOnlyStereo) would have returned.  Returns the total.
+// "Would have returned" with the map-point flags as they are AT ENTRY: the reference's loop creates points between two searches, and a
+// feature of pKF1 that got one is skipped by the later searches (src/ORBmatcher.cc:750-751), so the lists here can name a feature of pKF1
+// at several neighbours.  A caller that triangulates them must keep, per idx1, only the first neighbour whose tests pass --
+// adapter/triangulate/CreateNewMapPoints.h does the search and the triangulation with that rule.
 int SearchForTriangulationBatch(ORB_SLAM2::KeyFrame *pKF1, const std::vector<ORB_SLAM2::KeyFrame *> &vpKF2, const std::vector<cv::Mat> &vF12,
                                 std::vector<std::vector<std::pair<size_t, size_t> > > &vvMatchedPairs, bool bOnlyStereo,
                                 float nnratio = 0.6f, bool checkOri = false);

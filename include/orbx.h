@@ -816,6 +816,88 @@ int orbx_frame_pose_optimize(const orbx_frame *cur, const orbx_mappoints *m, con
                              const float *inv_level_sigma2, int nlevels, const float *cam, const float *Tcw, float *Tcw_out,
                              uint8_t *outlier, int *n_inliers, orbx_pose_report *report);
 
+/* ---- LocalMapping::CreateNewMapPoints: the triangulation half (src/LocalMapping.cc:327-511) ---------------------------
+ * The search half of the function is orbx_kf_search_for_triangulation.  This is the body of its match loop: per pair (idx1 of
+ * the current keyframe, idx2 of neighbour i) the parallax test, the 4x4 SVD triangulation or KeyFrame::UnprojectStereo, two depth
+ * tests, two reprojection gates and the scale-consistency gate -- one thread per pair, all neighbours in one launch (k_triangulate),
+ * followed by two short launches that apply the loop's order rule (k_tri_resolve).
+ * THE ORDER RULE.  The reference's loop is sequential over the neighbours: a point created for feature idx1 at neighbour i makes
+ * SearchForTriangulation skip idx1 at every later neighbour (src/ORBmatcher.cc:750-751).  vbMatched2 is never written there (:725,
+ * :773), so the rows of a search are independent, and with checkOri == false -- what CreateNewMapPoints passes -- dropping a row
+ * changes nothing else.  The loop therefore equals: search every neighbour with the flags as they are at entry, test every pair on
+ * its own, and per idx1 keep the pair of the FIRST neighbour whose tests pass.  A pair that passes at a later neighbour gets status
+ * 32 + its creating status.  An earlier pair that FAILS blocks nothing.  With checkOri == true the equality does not hold.
+ * The arithmetic follows the C++ types of the reference text; every operation is rounded on its own (no fused multiply-add).
+ * "dotd(a, b)" is ((double)a0*b0 + (double)a1*b1) + (double)a2*b2.  Rwc is the exact transpose of the rotation block of Tcw.
+ *   rays     xn = ((x - cx) * invfx, (y - cy) * invfy, 1) in float (:350-351); ray[r] = (float)dotd(Rwc.row(r), xn) (:353-355);
+ *            cosParallaxRays = (float)(dotd(ray1, ray2) / (sqrt(dotd(ray1, ray1)) * sqrt(dotd(ray2, ray2)))) (:358).
+ *   stereo   a feature is stereo where u_right >= 0.  cosParallaxStereo1 = cosParallaxStereo2 = cosParallaxRays + 1 in float;
+ *            `if (bStereo1) 1 = S(mb1, depth1[idx1]); else if (bStereo2) 2 = S(mb2, depth2[idx2])` as written at :364-367;
+ *            cosParallaxStereo = the smaller (:369).  S(mb, depth) stands for cos(2 atan2(mb / 2, depth)) and is evaluated as
+ *            (float)((d*d - h*h) / (d*d + h*h)) in double with h = (double)(mb / 2) (the division in float), d = (double)depth:
+ *            a STATED DEVIATION at rounding level (no device matches the C library's cos and atan2 bit for bit).
+ *   branch   :372-402 literally: triangulate if cosParallaxRays < cosParallaxStereo && cosParallaxRays > 0 && (bStereo1 ||
+ *            bStereo2 || (double)cosParallaxRays < 0.9998); else UnprojectStereo of keyframe 1 if bStereo1 && 1 < 2; else of
+ *            keyframe 2 if bStereo2 && 2 < 1; else status 16.
+ *   A        rows (xn1.x * T1.row(2)) - T1.row(0), (xn1.y * T1.row(2)) - T1.row(1), and the same two of view 2, in float (:376-379).
+ *   SVD      one-sided Jacobi on the four columns of A in float, the shape of OpenCV's JacobiSVDImpl_: V = I; W[i] = the squared
+ *            norm of column i, summed in double; sweeps over the column pairs (i, j), i < j, in lexicographic order.  Per pair
+ *            p = sum_k (double)A[k][i] * A[k][j]; the pair is skipped when |p| <= (double)(2 * FLT_EPSILON) * sqrt(W[i] * W[j]) --
+ *            this is the stopping test: a sweep that skipped all six pairs ends the iteration, which runs 30 sweeps at most.
+ *            Otherwise p *= 2, beta = W[i] - W[j], gamma = sqrt(p*p + beta*beta) (OpenCV calls hypot), and in double, cast to float:
+ *            beta < 0: s = sqrt(((gamma - beta) * 0.5) / gamma), c = p / ((gamma * s) * 2); else c = sqrt((gamma + beta) / (gamma *
+ *            2)), s = p / ((gamma * c) * 2).  Columns i, j of A and rows i, j of V become t0 = c*a + s*b, t1 = (-s)*a + c*b in
+ *            float; W[i], W[j] = the new columns' squared norms in double.  At the end the squared norms of all four columns are
+ *            summed again in double; the row of V of the SMALLEST one is the solution v, and of equal ones the LATER column.
+ *   point    v[3] == 0: status 17.  x3D = v[0..2] / v[3] in float (:390); the sign of v cancels.
+ *   Unproject (src/KeyFrame.cc:654-670) depth[i] <= 0 (or NaN): status 24 (the reference dereferences an empty Mat).  x = (raw_x[i] -
+ *            cx) * z * invfx, y likewise, left to right in float, from the RAW keypoint mvKeys[i]; x3D[r] = (float)(dotd(Rwc.row(r),
+ *            (x, y, z)) + (double)Ow[r]) (cv::gemm adds in double and casts once).
+ *   depth    z1 = (float)(dotd(R1.row(2), x3D) + (double)t1[2]); z1 <= 0: status 18; z2 likewise: 19 (:408-414).
+ *   gates    x, y as z; invz = (float)(1.0 / (double)z); u = fx * x * invz + cx, v = fy * y * invz + cy, left to right in float;
+ *            errors u - kp.x, v - kp.y and, for a stereo feature, (u - mbf * invz) - u_right, where mbf is the CURRENT keyframe's
+ *            for BOTH keyframes (the reference's :465).  Rejected (status 20 / 21) when (double)(float sum of the squares, left to
+ *            right) > 5.991 * (double)sigma2 (monocular) or 7.8 * (double)sigma2 (stereo), sigma2 = level_sigma2[octave].
+ *   scale    dist = (float)sqrt(squared norm of (x3D - Ow) summed in double), the difference in float; a zero distance: status 22;
+ *            ratioDist = dist2 / dist1, ratioOctave = scale_factors[octave1] / scale_factors[octave2]; status 23 when ratioDist *
+ *            ratio_factor < ratioOctave || ratioDist > ratioOctave * ratio_factor (:490), in float.
+ * status: 0 created by triangulation, 1 / 2 created from keyframe 1's / 2's stereo depth, 16 no stereo and low parallax, 17 w ==
+ * 0, 18 z1 <= 0, 19 z2 <= 0, 20 / 21 reprojection gate of keyframe 1 / 2, 22 zero distance, 23 scale ratio, 24 stereo feature
+ * without positive depth, 32 + (0, 1, 2) superseded by an earlier neighbour.  x3d holds the position of every pair that reached
+ * one (status 0-2, 18-23, 32-34) and zeros otherwise.  Against OpenCV's own arithmetic (its gemm, dot and SVD kernels differ by
+ * build) this restatement is unpinned: DESIGN.md. */
+typedef struct { float Tcw[12]; float Ow[3]; float fx, fy, cx, cy, invfx, invfy, mb, mbf; } orbx_tri_view; /* Tcw: 3 x 4 row major */
+typedef struct {
+    int n;
+    const float *x, *y;        /* mvKeysUn[i].pt */
+    const int32_t *octave;     /* mvKeysUn[i].octave */
+    const float *u_right;      /* mvuRight */
+    const float *depth;        /* mvDepth; may be NULL when no feature named by a pair is stereo */
+    const float *raw_x, *raw_y;/* mvKeys[i].pt; both NULL = x and y (rectified stereo: mvKeys == mvKeysUn) */
+} orbx_tri_feats;
+/* pairs[n2][2*cap] and npairs[n2] as orbx_kf_search_for_triangulation returns them; one table of level factors for all keyframes.
+ * status[n2][cap] and x3d[n2][cap][3] are written for the first npairs[i] entries of each row only; *n_new = pairs with status 0-2.
+ * One upload, three launches on one stream, one download.  ORBX_E_INVALID before any device work: a NULL argument or keyframe
+ * array (depth: see above), n2 outside [1, 64], cap < 1, npairs[i] outside [0, cap], a pair index outside its keyframe, nlevels
+ * outside [1, 16], an octave of a paired feature outside [0, nlevels).  ORBX_E_CAPACITY: more than 2^22 pairs in all. */
+int orbx_triangulate_pairs(int device, const orbx_tri_feats *k1, const orbx_tri_view *v1, const orbx_tri_feats *const *k2s,
+                           const orbx_tri_view *v2s, int n2, const int32_t *pairs, int cap, const int *npairs,
+                           const float *scale_factors, const float *level_sigma2, int nlevels, float ratio_factor,
+                           uint8_t *status, float *x3d, int *n_new);
+/* mvDepth and the raw positions mvKeys[i].pt ([n] each; raw_x = raw_y = NULL: the frame's own x / y) for a resident keyframe: one
+ * upload, once per frame -- a second call is ORBX_E_INVALID; they are immutable like the rest of the frame.  Only
+ * orbx_frame_triangulate reads them: the call may run beside other threads' searches on the frame, but not beside another
+ * orbx_frame_set_depth or an orbx_frame_triangulate on it. */
+int orbx_frame_set_depth(orbx_frame *f, const float *depth, const float *raw_x, const float *raw_y);
+/* orbx_triangulate_pairs on resident keyframes: up go the views and the pair lists, back come status and x3d, byte-equal to the
+ * host-pointer call on the same values.  The frames are only read (several threads may share them); a frame whose creation is
+ * pending is waited for through its event.  ORBX_E_INVALID also for frames on different devices and for a frame that has stereo
+ * features, or was made by orbx_frame_create_from_extraction, and has no depth attached.  (The octaves of a frame made from an
+ * extraction exist on the device only: the kernel checks them, and the call returns ORBX_E_INVALID after its launches.) */
+int orbx_frame_triangulate(const orbx_frame *k1, const orbx_tri_view *v1, const orbx_frame *const *k2s, const orbx_tri_view *v2s,
+                           int n2, const int32_t *pairs, int cap, const int *npairs, const float *scale_factors,
+                           const float *level_sigma2, int nlevels, float ratio_factor, uint8_t *status, float *x3d, int *n_new);
+
 /* ORBmatcher::SearchByProjection(Frame &CurrentFrame, const Frame &LastFrame, th, bMono) (src/ORBmatcher.cc:1396-1553;
  * Tracking::TrackWithMotionModel).  direction: 0 none, 1 bForward, 2 bBackward (:1412-1413).  match_cur[cur->n] =
  * index of the point each current feature finally holds (-1 none); *nmatches = the reference's return value

@@ -9,6 +9,7 @@ sitting directly on the C ABI of liborbx.so (include/orbx.h):
   KeyFrameDatabase      <- reference include/KeyFrameDatabase.h:42-70 (relocalisation and loop candidate queries)
   ORBextractor.extract_rgbd / rgbd_depth_batch_device <- reference src/Frame.cc:145-154, :754-774 (RGB-D frames)
   pose_optimize / DeviceFrame.pose_optimize <- reference src/Optimizer.cc:286-513 (motion-only pose optimisation)
+  triangulate_pairs / frame_triangulate <- reference src/LocalMapping.cc:327-511 (CreateNewMapPoints' triangulation)
 
 There is NO CPU fallback: importing works without a GPU (so that the ABI can be inspected), but
 every compute call raises OrbxError unless liborbx.so is built and a gfx950 device is present.
@@ -17,8 +18,10 @@ The directory name contains a '-', so load it with importlib (see tests/conftest
 from . import orbx, streams
 from .orbx import (OrbxError, KP_DTYPE, lib, lib_path, ORBextractor, ORBmatcher, ComputeStereoMatches,
                    FeatSet, make_featset, STAGES, BowDatabase, DeviceKeyFrame, DeviceFrame, MapPoints, BowFrames, KeyFrameDatabase, ORBVocabulary, ComputeDistinctiveDescriptors, Rectifier, UndistortKeyPoints,
-                   RGBDParams, depth_map_factor, rgbd_depth_batch_device, DEPTH_U16, DEPTH_F32, pose_optimize, pose_optimize_batch)
+                   RGBDParams, depth_map_factor, rgbd_depth_batch_device, DEPTH_U16, DEPTH_F32, pose_optimize, pose_optimize_batch,
+                   triangulate_pairs, frame_set_depth, frame_triangulate)
 
 __all__ = ["OrbxError", "KP_DTYPE", "lib", "lib_path", "ORBextractor", "ORBmatcher", "ComputeStereoMatches",
            "FeatSet", "make_featset", "STAGES", "BowDatabase", "DeviceKeyFrame", "DeviceFrame", "MapPoints", "BowFrames", "KeyFrameDatabase", "ORBVocabulary", "ComputeDistinctiveDescriptors", "Rectifier", "UndistortKeyPoints",
-           "RGBDParams", "depth_map_factor", "rgbd_depth_batch_device", "DEPTH_U16", "DEPTH_F32", "pose_optimize", "pose_optimize_batch"]
+           "RGBDParams", "depth_map_factor", "rgbd_depth_batch_device", "DEPTH_U16", "DEPTH_F32", "pose_optimize", "pose_optimize_batch",
+           "triangulate_pairs", "frame_set_depth", "frame_triangulate"]

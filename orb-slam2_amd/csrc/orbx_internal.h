@@ -326,6 +326,22 @@ struct PoseJob {
 };
 struct PoseOut { double pose[12], chi2[4]; float Tcw[16]; int32_t n_corr, rounds, n_bad[4], iterations[4], n_inliers, bad_octave; };
 ORBX_LOCAL void orbx_pose_launch(const PoseJob *d_jobs, PoseOut *d_out, int njobs, hipStream_t s);
+// orbx_triangulate.hip: what k_triangulate reads besides the pair list.  Every pointer is a device address; raw_x / raw_y are x / y and
+// depth is NULL (never read: no stereo feature) where a keyframe has no depth attached.  prefix[i] = pairs of the neighbours before i,
+// prefix[n2] = total; the call uploads the head up to nb[n2].
+struct TriFeat { const float *x, *y, *u_right, *depth, *raw_x, *raw_y; const int32_t *octave; };
+struct TriHead {
+    int n2, total, nlevels;
+    float ratio_factor;
+    int prefix[65];
+    float sf[ORBX_MAX_LEVELS], sigma2[ORBX_MAX_LEVELS];
+    orbx_tri_view v1; TriFeat f1;
+    struct Nb { orbx_tri_view v; TriFeat f; } nb[64];
+};
+// k_triangulate, then the two passes of k_tri_resolve, on stream s: d_status[total], d_x3d[total][3]; *d_bad becomes 1 if a pair names an
+// octave outside [0, nlevels); d_first[keyframe 1's n] must hold values > 63 (the call fills it with 0x7f bytes)
+ORBX_LOCAL void orbx_triangulate_launch(const TriHead *d_head, const int32_t *d_pairs, int total, uint8_t *d_status, float *d_x3d, int *d_bad,
+                                        int *d_first, hipStream_t s);
 // the kernel error flag: the int behind the level counts (set by k_tree, handed on by k_desc, read and cleared by orbx_sync)
 static inline int *orbx_err_flag(const orbx_extractor *e) { return e->d_lvl_cnt + (size_t)e->max_batch * ORBX_MAX_LEVELS; }
 void orbx_prof_begin(orbx_extractor *e, int stage, hipStream_t s);

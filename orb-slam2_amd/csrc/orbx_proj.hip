@@ -1181,6 +1181,10 @@ struct orbx_frame : FrameLayout {   // the block's layout: frame_layout(n)
     FrameBlock blk;
     bool pending;   // the creation may still be running: the first search waits for blk.ev on its own stream
     std::vector<int32_t> h_oct;   // a frame made from host pointers keeps its octaves: orbx_frame_pose_optimize checks them before any device work
+    // orbx_frame_set_depth: mvDepth and the raw positions in one allocation of the frame's own (raw == nullptr: x / y); has_stereo = some
+    // u_right >= 0 as far as the host saw them, from_extraction = it saw none
+    float *d_depth = nullptr, *d_raw_x = nullptr, *d_raw_y = nullptr;
+    bool depth_set = false, has_stereo = false, from_extraction = false;
 };
 
 static DevFrame frame_dev(const orbx_frame *f) { return dev_frame(f->blk.d, *f, f->n, f->bounds); }
@@ -1222,6 +1226,8 @@ extern "C" int orbx_frame_create(int device, const orbx_frame_feats *cur, orbx_f
     }
     if (rc) { frame_block_put(device, f->blk); delete f; return rc; }
     if (cur->n) f->h_oct.assign(cur->octave, cur->octave + cur->n);
+    for (int i = 0; i < cur->n; i++)
+        if (cur->u_right[i] >= 0.f) { f->has_stereo = true; break; }
     *out = f;
     return ORBX_OK;
 }
@@ -1280,6 +1286,7 @@ extern "C" int orbx_frame_create_from_extraction(int device, const void *d_kps, 
         return ORBX_E_HIP;
     }
     f->pending = true;
+    f->from_extraction = true;
     *out = f;
     return ORBX_OK;
 }
@@ -1306,7 +1313,10 @@ extern "C" int orbx_frame_read(const orbx_frame *f, float *x, float *y, int32_t 
 extern "C" void orbx_frame_destroy(orbx_frame *f)
 {
     if (!f) return;
-    if (orbx_use_device(f->device) == hipSuccess) frame_block_put(f->device, f->blk);
+    if (orbx_use_device(f->device) == hipSuccess) {
+        frame_block_put(f->device, f->blk);
+        if (f->d_depth) (void)hipFree(f->d_depth);
+    }
     delete f;
 }
 
@@ -1944,4 +1954,211 @@ extern "C" int orbx_frame_pose_optimize(const orbx_frame *cur, const orbx_mappoi
     const PoseArgs a = { nullptr, cam, Tcw, Tcw_out, outlier, n_inliers, report };
     pose_deliver(po, ho + outs_b, n, a, [&](int i) { return slot_of_feature[i] >= 0; });
     return ORBX_OK;
+}
+
+// ---------------------------------------------------------------- CreateNewMapPoints' triangulation (include/orbx.h: orbx_triangulate_pairs)
+// The kernels and their arithmetic are in orbx_triangulate.hip; here are the refusals, the staging and the delivery of the two calls.
+
+// what the host knows of one keyframe of a call (NULL: only the device has it)
+struct TriHostKf { int n; const int32_t *octave; const float *u_right; bool has_depth; };
+
+struct TriArgs {
+    int n2, cap, nlevels;
+    const int32_t *pairs; const int *npairs;
+    const orbx_tri_view *v1, *v2s;
+    const float *sf, *sigma2;
+    float ratio_factor;
+    uint8_t *status; float *x3d; int *n_new;
+};
+
+// the refusals both forms share; *total = the pairs of all lists
+static int tri_check(const char *who, const TriArgs &a, const TriHostKf &h1, const TriHostKf *h2, size_t *total)
+{
+    if (a.cap < 1 || a.nlevels < 1 || a.nlevels > ORBX_MAX_LEVELS) {
+        orbx_set_error("%s: invalid argument (cap >= 1, 1 <= nlevels <= %d)", who, ORBX_MAX_LEVELS);
+        return ORBX_E_INVALID;
+    }
+    size_t t = 0;
+    for (int i = 0; i < a.n2; i++) {
+        const int np = a.npairs[i];
+        if (np < 0 || np > a.cap) { orbx_set_error("%s: npairs[%d] = %d outside [0, cap = %d]", who, i, np, a.cap); return ORBX_E_INVALID; }
+        t += (size_t)np;
+        const int32_t *p = a.pairs + 2 * (size_t)i * (size_t)a.cap;
+        for (int k = 0; k < np; k++) {
+            const int i1 = p[2 * k], i2 = p[2 * k + 1];
+            if (i1 < 0 || i1 >= h1.n || i2 < 0 || i2 >= h2[i].n) {
+                orbx_set_error("%s: neighbour %d, pair %d: (%d, %d) outside the keyframes (%d, %d features)", who, i, k, i1, i2, h1.n, h2[i].n);
+                return ORBX_E_INVALID;
+            }
+            if ((h1.octave && (h1.octave[i1] < 0 || h1.octave[i1] >= a.nlevels)) || (h2[i].octave && (h2[i].octave[i2] < 0 || h2[i].octave[i2] >= a.nlevels))) {
+                orbx_set_error("%s: neighbour %d, pair %d: an octave outside [0, %d)", who, i, k, a.nlevels);
+                return ORBX_E_INVALID;
+            }
+            if ((h1.u_right && !h1.has_depth && h1.u_right[i1] >= 0.f) || (h2[i].u_right && !h2[i].has_depth && h2[i].u_right[i2] >= 0.f)) {
+                orbx_set_error("%s: neighbour %d, pair %d: a stereo feature of a keyframe without depth", who, i, k);
+                return ORBX_E_INVALID;
+            }
+        }
+    }
+    if (t > ((size_t)1 << 22)) { orbx_set_error("%s: %zu pairs in all, more than 2^22", who, t); return ORBX_E_CAPACITY; }
+    *total = t;
+    return ORBX_OK;
+}
+
+// blob: [TriHead up to nb[n2]] [pairs, packed] [whatever stage() adds]; work / download: [status] [x3d] [bad flag] | [first[n1]]
+// stage(H, h_blob, d_blob, offset) fills the TriFeat records (and, for host pointers, the blob behind offset)
+template <class Stage>
+static int tri_run(const char *who, ProjCtx *c, const TriArgs &a, int n1, size_t total, size_t extra_blob, Stage stage,
+                   const orbx_frame *const *wait, int nwait)
+{
+    *a.n_new = 0;
+    if (total == 0) return ORBX_OK;
+    const size_t head_b = a16(offsetof(TriHead, nb) + sizeof(TriHead::Nb) * (size_t)a.n2), pairs_b = a16(8 * total);
+    const size_t blob = head_b + pairs_b + extra_blob;
+    const size_t o_x3d = a16(total), o_bad = o_x3d + a16(12 * total), out = o_bad + 16, work = out + a16(4 * (size_t)n1);
+    int rc = proj_blob_reserve(c, blob);
+    if (!rc && work > c->work_cap) rc = ensure(&c->d_work, &c->work_cap, 2 * work);
+    if (!rc && out > c->out_cap) rc = ensure_pinned(&c->h_out, &c->out_cap, 2 * out);
+    if (rc) return rc;
+    TriHead &H = *(TriHead *)c->h_blob;
+    memset(&H, 0, head_b);
+    H.n2 = a.n2; H.total = (int)total; H.nlevels = a.nlevels; H.ratio_factor = a.ratio_factor;
+    memcpy(H.sf, a.sf, sizeof(float) * (size_t)a.nlevels); memcpy(H.sigma2, a.sigma2, sizeof(float) * (size_t)a.nlevels);
+    H.v1 = *a.v1;
+    int32_t *hp = (int32_t *)(c->h_blob + head_b);
+    size_t at = 0;
+    for (int i = 0; i < a.n2; i++) {
+        H.prefix[i] = (int)at;
+        H.nb[i].v = a.v2s[i];
+        memcpy(hp + 2 * at, a.pairs + 2 * (size_t)i * (size_t)a.cap, 8 * (size_t)a.npairs[i]);
+        at += (size_t)a.npairs[i];
+    }
+    H.prefix[a.n2] = (int)at;
+    stage(H, c->h_blob, c->d_blob, head_b + pairs_b);
+    for (int i = 0; i < nwait; i++)
+        if (wait[i]->pending) ORBX_HIP(hipStreamWaitEvent(c->stream, wait[i]->blk.ev, 0));   // the handles are not written: every call on a pending frame waits
+    ORBX_HIP(hipMemcpyAsync(c->d_blob, c->h_blob, blob, hipMemcpyHostToDevice, c->stream));
+    // 0x7f7f7f7f: larger than any neighbour index in first[], and not the 1 the kernel writes into the flag
+    ORBX_HIP(hipMemsetAsync(c->d_work + o_bad, 0x7f, work - o_bad, c->stream));
+    orbx_triangulate_launch((const TriHead *)c->d_blob, (const int32_t *)(c->d_blob + head_b), (int)total, c->d_work, (float *)(c->d_work + o_x3d),
+                            (int *)(c->d_work + o_bad), (int *)(c->d_work + out), c->stream);
+    ORBX_HIP(hipGetLastError());
+    ORBX_HIP(hipMemcpyAsync(c->h_out, c->d_work, out, hipMemcpyDeviceToHost, c->stream));
+    ORBX_HIP(hipStreamSynchronize(c->stream));
+    const uint8_t *ho = (const uint8_t *)c->h_out;
+    if (*(const int32_t *)(ho + o_bad) == 1) { orbx_set_error("%s: a paired feature has an octave outside [0, %d)", who, a.nlevels); return ORBX_E_INVALID; }
+    const float *hx = (const float *)(ho + o_x3d);
+    int n_new = 0;
+    at = 0;
+    for (int i = 0; i < a.n2; i++) {
+        const size_t np = (size_t)a.npairs[i], row = (size_t)i * (size_t)a.cap;
+        memcpy(a.status + row, ho + at, np);
+        memcpy(a.x3d + 3 * row, hx + 3 * at, 12 * np);
+        for (size_t k = 0; k < np; k++) n_new += ho[at + k] <= 2;
+        at += np;
+    }
+    *a.n_new = n_new;
+    return ORBX_OK;
+}
+
+extern "C" int orbx_triangulate_pairs(int device, const orbx_tri_feats *k1, const orbx_tri_view *v1, const orbx_tri_feats *const *k2s,
+                                      const orbx_tri_view *v2s, int n2, const int32_t *pairs, int cap, const int *npairs,
+                                      const float *scale_factors, const float *level_sigma2, int nlevels, float ratio_factor,
+                                      uint8_t *status, float *x3d, int *n_new)
+{
+    const char *who = "orbx_triangulate_pairs";
+    if (!k1 || !v1 || !k2s || !v2s || !pairs || !npairs || !scale_factors || !level_sigma2 || !status || !x3d || !n_new || n2 < 1 || n2 > 64) {
+        orbx_set_error("%s: invalid argument (no NULL argument, 1 <= n2 <= 64)", who);
+        return ORBX_E_INVALID;
+    }
+    auto host_kf = [&](const orbx_tri_feats *k, TriHostKf *h) {
+        if (!k || k->n < 0 || (k->n && (!k->x || !k->y || !k->octave || !k->u_right)) || (!k->raw_x) != (!k->raw_y)) return false;
+        h->n = k->n; h->octave = k->octave; h->u_right = k->u_right; h->has_depth = k->depth != nullptr;
+        return true;
+    };
+    TriHostKf h1, h2[64];
+    bool ok = host_kf(k1, &h1);
+    for (int i = 0; ok && i < n2; i++) ok = host_kf(k2s[i], &h2[i]);
+    if (!ok) { orbx_set_error("%s: a keyframe is NULL, has n < 0, lacks x / y / octave / u_right or gives one raw array only", who); return ORBX_E_INVALID; }
+    const TriArgs a = { n2, cap, nlevels, pairs, npairs, v1, v2s, scale_factors, level_sigma2, ratio_factor, status, x3d, n_new };
+    size_t total;
+    int rc = tri_check(who, a, h1, h2, &total);
+    if (rc) return rc;
+    ProjCtx *c;
+    if ((rc = orbx_ctx_get(g_proj, device, &c))) return rc;
+    auto kf_bytes = [](const orbx_tri_feats *k) { return (size_t)(4 + (k->depth ? 1 : 0) + (k->raw_x ? 2 : 0)) * a16(4 * (size_t)k->n); };
+    size_t extra = kf_bytes(k1);
+    for (int i = 0; i < n2; i++) extra += kf_bytes(k2s[i]);
+    return tri_run(who, c, a, k1->n, total, extra, [&](TriHead &H, uint8_t *h, const uint8_t *d, size_t o) {
+        auto put_kf = [&](const orbx_tri_feats *k, TriFeat &f) {
+            const size_t b = 4 * (size_t)k->n;
+            auto put = [&](const void *src) { const size_t at = o; o += a16(b); if (b) memcpy(h + at, src, b); return (const float *)(d + at); };
+            f.x = put(k->x); f.y = put(k->y); f.octave = (const int32_t *)put(k->octave); f.u_right = put(k->u_right);
+            f.depth = k->depth ? put(k->depth) : nullptr;
+            f.raw_x = k->raw_x ? put(k->raw_x) : f.x; f.raw_y = k->raw_y ? put(k->raw_y) : f.y;
+        };
+        put_kf(k1, H.f1);
+        for (int i = 0; i < n2; i++) put_kf(k2s[i], H.nb[i].f);
+    }, nullptr, 0);
+}
+
+extern "C" int orbx_frame_set_depth(orbx_frame *f, const float *depth, const float *raw_x, const float *raw_y)
+{
+    if (!f || !depth || (!raw_x) != (!raw_y)) { orbx_set_error("orbx_frame_set_depth: invalid argument (a frame, depth, raw_x and raw_y both or neither)"); return ORBX_E_INVALID; }
+    if (f->depth_set) { orbx_set_error("orbx_frame_set_depth: the frame has its depth already"); return ORBX_E_INVALID; }
+    if (f->n) {
+        ORBX_HIP(orbx_use_device(f->device));
+        const size_t b = 4 * (size_t)f->n, s = a16(b);
+        uint8_t *d = nullptr;
+        ORBX_HIP(hipMalloc((void **)&d, (raw_x ? 3 : 1) * s));
+        hipError_t e = hipMemcpy(d, depth, b, hipMemcpyHostToDevice);
+        if (e == hipSuccess && raw_x) e = hipMemcpy(d + s, raw_x, b, hipMemcpyHostToDevice);
+        if (e == hipSuccess && raw_x) e = hipMemcpy(d + 2 * s, raw_y, b, hipMemcpyHostToDevice);
+        if (e != hipSuccess) { (void)hipFree(d); orbx_set_error("orbx_frame_set_depth: upload failed: %s", hipGetErrorString(e)); return ORBX_E_HIP; }
+        f->d_depth = (float *)d;
+        if (raw_x) { f->d_raw_x = (float *)(d + s); f->d_raw_y = (float *)(d + 2 * s); }
+    }
+    f->depth_set = true;
+    return ORBX_OK;
+}
+
+extern "C" int orbx_frame_triangulate(const orbx_frame *k1, const orbx_tri_view *v1, const orbx_frame *const *k2s, const orbx_tri_view *v2s,
+                                      int n2, const int32_t *pairs, int cap, const int *npairs, const float *scale_factors,
+                                      const float *level_sigma2, int nlevels, float ratio_factor, uint8_t *status, float *x3d, int *n_new)
+{
+    const char *who = "orbx_frame_triangulate";
+    if (!k1 || !v1 || !k2s || !v2s || !pairs || !npairs || !scale_factors || !level_sigma2 || !status || !x3d || !n_new || n2 < 1 || n2 > 64) {
+        orbx_set_error("%s: invalid argument (no NULL argument, 1 <= n2 <= 64)", who);
+        return ORBX_E_INVALID;
+    }
+    const orbx_frame *fr[65];
+    TriHostKf h[65];
+    fr[0] = k1;
+    for (int i = 0; i < n2; i++) fr[1 + i] = k2s[i];
+    for (int i = 0; i <= n2; i++) {
+        const orbx_frame *f = fr[i];
+        if (!f) { orbx_set_error("%s: a NULL frame", who); return ORBX_E_INVALID; }
+        if (f->device != k1->device) { orbx_set_error("%s: the frames live on different devices", who); return ORBX_E_INVALID; }
+        if ((f->has_stereo || f->from_extraction) && !f->depth_set) {
+            orbx_set_error("%s: frame %d has stereo features or comes from an extraction, and no depth (orbx_frame_set_depth)", who, i);
+            return ORBX_E_INVALID;
+        }
+        h[i].n = f->n; h[i].octave = f->h_oct.empty() ? nullptr : f->h_oct.data(); h[i].u_right = nullptr; h[i].has_depth = f->depth_set;
+    }
+    const TriArgs a = { n2, cap, nlevels, pairs, npairs, v1, v2s, scale_factors, level_sigma2, ratio_factor, status, x3d, n_new };
+    size_t total;
+    int rc = tri_check(who, a, h[0], h + 1, &total);
+    if (rc) return rc;
+    ProjCtx *c;
+    if ((rc = orbx_ctx_get(g_proj, k1->device, &c))) return rc;
+    return tri_run(who, c, a, k1->n, total, 0, [&](TriHead &H, uint8_t *, const uint8_t *, size_t) {
+        for (int i = 0; i <= n2; i++) {
+            const orbx_frame *f = fr[i];
+            const DevFrame F = frame_dev(f);
+            TriFeat &t = i ? H.nb[i - 1].f : H.f1;
+            t.x = F.x; t.y = F.y; t.octave = F.octave; t.u_right = F.u_right;
+            t.depth = f->d_depth;
+            t.raw_x = f->d_raw_x ? f->d_raw_x : F.x; t.raw_y = f->d_raw_y ? f->d_raw_y : F.y;
+        }
+    }, fr, n2 + 1);
 }

@@ -132,6 +132,18 @@ class PoseJob(C.Structure):
                 ("outlier", C.c_void_p), ("n_inliers", C.c_int), ("report", C.POINTER(PoseReport))]
 
 
+class TriView(C.Structure):
+    """orbx_tri_view (include/orbx.h)"""
+    _fields_ = [("Tcw", C.c_float * 12), ("Ow", C.c_float * 3), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("invfx", C.c_float), ("invfy", C.c_float), ("mb", C.c_float), ("mbf", C.c_float)]
+
+
+class TriFeats(C.Structure):
+    """orbx_tri_feats (include/orbx.h)"""
+    _fields_ = [("n", C.c_int), ("x", C.c_void_p), ("y", C.c_void_p), ("octave", C.c_void_p), ("u_right", C.c_void_p), ("depth", C.c_void_p),
+                ("raw_x", C.c_void_p), ("raw_y", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -236,6 +248,10 @@ def lib():
     L.orbx_pose_optimize.argtypes = [i, C.POINTER(PoseObs), vp, vp, vp, vp, ip, C.POINTER(PoseReport)]
     L.orbx_pose_optimize_batch.argtypes = [i, C.POINTER(PoseJob), i]
     L.orbx_frame_pose_optimize.argtypes = [vp, vp, vp, vp, i, vp, vp, vp, vp, ip, C.POINTER(PoseReport)]
+    L.orbx_triangulate_pairs.argtypes = [i, C.POINTER(TriFeats), C.POINTER(TriView), C.POINTER(C.POINTER(TriFeats)), C.POINTER(TriView), i, vp, i, vp,
+                                         vp, vp, i, f, vp, vp, ip]
+    L.orbx_frame_set_depth.argtypes = [vp, vp, vp, vp]
+    L.orbx_frame_triangulate.argtypes = [vp, C.POINTER(TriView), C.POINTER(vp), C.POINTER(TriView), i, vp, i, vp, vp, vp, i, f, vp, vp, ip]
     L.orbx_bow_frames_create.argtypes = [i, i, i, C.POINTER(vp)]
     L.orbx_bow_frames_destroy.argtypes = [vp]; L.orbx_bow_frames_destroy.restype = None
     L.orbx_bow_transform_batch_device.argtypes = [vp, vp, vp, vp, vp, i, i, vp]
@@ -966,6 +982,83 @@ def pose_optimize_batch(jobs, device=0):
         arr[j].report = C.pointer(rep)
     _check(lib().orbx_pose_optimize_batch(device, arr, nj))
     return [_pose_result(k[4], k[5], arr[j].n_inliers, k[6]) for j, k in enumerate(keep)]
+
+
+def _tri_view(v, who):
+    """dict(Tcw 3 x 4 (or 4 x 4: the top rows), Ow[3], fx, fy, cx, cy, invfx, invfy, mb, mbf) -> TriView"""
+    T = np.ascontiguousarray(v["Tcw"], np.float32).reshape(-1)
+    ow = np.ascontiguousarray(v["Ow"], np.float32).reshape(-1)
+    if len(T) not in (12, 16) or len(ow) != 3:
+        raise OrbxError(-1, f"{who}: a view needs Tcw 3 x 4 (or 4 x 4) and Ow[3]")
+    return TriView((C.c_float * 12)(*T[:12]), (C.c_float * 3)(*ow), *[float(v[k]) for k in ("fx", "fy", "cx", "cy", "invfx", "invfy", "mb", "mbf")])
+
+
+def _tri_feats(k, who):
+    """dict(x, y, octave, u_right[, depth, raw_x, raw_y]) -> (TriFeats, the arrays it points into)"""
+    keep = [np.ascontiguousarray(k["x"], np.float32), np.ascontiguousarray(k["y"], np.float32), np.ascontiguousarray(k["octave"], np.int32),
+            np.ascontiguousarray(k["u_right"], np.float32)]
+    n = len(keep[0])
+    for name in ("depth", "raw_x", "raw_y"):
+        a = k.get(name)
+        keep.append(None if a is None else np.ascontiguousarray(a, np.float32))
+    if any(a is not None and (a.ndim != 1 or len(a) != n) for a in keep):
+        raise OrbxError(-1, f"{who}: the arrays of a keyframe need one entry per feature")
+    return TriFeats(n, *[_p(a) for a in keep]), keep
+
+
+def _tri_lists(n2, pairs, npairs, scaleFactors, levelSigma2, who):
+    """pairs [n2][2*cap] (or [n2][cap][2]) int32 and npairs[n2] as SearchForTriangulationBatch's ABI call returns them"""
+    pr = np.ascontiguousarray(pairs, np.int32)
+    npr = np.ascontiguousarray(npairs, np.int32).reshape(-1)
+    if pr.size == 0 or len(npr) != n2 or n2 == 0 or pr.size % (2 * n2):
+        raise OrbxError(-1, f"{who}: pairs is [n2][2*cap] with cap >= 1 and npairs [n2], n2 = {n2} keyframes >= 1")
+    sf = np.ascontiguousarray(scaleFactors, np.float32).reshape(-1); sg = np.ascontiguousarray(levelSigma2, np.float32).reshape(-1)
+    if len(sf) != len(sg):
+        raise OrbxError(-1, f"{who}: scaleFactors and levelSigma2 are one table of levels each")
+    cap = pr.size // (2 * n2)
+    return pr, npr, cap, sf, sg, np.zeros((n2, cap), np.uint8), np.zeros((n2, cap, 3), np.float32)
+
+
+def triangulate_pairs(k1, v1, k2s, v2s, pairs, npairs, scaleFactors, levelSigma2, ratioFactor, device=0):
+    """The match loop body of LocalMapping::CreateNewMapPoints (orbx_triangulate_pairs): k1 / k2s[i] = dict(x, y, octave, u_right[, depth,
+    raw_x, raw_y]), v1 / v2s[i] = dict(Tcw, Ow, fx, fy, cx, cy, invfx, invfy, mb, mbf), pairs[n2][2*cap], npairs[n2]
+    -> (status[n2][cap], x3d[n2][cap][3], n_new); rows are written up to npairs[i]"""
+    who = "triangulate_pairs"
+    n2 = len(k2s)
+    if len(v2s) != n2:
+        raise OrbxError(-1, f"{who}: {n2} keyframes, {len(v2s)} views")
+    pr, npr, cap, sf, sg, status, x3d = _tri_lists(n2, pairs, npairs, scaleFactors, levelSigma2, who)
+    f1, keep1 = _tri_feats(k1, who)
+    fs = [_tri_feats(k, who) for k in k2s]
+    ptrs = (C.POINTER(TriFeats) * n2)(*[C.pointer(f[0]) for f in fs])
+    views = (TriView * n2)(*[_tri_view(v, who) for v in v2s])
+    n_new = C.c_int()
+    _check(lib().orbx_triangulate_pairs(device, C.byref(f1), C.byref(_tri_view(v1, who)), ptrs, views, n2, _p(pr), cap, _p(npr), _p(sf), _p(sg),
+                                        len(sf), float(ratioFactor), _p(status), _p(x3d), C.byref(n_new)))
+    return status, x3d, n_new.value
+
+
+def frame_set_depth(frame, depth, raw_x=None, raw_y=None):
+    """orbx_frame_set_depth: mvDepth and, where they differ from the undistorted ones, the raw positions of a DeviceFrame; once per frame"""
+    arrs = [None if a is None else np.ascontiguousarray(a, np.float32).reshape(-1) for a in (depth, raw_x, raw_y)]
+    if any(a is not None and len(a) != frame.n for a in arrs):
+        raise OrbxError(-1, f"frame_set_depth: the frame has {frame.n} features")
+    _check(lib().orbx_frame_set_depth(frame._h, *[_p(a) for a in arrs]))
+
+
+def frame_triangulate(k1, v1, k2s, v2s, pairs, npairs, scaleFactors, levelSigma2, ratioFactor):
+    """triangulate_pairs on DeviceFrames (orbx_frame_triangulate): only the views and the pair lists go up"""
+    who = "frame_triangulate"
+    n2 = len(k2s)
+    if len(v2s) != n2:
+        raise OrbxError(-1, f"{who}: {n2} keyframes, {len(v2s)} views")
+    pr, npr, cap, sf, sg, status, x3d = _tri_lists(n2, pairs, npairs, scaleFactors, levelSigma2, who)
+    hs = (C.c_void_p * n2)(*[k._h for k in k2s])
+    views = (TriView * n2)(*[_tri_view(v, who) for v in v2s])
+    n_new = C.c_int()
+    _check(lib().orbx_frame_triangulate(k1._h, C.byref(_tri_view(v1, who)), hs, views, n2, _p(pr), cap, _p(npr), _p(sf), _p(sg), len(sf),
+                                        float(ratioFactor), _p(status), _p(x3d), C.byref(n_new)))
+    return status, x3d, n_new.value
 
 
 def _pose_cam(pose, cam, who):
