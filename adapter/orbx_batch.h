@@ -6,6 +6,8 @@
 //     for each of 10-20 neighbour keyframes: ComputeF12 + matcher.SearchForTriangulation(mpCurrentKeyFrame, pKF2, F12, vMatchedIndices, false)
 //   LoopClosing::ComputeSim3, src/LoopClosing.cc:293-323                      SearchByBoWBatch(cur, candidates, ...)
 //     for each loop candidate: matcher.SearchByBoW(mpCurrentKF, pKF, vvpMapPointMatches[i])
+//   LoopClosing::ComputeSim3, src/LoopClosing.cc:343-400                      Sim3SolverBatch(vpSim3Solvers)   (adapter/sim3/Sim3Solver.h)
+//     for each loop candidate, five at a time: pSolver->iterate(5, ...) -- every hypothesis of every solver in one launch, then replayed
 //   Tracking::Relocalization, src/Tracking.cc:1661-1682                       SearchByBoWBatch(candidates, mCurrentFrame, ...)
 //     for each relocalisation candidate: matcher.SearchByBoW(pKF, mCurrentFrame, vvpMapPointMatches[i])
 //

@@ -898,6 +898,78 @@ int orbx_frame_triangulate(const orbx_frame *k1, const orbx_tri_view *v1, const 
                            int n2, const int32_t *pairs, int cap, const int *npairs, const float *scale_factors,
                            const float *level_sigma2, int nlevels, float ratio_factor, uint8_t *status, float *x3d, int *n_new);
 
+/* ---- Sim3Solver: the hypotheses of LoopClosing::ComputeSim3's RANSAC (src/Sim3Solver.cc:233-433) ----------------------
+ * Sim3Solver::iterate draws three correspondences, solves Horn's closed form on them (ComputeSim3), reprojects EVERY
+ * correspondence both ways (CheckInliers) and counts.  The early return and the best-so-far bookkeeping of iterate depend on the
+ * order of the hypotheses and cost nothing; they stay on the host.  The device evaluates the WHOLE TABLE of hypotheses of a
+ * solver -- of every solver of a ComputeSim3 call -- in one launch (k_sim3: one wave per hypothesis, one lane per point, the
+ * ballot of the inlier test is the mask word), and the host replays iterate over the table (adapter/sim3, Sim3Ransac in orbx.py).
+ * The arithmetic follows the C++ types of the reference text; every operation is rounded on its own (no fused multiply-add).
+ * "dotd(a, b)" is ((double)a0*b0 + (double)a1*b1) + (double)a2*b2, cast to float ONCE where a cv::Mat product stores it.
+ *   points   P1 / P2 = the three sampled columns of X1 / X2 (:176-177), in the order of the sample row.
+ *   centroid O[r] = (float)((double)((P[r][0] + P[r][1]) + P[r][2]) * (1.0 / 3.0)), the sum in float (cv::reduce, then C / P.cols);
+ *            Pr[r][i] = P[r][i] - O[r] in float (:219-228).
+ *   M        M[r][c] = (float)dotd(Pr2.row(r), Pr1.row(c)) (:250).
+ *   N        the ten entries of :258-267 as sums and differences of FLOATS, left to right, the leading minus first ((-M00) + M11) -
+ *            M22; the double variables of the text hold float values, N stores them as float.
+ *   eigen    cv::eigen(N) is restated as a cyclic Jacobi in float on the upper triangle A = N, diagonal W[i] = A[i][i], V = I
+ *            (eigenvectors are V's rows).  Sweeps over the pivots (k, l), k < l, in lexicographic order.  With p = A[k][l] the
+ *            pivot is skipped when (double)p * p <= 2^-46 * |(double)W[k] * W[l]| (|p| <= FLT_EPSILON * sqrt|W[k] W[l]|, evaluated
+ *            exactly) -- this is the stopping test: a sweep that skipped all six pivots ends the iteration, which runs 30 sweeps
+ *            at most.  Otherwise, in float, hyp(a, b) = (float)sqrt((double)a*a + (double)b*b) where OpenCV calls hypot:
+ *            y = (W[l] - W[k]) * 0.5; t = |y| + hyp(p, y); s = hyp(p, t); c = t / s; s = p / s; t = (p / t) * p; y < 0 negates s
+ *            and t; A[k][l] = 0; W[k] -= t; W[l] += t; then rot(a, b) = (a*c - b*s, a*s + b*c) on (A[i][k], A[i][l]) for i < k,
+ *            (A[k][i], A[i][l]) for k < i < l, (A[k][i], A[l][i]) for i > l and (V[k][i], V[l][i]) for every i (the shape of
+ *            OpenCV's JacobiImpl_, which picks the largest pivot instead of sweeping).  q = the row of V of the LARGEST W, and of
+ *            equal ones the EARLIER (cv::eigen sorts descending; the reference reads evec.row(0)).  The sign of q cancels below.
+ *   rotation a STATED DEVIATION at rounding level: the reference goes q -> atan2 -> angle-axis -> cv::Rodrigues (:281-291), and no
+ *            device matches the C library's atan2, sin and cos bit for bit.  The same rotation is evaluated algebraically: with
+ *            (w, x, y, z) = q widened to double, every product formed once in double and n2 = ((ww + xx) + yy) + zz,
+ *              R00 = (((ww + xx) - yy) - zz) / n2   R01 = (2 (xy - wz)) / n2             R02 = (2 (xz + wy)) / n2
+ *              R10 = (2 (xy + wz)) / n2             R11 = (((ww - xx) + yy) - zz) / n2   R12 = (2 (yz - wx)) / n2
+ *              R20 = (2 (xz - wy)) / n2             R21 = (2 (yz + wx)) / n2             R22 = (((ww - xx) - yy) + zz) / n2
+ *            each cast to float.  It depends on q's direction only, as the reference's does.
+ *   degenerate  x == y == z == 0 exactly (norm(vec) == 0: the reference divides by it and every entry becomes NaN): n_inliers =
+ *            0, the mask is 0 and all 13 floats of srt are the quiet NaN 0x7fc00000, with fix_scale too.  Nothing else is special-
+ *            cased: a NaN or infinite s, R or t makes every comparison below false, which is the reference's outcome.
+ *   scale    P3[r][i] = (float)dotd(R.row(r), Pr2.col(i)) (:295).  nom = sum of (double)Pr1[r][i] * (double)P3[r][i], den = sum of
+ *            (double)(P3[r][i] * P3[r][i]) -- the square in FLOAT (cv::pow) -- both from 0.0 in row-major order; ms12i =
+ *            (float)(nom / den), or 1.0f with fix_scale (:299-318).
+ *   t12      mt12i[r] = (float)((double)O1[r] - (double)ms12i * dotd(R.row(r), O2)) (:323: one gemm, one cast).
+ *   T12, T21 sR[r][c] = (float)((double)ms12i * (double)R[r][c]); sRinv[r][c] = (float)((1.0 / (double)ms12i) * (double)R[c][r]);
+ *            tinv[r] = (float)(-dotd(sRinv.row(r), mt12i)) (:330-343).
+ *   Project  (:389-410) Pc[r] = (float)(dotd(sR.row(r), X) + (double)t[r]); invz = 1 / Pc[2], a FLOAT division; x = Pc[0] * invz,
+ *            y = Pc[1] * invz; u = fx * x + cx, v = fy * y + cy, left to right in float.  FromCameraToImage (:414-433) is the same
+ *            from X itself.  A point behind the camera projects mirrored, as in the reference; z == 0 gives a non-finite error.
+ *   inliers  err1 = |P1im1 - Project(X2, T12, K1)|^2, err2 = |Project(X1, T21, K2) - P2im2|^2, each difference in float and the two
+ *            squares summed as (float)((double)d0*d0 + (double)d1*d1); inlier = err1 < max_err1[i] && err2 < max_err2[i], strict
+ *            and false for NaN (:355-370).
+ *   size_t   include/Sim3Solver.h:78-79 declares mvnMaxError1/2 as vector<size_t>, so push_back(9.210 * sigmaSquare) (:87-88)
+ *            TRUNCATES: the threshold the comparison sees is (float)(size_t)(9.210 * (double)sigma2) -- 9 at level 0, not 9.21.
+ *            The caller computes it so; max_err1 / max_err2 take the resulting float.
+ * Against OpenCV's own arithmetic (its reduce, gemm and dot kernels differ by build, and JacobiImpl_ pivots differently) this
+ * restatement is unpinned: DESIGN.md. */
+typedef struct {
+    int n;                          /* correspondences, Sim3Solver's N: 3 .. 65535 */
+    const float *X1, *X2;           /* [n][3] mvX3Dc1 / mvX3Dc2: the points in camera 1 / camera 2 coordinates */
+    const float *max_err1, *max_err2; /* [n] mvnMaxError1/2 as the float the comparison sees ("size_t" above) */
+    float K1[4], K2[4];             /* fx fy cx cy */
+    int fix_scale;                  /* mbFixScale */
+    int n_hyp;                      /* hypotheses to evaluate: 1 .. 1024 */
+    const int32_t *samples;         /* [n_hyp][3] indices into 0 .. n-1, the three of a row distinct */
+    /* out */
+    int32_t *n_inliers;             /* [n_hyp] mnInliersi */
+    float *srt;                     /* [n_hyp][13] ms12i, mR12i row major, mt12i */
+    uint64_t *inlier_bits;          /* [n_hyp][(n+63)/64] bit i%64 of word i/64 = mvbInliersi[i]; bits >= n are 0 */
+} orbx_sim3_job;
+/* One upload, one launch, one download.  ORBX_E_INVALID before any device work: a NULL job or array, n outside [3, 65535], n_hyp
+ * outside [1, 1024], a sample index outside [0, n), a row of samples with two equal indices. */
+int orbx_sim3_hypotheses(int device, orbx_sim3_job *job);
+/* The solvers of one ComputeSim3 call as ONE upload, ONE launch, ONE download; every job's results are byte-equal to its single
+ * call.  ORBX_E_INVALID: njobs outside [1, 64], any refusal of the single call in any job; ORBX_E_CAPACITY: more than 2^22 mask
+ * words in all. */
+int orbx_sim3_hypotheses_batch(int device, orbx_sim3_job *jobs, int njobs);
+
 /* ORBmatcher::SearchByProjection(Frame &CurrentFrame, const Frame &LastFrame, th, bMono) (src/ORBmatcher.cc:1396-1553;
  * Tracking::TrackWithMotionModel).  direction: 0 none, 1 bForward, 2 bBackward (:1412-1413).  match_cur[cur->n] =
  * index of the point each current feature finally holds (-1 none); *nmatches = the reference's return value

@@ -342,6 +342,17 @@ struct TriHead {
 // octave outside [0, nlevels); d_first[keyframe 1's n] must hold values > 63 (the call fills it with 0x7f bytes)
 ORBX_LOCAL void orbx_triangulate_launch(const TriHead *d_head, const int32_t *d_pairs, int total, uint8_t *d_status, float *d_x3d, int *d_bad,
                                         int *d_first, hipStream_t s);
+// orbx_sim3.hip: one job of k_sim3 (Sim3Solver's hypotheses).  Every pointer is a device address.  first = the number of this job's
+// first wave: wave first + h evaluates hypothesis h; the jobs of a call are in rising order of it.
+struct Sim3Job {
+    int n, n_hyp, fix_scale, first;
+    const float *X1, *X2, *max_err1, *max_err2;
+    const int32_t *samples;
+    int32_t *n_inliers; float *srt; uint64_t *inlier_bits;
+    float K1[4], K2[4];
+};
+// k_sim3 on stream s: total = the hypotheses of all jobs, one wave each
+ORBX_LOCAL void orbx_sim3_launch(const Sim3Job *d_jobs, int njobs, int total, hipStream_t s);
 // the kernel error flag: the int behind the level counts (set by k_tree, handed on by k_desc, read and cleared by orbx_sync)
 static inline int *orbx_err_flag(const orbx_extractor *e) { return e->d_lvl_cnt + (size_t)e->max_batch * ORBX_MAX_LEVELS; }
 void orbx_prof_begin(orbx_extractor *e, int stage, hipStream_t s);

@@ -2162,3 +2162,99 @@ extern "C" int orbx_frame_triangulate(const orbx_frame *k1, const orbx_tri_view 
         }
     }, fr, n2 + 1);
 }
+
+// ---------------------------------------------------------------- Sim3Solver's hypotheses (include/orbx.h: orbx_sim3_hypotheses)
+// The kernel and its arithmetic are in orbx_sim3.hip; here are the refusals, the staging (the pose optimisation's: one blob up, one
+// block down) and the delivery of the two calls.
+
+static int sim3_check(const char *who, int j, const orbx_sim3_job &J)
+{
+    if (!J.X1 || !J.X2 || !J.max_err1 || !J.max_err2 || !J.samples || !J.n_inliers || !J.srt || !J.inlier_bits) {
+        orbx_set_error("%s: job %d: a NULL array", who, j);
+        return ORBX_E_INVALID;
+    }
+    if (J.n < 3 || J.n > 65535) { orbx_set_error("%s: job %d: n = %d outside [3, 65535]", who, j, J.n); return ORBX_E_INVALID; }
+    if (J.n_hyp < 1 || J.n_hyp > 1024) { orbx_set_error("%s: job %d: n_hyp = %d outside [1, 1024]", who, j, J.n_hyp); return ORBX_E_INVALID; }
+    for (int h = 0; h < J.n_hyp; h++) {
+        const int32_t *s = J.samples + 3 * (size_t)h;
+        if (s[0] < 0 || s[0] >= J.n || s[1] < 0 || s[1] >= J.n || s[2] < 0 || s[2] >= J.n) {
+            orbx_set_error("%s: job %d: hypothesis %d: a sample index outside [0, %d)", who, j, h, J.n);
+            return ORBX_E_INVALID;
+        }
+        if (s[0] == s[1] || s[0] == s[2] || s[1] == s[2]) {
+            orbx_set_error("%s: job %d: hypothesis %d: two equal sample indices", who, j, h);
+            return ORBX_E_INVALID;
+        }
+    }
+    return ORBX_OK;
+}
+
+static int sim3_run(const char *who, int device, orbx_sim3_job *jobs, int njobs)
+{
+    if (!jobs || njobs < 1 || njobs > 64) { orbx_set_error("%s: invalid argument (jobs, 1 <= njobs <= 64)", who); return ORBX_E_INVALID; }
+    size_t words = 0, total = 0;
+    for (int j = 0; j < njobs; j++) {
+        const int rc = sim3_check(who, j, jobs[j]);
+        if (rc) return rc;
+        words += (size_t)jobs[j].n_hyp * (((size_t)jobs[j].n + 63) / 64);
+        total += (size_t)jobs[j].n_hyp;
+    }
+    if (words > ((size_t)1 << 22)) { orbx_set_error("%s: %zu mask words in all, more than 2^22", who, words); return ORBX_E_CAPACITY; }
+    ProjCtx *c;
+    int rc = orbx_ctx_get(g_proj, device, &c);
+    if (rc) return rc;
+    const size_t jobs_b = a16(sizeof(Sim3Job) * (size_t)njobs);
+    size_t blob = jobs_b, out = 0;
+    for (int j = 0; j < njobs; j++) {
+        const size_t n = (size_t)jobs[j].n, nh = (size_t)jobs[j].n_hyp;
+        blob += 2 * a16(12 * n) + 2 * a16(4 * n) + a16(12 * nh);
+        out += a16(4 * nh) + a16(52 * nh) + a16(8 * nh * ((n + 63) / 64));
+    }
+    if ((rc = pose_reserve(c, blob, out))) return rc;
+    uint8_t *h = c->h_blob;
+    const uint8_t *d = c->d_blob;
+    Sim3Job *hj = (Sim3Job *)h;
+    size_t o = jobs_b, oo = 0;
+    int first = 0;
+    for (int j = 0; j < njobs; j++) {
+        const orbx_sim3_job &in = jobs[j];
+        const size_t n = (size_t)in.n, nh = (size_t)in.n_hyp;
+        auto put = [&](const void *src, size_t bytes) { const size_t at = o; o += a16(bytes); memcpy(h + at, src, bytes); return d + at; };
+        auto res = [&](size_t bytes) { const size_t at = oo; oo += a16(bytes); return c->d_work + at; };
+        Sim3Job &J = hj[j];
+        memset(&J, 0, sizeof J);
+        J.n = in.n; J.n_hyp = in.n_hyp; J.fix_scale = in.fix_scale ? 1 : 0; J.first = first;
+        first += in.n_hyp;
+        J.X1 = (const float *)put(in.X1, 12 * n); J.X2 = (const float *)put(in.X2, 12 * n);
+        J.max_err1 = (const float *)put(in.max_err1, 4 * n); J.max_err2 = (const float *)put(in.max_err2, 4 * n);
+        J.samples = (const int32_t *)put(in.samples, 12 * nh);
+        J.n_inliers = (int32_t *)res(4 * nh); J.srt = (float *)res(52 * nh); J.inlier_bits = (uint64_t *)res(8 * nh * ((n + 63) / 64));
+        memcpy(J.K1, in.K1, sizeof J.K1); memcpy(J.K2, in.K2, sizeof J.K2);
+    }
+    ORBX_HIP(hipMemcpyAsync(c->d_blob, c->h_blob, blob, hipMemcpyHostToDevice, c->stream));
+    orbx_sim3_launch((const Sim3Job *)c->d_blob, njobs, (int)total, c->stream);
+    ORBX_HIP(hipGetLastError());
+    ORBX_HIP(hipMemcpyAsync(c->h_out, c->d_work, out, hipMemcpyDeviceToHost, c->stream));
+    ORBX_HIP(hipStreamSynchronize(c->stream));
+    const uint8_t *ho = (const uint8_t *)c->h_out;
+    oo = 0;
+    for (int j = 0; j < njobs; j++) {
+        const orbx_sim3_job &in = jobs[j];
+        const size_t nh = (size_t)in.n_hyp, wb = 8 * nh * (((size_t)in.n + 63) / 64);
+        memcpy(in.n_inliers, ho + oo, 4 * nh); oo += a16(4 * nh);
+        memcpy(in.srt, ho + oo, 52 * nh); oo += a16(52 * nh);
+        memcpy(in.inlier_bits, ho + oo, wb); oo += a16(wb);
+    }
+    return ORBX_OK;
+}
+
+extern "C" int orbx_sim3_hypotheses(int device, orbx_sim3_job *job)
+{
+    if (!job) { orbx_set_error("orbx_sim3_hypotheses: a NULL job"); return ORBX_E_INVALID; }
+    return sim3_run("orbx_sim3_hypotheses", device, job, 1);
+}
+
+extern "C" int orbx_sim3_hypotheses_batch(int device, orbx_sim3_job *jobs, int njobs)
+{
+    return sim3_run("orbx_sim3_hypotheses_batch", device, jobs, njobs);
+}

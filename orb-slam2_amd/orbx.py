@@ -144,6 +144,13 @@ class TriFeats(C.Structure):
                 ("raw_x", C.c_void_p), ("raw_y", C.c_void_p)]
 
 
+class Sim3Job(C.Structure):
+    """orbx_sim3_job (include/orbx.h)"""
+    _fields_ = [("n", C.c_int), ("X1", C.c_void_p), ("X2", C.c_void_p), ("max_err1", C.c_void_p), ("max_err2", C.c_void_p),
+                ("K1", C.c_float * 4), ("K2", C.c_float * 4), ("fix_scale", C.c_int), ("n_hyp", C.c_int), ("samples", C.c_void_p),
+                ("n_inliers", C.c_void_p), ("srt", C.c_void_p), ("inlier_bits", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -252,6 +259,8 @@ def lib():
                                          vp, vp, i, f, vp, vp, ip]
     L.orbx_frame_set_depth.argtypes = [vp, vp, vp, vp]
     L.orbx_frame_triangulate.argtypes = [vp, C.POINTER(TriView), C.POINTER(vp), C.POINTER(TriView), i, vp, i, vp, vp, vp, i, f, vp, vp, ip]
+    L.orbx_sim3_hypotheses.argtypes = [i, C.POINTER(Sim3Job)]
+    L.orbx_sim3_hypotheses_batch.argtypes = [i, C.POINTER(Sim3Job), i]
     L.orbx_bow_frames_create.argtypes = [i, i, i, C.POINTER(vp)]
     L.orbx_bow_frames_destroy.argtypes = [vp]; L.orbx_bow_frames_destroy.restype = None
     L.orbx_bow_transform_batch_device.argtypes = [vp, vp, vp, vp, vp, i, i, vp]
@@ -1059,6 +1068,127 @@ def frame_triangulate(k1, v1, k2s, v2s, pairs, npairs, scaleFactors, levelSigma2
     _check(lib().orbx_frame_triangulate(k1._h, C.byref(_tri_view(v1, who)), hs, views, n2, _p(pr), cap, _p(npr), _p(sf), _p(sg), len(sf),
                                         float(ratioFactor), _p(status), _p(x3d), C.byref(n_new)))
     return status, x3d, n_new.value
+
+
+def _sim3_job(job, who):
+    """dict(X1[n][3], X2[n][3], max_err1[n], max_err2[n], K1[4], K2[4], fix_scale, samples[n_hyp][3]) -> (Sim3Job, inputs, outputs)"""
+    X1, X2 = np.ascontiguousarray(job["X1"], np.float32), np.ascontiguousarray(job["X2"], np.float32)
+    e1, e2 = np.ascontiguousarray(job["max_err1"], np.float32).reshape(-1), np.ascontiguousarray(job["max_err2"], np.float32).reshape(-1)
+    sa = np.ascontiguousarray(job["samples"], np.int32)
+    k1, k2 = np.asarray(job["K1"], np.float32).reshape(-1), np.asarray(job["K2"], np.float32).reshape(-1)
+    n = len(X1)
+    if X1.shape != (n, 3) or X2.shape != (n, 3) or len(e1) != n or len(e2) != n or sa.ndim != 2 or sa.shape[1] != 3 or len(k1) != 4 or len(k2) != 4:
+        raise OrbxError(-1, f"{who}: X1, X2 [n][3], max_err1, max_err2 [n], samples [n_hyp][3], K1, K2 [4]")
+    nh = len(sa)
+    out = (np.zeros(nh, np.int32), np.zeros((nh, 13), np.float32), np.zeros((nh, (n + 63) // 64), np.uint64))
+    J = Sim3Job(n, _p(X1), _p(X2), _p(e1), _p(e2), (C.c_float * 4)(*k1), (C.c_float * 4)(*k2), int(bool(job["fix_scale"])), nh, _p(sa),
+                *[_p(a) for a in out])
+    return J, (X1, X2, e1, e2, sa), out
+
+
+def sim3_hypotheses(job, device=0):
+    """Sim3Solver's ComputeSim3 + CheckInliers for every sample row of one solver (orbx_sim3_hypotheses): job = dict(X1, X2, max_err1,
+    max_err2, K1, K2, fix_scale, samples) -> (n_inliers[n_hyp] int32, srt[n_hyp][13] float32, inlier_bits[n_hyp][(n+63)/64] uint64)"""
+    J, keep, out = _sim3_job(job, "sim3_hypotheses")
+    _check(lib().orbx_sim3_hypotheses(device, C.byref(J)))
+    return out
+
+
+def sim3_hypotheses_batch(jobs, device=0):
+    """orbx_sim3_hypotheses_batch: the solvers of one ComputeSim3 call in one upload, one launch, one download -> [as sim3_hypotheses]"""
+    nj = len(jobs)
+    arr = (Sim3Job * max(nj, 1))()
+    keep = []
+    for j, job in enumerate(jobs):
+        J, k, out = _sim3_job(job, "sim3_hypotheses_batch")
+        arr[j] = J
+        keep.append((J, k, out))
+    _check(lib().orbx_sim3_hypotheses_batch(device, arr, nj))
+    return [k[2] for k in keep]
+
+
+def sim3_max_error(sigma2):
+    """mvnMaxError1/2 (reference include/Sim3Solver.h:78-79 keeps 9.210 * sigma2 in a vector<size_t>): the float the comparison sees"""
+    return np.float32(int(9.210 * float(np.float32(sigma2))))
+
+
+class Sim3Ransac:
+    """Sim3Solver's RANSAC state machine (reference src/Sim3Solver.cc:117-217) over a table of hypotheses: the first iterate() or find()
+    evaluates every row of `samples` (at least mRansacMaxIts of them) on the device, in one call, and every call replays the reference's
+    loop over the table.  job as sim3_hypotheses; indices1 = mvnIndices1 and n_matches = mN1 scatter the inliers as the reference does.
+    sim3_hypotheses_batch([r.job for r in solvers]) + r.set_table(...) evaluates several solvers in one launch."""
+
+    def __init__(self, job, indices1=None, n_matches=None, probability=0.99, min_inliers=6, max_iterations=300, device=0):
+        self.job, self.device = job, device
+        self.N = len(job["X1"])
+        self.indices1 = np.arange(self.N) if indices1 is None else np.asarray(indices1, np.int64)
+        self.mN1 = self.N if n_matches is None else int(n_matches)
+        self.table = None
+        self.best_inliers, self.best = 0, None
+        self.set_ransac_parameters(probability, min_inliers, max_iterations)
+
+    def set_ransac_parameters(self, probability=0.99, min_inliers=6, max_iterations=300):
+        import math
+        self.min_inliers = min_inliers
+        n_it = 1
+        if min_inliers != self.N:
+            with np.errstate(all="ignore"):
+                eps = np.float32(min_inliers) / np.float32(self.N)
+                x = np.log(np.float64(1.0) - np.float64(probability)) / np.log(np.float64(1.0) - np.float64(eps) ** 3)
+            n_it = int(math.ceil(float(x))) if np.isfinite(x) else -2 ** 31
+        self.max_its = max(1, min(n_it, max_iterations))
+        self.iterations = 0
+        self.table = None
+
+    def set_table(self, table):
+        self.table = table
+
+    def _row(self, k):
+        ni, srt, bits = self.table
+        inl = np.unpackbits(np.ascontiguousarray(bits[k], "<u8").view(np.uint8), bitorder="little")[:self.N].astype(bool)
+        return int(ni[k]), srt[k], inl
+
+    def iterate(self, n_iterations):
+        """-> (T12 4 x 4 float32 or None, bNoMore, vbInliers[mN1], nInliers)"""
+        vb = np.zeros(self.mN1, bool)
+        if self.N < self.min_inliers:
+            return None, True, vb, 0
+        if self.table is None:
+            if len(self.job["samples"]) < self.max_its:
+                raise OrbxError(-1, f"Sim3Ransac: {len(self.job['samples'])} sample rows for {self.max_its} iterations")
+            self.table = sim3_hypotheses(dict(self.job, samples=np.asarray(self.job["samples"])[:self.max_its]), self.device)
+        cur = 0
+        while self.iterations < self.max_its and cur < n_iterations:
+            cur += 1
+            self.iterations += 1
+            ni, srt, inl = self._row(self.iterations - 1)
+            if ni >= self.best_inliers:
+                self.best_inliers, self.best = ni, (srt.copy(), inl)
+                if ni > self.min_inliers:
+                    vb[self.indices1[inl]] = True
+                    return self.T12(srt), False, vb, ni
+        return None, self.iterations >= self.max_its, vb, 0
+
+    def find(self):
+        T, _, vb, ni = self.iterate(self.max_its)
+        return T, vb, ni
+
+    @staticmethod
+    def T12(srt):
+        T = np.eye(4, dtype=np.float32)
+        with np.errstate(all="ignore"):
+            T[:3, :3] = (np.float64(srt[0]) * srt[1:10].astype(np.float64)).astype(np.float32).reshape(3, 3)
+        T[:3, 3] = srt[10:13]
+        return T
+
+    def estimated_scale(self):
+        return self.best[0][0]
+
+    def estimated_rotation(self):
+        return self.best[0][1:10].reshape(3, 3).copy()
+
+    def estimated_translation(self):
+        return self.best[0][10:13].copy()
 
 
 def _pose_cam(pose, cam, who):
