@@ -262,7 +262,7 @@ __device__ __forceinline__ void three_maxima(const int *hist, int *i1, int *i2, 
 }
 
 // ---- Frame::UndistortKeyPoints (src/Frame.cc:470-515) on one point: cv::undistortPoints(mat, mat, mK, mDistCoef, cv::Mat(), mK).  Shared by
-// k_undistort (orbx_frame.hip) and the resident-frame ingest (orbx_proj.hip) so that both give the same bits (-ffp-contract=off in both).
+// k_undistort (orbx_frame.hip) and the resident-frame ingest (orbx_resident.hip) so that both give the same bits (-ffp-contract=off in both).
 struct UndistortParams { double fx, fy, ifx, ify, cx, cy, k[5]; };
 
 static inline UndistortParams orbx_undistort_params(float fx, float fy, float cx, float cy, const float *dist_coef, int ndist)

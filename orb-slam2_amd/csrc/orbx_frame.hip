@@ -13,7 +13,7 @@ __global__ __launch_bounds__(256) void k_undistort(const float2 *__restrict__ in
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    out[i] = dev_undistort(in[i], p);   // orbx_device.h: the same arithmetic the resident-frame ingest runs (orbx_proj.hip)
+    out[i] = dev_undistort(in[i], p);   // orbx_device.h: the same arithmetic the resident-frame ingest runs (orbx_resident.hip)
 }
 
 struct FrameCtx : ThreadCtx {

@@ -263,7 +263,7 @@ static inline hipError_t orbx_use_device(int device)
 int orbx_check_device(int device);
 
 // What a thread needs to run per-call searches on one device: its own stream.  The four families (MatchCtx orbx_match.hip, BowCtx
-// orbx_bow.hip, ProjCtx orbx_proj.hip, FrameCtx orbx_frame.hip) derive from it, add their staging buffers, and keep one thread_local array
+// orbx_bow.hip, CallCtx orbx_resident.h / orbx_resident.hip, FrameCtx orbx_frame.hip) derive from it, add their staging buffers, and keep one thread_local array
 // [ORBX_MAX_DEVICES] each.  Each has release(): orbx_ctx_leave, then -- if that says so -- its buffers freed, then every pointer and
 // capacity reset; and a destructor calling release(), so a thread that ends gives everything back.
 struct ThreadCtx { int device = -1; hipStream_t stream = nullptr; };
@@ -283,7 +283,7 @@ static inline int orbx_ctx_get(C (&slots)[ORBX_MAX_DEVICES], int device, C **out
 }
 void orbx_match_thread_release();   // the calling thread's contexts of one family, every device (orbx_thread_release walks the four)
 void orbx_bow_thread_release();
-void orbx_proj_thread_release();
+void orbx_proj_thread_release();    // (the CallCtx family)
 void orbx_frame_thread_release();
 
 // host-side exact arithmetic helpers shared by the .hip files
@@ -310,49 +310,6 @@ ORBX_LOCAL void orbx_desc_launch(orbx_extractor *e, const PyrRef &pr, int batch,
 ORBX_LOCAL int orbx_fast_diag_spans(unsigned *out, int reset);
 ORBX_LOCAL int orbx_desc_diag_spans(unsigned *out, int reset);
 #endif
-// orbx_pose.hip: one job of k_pose_opt (Optimizer::PoseOptimization).  Every pointer is a device address.  The host-pointer calls give
-// inv_sigma2 / Xw / has_point and leave octave / geom / slot NULL; the resident call gives octave (with lvl_isig), the table's geom and
-// slot (a feature has a point where slot >= 0) and leaves the other three NULL.  outlier[n] is the kernel's per-edge state and its output.
-struct PoseJob {
-    int n, nlevels;      // nlevels: entries of lvl_isig (resident form)
-    const float *x, *y, *u_right;
-    const float *inv_sigma2; const int32_t *octave;
-    const float *Xw; const float4 *geom; const int32_t *slot;
-    const uint8_t *has_point;
-    uint8_t *outlier;
-    float lvl_isig[ORBX_MAX_LEVELS];
-    float cam[5];        // fx fy cx cy mbf
-    float Tcw[16];
-};
-struct PoseOut { double pose[12], chi2[4]; float Tcw[16]; int32_t n_corr, rounds, n_bad[4], iterations[4], n_inliers, bad_octave; };
-ORBX_LOCAL void orbx_pose_launch(const PoseJob *d_jobs, PoseOut *d_out, int njobs, hipStream_t s);
-// orbx_triangulate.hip: what k_triangulate reads besides the pair list.  Every pointer is a device address; raw_x / raw_y are x / y and
-// depth is NULL (never read: no stereo feature) where a keyframe has no depth attached.  prefix[i] = pairs of the neighbours before i,
-// prefix[n2] = total; the call uploads the head up to nb[n2].
-struct TriFeat { const float *x, *y, *u_right, *depth, *raw_x, *raw_y; const int32_t *octave; };
-struct TriHead {
-    int n2, total, nlevels;
-    float ratio_factor;
-    int prefix[65];
-    float sf[ORBX_MAX_LEVELS], sigma2[ORBX_MAX_LEVELS];
-    orbx_tri_view v1; TriFeat f1;
-    struct Nb { orbx_tri_view v; TriFeat f; } nb[64];
-};
-// k_triangulate, then the two passes of k_tri_resolve, on stream s: d_status[total], d_x3d[total][3]; *d_bad becomes 1 if a pair names an
-// octave outside [0, nlevels); d_first[keyframe 1's n] must hold values > 63 (the call fills it with 0x7f bytes)
-ORBX_LOCAL void orbx_triangulate_launch(const TriHead *d_head, const int32_t *d_pairs, int total, uint8_t *d_status, float *d_x3d, int *d_bad,
-                                        int *d_first, hipStream_t s);
-// orbx_sim3.hip: one job of k_sim3 (Sim3Solver's hypotheses).  Every pointer is a device address.  first = the number of this job's
-// first wave: wave first + h evaluates hypothesis h; the jobs of a call are in rising order of it.
-struct Sim3Job {
-    int n, n_hyp, fix_scale, first;
-    const float *X1, *X2, *max_err1, *max_err2;
-    const int32_t *samples;
-    int32_t *n_inliers; float *srt; uint64_t *inlier_bits;
-    float K1[4], K2[4];
-};
-// k_sim3 on stream s: total = the hypotheses of all jobs, one wave each
-ORBX_LOCAL void orbx_sim3_launch(const Sim3Job *d_jobs, int njobs, int total, hipStream_t s);
 // the kernel error flag: the int behind the level counts (set by k_tree, handed on by k_desc, read and cleared by orbx_sync)
 static inline int *orbx_err_flag(const orbx_extractor *e) { return e->d_lvl_cnt + (size_t)e->max_batch * ORBX_MAX_LEVELS; }
 void orbx_prof_begin(orbx_extractor *e, int stage, hipStream_t s);

@@ -9,10 +9,26 @@
 // a job's result does not depend on the run or on the other jobs of the launch.
 // Per-edge state is one byte, the outlier flag in the job's output array; the error an active edge "keeps" between rounds (the one of the
 // last evaluated trial, base of the classification at :441-502) is recomputed from that trial's pose, which gives the same bits.
-// The arithmetic is restated in include/orbx.h (orbx_pose_optimize) and, in numpy, in tests/pose_model.py; the host side of the three
-// calls is in orbx_proj.hip, beside the handles it reads.
-#include "orbx_internal.h"
+// The arithmetic is restated in include/orbx.h (orbx_pose_optimize) and, in numpy, in tests/pose_model.py.  Behind the kernel: the
+// refusals, the staging and the delivery of the three calls (pose_check, pose_run, pose_deliver and the entry points).
+#include "orbx_resident.h"
 #include <float.h>
+
+// One job of k_pose_opt.  Every pointer is a device address.  The host-pointer calls give
+// inv_sigma2 / Xw / has_point and leave octave / geom / slot NULL; the resident call gives octave (with lvl_isig), the table's geom and
+// slot (a feature has a point where slot >= 0) and leaves the other three NULL.  outlier[n] is the kernel's per-edge state and its output.
+struct PoseJob {
+    int n, nlevels;      // nlevels: entries of lvl_isig (resident form)
+    const float *x, *y, *u_right;
+    const float *inv_sigma2; const int32_t *octave;
+    const float *Xw; const float4 *geom; const int32_t *slot;
+    const uint8_t *has_point;
+    uint8_t *outlier;
+    float lvl_isig[ORBX_MAX_LEVELS];
+    float cam[5];        // fx fy cx cy mbf
+    float Tcw[16];
+};
+struct PoseOut { double pose[12], chi2[4]; float Tcw[16]; int32_t n_corr, rounds, n_bad[4], iterations[4], n_inliers, bad_octave; };
 
 namespace {
 
@@ -420,7 +436,160 @@ __global__ __launch_bounds__(256) void k_pose_opt(const PoseJob *__restrict__ jo
 
 }   // namespace
 
-void orbx_pose_launch(const PoseJob *d_jobs, PoseOut *d_out, int njobs, hipStream_t s)
+// ---------------------------------------------------------------- host side (include/orbx.h: orbx_pose_optimize)
+
+struct PoseArgs {
+    const orbx_pose_obs *obs; const float *cam, *Tcw;
+    float *Tcw_out; uint8_t *outlier; int *n_inliers; orbx_pose_report *report;
+};
+
+static int pose_check(const char *who, int job, const PoseArgs &a)
 {
-    hipLaunchKernelGGL(k_pose_opt, dim3(njobs), dim3(256), 0, s, d_jobs, d_out);
+    if (!a.obs || !a.cam || !a.Tcw || !a.Tcw_out || !a.n_inliers) { orbx_set_error("%s: job %d: NULL obs, cam, Tcw, Tcw_out or n_inliers", who, job); return ORBX_E_INVALID; }
+    const orbx_pose_obs &o = *a.obs;
+    if (o.n < 0 || o.n > 65535) { orbx_set_error("%s: job %d: n = %d outside [0, 65535]", who, job, o.n); return ORBX_E_INVALID; }
+    if (o.n && (!o.x || !o.y || !o.u_right || !o.inv_sigma2 || !o.Xw || !o.has_point || !a.outlier)) {
+        orbx_set_error("%s: job %d: observation arrays or outlier missing", who, job);
+        return ORBX_E_INVALID;
+    }
+    return ORBX_OK;
+}
+
+// what a job's PoseOut and flag bytes (present(i) says where they count) give the caller
+template <typename Present>
+static void pose_deliver(const PoseOut &o, const uint8_t *flags, int n, const PoseArgs &a, Present present)
+{
+    memcpy(a.Tcw_out, o.Tcw, sizeof o.Tcw);
+    for (int i = 0; i < n; i++)
+        if (present(i)) a.outlier[i] = flags[i];
+    *a.n_inliers = o.n_inliers;
+    if (!a.report) return;
+    orbx_pose_report &r = *a.report;
+    r.n_corr = o.n_corr; r.rounds = o.rounds;
+    for (int k = 0; k < 4; k++) { r.n_bad[k] = o.n_bad[k]; r.iterations[k] = o.iterations[k]; r.chi2[k] = o.chi2[k]; }
+    memcpy(r.pose, o.pose, sizeof o.pose);
+}
+
+// staging of the two forms: up [PoseJob x njobs | the jobs' arrays], down [PoseOut x njobs | the jobs' flag bytes]
+static int pose_launch_and_fetch(CallCtx *c, size_t blob, size_t out, int njobs)
+{
+    int rc = call_upload(c, blob);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_pose_opt, dim3(njobs), dim3(256), 0, c->stream, (const PoseJob *)c->d_blob, (PoseOut *)c->d_work);
+    return call_fetch(c, out);
+}
+
+static int pose_run(const char *who, int device, const PoseArgs *a, int njobs)
+{
+    size_t total = 0;
+    for (int j = 0; j < njobs; j++) {
+        const int rc = pose_check(who, j, a[j]);
+        if (rc) return rc;
+        total += (size_t)a[j].obs->n;
+    }
+    if (total > ((size_t)1 << 22)) { orbx_set_error("%s: %zu features in all, more than 2^22", who, total); return ORBX_E_CAPACITY; }
+    CallCtx *c;
+    int rc = orbx_call_ctx(device, &c);
+    if (rc) return rc;
+    const size_t jobs_b = a16(sizeof(PoseJob) * (size_t)njobs), outs_b = a16(sizeof(PoseOut) * (size_t)njobs);
+    size_t blob = jobs_b, out = outs_b;
+    for (int j = 0; j < njobs; j++) {
+        const size_t n = (size_t)a[j].obs->n;
+        blob += 4 * a16(4 * n) + a16(12 * n) + a16(n);
+        out += a16(n);
+    }
+    if ((rc = call_reserve(c, blob, out, out))) return rc;
+    PoseJob *hj = (PoseJob *)c->h_blob;
+    BlobCursor b = { c->h_blob, c->d_blob, jobs_b };
+    size_t fo = outs_b;
+    for (int j = 0; j < njobs; j++) {
+        const orbx_pose_obs &ob = *a[j].obs;
+        const size_t n = (size_t)ob.n;
+        PoseJob &J = hj[j];
+        memset(&J, 0, sizeof J);
+        J.n = ob.n;
+        J.x = (const float *)b.put(ob.x, 4 * n); J.y = (const float *)b.put(ob.y, 4 * n); J.u_right = (const float *)b.put(ob.u_right, 4 * n);
+        J.inv_sigma2 = (const float *)b.put(ob.inv_sigma2, 4 * n); J.Xw = (const float *)b.put(ob.Xw, 12 * n);
+        J.has_point = b.put(ob.has_point, n);
+        J.outlier = c->d_work + fo;
+        fo += a16(n);
+        memcpy(J.cam, a[j].cam, sizeof J.cam); memcpy(J.Tcw, a[j].Tcw, sizeof J.Tcw);
+    }
+    if ((rc = pose_launch_and_fetch(c, blob, out, njobs))) return rc;
+    const uint8_t *ho = (const uint8_t *)c->h_out;
+    fo = outs_b;
+    for (int j = 0; j < njobs; j++) {
+        const orbx_pose_obs &ob = *a[j].obs;
+        pose_deliver(((const PoseOut *)ho)[j], ho + fo, ob.n, a[j], [&](int i) { return ob.has_point[i] != 0; });
+        fo += a16((size_t)ob.n);
+    }
+    return ORBX_OK;
+}
+
+extern "C" int orbx_pose_optimize(int device, const orbx_pose_obs *obs, const float *cam, const float *Tcw, float *Tcw_out, uint8_t *outlier,
+                                  int *n_inliers, orbx_pose_report *report)
+{
+    const PoseArgs a = { obs, cam, Tcw, Tcw_out, outlier, n_inliers, report };
+    return pose_run("orbx_pose_optimize", device, &a, 1);
+}
+
+extern "C" int orbx_pose_optimize_batch(int device, orbx_pose_job *jobs, int njobs)
+{
+    if (!jobs || njobs < 1 || njobs > 1024) { orbx_set_error("orbx_pose_optimize_batch: invalid argument (1 <= njobs <= 1024)"); return ORBX_E_INVALID; }
+    std::vector<PoseArgs> a((size_t)njobs);
+    for (int j = 0; j < njobs; j++) a[j] = { jobs[j].obs, jobs[j].cam, jobs[j].Tcw, jobs[j].Tcw_out, jobs[j].outlier, &jobs[j].n_inliers, jobs[j].report };
+    return pose_run("orbx_pose_optimize_batch", device, a.data(), njobs);
+}
+
+extern "C" int orbx_frame_pose_optimize(const orbx_frame *cur, const orbx_mappoints *m, const int32_t *slot_of_feature,
+                                        const float *inv_level_sigma2, int nlevels, const float *cam, const float *Tcw, float *Tcw_out,
+                                        uint8_t *outlier, int *n_inliers, orbx_pose_report *report)
+{
+    const char *who = "orbx_frame_pose_optimize";
+    if (!cur || !m || !inv_level_sigma2 || !cam || !Tcw || !Tcw_out || !n_inliers || nlevels < 1 || nlevels > ORBX_MAX_LEVELS ||
+        (cur->n && (!slot_of_feature || !outlier))) {
+        orbx_set_error("%s: invalid argument (a frame, a table, slots and outlier for its features, 1 <= nlevels <= %d, cam, Tcw, Tcw_out, n_inliers)", who, ORBX_MAX_LEVELS);
+        return ORBX_E_INVALID;
+    }
+    if (cur->device != m->device) { orbx_set_error("%s: the frame and the table live on different devices", who); return ORBX_E_INVALID; }
+    std::shared_lock<std::shared_timed_mutex> lk(m->mu);
+    const int n = cur->n;
+    for (int i = 0; i < n; i++) {
+        const int s = slot_of_feature[i];
+        if (s == -1) continue;
+        if (s < 0 || s >= m->capacity) { orbx_set_error("%s: feature %d: slot %d outside [0, %d)", who, i, s, m->capacity); return ORBX_E_INVALID; }
+        if (m->have[s] != 3) { orbx_set_error("%s: feature %d: slot %d is not set", who, i, s); return ORBX_E_INVALID; }
+        if (!cur->h_oct.empty() && (cur->h_oct[i] < 0 || cur->h_oct[i] >= nlevels)) {
+            orbx_set_error("%s: feature %d: octave %d outside [0, %d)", who, i, cur->h_oct[i], nlevels);
+            return ORBX_E_INVALID;
+        }
+    }
+    CallCtx *c;
+    int rc = orbx_call_ctx(cur->device, &c);
+    if (rc) return rc;
+    const size_t nn = (size_t)n, jobs_b = a16(sizeof(PoseJob)), outs_b = a16(sizeof(PoseOut));
+    const size_t blob = jobs_b + a16(4 * nn), out = outs_b + a16(nn);
+    if ((rc = call_reserve(c, blob, out, out))) return rc;
+    PoseJob &J = *(PoseJob *)c->h_blob;
+    memset(&J, 0, sizeof J);
+    const DevFrame F = frame_dev(cur);
+    J.n = n; J.nlevels = nlevels;
+    J.x = F.x; J.y = F.y; J.u_right = F.u_right; J.octave = F.octave;
+    J.geom = m->d_geom; J.slot = (const int32_t *)(c->d_blob + jobs_b);
+    J.outlier = c->d_work + outs_b;
+    memcpy(J.lvl_isig, inv_level_sigma2, sizeof(float) * (size_t)nlevels);
+    memcpy(J.cam, cam, sizeof J.cam); memcpy(J.Tcw, Tcw, sizeof J.Tcw);
+    if (n) memcpy(c->h_blob + jobs_b, slot_of_feature, 4 * nn);
+    if ((rc = frame_order_before(cur, c->stream))) return rc;
+    if ((rc = mappoints_order_before(m, c->stream))) return rc;
+    if ((rc = pose_launch_and_fetch(c, blob, out, 1))) return rc;
+    const uint8_t *ho = (const uint8_t *)c->h_out;
+    const PoseOut &po = *(const PoseOut *)ho;
+    if (po.bad_octave) {   // a frame made from extraction outputs has its octaves on the device only: the kernel checks them first and stops
+        orbx_set_error("%s: a feature with a point has an octave outside [0, %d)", who, nlevels);
+        return ORBX_E_INVALID;
+    }
+    const PoseArgs a = { nullptr, cam, Tcw, Tcw_out, outlier, n_inliers, report };
+    pose_deliver(po, ho + outs_b, n, a, [&](int i) { return slot_of_feature[i] >= 0; });
+    return ORBX_OK;
 }

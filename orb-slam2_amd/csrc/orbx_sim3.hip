@@ -5,9 +5,19 @@
 // T21.  Its lanes then stride over the job's points, 64 at a time: both reprojections, both strict comparisons, and __ballot of the
 // predicate IS the mask word (lane 0 stores it, __popcll adds it to the count).  No LDS, no atomics; a job's points are a few KB that
 // many waves read: L2 serves them.
-// The arithmetic is restated in include/orbx.h (orbx_sim3_hypotheses) and, in numpy, in tests/sim3_model.py; the host side of the two
-// calls is in orbx_proj.hip, beside the staging it shares with the pose optimisation.
-#include "orbx_internal.h"
+// The arithmetic is restated in include/orbx.h (orbx_sim3_hypotheses) and, in numpy, in tests/sim3_model.py.  Behind the kernel: the
+// refusals, the staging (one blob up, one block down) and the delivery of the two calls (sim3_check, sim3_run and the entry points).
+#include "orbx_resident.h"
+
+// One job of k_sim3.  Every pointer is a device address.  first = the number of this job's
+// first wave: wave first + h evaluates hypothesis h; the jobs of a call are in rising order of it.
+struct Sim3Job {
+    int n, n_hyp, fix_scale, first;
+    const float *X1, *X2, *max_err1, *max_err2;
+    const int32_t *samples;
+    int32_t *n_inliers; float *srt; uint64_t *inlier_bits;
+    float K1[4], K2[4];
+};
 
 namespace {
 
@@ -235,7 +245,91 @@ __global__ __launch_bounds__(256) void k_sim3(const Sim3Job *__restrict__ jobs, 
 
 }   // namespace
 
-void orbx_sim3_launch(const Sim3Job *d_jobs, int njobs, int total, hipStream_t s)
+// ---------------------------------------------------------------- host side (include/orbx.h: orbx_sim3_hypotheses)
+
+static int sim3_check(const char *who, int j, const orbx_sim3_job &J)
 {
-    hipLaunchKernelGGL(k_sim3, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, s, d_jobs, njobs, total);
+    if (!J.X1 || !J.X2 || !J.max_err1 || !J.max_err2 || !J.samples || !J.n_inliers || !J.srt || !J.inlier_bits) {
+        orbx_set_error("%s: job %d: a NULL array", who, j);
+        return ORBX_E_INVALID;
+    }
+    if (J.n < 3 || J.n > 65535) { orbx_set_error("%s: job %d: n = %d outside [3, 65535]", who, j, J.n); return ORBX_E_INVALID; }
+    if (J.n_hyp < 1 || J.n_hyp > 1024) { orbx_set_error("%s: job %d: n_hyp = %d outside [1, 1024]", who, j, J.n_hyp); return ORBX_E_INVALID; }
+    for (int h = 0; h < J.n_hyp; h++) {
+        const int32_t *s = J.samples + 3 * (size_t)h;
+        if (s[0] < 0 || s[0] >= J.n || s[1] < 0 || s[1] >= J.n || s[2] < 0 || s[2] >= J.n) {
+            orbx_set_error("%s: job %d: hypothesis %d: a sample index outside [0, %d)", who, j, h, J.n);
+            return ORBX_E_INVALID;
+        }
+        if (s[0] == s[1] || s[0] == s[2] || s[1] == s[2]) {
+            orbx_set_error("%s: job %d: hypothesis %d: two equal sample indices", who, j, h);
+            return ORBX_E_INVALID;
+        }
+    }
+    return ORBX_OK;
+}
+
+static int sim3_run(const char *who, int device, orbx_sim3_job *jobs, int njobs)
+{
+    if (!jobs || njobs < 1 || njobs > 64) { orbx_set_error("%s: invalid argument (jobs, 1 <= njobs <= 64)", who); return ORBX_E_INVALID; }
+    size_t words = 0, total = 0;
+    for (int j = 0; j < njobs; j++) {
+        const int rc = sim3_check(who, j, jobs[j]);
+        if (rc) return rc;
+        words += (size_t)jobs[j].n_hyp * (((size_t)jobs[j].n + 63) / 64);
+        total += (size_t)jobs[j].n_hyp;
+    }
+    if (words > ((size_t)1 << 22)) { orbx_set_error("%s: %zu mask words in all, more than 2^22", who, words); return ORBX_E_CAPACITY; }
+    CallCtx *c;
+    int rc = orbx_call_ctx(device, &c);
+    if (rc) return rc;
+    const size_t jobs_b = a16(sizeof(Sim3Job) * (size_t)njobs);
+    size_t blob = jobs_b, out = 0;
+    for (int j = 0; j < njobs; j++) {
+        const size_t n = (size_t)jobs[j].n, nh = (size_t)jobs[j].n_hyp;
+        blob += 2 * a16(12 * n) + 2 * a16(4 * n) + a16(12 * nh);
+        out += a16(4 * nh) + a16(52 * nh) + a16(8 * nh * ((n + 63) / 64));
+    }
+    if ((rc = call_reserve(c, blob, out, out))) return rc;
+    Sim3Job *hj = (Sim3Job *)c->h_blob;
+    BlobCursor b = { c->h_blob, c->d_blob, jobs_b }, res = { nullptr, c->d_work, 0 };   // the arrays up; the results in the work area
+    int first = 0;
+    for (int j = 0; j < njobs; j++) {
+        const orbx_sim3_job &in = jobs[j];
+        const size_t n = (size_t)in.n, nh = (size_t)in.n_hyp;
+        Sim3Job &J = hj[j];
+        memset(&J, 0, sizeof J);
+        J.n = in.n; J.n_hyp = in.n_hyp; J.fix_scale = in.fix_scale ? 1 : 0; J.first = first;
+        first += in.n_hyp;
+        J.X1 = (const float *)b.put(in.X1, 12 * n); J.X2 = (const float *)b.put(in.X2, 12 * n);
+        J.max_err1 = (const float *)b.put(in.max_err1, 4 * n); J.max_err2 = (const float *)b.put(in.max_err2, 4 * n);
+        J.samples = (const int32_t *)b.put(in.samples, 12 * nh);
+        J.n_inliers = (int32_t *)(res.d + res.take(4 * nh)); J.srt = (float *)(res.d + res.take(52 * nh));
+        J.inlier_bits = (uint64_t *)(res.d + res.take(8 * nh * ((n + 63) / 64)));
+        memcpy(J.K1, in.K1, sizeof J.K1); memcpy(J.K2, in.K2, sizeof J.K2);
+    }
+    if ((rc = call_upload(c, blob))) return rc;
+    hipLaunchKernelGGL(k_sim3, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, c->stream, (const Sim3Job *)c->d_blob, njobs, (int)total);   // one wave per hypothesis
+    if ((rc = call_fetch(c, out))) return rc;
+    const uint8_t *ho = (const uint8_t *)c->h_out;
+    size_t oo = 0;
+    for (int j = 0; j < njobs; j++) {
+        const orbx_sim3_job &in = jobs[j];
+        const size_t nh = (size_t)in.n_hyp, wb = 8 * nh * (((size_t)in.n + 63) / 64);
+        memcpy(in.n_inliers, ho + oo, 4 * nh); oo += a16(4 * nh);
+        memcpy(in.srt, ho + oo, 52 * nh); oo += a16(52 * nh);
+        memcpy(in.inlier_bits, ho + oo, wb); oo += a16(wb);
+    }
+    return ORBX_OK;
+}
+
+extern "C" int orbx_sim3_hypotheses(int device, orbx_sim3_job *job)
+{
+    if (!job) { orbx_set_error("orbx_sim3_hypotheses: a NULL job"); return ORBX_E_INVALID; }
+    return sim3_run("orbx_sim3_hypotheses", device, job, 1);
+}
+
+extern "C" int orbx_sim3_hypotheses_batch(int device, orbx_sim3_job *jobs, int njobs)
+{
+    return sim3_run("orbx_sim3_hypotheses_batch", device, jobs, njobs);
 }

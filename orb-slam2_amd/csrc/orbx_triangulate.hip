@@ -6,9 +6,23 @@
 // every matrix index is a constant).  It writes one status byte and three floats.
 // k_tri_resolve<0 / 1>: first neighbour wins.  Pass 0: a created pair does atomicMin(first[idx1], neighbour); pass 1: a created pair whose
 // neighbour is larger than first[idx1] becomes 32 + status.  An integer minimum does not depend on the order of the threads.
-// The arithmetic is restated in include/orbx.h (orbx_triangulate_pairs) and, in numpy, in tests/triangulate_model.py; the host side of
-// the calls is in orbx_proj.hip, beside the frame handle it reads.
-#include "orbx_internal.h"
+// The arithmetic is restated in include/orbx.h (orbx_triangulate_pairs) and, in numpy, in tests/triangulate_model.py.  Behind the kernels:
+// the refusals, the staging and the delivery of the two calls (tri_check, tri_run and the entry points).
+#include "orbx_resident.h"
+#include <stddef.h>
+
+// What k_triangulate reads besides the pair list.  Every pointer is a device address; raw_x / raw_y are x / y and
+// depth is NULL (never read: no stereo feature) where a keyframe has no depth attached.  prefix[i] = pairs of the neighbours before i,
+// prefix[n2] = total; the call uploads the head up to nb[n2].
+struct TriFeat { const float *x, *y, *u_right, *depth, *raw_x, *raw_y; const int32_t *octave; };
+struct TriHead {
+    int n2, total, nlevels;
+    float ratio_factor;
+    int prefix[65];
+    float sf[ORBX_MAX_LEVELS], sigma2[ORBX_MAX_LEVELS];
+    orbx_tri_view v1; TriFeat f1;
+    struct Nb { orbx_tri_view v; TriFeat f; } nb[64];
+};
 
 namespace {
 
@@ -237,11 +251,192 @@ __global__ __launch_bounds__(256) void k_tri_resolve(const TriHead *__restrict__
 
 }   // namespace
 
-void orbx_triangulate_launch(const TriHead *d_head, const int32_t *d_pairs, int total, uint8_t *d_status, float *d_x3d, int *d_bad, int *d_first,
-                             hipStream_t s)
+// ---------------------------------------------------------------- host side (include/orbx.h: orbx_triangulate_pairs)
+
+// what the host knows of one keyframe of a call (NULL: only the device has it)
+struct TriHostKf { int n; const int32_t *octave; const float *u_right; bool has_depth; };
+
+struct TriArgs {
+    int n2, cap, nlevels;
+    const int32_t *pairs; const int *npairs;
+    const orbx_tri_view *v1, *v2s;
+    const float *sf, *sigma2;
+    float ratio_factor;
+    uint8_t *status; float *x3d; int *n_new;
+};
+
+// the refusals of both forms, in their order: the arguments, the keyframes (host_kfs(h) fills h[0] for k1 and h[1 + i] for k2s[i], or
+// refuses), the pair lists; *total = the pairs of all lists
+template <class HostKfs>
+static int tri_check(const char *who, const void *k1, const void *k2s, const TriArgs &a, HostKfs host_kfs, size_t *total)
 {
+    if (!k1 || !a.v1 || !k2s || !a.v2s || !a.pairs || !a.npairs || !a.sf || !a.sigma2 || !a.status || !a.x3d || !a.n_new || a.n2 < 1 || a.n2 > 64) {
+        orbx_set_error("%s: invalid argument (no NULL argument, 1 <= n2 <= 64)", who);
+        return ORBX_E_INVALID;
+    }
+    TriHostKf h[65];
+    if (const int rc = host_kfs(h)) return rc;
+    const TriHostKf &h1 = h[0], *h2 = h + 1;
+    if (a.cap < 1 || a.nlevels < 1 || a.nlevels > ORBX_MAX_LEVELS) {
+        orbx_set_error("%s: invalid argument (cap >= 1, 1 <= nlevels <= %d)", who, ORBX_MAX_LEVELS);
+        return ORBX_E_INVALID;
+    }
+    size_t t = 0;
+    for (int i = 0; i < a.n2; i++) {
+        const int np = a.npairs[i];
+        if (np < 0 || np > a.cap) { orbx_set_error("%s: npairs[%d] = %d outside [0, cap = %d]", who, i, np, a.cap); return ORBX_E_INVALID; }
+        t += (size_t)np;
+        const int32_t *p = a.pairs + 2 * (size_t)i * (size_t)a.cap;
+        for (int k = 0; k < np; k++) {
+            const int i1 = p[2 * k], i2 = p[2 * k + 1];
+            if (i1 < 0 || i1 >= h1.n || i2 < 0 || i2 >= h2[i].n) {
+                orbx_set_error("%s: neighbour %d, pair %d: (%d, %d) outside the keyframes (%d, %d features)", who, i, k, i1, i2, h1.n, h2[i].n);
+                return ORBX_E_INVALID;
+            }
+            if ((h1.octave && (h1.octave[i1] < 0 || h1.octave[i1] >= a.nlevels)) || (h2[i].octave && (h2[i].octave[i2] < 0 || h2[i].octave[i2] >= a.nlevels))) {
+                orbx_set_error("%s: neighbour %d, pair %d: an octave outside [0, %d)", who, i, k, a.nlevels);
+                return ORBX_E_INVALID;
+            }
+            if ((h1.u_right && !h1.has_depth && h1.u_right[i1] >= 0.f) || (h2[i].u_right && !h2[i].has_depth && h2[i].u_right[i2] >= 0.f)) {
+                orbx_set_error("%s: neighbour %d, pair %d: a stereo feature of a keyframe without depth", who, i, k);
+                return ORBX_E_INVALID;
+            }
+        }
+    }
+    if (t > ((size_t)1 << 22)) { orbx_set_error("%s: %zu pairs in all, more than 2^22", who, t); return ORBX_E_CAPACITY; }
+    *total = t;
+    return ORBX_OK;
+}
+
+// blob: [TriHead up to nb[n2]] [pairs, packed] [whatever stage() adds]; work / download: [status] [x3d] [bad flag] | [first[n1]]
+// stage(H, cursor) fills the TriFeat records (and, for host pointers, the blob at the cursor)
+template <class Stage>
+static int tri_run(const char *who, CallCtx *c, const TriArgs &a, int n1, size_t total, size_t extra_blob, Stage stage,
+                   const orbx_frame *const *wait, int nwait)
+{
+    *a.n_new = 0;
+    if (total == 0) return ORBX_OK;
+    const size_t head_b = a16(offsetof(TriHead, nb) + sizeof(TriHead::Nb) * (size_t)a.n2), pairs_b = a16(8 * total);
+    const size_t blob = head_b + pairs_b + extra_blob;
+    const size_t o_x3d = a16(total), o_bad = o_x3d + a16(12 * total), out = o_bad + 16, work = out + a16(4 * (size_t)n1);
+    int rc = call_reserve(c, blob, work, out);
+    if (rc) return rc;
+    TriHead &H = *(TriHead *)c->h_blob;
+    memset(&H, 0, head_b);
+    H.n2 = a.n2; H.total = (int)total; H.nlevels = a.nlevels; H.ratio_factor = a.ratio_factor;
+    memcpy(H.sf, a.sf, sizeof(float) * (size_t)a.nlevels); memcpy(H.sigma2, a.sigma2, sizeof(float) * (size_t)a.nlevels);
+    H.v1 = *a.v1;
+    int32_t *hp = (int32_t *)(c->h_blob + head_b);
+    size_t at = 0;
+    for (int i = 0; i < a.n2; i++) {
+        H.prefix[i] = (int)at;
+        H.nb[i].v = a.v2s[i];
+        memcpy(hp + 2 * at, a.pairs + 2 * (size_t)i * (size_t)a.cap, 8 * (size_t)a.npairs[i]);
+        at += (size_t)a.npairs[i];
+    }
+    H.prefix[a.n2] = (int)at;
+    BlobCursor b = { c->h_blob, c->d_blob, head_b + pairs_b };
+    stage(H, b);
+    for (int i = 0; i < nwait; i++)
+        if ((rc = frame_order_before(wait[i], c->stream))) return rc;
+    if ((rc = call_upload(c, blob))) return rc;
+    // 0x7f7f7f7f: larger than any neighbour index in first[], and not the 1 the kernel writes into the flag
+    ORBX_HIP(hipMemsetAsync(c->d_work + o_bad, 0x7f, work - o_bad, c->stream));
+    // k_triangulate, then first neighbour wins: d_work = status[total] | x3d[total][3] | bad flag | first[n1]
+    const TriHead *d_head = (const TriHead *)c->d_blob;
+    const int32_t *d_pairs = (const int32_t *)(c->d_blob + head_b);
+    int *d_first = (int *)(c->d_work + out);
     const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-    hipLaunchKernelGGL(k_triangulate, grid, block, 0, s, d_head, d_pairs, d_status, d_x3d, d_bad);
-    hipLaunchKernelGGL(k_tri_resolve<0>, grid, block, 0, s, d_head, d_pairs, d_status, d_first);
-    hipLaunchKernelGGL(k_tri_resolve<1>, grid, block, 0, s, d_head, d_pairs, d_status, d_first);
+    hipLaunchKernelGGL(k_triangulate, grid, block, 0, c->stream, d_head, d_pairs, c->d_work, (float *)(c->d_work + o_x3d), (int *)(c->d_work + o_bad));
+    hipLaunchKernelGGL(k_tri_resolve<0>, grid, block, 0, c->stream, d_head, d_pairs, c->d_work, d_first);
+    hipLaunchKernelGGL(k_tri_resolve<1>, grid, block, 0, c->stream, d_head, d_pairs, c->d_work, d_first);
+    if ((rc = call_fetch(c, out))) return rc;
+    const uint8_t *ho = (const uint8_t *)c->h_out;
+    if (*(const int32_t *)(ho + o_bad) == 1) { orbx_set_error("%s: a paired feature has an octave outside [0, %d)", who, a.nlevels); return ORBX_E_INVALID; }
+    const float *hx = (const float *)(ho + o_x3d);
+    int n_new = 0;
+    at = 0;
+    for (int i = 0; i < a.n2; i++) {
+        const size_t np = (size_t)a.npairs[i], row = (size_t)i * (size_t)a.cap;
+        memcpy(a.status + row, ho + at, np);
+        memcpy(a.x3d + 3 * row, hx + 3 * at, 12 * np);
+        for (size_t k = 0; k < np; k++) n_new += ho[at + k] <= 2;
+        at += np;
+    }
+    *a.n_new = n_new;
+    return ORBX_OK;
+}
+
+extern "C" int orbx_triangulate_pairs(int device, const orbx_tri_feats *k1, const orbx_tri_view *v1, const orbx_tri_feats *const *k2s,
+                                      const orbx_tri_view *v2s, int n2, const int32_t *pairs, int cap, const int *npairs,
+                                      const float *scale_factors, const float *level_sigma2, int nlevels, float ratio_factor,
+                                      uint8_t *status, float *x3d, int *n_new)
+{
+    const char *who = "orbx_triangulate_pairs";
+    const TriArgs a = { n2, cap, nlevels, pairs, npairs, v1, v2s, scale_factors, level_sigma2, ratio_factor, status, x3d, n_new };
+    size_t total;
+    int rc = tri_check(who, k1, k2s, a, [&](TriHostKf *h) -> int {
+        for (int i = 0; i <= n2; i++) {
+            const orbx_tri_feats *k = i ? k2s[i - 1] : k1;
+            if (!k || k->n < 0 || (k->n && (!k->x || !k->y || !k->octave || !k->u_right)) || (!k->raw_x) != (!k->raw_y)) {
+                orbx_set_error("%s: a keyframe is NULL, has n < 0, lacks x / y / octave / u_right or gives one raw array only", who);
+                return ORBX_E_INVALID;
+            }
+            h[i].n = k->n; h[i].octave = k->octave; h[i].u_right = k->u_right; h[i].has_depth = k->depth != nullptr;
+        }
+        return ORBX_OK;
+    }, &total);
+    if (rc) return rc;
+    CallCtx *c;
+    if ((rc = orbx_call_ctx(device, &c))) return rc;
+    auto kf_bytes = [](const orbx_tri_feats *k) { return (size_t)(4 + (k->depth ? 1 : 0) + (k->raw_x ? 2 : 0)) * a16(4 * (size_t)k->n); };
+    size_t extra = kf_bytes(k1);
+    for (int i = 0; i < n2; i++) extra += kf_bytes(k2s[i]);
+    return tri_run(who, c, a, k1->n, total, extra, [&](TriHead &H, BlobCursor &b) {
+        auto put_kf = [&](const orbx_tri_feats *k, TriFeat &f) {
+            const size_t nb = 4 * (size_t)k->n;
+            f.x = (const float *)b.put(k->x, nb); f.y = (const float *)b.put(k->y, nb);
+            f.octave = (const int32_t *)b.put(k->octave, nb); f.u_right = (const float *)b.put(k->u_right, nb);
+            f.depth = k->depth ? (const float *)b.put(k->depth, nb) : nullptr;
+            f.raw_x = k->raw_x ? (const float *)b.put(k->raw_x, nb) : f.x; f.raw_y = k->raw_y ? (const float *)b.put(k->raw_y, nb) : f.y;
+        };
+        put_kf(k1, H.f1);
+        for (int i = 0; i < n2; i++) put_kf(k2s[i], H.nb[i].f);
+    }, nullptr, 0);
+}
+
+extern "C" int orbx_frame_triangulate(const orbx_frame *k1, const orbx_tri_view *v1, const orbx_frame *const *k2s, const orbx_tri_view *v2s,
+                                      int n2, const int32_t *pairs, int cap, const int *npairs, const float *scale_factors,
+                                      const float *level_sigma2, int nlevels, float ratio_factor, uint8_t *status, float *x3d, int *n_new)
+{
+    const char *who = "orbx_frame_triangulate";
+    const orbx_frame *fr[65];
+    const TriArgs a = { n2, cap, nlevels, pairs, npairs, v1, v2s, scale_factors, level_sigma2, ratio_factor, status, x3d, n_new };
+    size_t total;
+    int rc = tri_check(who, k1, k2s, a, [&](TriHostKf *h) -> int {
+        for (int i = 0; i <= n2; i++) {
+            const orbx_frame *f = fr[i] = i ? k2s[i - 1] : k1;
+            if (!f) { orbx_set_error("%s: a NULL frame", who); return ORBX_E_INVALID; }
+            if (f->device != k1->device) { orbx_set_error("%s: the frames live on different devices", who); return ORBX_E_INVALID; }
+            if ((f->has_stereo || f->from_extraction) && !f->depth_set) {
+                orbx_set_error("%s: frame %d has stereo features or comes from an extraction, and no depth (orbx_frame_set_depth)", who, i);
+                return ORBX_E_INVALID;
+            }
+            h[i].n = f->n; h[i].octave = f->h_oct.empty() ? nullptr : f->h_oct.data(); h[i].u_right = nullptr; h[i].has_depth = f->depth_set;
+        }
+        return ORBX_OK;
+    }, &total);
+    if (rc) return rc;
+    CallCtx *c;
+    if ((rc = orbx_call_ctx(k1->device, &c))) return rc;
+    return tri_run(who, c, a, k1->n, total, 0, [&](TriHead &H, BlobCursor &) {
+        for (int i = 0; i <= n2; i++) {
+            const orbx_frame *f = fr[i];
+            const DevFrame F = frame_dev(f);
+            TriFeat &t = i ? H.nb[i - 1].f : H.f1;
+            t.x = F.x; t.y = F.y; t.octave = F.octave; t.u_right = F.u_right;
+            t.depth = f->d_depth;
+            t.raw_x = f->d_raw_x ? f->d_raw_x : F.x; t.raw_y = f->d_raw_y ? f->d_raw_y : F.y;
+        }
+    }, fr, n2 + 1);
 }
