@@ -739,7 +739,7 @@ int orbx_frame_search_local_points(orbx_frame *cur, const uint8_t *occupied, con
  * Relocalization up to three times per candidate, src/Tracking.cc:1730-1800): one 6-DoF vertex, one unary edge per feature that
  * holds a map point.  The whole function -- four rounds of at most ten Levenberg iterations with at most ten damping trials each,
  * and the inlier / outlier classification between the rounds -- is ONE kernel launch, one workgroup per job.  Only this function:
- * the bundle adjustments, OptimizeSim3 and the essential graph stay with g2o.
+ * the bundle adjustments and the essential graph stay with g2o (OptimizeSim3, the other single-vertex problem: orbx_sim3_optimize).
  * The arithmetic, in double unless a step says float, every operation rounded on its own (no fused multiply-add):
  *   edges    feature i with has_point[i] is a monocular edge (src/Optimizer.cc:335-377) if u_right[i] < 0, else a stereo edge
  *            (:378-416).  Measurement, Xw, cam and inv_sigma2 are floats widened to double; information = inv_sigma2[i] * I.
@@ -815,6 +815,74 @@ int orbx_pose_optimize_batch(int device, orbx_pose_job *jobs, int njobs);
 int orbx_frame_pose_optimize(const orbx_frame *cur, const orbx_mappoints *m, const int32_t *slot_of_feature,
                              const float *inv_level_sigma2, int nlevels, const float *cam, const float *Tcw, float *Tcw_out,
                              uint8_t *outlier, int *n_inliers, orbx_pose_report *report);
+
+/* ---- Optimizer::OptimizeSim3: the Sim3 between two keyframes (src/Optimizer.cc:1164-1365) ------------------------------
+ * Step 4 of LoopClosing::ComputeSim3 (src/LoopClosing.cc:282-460), between SearchBySim3 and the Sim3 SearchByProjection.  Every
+ * VertexSBAPointXYZ of the function is fixed: the one free vertex is a 7-DoF VertexSim3Expmap, and the whole function -- two rounds
+ * of Levenberg iterations and the classification after each -- is ONE kernel launch, one workgroup per job (k_sim3_opt).
+ * The arithmetic, in double unless a step says float, every operation rounded on its own (no fused multiply-add):
+ *   pairs    feature i of KF1 with has_pair[i] carries two edges.  Edge 12 (EdgeSim3ProjectXYZ): obs (x1, y1) - cam_map1(project(
+ *            S12.map(P2c))).  Edge 21 (EdgeInverseSim3ProjectXYZ): obs (x2, y2) - cam_map2(project(S12.inverse().map(P1c))).
+ *            project = (x / z, y / z); cam_map = v * f + c; information = inv_sigma2 * I; chi2 = sum_r e_r * (inv_sigma2 * e_r).
+ *            Points, observations, cameras and inv_sigma2 are floats widened to double.
+ *   Sim3     sim3.h, literally: the estimate is (r, t, s) with r a quaternion that is NEVER normalised -- the start is S12 exactly as
+ *            handed in; map(p) = s * (r * p) + t with Eigen's r * p (uv = 2 r.vec x p; p + r.w uv + r.vec x uv); inverse() =
+ *            (conj r, conj r * ((-1 / s) * t), 1 / s); a * b = (a.r * b.r, a.s * (a.r * b.t) + a.t, a.s * b.s), no normalisation.
+ *   exp      Sim3(Vector7d), update = (omega, upsilon, sigma): s = exp(sigma), theta = |omega|, R = I + Omega + Omega^2 where theta
+ *            < 1e-5, else I + sin(theta) / theta Omega + (1 - cos(theta)) / theta^2 Omega^2; r = Quaterniond(R), not normalised; t =
+ *            (A Omega + B Omega^2 + C I) upsilon with A, B, C from the four branches on |sigma| < 1e-5 and theta < 1e-5 (sim3.h:92-135).
+ *   update   estimate = exp(x) * estimate.  fix_scale: x[6] = 0 first, written into the solver's x (VertexSim3Expmap::oplusImpl).
+ *   Jacobian the reference's central difference (both edges leave linearizeOplus commented out; base_binary_edge.hpp:131-205): column
+ *            d = (e(exp(+1e-9 e_d) * S) - e(exp(-1e-9 e_d) * S)) * (1 / 2e-9).  With fix_scale column 6 is exactly 0.
+ *   Huber    delta = (float)sqrt(th2) in both rounds; b -= rho1 * A^T (w e), H += A^T (rho1 w) A, the active robust chi2 sums rho0
+ *            (base_binary_edge.hpp:55-120), edge 12 then edge 21 of a pair.
+ *   system   28 + 7 + 1 sums over the edges of the pairs still in the graph, in an order that is a fixed function of (n, thread
+ *            index): results are bit-reproducible from run to run and do not depend on the other jobs of a launch.  No atomics.
+ *   solve    (H + lambda I) x = b by LDL^T without pivoting; a pivot <= 0 makes the trial's chi2 DBL_MAX and leaves x as it was --
+ *            x survives from the first round into the second (Solver::resizeVector does not reallocate), and starts as zeros.
+ *   Levenberg as orbx_pose_optimize; lambda and ni are set anew at iteration 0 of each round.
+ *   rounds   optimize(5); a pair with chi2_12 > th2 || chi2_21 > th2 (double against the float th2), at the errors of the LAST
+ *            EVALUATED TRIAL, leaves the graph for good and its match is cleared; n_bad of them.  n_corr - n_bad < 10: the return
+ *            value is 0 and S12_out is S12 bit for bit (the matches round 1 threw out stay cleared).  Else optimize(n_bad > 0 ? 10
+ *            : 5) CONTINUING from the first round's estimate, the same test once more, and the return value counts what is left.
+ * Outside the contract: a pair whose projection is not finite at an estimate the solver visits.  Against g2o's own arithmetic (Eigen's
+ * LDLT, its product evaluation order) and the C library's sin / cos / exp this restatement is unpinned: DESIGN.md. */
+typedef struct {
+    int n;                     /* vpMatches1.size(), 0 .. 65535 */
+    const uint8_t *has_pair;   /* the test of :1223-1260 passed: both points, neither bad, i2 >= 0 */
+    const float *P1c, *P2c;    /* [n][3] R1w * P3D1w + t1w and R2w * P3D2w + t2w (:1241-1251); read only where has_pair[i] */
+    const float *x1, *y1;      /* pKF1->mvKeysUn[i].pt */
+    const float *inv_sigma2_1; /* pKF1->mvInvLevelSigma2[octave of that keypoint] */
+    const float *x2, *y2;      /* pKF2->mvKeysUn[i2].pt */
+    const float *inv_sigma2_2;
+} orbx_sim3opt_obs;
+typedef struct {
+    int n_corr;                /* nCorrespondences */
+    int rounds;                /* 0 (no correspondence), 1 (fewer than 10 left after the first) or 2 */
+    int n_bad;                 /* nBad after round 1 */
+    int more_iterations;       /* nMoreIterations: 5 or 10 */
+    int iterations[2];         /* Levenberg iterations of each round */
+    double chi2[2];            /* the active robust chi2 each round ended with */
+    double S12[8];             /* S12_out */
+} orbx_sim3opt_report;
+/* cam1 / cam2 = fx fy cx cy of pKF1->mK / pKF2->mK; S12 / S12_out = qx qy qz qw tx ty tz s in double (may alias).  inlier[i] = 1
+ * where vpMatches1[i] is still non-NULL on return, written only where has_pair[i]; *n_inliers = the reference's return value;
+ * report may be NULL.  One upload, one launch, one download; no correspondence at all: ORBX_OK without a launch.  ORBX_E_INVALID
+ * before any device work: NULL obs / cam1 / cam2 / S12 / S12_out / n_inliers, n outside [0, 65535], th2 not positive and finite,
+ * with n > 0 a NULL array of obs or NULL inlier. */
+int orbx_sim3_optimize(int device, const orbx_sim3opt_obs *obs, const float *cam1, const float *cam2, const double *S12, float th2,
+                       int fix_scale, double *S12_out, uint8_t *inlier, int *n_inliers, orbx_sim3opt_report *report);
+/* one job of a batch: the arguments of orbx_sim3_optimize */
+typedef struct {
+    const orbx_sim3opt_obs *obs; const float *cam1, *cam2; const double *S12;
+    float th2; int fix_scale;
+    double *S12_out; uint8_t *inlier;
+    int n_inliers;                               /* out */
+    orbx_sim3opt_report *report;                 /* out, may be NULL */
+} orbx_sim3opt_job;
+/* njobs optimisations (the loop candidates of one ComputeSim3) as ONE upload, ONE launch of njobs workgroups, ONE download; every
+ * job's results are byte-equal to its single call.  ORBX_E_INVALID: njobs outside [1, 64], any refusal of the single call. */
+int orbx_sim3_optimize_batch(int device, orbx_sim3opt_job *jobs, int njobs);
 
 /* ---- LocalMapping::CreateNewMapPoints: the triangulation half (src/LocalMapping.cc:327-511) ---------------------------
  * The search half of the function is orbx_kf_search_for_triangulation.  This is the body of its match loop: per pair (idx1 of

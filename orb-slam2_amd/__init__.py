@@ -11,6 +11,7 @@ sitting directly on the C ABI of liborbx.so (include/orbx.h):
   pose_optimize / DeviceFrame.pose_optimize <- reference src/Optimizer.cc:286-513 (motion-only pose optimisation)
   triangulate_pairs / frame_triangulate <- reference src/LocalMapping.cc:327-511 (CreateNewMapPoints' triangulation)
   sim3_hypotheses / Sim3Ransac <- reference src/Sim3Solver.cc:117-433 (LoopClosing::ComputeSim3's RANSAC)
+  sim3_optimize / sim3_optimize_batch <- reference src/Optimizer.cc:1164-1365 (Optimizer::OptimizeSim3)
 
 There is NO CPU fallback: importing works without a GPU (so that the ABI can be inspected), but
 every compute call raises OrbxError unless liborbx.so is built and a gfx950 device is present.
@@ -20,9 +21,11 @@ from . import orbx, streams
 from .orbx import (OrbxError, KP_DTYPE, lib, lib_path, ORBextractor, ORBmatcher, ComputeStereoMatches,
                    FeatSet, make_featset, STAGES, BowDatabase, DeviceKeyFrame, DeviceFrame, MapPoints, BowFrames, KeyFrameDatabase, ORBVocabulary, ComputeDistinctiveDescriptors, Rectifier, UndistortKeyPoints,
                    RGBDParams, depth_map_factor, rgbd_depth_batch_device, DEPTH_U16, DEPTH_F32, pose_optimize, pose_optimize_batch,
-                   triangulate_pairs, frame_set_depth, frame_triangulate, sim3_hypotheses, sim3_hypotheses_batch, sim3_max_error, Sim3Ransac)
+                   triangulate_pairs, frame_set_depth, frame_triangulate, sim3_hypotheses, sim3_hypotheses_batch, sim3_max_error, Sim3Ransac,
+                   sim3_optimize, sim3_optimize_batch, sim3opt_camera_points)
 
 __all__ = ["OrbxError", "KP_DTYPE", "lib", "lib_path", "ORBextractor", "ORBmatcher", "ComputeStereoMatches",
            "FeatSet", "make_featset", "STAGES", "BowDatabase", "DeviceKeyFrame", "DeviceFrame", "MapPoints", "BowFrames", "KeyFrameDatabase", "ORBVocabulary", "ComputeDistinctiveDescriptors", "Rectifier", "UndistortKeyPoints",
            "RGBDParams", "depth_map_factor", "rgbd_depth_batch_device", "DEPTH_U16", "DEPTH_F32", "pose_optimize", "pose_optimize_batch",
-           "triangulate_pairs", "frame_set_depth", "frame_triangulate", "sim3_hypotheses", "sim3_hypotheses_batch", "sim3_max_error", "Sim3Ransac"]
+           "triangulate_pairs", "frame_set_depth", "frame_triangulate", "sim3_hypotheses", "sim3_hypotheses_batch", "sim3_max_error", "Sim3Ransac",
+           "sim3_optimize", "sim3_optimize_batch", "sim3opt_camera_points"]

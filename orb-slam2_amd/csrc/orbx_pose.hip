@@ -12,6 +12,7 @@
 // The arithmetic is restated in include/orbx.h (orbx_pose_optimize) and, in numpy, in tests/pose_model.py.  Behind the kernel: the
 // refusals, the staging and the delivery of the three calls (pose_check, pose_run, pose_deliver and the entry points).
 #include "orbx_resident.h"
+#include "orbx_lm.h"
 #include <float.h>
 
 // One job of k_pose_opt.  Every pointer is a device address.  The host-pointer calls give
@@ -86,67 +87,7 @@ __device__ __forceinline__ double edge_chi2(const PoseJob &J, int i, const Pose 
     return edge_error(e, K, x, y, z, err);
 }
 
-// robust_kernel_impl.cpp:78-91 (rho[2] is never used: base_edge.h:96-102)
-__device__ __forceinline__ void huber(double e, double delta, double &rho0, double &rho1)
-{
-    const double dsqr = delta * delta;
-    if (e <= dsqr) { rho0 = e; rho1 = 1.0; return; }
-    const double sqrte = sqrt(e);
-    rho0 = 2.0 * sqrte * delta - dsqr;
-    rho1 = delta / sqrte;
-}
-
-__device__ __forceinline__ double wave_sum(double v)
-{
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
-template <int K>
-__device__ __forceinline__ void block_sum(double (&a)[K], double *red)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < K; k++) a[k] = wave_sum(a[k]);
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < K; k++) red[wave * K + k] = a[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; k++) a[k] = (red[k] + red[K + k]) + (red[2 * K + k] + red[3 * K + k]);
-    __syncthreads();
-}
-
-// Eigen's Quaternion(Matrix3): m row-major
-__device__ __forceinline__ void quat_from_matrix(const double m[9], double &qx, double &qy, double &qz, double &qw)
-{
-    double t = (m[0] + m[4]) + m[8];
-    if (t > 0.0) {
-        t = sqrt(t + 1.0);
-        qw = 0.5 * t;
-        t = 0.5 / t;
-        qx = (m[7] - m[5]) * t; qy = (m[2] - m[6]) * t; qz = (m[3] - m[1]) * t;
-        return;
-    }
-    // i = the largest diagonal entry, j = i + 1, k = i + 2 (mod 3); the three cases written out (no indexed register arrays)
-    int i = 0;
-    if (m[4] > m[0]) i = 1;
-    if (m[8] > (i ? m[4] : m[0])) i = 2;
-    if (i == 0) {
-        t = sqrt(((m[0] - m[4]) - m[8]) + 1.0);
-        qx = 0.5 * t; t = 0.5 / t;
-        qw = (m[7] - m[5]) * t; qy = (m[3] + m[1]) * t; qz = (m[6] + m[2]) * t;
-    } else if (i == 1) {
-        t = sqrt(((m[4] - m[8]) - m[0]) + 1.0);
-        qy = 0.5 * t; t = 0.5 / t;
-        qw = (m[2] - m[6]) * t; qz = (m[7] + m[5]) * t; qx = (m[1] + m[3]) * t;
-    } else {
-        t = sqrt(((m[8] - m[0]) - m[4]) + 1.0);
-        qz = 0.5 * t; t = 0.5 / t;
-        qw = (m[3] - m[1]) * t; qx = (m[2] + m[6]) * t; qy = (m[5] + m[7]) * t;
-    }
-}
+// huber, block_sum (its fixed order: header comment) and Eigen's Quaternion(Matrix3) are orbx_lm.h's, shared with k_sim3_opt
 
 // SE3Quat::normalizeRotation
 __device__ __forceinline__ void quat_normalize(double &qx, double &qy, double &qz, double &qw)

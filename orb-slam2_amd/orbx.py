@@ -151,6 +151,25 @@ class Sim3Job(C.Structure):
                 ("n_inliers", C.c_void_p), ("srt", C.c_void_p), ("inlier_bits", C.c_void_p)]
 
 
+class Sim3OptObs(C.Structure):
+    """orbx_sim3opt_obs (include/orbx.h)"""
+    _fields_ = [("n", C.c_int), ("has_pair", C.c_void_p), ("P1c", C.c_void_p), ("P2c", C.c_void_p), ("x1", C.c_void_p), ("y1", C.c_void_p),
+                ("inv_sigma2_1", C.c_void_p), ("x2", C.c_void_p), ("y2", C.c_void_p), ("inv_sigma2_2", C.c_void_p)]
+
+
+class Sim3OptReport(C.Structure):
+    """orbx_sim3opt_report (include/orbx.h)"""
+    _fields_ = [("n_corr", C.c_int), ("rounds", C.c_int), ("n_bad", C.c_int), ("more_iterations", C.c_int), ("iterations", C.c_int * 2),
+                ("chi2", C.c_double * 2), ("S12", C.c_double * 8)]
+
+
+class Sim3OptJob(C.Structure):
+    """orbx_sim3opt_job (include/orbx.h)"""
+    _fields_ = [("obs", C.POINTER(Sim3OptObs)), ("cam1", C.c_void_p), ("cam2", C.c_void_p), ("S12", C.c_void_p), ("th2", C.c_float),
+                ("fix_scale", C.c_int), ("S12_out", C.c_void_p), ("inlier", C.c_void_p), ("n_inliers", C.c_int),
+                ("report", C.POINTER(Sim3OptReport))]
+
+
 _lib = None
 
 
@@ -261,6 +280,8 @@ def lib():
     L.orbx_frame_triangulate.argtypes = [vp, C.POINTER(TriView), C.POINTER(vp), C.POINTER(TriView), i, vp, i, vp, vp, vp, i, f, vp, vp, ip]
     L.orbx_sim3_hypotheses.argtypes = [i, C.POINTER(Sim3Job)]
     L.orbx_sim3_hypotheses_batch.argtypes = [i, C.POINTER(Sim3Job), i]
+    L.orbx_sim3_optimize.argtypes = [i, C.POINTER(Sim3OptObs), vp, vp, vp, f, i, vp, vp, ip, C.POINTER(Sim3OptReport)]
+    L.orbx_sim3_optimize_batch.argtypes = [i, C.POINTER(Sim3OptJob), i]
     L.orbx_bow_frames_create.argtypes = [i, i, i, C.POINTER(vp)]
     L.orbx_bow_frames_destroy.argtypes = [vp]; L.orbx_bow_frames_destroy.restype = None
     L.orbx_bow_transform_batch_device.argtypes = [vp, vp, vp, vp, vp, i, i, vp]
@@ -991,6 +1012,74 @@ def pose_optimize_batch(jobs, device=0):
         arr[j].report = C.pointer(rep)
     _check(lib().orbx_pose_optimize_batch(device, arr, nj))
     return [_pose_result(k[4], k[5], arr[j].n_inliers, k[6]) for j, k in enumerate(keep)]
+
+
+SIM3OPT_FIELDS = ("x1", "y1", "inv_sigma2_1", "x2", "y2", "inv_sigma2_2")
+
+
+def sim3opt_camera_points(Xw, Rcw, tcw):
+    """the camera-frame points Optimizer::OptimizeSim3 hands g2o (src/Optimizer.cc:1241-1251: `R1w*P3D1w + t1w` on CV_32F matrices), by the
+    rule of include/orbx.h for cv::Mat products: (float)dotd(R.row(r), Xw) -- double products, double sum, one cast -- then the float add
+    of t[r].  Xw [n][3], Rcw 3 x 3, tcw [3], all float32 -> [n][3] float32"""
+    X = np.ascontiguousarray(Xw, np.float32).reshape(-1, 3).astype(np.float64)
+    R = np.ascontiguousarray(Rcw, np.float32).reshape(3, 3).astype(np.float64)
+    t = np.ascontiguousarray(tcw, np.float32).reshape(3)
+    P = ((X[:, None, 0] * R[None, :, 0] + X[:, None, 1] * R[None, :, 1]) + X[:, None, 2] * R[None, :, 2]).astype(np.float32)
+    return P + t[None, :]
+
+
+def _sim3opt_obs(obs, who):
+    """obs = dict(has_pair, P1c[n][3], P2c[n][3], x1, y1, inv_sigma2_1, x2, y2, inv_sigma2_2) -> (Sim3OptObs, the arrays it points into)"""
+    keep = [np.ascontiguousarray(obs["has_pair"], np.uint8)]
+    n = len(keep[0])
+    keep += [np.ascontiguousarray(obs[k], np.float32).reshape(-1, 3) for k in ("P1c", "P2c")]
+    keep += [np.ascontiguousarray(obs[k], np.float32) for k in SIM3OPT_FIELDS]
+    if keep[0].ndim != 1 or any(a.shape != (n, 3) for a in keep[1:3]) or any(a.shape != (n,) for a in keep[3:]):
+        raise OrbxError(-1, f"{who}: has_pair, x1, y1, inv_sigma2_1, x2, y2, inv_sigma2_2 need n entries, P1c and P2c [n][3]")
+    return Sim3OptObs(n, *[_p(a) for a in keep]), keep
+
+
+def _sim3opt_inputs(cam1, cam2, S12, who):
+    c1 = np.ascontiguousarray(cam1, np.float32).reshape(-1); c2 = np.ascontiguousarray(cam2, np.float32).reshape(-1)
+    s = np.ascontiguousarray(S12, np.float64).reshape(-1)
+    if len(c1) != 4 or len(c2) != 4 or len(s) != 8:
+        raise OrbxError(-1, f"{who}: cam1 and cam2 are fx fy cx cy, S12 is qx qy qz qw tx ty tz s")
+    return c1, c2, s
+
+
+def _sim3opt_result(S12_out, inlier, n_inliers, rep):
+    return dict(S12=S12_out, inlier=inlier, n_inliers=n_inliers, n_corr=rep.n_corr, rounds=rep.rounds, n_bad=rep.n_bad,
+                more_iterations=rep.more_iterations, iterations=np.array(rep.iterations[:], np.int32),
+                chi2=np.array(rep.chi2[:], np.float64), report_S12=np.array(rep.S12[:], np.float64))
+
+
+def sim3_optimize(obs, cam1, cam2, S12, th2, fix_scale, device=0):
+    """Optimizer::OptimizeSim3 (orbx_sim3_optimize): obs = dict(has_pair, P1c, P2c, x1, y1, inv_sigma2_1, x2, y2, inv_sigma2_2), cam =
+    fx fy cx cy, S12 = qx qy qz qw tx ty tz s -> dict(S12, inlier, n_inliers, n_corr, rounds, n_bad, more_iterations, iterations, chi2,
+    report_S12)"""
+    so, keep = _sim3opt_obs(obs, "sim3_optimize")
+    c1, c2, s = _sim3opt_inputs(cam1, cam2, S12, "sim3_optimize")
+    out = np.zeros(8, np.float64); fl = np.zeros(so.n, np.uint8); ni = C.c_int(); rep = Sim3OptReport()
+    _check(lib().orbx_sim3_optimize(device, C.byref(so), _p(c1), _p(c2), _p(s), float(th2), int(bool(fix_scale)), _p(out), _p(fl), C.byref(ni),
+                                    C.byref(rep)))
+    return _sim3opt_result(out, fl, ni.value, rep)
+
+
+def sim3_optimize_batch(jobs, device=0):
+    """orbx_sim3_optimize_batch: jobs = [(obs, cam1, cam2, S12, th2, fix_scale), ...] in one upload, one launch, one download
+    -> [dict as sim3_optimize]"""
+    nj = len(jobs)
+    arr = (Sim3OptJob * max(nj, 1))()
+    keep = []
+    for j, (obs, cam1, cam2, S12, th2, fix_scale) in enumerate(jobs):
+        so, k = _sim3opt_obs(obs, "sim3_optimize_batch")
+        c1, c2, s = _sim3opt_inputs(cam1, cam2, S12, "sim3_optimize_batch")
+        out = np.zeros(8, np.float64); fl = np.zeros(so.n, np.uint8); rep = Sim3OptReport()
+        keep.append((so, k, c1, c2, s, out, fl, rep))
+        arr[j].obs = C.pointer(so); arr[j].cam1 = _p(c1); arr[j].cam2 = _p(c2); arr[j].S12 = _p(s); arr[j].th2 = float(th2)
+        arr[j].fix_scale = int(bool(fix_scale)); arr[j].S12_out = _p(out); arr[j].inlier = _p(fl); arr[j].report = C.pointer(rep)
+    _check(lib().orbx_sim3_optimize_batch(device, arr, nj))
+    return [_sim3opt_result(k[5], k[6], arr[j].n_inliers, k[7]) for j, k in enumerate(keep)]
 
 
 def _tri_view(v, who):
