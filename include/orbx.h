@@ -1038,6 +1038,94 @@ int orbx_sim3_hypotheses(int device, orbx_sim3_job *job);
  * words in all. */
 int orbx_sim3_hypotheses_batch(int device, orbx_sim3_job *jobs, int njobs);
 
+/* ---- PnPsolver: the hypotheses of Tracking::Relocalization's EPnP RANSAC (src/PnPsolver.cc:176-350, 386-961) --------------
+ * PnPsolver::iterate draws four correspondences, runs EPnP on them (compute_pose), reprojects EVERY correspondence (CheckInliers)
+ * and, when the count reaches mRansacMinInliers, runs EPnP again on the inliers and reprojects again (Refine).  As for Sim3Solver
+ * the bookkeeping of iterate stays on the host and the device evaluates the WHOLE TABLE of hypotheses of a solver -- of every
+ * candidate's solver of one Relocalization -- in one launch (k_pnp: one wave per hypothesis), and the host replays iterate over
+ * the table (PnPRansac in orbx.py).  Refine in the reference reads mvbBestInliers, the best set so far, so it depends on the
+ * replay's state; but the best set changes only at a row that beats it, and refining an UNCHANGED set repeats a refinement that
+ * has already failed (had it succeeded, iterate would have returned).  So a refinement of every qualifying row from its OWN
+ * mask is all a replay can ever ask for: a row that qualifies without beating the best set re-fails, which the replay knows
+ * without looking.  The table therefore holds two results per row.
+ * All of compute_pose is fp64 as in the reference text; every operation is rounded on its own (no fused multiply-add); sums and
+ * products associate left to right unless brackets say otherwise.  dot(a, b) = (a0*b0 + a1*b1) + a2*b2.
+ *   members  compute_pose runs on a list of correspondences: the four of a sample row in the row's order, or (Refine) the set bits
+ *            of the row's mask in rising index.  pw = (double)P3Dw[i], (u, v) = (double)P2D[i], nc = (double)(their number).
+ *   sums     "SUM x" over the members: for the four of a sample row, serially in the row's order from 0.0.  For a mask: lane l of
+ *            64 adds the members i = l (mod 64) in rising i from 0.0 (non-members add nothing), then a xor butterfly over the
+ *            strides 32, 16, 8, 4, 2, 1 (v[l] = v[l] + v[l ^ stride]); every lane ends with the same bits because a + b == b + a.
+ *   SVD      every OpenCV call of the text (cvMulTransposed is the SUM of products itself; cvSVD of PW0tPW0, MtM and ABt;
+ *            cvInvert(CV_SVD); cvSolve(CV_SVD)) is restated through ONE routine, a one-sided cyclic Jacobi on an m x n matrix A,
+ *            m >= n, V = I (n x n): with N = n rounded up to even, a sweep is the N - 1 rounds r = 0 .. N-2 of the round-robin
+ *            schedule, round r holding the pivots {N-1, r} and {(r + k) mod (N-1), (r - k) mod (N-1)} for k = 1 .. N/2 - 1, each
+ *            taken as (p, q) with p < q and left out when q >= n; the pivots of a round touch disjoint columns, so their order
+ *            is immaterial.  For a pivot: a = SUM_i A[i][p]^2, b = SUM_i A[i][q]^2, g = SUM_i A[i][p] A[i][q], i rising from 0.0.
+ *            The pivot is skipped when |g| <= 2^-49 * sqrt(a * b) (false for NaN) -- this is the stopping test: a sweep that
+ *            skipped every pivot ends the iteration, which runs 30 sweeps at most.  Otherwise g2 = g * 2, beta = a - b, gamma =
+ *            sqrt(g2 * g2 + beta * beta); beta < 0: delta = (gamma - beta) * 0.5, s = sqrt(delta / gamma), c = g2 / ((gamma * s)
+ *            * 2); else c = sqrt((gamma + beta) / (gamma * 2)), s = g2 / ((gamma * c) * 2); then every row (x, y) = (.[p], .[q])
+ *            of A and of V becomes (c*x + s*y, c*y - s*x) (the shape of OpenCV's JacobiSVDImpl_, which sweeps lexicographically
+ *            and rotates with its own hypot).  Afterwards w[j] = sqrt(SUM_i A[i][j]^2).
+ *   sort     where an order is needed: descending w, of equal values the earlier index first (selection: the r-th is the first
+ *            unused j whose w no later unused one exceeds).
+ *   eigen    cvSVD(.., CV_SVD_U_T) of the symmetric PW0tPW0 and MtM: dc / d = the sorted w, row k of uct / ut = COLUMN order[k]
+ *            of V (U = V where w > 0 for such a matrix, and V is defined where w = 0).  With four points MtM has rank <= 8; the
+ *            four vectors compute_L_6x10 reads span a null space and their order among near-zero values is what the sort gives.
+ *   solve    cvSolve(A, b, x, CV_SVD): thr = (SUM_k w[k], k rising from 0.0) * 2^-51; x = 0.0; for k rising with w[k] > thr:
+ *            t = ((SUM_i A[i][k] b[i]) / w[k]) / w[k] on the rotated A, x[j] = x[j] + V[j][k] * t.  cvInvert(CC, CV_SVD): column j
+ *            of CC_inv is the solve with b = the j-th unit vector.
+ *   control  cws[0] = (SUM pw) / nc.  PW0tPW0[j][k] (j <= k, mirrored) = SUM (pw[j] - cws[0][j]) * (pw[k] - cws[0][k]).
+ *            cws[i][j] = cws[0][j] + sqrt(dc[i-1] / nc) * uct[i-1][j] (:386-420).
+ *   alphas   (:422-445) with d = pw - cws[0]: a[1+j] = (ci[3j] d0 + ci[3j+1] d1) + ci[3j+2] d2, a[0] = ((1.0 - a[1]) - a[2]) - a[3]
+ *            (the text's 1.0f widens exactly); they are recomputed from the same values wherever they are read.
+ *   MtM      rows M1, M2 of fill_M (:447-462) literally, zeros included; MtM[j][k] (j <= k, mirrored) = SUM of the two products
+ *            M1[j] M1[k] then M2[j] M2[k], added in turn to the running value.
+ *   betas    compute_L_6x10 (2.0f widens exactly), compute_rho, find_betas_approx_1/2/3, compute_A_and_b_gauss_newton and
+ *            qr_solve are the text's own scalar code (:678-961), left to right.  qr_solve's pivot scan (:891-896) never looks at
+ *            the last row; on a zero pivot it returns and leaves x as it was, and x is DEFINED as zero at the start of each
+ *            gauss_newton (the reference reads it uninitialised: a stated deviation).
+ *   R, t     compute_ccs (from 0.0, i rising); solve_for_sign looks at the first member only: its pc[2] < 0 negates ccs (and with
+ *            them every pc).  pc0 = (SUM pc) / nc; pw0 IS cws[0] (the same sum, the same division).  ABt[j][c] = SUM (pc[j] -
+ *            pc0[j]) * (pw[c] - pw0[c]).  cvSVD(ABt): U[i][k] = A[i][k] / w[k] on the rotated A, columns in place (no sort, no
+ *            completion of a zero singular value: the pose is then not finite); R[i][j] = dot(U row i, V row j); det as the text
+ *            writes it, each triple product (x*y)*z; det < 0 negates row 2; t[i] = pc0[i] - dot(R row i, pw0).
+ *            reprojection_error: SUM sqrt(eu*eu + ev*ev) / nc with ue = uc + (fu * Xc) * inv_Zc.  The second and third solution
+ *            replace the kept one when their error is strictly smaller (:529-531).
+ *   inliers  CheckInliers (:319-350) with the text's mix: Xc, Yc = (float)(dot(R row, P) + t) with P widened; invZc = (float)(1.0 /
+ *            (dot(R row 2, P) + t[2])); ue = uc + (fu * (double)Xc) * (double)invZc in double; distX = (float)((double)P2D.x - ue);
+ *            error2 = distX * distX + distY * distY in float; inlier = error2 < max_err[i], strict and false for NaN.  A point
+ *            behind the camera projects mirrored, as in the reference.
+ *   special  a pose with a NaN or an infinity among its twelve numbers: n_inliers = 0, the mask is 0 and all twelve doubles are
+ *            the quiet NaN 0x7ff8000000000000 (stated, by analogy with srt: an infinite t[2] alone would otherwise pass points).
+ *            A row whose n_inliers is below min_inliers is not refined: n_refined = -1, a zero mask, twelve quiet NaNs.
+ * Against OpenCV's own arithmetic (its SVD sweeps and rotates differently, completes zero singular values and cuts by its own
+ * threshold) this restatement is unpinned: DESIGN.md. */
+typedef struct {
+    int n;                          /* correspondences, PnPsolver's N: 4 .. 65535 */
+    const float *P3Dw;              /* [n][3] mvP3Dw */
+    const float *P2D;               /* [n][2] mvP2D */
+    const float *max_err;           /* [n] mvMaxError = mvSigma2[i] * th2, the float product */
+    double K[4];                    /* fu fv uc vc: the reference widens F.fx .. to double members */
+    int min_inliers;                /* mRansacMinInliers after SetRansacParameters' adjustment: >= 4 */
+    int n_hyp;                      /* hypotheses to evaluate: 1 .. 1024 */
+    const int32_t *samples;         /* [n_hyp][4] indices into 0 .. n-1, the four of a row distinct */
+    /* out */
+    int32_t *n_inliers;             /* [n_hyp] mnInliersi */
+    double *Rt;                     /* [n_hyp][12] mRi row major, then mti */
+    uint64_t *inlier_bits;          /* [n_hyp][(n+63)/64] bit i%64 of word i/64 = mvbInliersi[i]; bits >= n are 0 */
+    int32_t *n_refined;             /* [n_hyp] mnRefinedInliers of Refine from this row's mask; -1: the row did not qualify */
+    double *Rt_refined;             /* [n_hyp][12] */
+    uint64_t *refined_bits;         /* [n_hyp][(n+63)/64] mvbRefinedInliers */
+} orbx_pnp_job;
+/* One upload, one launch, one download.  ORBX_E_INVALID before any device work: a NULL job or array, n outside [4, 65535], n_hyp
+ * outside [1, 1024], min_inliers < 4, a sample index outside [0, n), a row of samples with two equal indices. */
+int orbx_pnp_hypotheses(int device, orbx_pnp_job *job);
+/* The solvers of one Relocalization as ONE upload, ONE launch, ONE download; every job's results are byte-equal to its single
+ * call.  ORBX_E_INVALID: njobs outside [1, 64], any refusal of the single call in any job; ORBX_E_CAPACITY: more than 2^22 mask
+ * words in all (both masks counted). */
+int orbx_pnp_hypotheses_batch(int device, orbx_pnp_job *jobs, int njobs);
+
 /* ORBmatcher::SearchByProjection(Frame &CurrentFrame, const Frame &LastFrame, th, bMono) (src/ORBmatcher.cc:1396-1553;
  * Tracking::TrackWithMotionModel).  direction: 0 none, 1 bForward, 2 bBackward (:1412-1413).  match_cur[cur->n] =
  * index of the point each current feature finally holds (-1 none); *nmatches = the reference's return value

@@ -151,6 +151,14 @@ class Sim3Job(C.Structure):
                 ("n_inliers", C.c_void_p), ("srt", C.c_void_p), ("inlier_bits", C.c_void_p)]
 
 
+class PnpJob(C.Structure):
+    """orbx_pnp_job (include/orbx.h)"""
+    _fields_ = [("n", C.c_int), ("P3Dw", C.c_void_p), ("P2D", C.c_void_p), ("max_err", C.c_void_p), ("K", C.c_double * 4),
+                ("min_inliers", C.c_int), ("n_hyp", C.c_int), ("samples", C.c_void_p),
+                ("n_inliers", C.c_void_p), ("Rt", C.c_void_p), ("inlier_bits", C.c_void_p),
+                ("n_refined", C.c_void_p), ("Rt_refined", C.c_void_p), ("refined_bits", C.c_void_p)]
+
+
 class Sim3OptObs(C.Structure):
     """orbx_sim3opt_obs (include/orbx.h)"""
     _fields_ = [("n", C.c_int), ("has_pair", C.c_void_p), ("P1c", C.c_void_p), ("P2c", C.c_void_p), ("x1", C.c_void_p), ("y1", C.c_void_p),
@@ -280,6 +288,8 @@ def lib():
     L.orbx_frame_triangulate.argtypes = [vp, C.POINTER(TriView), C.POINTER(vp), C.POINTER(TriView), i, vp, i, vp, vp, vp, i, f, vp, vp, ip]
     L.orbx_sim3_hypotheses.argtypes = [i, C.POINTER(Sim3Job)]
     L.orbx_sim3_hypotheses_batch.argtypes = [i, C.POINTER(Sim3Job), i]
+    L.orbx_pnp_hypotheses.argtypes = [i, C.POINTER(PnpJob)]
+    L.orbx_pnp_hypotheses_batch.argtypes = [i, C.POINTER(PnpJob), i]
     L.orbx_sim3_optimize.argtypes = [i, C.POINTER(Sim3OptObs), vp, vp, vp, f, i, vp, vp, ip, C.POINTER(Sim3OptReport)]
     L.orbx_sim3_optimize_batch.argtypes = [i, C.POINTER(Sim3OptJob), i]
     L.orbx_bow_frames_create.argtypes = [i, i, i, C.POINTER(vp)]
@@ -1278,6 +1288,146 @@ class Sim3Ransac:
 
     def estimated_translation(self):
         return self.best[0][10:13].copy()
+
+
+def _pnp_job(job, who):
+    """dict(P3Dw[n][3], P2D[n][2], max_err[n], K[4] = fu fv uc vc, min_inliers, samples[n_hyp][4]) -> (PnpJob, inputs, outputs)"""
+    P3, P2 = np.ascontiguousarray(job["P3Dw"], np.float32), np.ascontiguousarray(job["P2D"], np.float32)
+    me = np.ascontiguousarray(job["max_err"], np.float32).reshape(-1)
+    sa = np.ascontiguousarray(job["samples"], np.int32)
+    k = np.asarray(job["K"], np.float64).reshape(-1)
+    n = len(P3)
+    if P3.shape != (n, 3) or P2.shape != (n, 2) or len(me) != n or sa.ndim != 2 or sa.shape[1] != 4 or len(k) != 4:
+        raise OrbxError(-1, f"{who}: P3Dw [n][3], P2D [n][2], max_err [n], samples [n_hyp][4], K [4]")
+    nh, words = len(sa), (n + 63) // 64
+    out = (np.zeros(nh, np.int32), np.zeros((nh, 12), np.float64), np.zeros((nh, words), np.uint64),
+           np.zeros(nh, np.int32), np.zeros((nh, 12), np.float64), np.zeros((nh, words), np.uint64))
+    J = PnpJob(n, _p(P3), _p(P2), _p(me), (C.c_double * 4)(*k), int(job["min_inliers"]), nh, _p(sa), *[_p(a) for a in out])
+    return J, (P3, P2, me, sa), out
+
+
+def pnp_hypotheses(job, device=0):
+    """PnPsolver's compute_pose + CheckInliers + Refine for every sample row of one solver (orbx_pnp_hypotheses): job = dict(P3Dw, P2D,
+    max_err, K, min_inliers, samples) -> (n_inliers[n_hyp] int32, Rt[n_hyp][12] float64, inlier_bits[n_hyp][(n+63)/64] uint64, n_refined,
+    Rt_refined, refined_bits); a row below min_inliers has n_refined = -1"""
+    J, keep, out = _pnp_job(job, "pnp_hypotheses")
+    _check(lib().orbx_pnp_hypotheses(device, C.byref(J)))
+    return out
+
+
+def pnp_hypotheses_batch(jobs, device=0):
+    """orbx_pnp_hypotheses_batch: the solvers of one Relocalization in one upload, one launch, one download -> [as pnp_hypotheses]"""
+    nj = len(jobs)
+    arr = (PnpJob * max(nj, 1))()
+    keep = []
+    for j, job in enumerate(jobs):
+        J, k, out = _pnp_job(job, "pnp_hypotheses_batch")
+        arr[j] = J
+        keep.append((J, k, out))
+    _check(lib().orbx_pnp_hypotheses_batch(device, arr, nj))
+    return [k[2] for k in keep]
+
+
+class PnPRansac:
+    """PnPsolver's RANSAC state machine (reference src/PnPsolver.cc:128-316) over a table of hypotheses.  solver = dict(P3Dw, P2D, sigma2,
+    K, samples): mvP3Dw, mvP2D, mvSigma2, (fu, fv, uc, vc) and the sample rows, four distinct indices each, drawn by the caller (the
+    swap-remove draw of :199-212 from a generator of the caller's: a stated deviation from DUtils::Random).  indices = mvKeyPointIndices and
+    n_matches = mvpMapPointMatches.size() scatter the inliers as the reference does.  The first iterate() or find() evaluates the first
+    mRansacMaxIts rows on the device in one call -- the reference's loop condition is an OR, so the first call walks them all unless a
+    refinement returns early -- and rows beyond them in blocks of n, by a second small call, only when the replay reaches them.
+    pnp_hypotheses_batch([r.table_job() for r in solvers]) + r.set_table(...) evaluates several solvers in one launch."""
+
+    def __init__(self, solver, indices=None, n_matches=None, device=0):
+        self.solver, self.device = solver, device
+        self.N = len(solver["P3Dw"])
+        self.indices = np.arange(self.N) if indices is None else np.asarray(indices, np.int64)
+        self.n_matches = self.N if n_matches is None else int(n_matches)
+        self.iterations = 0
+        self.best_inliers, self.best, self.best_row = 0, None, -1
+        self.set_ransac_parameters()
+
+    def set_ransac_parameters(self, probability=0.99, min_inliers=8, max_iterations=300, min_set=4, epsilon=0.4, th2=5.991):
+        import math
+        N, f32 = self.N, np.float32
+        eps = f32(epsilon)
+        n_min = max(int(f32(N) * eps), min_inliers, min_set)          # int nMinInliers = N*mRansacEpsilon: a float product, truncated
+        with np.errstate(all="ignore"):
+            if eps < f32(n_min) / f32(N):
+                eps = f32(n_min) / f32(N)
+            n_it = 1
+            if n_min != N:
+                x = np.log(np.float64(1.0) - np.float64(probability)) / np.log(np.float64(1.0) - np.float64(math.pow(float(eps), 3.0)))
+                n_it = int(math.ceil(float(x))) if np.isfinite(x) else -2 ** 31
+        self.min_inliers, self.epsilon = n_min, eps
+        self.max_its = max(1, min(n_it, max_iterations))
+        self.max_err = (np.asarray(self.solver["sigma2"], f32) * f32(th2)).astype(f32)
+        self.table = None
+
+    def table_job(self, lo=0, hi=None):
+        """the job of rows lo .. hi-1 (default: the first mRansacMaxIts)"""
+        hi = self.max_its if hi is None else hi
+        sa = np.asarray(self.solver["samples"])
+        if len(sa) < hi:
+            raise OrbxError(-1, f"PnPRansac: {len(sa)} sample rows, row {hi - 1} is needed")
+        return dict(P3Dw=self.solver["P3Dw"], P2D=self.solver["P2D"], max_err=self.max_err, K=self.solver["K"], min_inliers=self.min_inliers,
+                    samples=sa[lo:hi])
+
+    def set_table(self, table):
+        self.table = tuple(np.asarray(a) for a in table)
+
+    def _bits(self, words):
+        return np.unpackbits(np.ascontiguousarray(words, "<u8").view(np.uint8), bitorder="little")[:self.N].astype(bool)
+
+    def _need(self, k, block):
+        if self.table is None:
+            self.set_table(pnp_hypotheses(self.table_job(), self.device))
+        have = len(self.table[0])
+        if k >= have:      # the lazy tail: a solver called again past mRansacMaxIts
+            more = pnp_hypotheses(self.table_job(have, max(k + 1, have + block)), self.device)
+            self.table = tuple(np.concatenate([a, b]) for a, b in zip(self.table, more))
+
+    def _scatter(self, inl):
+        vb = np.zeros(self.n_matches, bool)
+        vb[self.indices[inl]] = True
+        return vb
+
+    @staticmethod
+    def Tcw(rt):
+        """mBestTcw / mRefinedTcw: the CV_64F -> CV_32F conversion of :228-234"""
+        T = np.eye(4, dtype=np.float32)
+        with np.errstate(all="ignore"):
+            T[:3, :3] = rt[:9].astype(np.float32).reshape(3, 3)
+            T[:3, 3] = rt[9:12].astype(np.float32)
+        return T
+
+    def iterate(self, n_iterations):
+        """-> (Tcw 4 x 4 float32 or None, bNoMore, vbInliers[n_matches], nInliers)"""
+        vb = np.zeros(self.n_matches, bool)
+        if self.N < self.min_inliers:
+            return None, True, vb, 0
+        cur = 0
+        while self.iterations < self.max_its or cur < n_iterations:
+            cur += 1
+            self.iterations += 1
+            k = self.iterations - 1
+            self._need(k, max(1, n_iterations))
+            ni, rt, bits, nr, rtr, rbits = self.table
+            if ni[k] >= self.min_inliers:
+                if ni[k] > self.best_inliers:
+                    self.best_inliers, self.best, self.best_row = int(ni[k]), (rt[k].copy(), self._bits(bits[k])), k
+                # Refine reads mvbBestInliers: the best row's own refinement, already in the table
+                b = self.best_row
+                if nr[b] > self.min_inliers:
+                    return self.Tcw(rtr[b]), False, self._scatter(self._bits(rbits[b])), int(nr[b])
+        if self.iterations >= self.max_its:
+            if self.best_inliers >= self.min_inliers:
+                return self.Tcw(self.best[0]), True, self._scatter(self.best[1]), self.best_inliers
+            return None, True, vb, 0
+        return None, False, vb, 0
+
+    def find(self):
+        T, _, vb, ni = self.iterate(self.max_its)
+        return T, vb, ni
 
 
 def _pose_cam(pose, cam, who):
