@@ -1231,6 +1231,16 @@ int orbx_debug_fast_form(const orbx_extractor *e);
  *   [9] k_desc row pass: 2 = matrix cores, 1 = vector ALUs (ORBX_DESC_VALU_ROWPASS=1 when the handle was created)
  * All 0 before the first launch. */
 int orbx_debug_launch_forms(const orbx_extractor *e, int32_t *out, int n);
+/* The per-lane geometry of the FAST kernel's pretest and list phases as the host tabulates it for one detect shape (dw x dh pixels of a cell,
+ * tile pitch 48 or 80): out[64][4] = the 64 lanes' 16-byte entries, uni[0] = detect rows per pretest iteration, uni[1] = 1 for half-row list
+ * segments.  Entry: [0] pixel mask of the lane's pretest group (0: idle lane); [1] bits 0-15 tile byte offset of the group's centre dword,
+ * bits 16-31 byte offset of its bitmap word; [2] bits 0-15 list segment (row << 6 | first bit), bit 16 row exists, bits 24-28 nibble shift;
+ * [3] 0.  A pure host function: needs no device. */
+int orbx_debug_fast_lane_table(int tile_pitch, int dw, int dh, uint32_t *out, int32_t *uni);
+/* The FAST cell records of the handle's current geometry, eight ints per cell: level, skip, ini_x, ini_y, tw, th (rectangle incl. the 3-px
+ * halo), level pitch, shape class (the cell's block of the lane table).  Writes them if cap >= the number of cells; returns that number
+ * (0 before the first extraction). */
+int orbx_debug_fast_cells(const orbx_extractor *e, int32_t *out, int cap);
 /* test hook: the SearchByBoW kernels exist in a latency form (one 16-wave workgroup per pair) and a throughput form
  * (LDS distance table + row fixpoint); a call picks by problem size.  form = 1 / 2 forces the wave / table form for
  * every later call of the process, 0 restores the automatic choice.  Both forms return identical matches. */

@@ -119,6 +119,36 @@ __device__ __forceinline__ unsigned wave_max_u32(unsigned v)
     return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
 }
 
+// ---- LDS-direct load (global_load_lds_dword / _dwordx4) addressed as a wave-uniform 64-bit base plus a 32-bit lane offset: lane i's
+// BYTES bytes at sbase + voff land at lds_dst + BYTES * i.  __builtin_amdgcn_global_load_lds only takes a flat per-lane pointer, for which the
+// compiler forms sbase + voff with a 64-bit vector add (v_lshl_add_u64) in front of EVERY load, also when the caller advances the base on
+// the scalar unit; the instruction's own `saddr` form takes the SGPR pair and the 32-bit VGPR as they are.  M0 (the LDS destination) is set
+// inside the statement and put back, the compiler may keep a value of its own there.  The compiler does not count these loads: the caller
+// waits with an explicit s_waitcnt vmcnt(0) before the data is read (every site had that wait already).  sbase and lds_dst must be
+// wave-uniform and computed on the scalar unit (a base fresh from v_readfirstlane would need wait states in front of the load).
+// Used by the tile loads of k_fast / k_fast2, where it measured (k_fast is bound by vector issue, and the compiler also held the zeroing
+// of the score tile behind the builtin's loads).  k_desc's patch loads and k_resize's row groups (the dwordx4 form) measured 0.5 % slower
+// with it -- neither is bound by vector issue, and the four scalar instructions around each load lengthen the wave -- and keep the
+// builtin ("Where the next percent is").  -DORBX_LDS_LOAD_FLAT: the builtin form here too, for A/B timing.
+template <int BYTES>
+__device__ __forceinline__ void lds_load_sbase(const uint8_t *sbase, unsigned voff, const void *lds_dst)
+{
+    static_assert(BYTES == 4 || BYTES == 16, "global_load_lds_dword / global_load_lds_dwordx4");
+#ifdef ORBX_LDS_LOAD_FLAT
+    __builtin_amdgcn_global_load_lds(reinterpret_cast<const uint32_t *>(sbase + voff),
+                                     reinterpret_cast<uint32_t *>(const_cast<void *>(lds_dst)), BYTES, 0, 0);
+#elif defined(__HIP_DEVICE_COMPILE__)
+    const unsigned lds = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void *)lds_dst;
+    unsigned keep;
+    if constexpr (BYTES == 4)
+        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0"
+                     : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds) : "memory");
+    else
+        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+                     : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds) : "memory");
+#endif
+}
+
 // exclusive scan of one value per thread over an NT-thread workgroup (NT = 256 or 1024); s_w = NT / 64 ints of LDS
 template <int NT>
 __device__ __forceinline__ int block_excl_scan(int v, int *total, int *s_w)

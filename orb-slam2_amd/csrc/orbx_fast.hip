@@ -155,8 +155,57 @@ struct FastArgs {
     int bm_rows;                    // bitmap rows (u64 each): tallest detect area plus the row overrun of the last pretest iteration
     int ini_th, min_th;
     int list_cap;                   // entries of the candidate list (used by the several-waves-per-cell form; one wave: ORBX_FAST_LIST_CAP)
+    int lane_tab_off;               // byte offset of the lane table behind the cell records (orbx_fast_plan)
     long long cand_total;
 };
+
+// Lane geometry of k_fast's pretest and list phases from the host.  Everything a lane derives from its number and the cell's detect shape
+// (dw, dh) -- its pretest row and group, pixel mask and bitmap slot, its list segment -- is the same for every cell of that shape, and a
+// geometry has a handful of shapes (interior, last column, last row, corner of each level: under 32 at 1241 x 376, for ~640 k waves per
+// launch).  The host tabulates it: one 16-byte entry per (shape class, lane), the class rides above the level number in CellRec::level.  A wave
+// requests its entry before the tile loads and reads it behind the same wait, so the fetch costs no round trip of its own.
+//   x  pixel mask of the lane's pretest group (0: the lane idles)
+//   y  bits 0-15 tile byte offset of the group's centre dword in the first pretest iteration, bits 16-31 byte offset of its bitmap word
+//   z  bits 0-15 list segment as the entries carry it (row << 6 | first bit), bit 16 the segment's row exists, bits 24-28 shift of the
+//      group's nibble inside its bitmap word
+//   w  0
+// (The tile-load geometry, lane / DWR and lane % DWR, stays in the kernel: the loads it addresses are what covers the fetch.)
+// The wave-uniform part (rows per pretest iteration, half-row segments) stays on the scalar unit, which has time to spare.
+// One pure function of (P, dw, dh, lane) serves the plan and orbx_debug_fast_lane_table; uni[0] = rpi, uni[1] = half_mode.
+#define FAST_MAX_CLASSES 2048       // the class shares CellRec::level (a short) with the level number: level in bits 0-3, class in bits 4-14
+static_assert(ORBX_MAX_LEVELS <= 16, "CellRec::level: four bits of level number");
+static void fast_lane_entry(int P, int dw, int dh, int lane, uint32_t out[4], int uni[2])
+{
+    const int gpr = (dw + 3) >> 2;
+    const unsigned magic = 0xFFFFFFFFu / (unsigned)gpr + 1u;
+    const int lq = gpr == 1 ? lane : (int)(((unsigned long long)(unsigned)lane * magic) >> 32);
+    const int rpi = std::min(gpr == 1 ? 64 : (int)((64ull * magic) >> 32), 8);
+    const int lr = std::min(lq, rpi), gq = lane - lq * gpr;
+    const int nvalid = std::max(1, std::min(4, dw - 4 * gq));
+    const unsigned vmask = lr < rpi ? (0x80808080u >> (8 * (4 - nvalid))) : 0u;
+    const int bm_sh = 4 * (gq & 7);
+    const bool half_mode = dh <= 32 && dw <= 32;
+    const int brow = half_mode ? lane >> 1 : lane;
+    const unsigned bsh = half_mode ? 16u * (lane & 1) : 0u;
+    const unsigned pc_off = (unsigned)((lr + 3) * P + 4 * (1 + gq)), pb_off = 4u * (unsigned)(lr * 2 + (gq >> 3));
+    out[0] = vmask;
+    out[1] = pc_off | (pb_off << 16);
+    out[2] = ((unsigned)brow << 6) | bsh | (brow < dh ? 0x10000u : 0u) | ((unsigned)bm_sh << 24);
+    out[3] = 0;
+    uni[0] = rpi; uni[1] = half_mode ? 1 : 0;
+}
+
+// debug: the lane table of one detect shape, out[64][4], and the wave-uniform pair uni[2] = (rpi, half_mode); needs no device
+extern "C" int orbx_debug_fast_lane_table(int tile_pitch, int dw, int dh, uint32_t *out, int32_t *uni)
+{
+    if ((tile_pitch != 48 && tile_pitch != ORBX_TILE_PITCH) || dw < 1 || dh < 1 || dw > (tile_pitch == 48 ? 38 : 59) || dh > 64 || !out || !uni) {
+        orbx_set_error("orbx_debug_fast_lane_table: invalid argument"); return ORBX_E_INVALID;
+    }
+    int u[2] = { 0, 0 };
+    for (int lane = 0; lane < 64; lane++) fast_lane_entry(tile_pitch, dw, dh, lane, out + 4 * lane, u);
+    uni[0] = u[0]; uni[1] = u[1];
+    return ORBX_OK;
+}
 
 #ifdef ORBX_DIAG
 __device__ unsigned long long g_fast_stamp[4096 * 8]; // diagnostic build only: summed phase cycles of k_fast, 4096 slots
@@ -221,12 +270,14 @@ __global__ __launch_bounds__(64 * NW) void k_fast(const FastArgs fa, const CellR
     SPAN_BEGIN();
     // the 40-byte record as ten dwords (scalar loads; 16-bit fields fetched by themselves become vector loads on gfx950)
     CellRec rec;
+    int cls;
     {
         const uint32_t *cw = reinterpret_cast<const uint32_t *>(cells + cell);
         uint32_t w[10];
 #pragma unroll
         for (int i = 0; i < 10; i++) w[i] = cw[i];
-        rec.level = (short)(w[0] & 0xFFFF); rec.skip = (short)(w[0] >> 16);
+        rec.level = (short)(w[0] & 0xF); rec.skip = (short)(w[0] >> 16);
+        cls = (int)((w[0] >> 4) & 0x7FF);       // shape class of the cell: its block of the lane table
         rec.ini_x = (short)(w[1] & 0xFFFF); rec.ini_y = (short)(w[1] >> 16);
         rec.tw = (short)(w[2] & 0xFFFF); rec.th = (short)(w[2] >> 16);
         rec.pitch = (int)w[3]; rec.cand_cap = (int)w[4]; rec.gpr_magic = w[5];
@@ -238,6 +289,10 @@ __global__ __launch_bounds__(64 * NW) void k_fast(const FastArgs fa, const CellR
         if (lane == 0) *my_cnt = 0;
         return;
     }
+#ifndef ORBX_FAST_LANE_INLINE
+    // the lane's pretest / list geometry (fast_lane_entry), requested ahead of the tile loads and first read behind their wait
+    const uint4 lg = reinterpret_cast<const uint4 *>(reinterpret_cast<const uint8_t *>(cells) + fa.lane_tab_off)[cls * 64 + lane];
+#endif
     const int ini_x = rec.ini_x, ini_y = rec.ini_y, tw = rec.tw, th = rec.th, dw = tw - 6, dh = th - 6;
     const int pitch = rec.level == 0 ? pr.img0_pitch : rec.pitch;
     const uint8_t *img = rec.level == 0 ? pr.img0 + (long long)b * pr.img0_stride
@@ -250,18 +305,20 @@ __global__ __launch_bounds__(64 * NW) void k_fast(const FastArgs fa, const CellR
     {
         const int lr0 = lane / DWR, lc = lane - lr0 * DWR;
         const int ndw = (tw + xo + 3) >> 2;             // dwords per row that hold cell pixels (<= 17)
-        // scalar row base + one 32-bit lane offset: the row groups advance on the scalar unit, no 64-bit vector adds per load
+        // scalar row base + one 32-bit lane offset (lds_load_sbase: the load's saddr form): the row groups advance on the scalar unit,
+        // no 64-bit vector add per load
         const uint8_t *base = img + (long long)ini_y * pitch + (ini_x - xo);
         const unsigned voff = (unsigned)(lr0 * pitch + 4 * lc);
         const int full = th / RPL;
         if (lc < ndw && lr0 < RPL) {
-            base += (long long)wv * RPL * pitch;
-            for (int k = wv; k < full; k += NW, base += (long long)NW * RPL * pitch)
-                __builtin_amdgcn_global_load_lds(reinterpret_cast<const uint32_t *>(base + voff), reinterpret_cast<uint32_t *>(tile + RPL * P * k), 4, 0, 0);
+            const int wvu = NW == 1 ? 0 : __builtin_amdgcn_readfirstlane(wv);   // (wave-uniform, but not provably so from threadIdx.x >> 6)
+            base += (long long)wvu * RPL * pitch;
+            for (int k = wvu; k < full; k += NW, base += (long long)NW * RPL * pitch)
+                lds_load_sbase<4>(base, voff, tile + RPL * P * k);
             // the last, partial group of rows never reads below the cell (after the loop `base` stands at this wave's next group:
             // the partial group is `full`, taken by the wave whose turn it is)
-            if ((NW == 1 || full % NW == wv) && full * RPL + lr0 < th)
-                __builtin_amdgcn_global_load_lds(reinterpret_cast<const uint32_t *>(base + voff), reinterpret_cast<uint32_t *>(tile + RPL * P * full), 4, 0, 0);
+            if ((NW == 1 || full % NW == wvu) && full * RPL + lr0 < th)
+                lds_load_sbase<4>(base, voff, tile + RPL * P * full);
         }
     }
     {   // meanwhile: zero score tile (1-px zero rim included) and both bitmaps
@@ -278,20 +335,32 @@ __global__ __launch_bounds__(64 * NW) void k_fast(const FastArgs fa, const CellR
     // rpi whole rows, lane = (row lr, group gq); lanes beyond rpi * gpr idle with an empty pixel mask
     const int gpr = (dw + 3) >> 2;
     // floor(i / gpr) by multiply-high with the host's magic number (an integer division costs ~30 instructions here)
-    const int lq = gpr == 1 ? lane : (int)__umulhi((unsigned)lane, rec.gpr_magic);
     const int rpi = min(gpr == 1 ? 64 : (int)__umulhi(64u, rec.gpr_magic), 8);   // (the last column's cells can be narrow: keep the row overrun <= 8)
-    const int lr = min(lq, rpi), gq = lane - lq * gpr;
-    const int nvalid = max(1, min(4, dw - 4 * gq));      // only the last group of a row can be partial
-    const unsigned vmask = lr < rpi ? (0x80808080u >> (8 * (4 - nvalid))) : 0u;
-    const int bm_sh = 4 * (gq & 7);
-    uint32_t *slot = cand + (long long)b * fa.cand_total + rec.cand_slot;
-    uint32_t *prim = cand_prim + ((long long)b * fa.total_cells + cell) * ORBX_CAND_PRIM;   // the first 16 candidates: dense, 64 B per cell
     // Bitmap rows are walked with one lane per SEGMENT: a whole row (64 bits, low word then high word), or -- when the detect
     // area is at most 32 x 32, most cells of a 30-px grid -- half a 32-bit row word: the bit loops below run as long as the
     // fullest segment, and half rows are half as full
     const bool half_mode = dh <= 32 && dw <= 32;
+#ifdef ORBX_FAST_LANE_INLINE   // the lane's geometry computed by every wave (the form before the host table; fast_lane_entry restates it)
+    const int lq = gpr == 1 ? lane : (int)__umulhi((unsigned)lane, rec.gpr_magic);
+    const int lr = min(lq, rpi), gq = lane - lq * gpr;
+    const int nvalid = max(1, min(4, dw - 4 * gq));      // only the last group of a row can be partial
+    const unsigned vmask = lr < rpi ? (0x80808080u >> (8 * (4 - nvalid))) : 0u;
+    const int bm_sh = 4 * (gq & 7);
+    const int pc_off = (lr + 3) * P + 4 * (1 + gq), pb_off = 4 * (lr * 2 + (gq >> 3));
     const int brow = half_mode ? lane >> 1 : lane;
     const unsigned bsh = half_mode ? 16u * (lane & 1) : 0u;
+    const bool row_ok = brow < dh;
+    (void)cls;
+#else
+    const unsigned vmask = lg.x;
+    const int pc_off = (int)(lg.y & 0xFFFFu), pb_off = (int)(lg.y >> 16);
+    const int bm_sh = (int)(lg.z >> 24);
+    const int brow = (int)((lg.z & 0xFFFFu) >> 6);
+    const unsigned bsh = lg.z & 63u;
+    const bool row_ok = (lg.z & 0x10000u) != 0;
+#endif
+    uint32_t *slot = cand + (long long)b * fa.cand_total + rec.cand_slot;
+    uint32_t *prim = cand_prim + ((long long)b * fa.total_cells + cell) * ORBX_CAND_PRIM;   // the first 16 candidates: dense, 64 B per cell
     int th_cur = ini_th, nsurv = 0;
     int emitted = 0;            // one wave, one round: maxima written straight from the corner list (see below)
     bool direct = false;
@@ -303,8 +372,8 @@ __global__ __launch_bounds__(64 * NW) void k_fast(const FastArgs fa, const CellR
         // KB = (RB | 0x80) - 0x7f.  Corner candidates: (N | S) & (E | W) on either side.
         {
             const unsigned s7 = (unsigned)((th_cur + 1) >> 1) * 0x01010101u;
-            const uint8_t *pc = tile + (lr + 3 + wv * rpi) * P + 4 * (1 + gq);
-            uint32_t *pb = bm + (lr + wv * rpi) * 2 + (gq >> 3);
+            const uint8_t *pc = tile + pc_off + wv * rpi * P;
+            uint32_t *pb = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(bm) + pb_off) + wv * rpi * 2;
             for (int r0 = wv * rpi; r0 < dh; r0 += NW * rpi, pc += NW * rpi * P, pb += NW * rpi * 2) {
                 const uint32_t *rc = reinterpret_cast<const uint32_t *>(pc);
                 const unsigned C = rc[0], Wd = rc[-1], Ed = rc[1], N = rc[3 * DWR], S = rc[-3 * DWR];
@@ -327,7 +396,7 @@ __global__ __launch_bounds__(64 * NW) void k_fast(const FastArgs fa, const CellR
         // ORBX_FAST_LIST_CAP entries (LDS is what limits the waves per CU, and a textured cell lists ~130 of its ~1000 pixels);
         // a cell with more candidates takes them in rounds of that many: all scores first, then the maxima
         unsigned c_lo = 0, c_hi = 0;
-        if (brow < dh) { const uint2 m = *reinterpret_cast<const uint2 *>(bm + 2 * brow); c_lo = half_mode ? (m.x >> bsh) & 0xFFFFu : m.x; c_hi = half_mode ? 0u : m.y; }
+        if (row_ok) { const uint2 m = *reinterpret_cast<const uint2 *>(bm + 2 * brow); c_lo = half_mode ? (m.x >> bsh) & 0xFFFFu : m.x; c_hi = half_mode ? 0u : m.y; }
         const int c_cnt = __popc(c_lo) + __popc(c_hi);
         const int c_incl = wave_incl_scan(c_cnt);
         const int nlist = __builtin_amdgcn_readlane(c_incl, 63);
@@ -479,7 +548,7 @@ __global__ __launch_bounds__(64 * NW) void k_fast(const FastArgs fa, const CellR
         }
         {
             unsigned lo = 0, hi = 0;
-            if (brow < dh) { const uint2 m = *reinterpret_cast<const uint2 *>(sv + 2 * brow); lo = half_mode ? (m.x >> bsh) & 0xFFFFu : m.x; hi = half_mode ? 0u : m.y; }
+            if (row_ok) { const uint2 m = *reinterpret_cast<const uint2 *>(sv + 2 * brow); lo = half_mode ? (m.x >> bsh) & 0xFFFFu : m.x; hi = half_mode ? 0u : m.y; }
             nsurv = __popc(lo) + __popc(hi);
         }
         // the cell falls back to minThFAST only if iniThFAST kept nothing (:991-995); pretest, scores and bitmaps of the
@@ -493,7 +562,7 @@ __global__ __launch_bounds__(64 * NW) void k_fast(const FastArgs fa, const CellR
     // ---- ordered (row-major) emission into the cell's candidate slots: lane = bitmap segment (row, or half a row)
     if (wv == 0) {
         unsigned lo = 0, hi = 0;
-        if (brow < dh) { const uint2 m = *reinterpret_cast<const uint2 *>(sv + 2 * brow); lo = half_mode ? (m.x >> bsh) & 0xFFFFu : m.x; hi = half_mode ? 0u : m.y; }
+        if (row_ok) { const uint2 m = *reinterpret_cast<const uint2 *>(sv + 2 * brow); lo = half_mode ? (m.x >> bsh) & 0xFFFFu : m.x; hi = half_mode ? 0u : m.y; }
         const int incl = wave_incl_scan(nsurv);
         const int total = __builtin_amdgcn_readlane(incl, 63);
         int o = incl - nsurv;
@@ -618,9 +687,9 @@ __global__ __launch_bounds__(64) void k_fast2(const FastArgs fa, const PairRec *
         const int full = th / RPL;
         if (lc < ndw && lr0 < RPL) {
             for (int k = 0; k < full; k++, base += (long long)RPL * pitch)
-                __builtin_amdgcn_global_load_lds(reinterpret_cast<const uint32_t *>(base + voff), reinterpret_cast<uint32_t *>(tile + RPL * P * k), 4, 0, 0);
+                lds_load_sbase<4>(base, voff, tile + RPL * P * k);
             if (full * RPL + lr0 < th)      // the last, partial group of rows never reads below the cells
-                __builtin_amdgcn_global_load_lds(reinterpret_cast<const uint32_t *>(base + voff), reinterpret_cast<uint32_t *>(tile + RPL * P * full), 4, 0, 0);
+                lds_load_sbase<4>(base, voff, tile + RPL * P * full);
         }
     }
     {   // meanwhile: zero score tile (rim and the column between the cells included) and both bitmaps
@@ -935,9 +1004,50 @@ void orbx_fast_plan(const orbx_extractor *e, Geom &G, std::vector<CellRec> &cell
             G.total_pairs = (int)pairs.size();
         }
     }
+    // Shape classes and the lane table of k_fast (fast_lane_entry): one class per distinct detect shape (dw, dh), its id above the level number
+    // in CellRec::level; the table follows the records in the same upload, 16-byte aligned (G.fast_lane_tab_off bytes behind the first record)
+    {
+        const int P = G.fast_small ? 48 : ORBX_TILE_PITCH;
+        std::vector<std::pair<int, int>> shapes;
+        for (int l = 0; l < e->nlevels; l++)
+            for (int ci = 0; ci < G.lv[l].n_cells; ci++) {
+                CellRec &c = cells[G.lv[l].cell_base + ci];
+                if (c.skip) continue;               // (a skipped cell keeps class 0 and never reads the table)
+                const std::pair<int, int> sh(c.tw - 6, c.th - 6);
+                size_t k = std::find(shapes.begin(), shapes.end(), sh) - shapes.begin();
+                if (k == shapes.size()) shapes.push_back(sh);
+                c.level = (short)(l | ((int)k << 4));   // (k < FAST_MAX_CLASSES: dw <= 59 and dh <= 64 per level, ORBX_MAX_LEVELS levels, in practice four shapes per level)
+            }
+        const size_t tab_off = align_up((size_t)G.total_cells * sizeof(CellRec), 16), tab_bytes = shapes.size() * 64 * 16;
+        G.fast_lane_tab_off = (int)tab_off;
+        cells.resize((tab_off + tab_bytes + sizeof(CellRec) - 1) / sizeof(CellRec));   // whole records: the upload copies cells.size() of them
+        uint32_t *tab = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(cells.data()) + tab_off);
+        int uni[2];
+        for (size_t k = 0; k < shapes.size(); k++)
+            for (int lane = 0; lane < 64; lane++) fast_lane_entry(P, shapes[k].first, shapes[k].second, lane, tab + (k * 64 + lane) * 4, uni);
+    }
     std::vector<uint8_t> pb(pairs.size() * sizeof(PairRec));
     if (!pairs.empty()) memcpy(pb.data(), pairs.data(), pb.size());
     cells_out.swap(cells); pair_bytes.swap(pb);
+}
+
+// debug: the cell records of the handle's current geometry as the plan builds them, eight ints per cell: level, skip, ini_x, ini_y, tw, th,
+// level pitch, shape class.  Returns the number of cells (also when cap is smaller: nothing is written then), 0 before the first extraction.
+extern "C" int orbx_debug_fast_cells(const orbx_extractor *e, int32_t *out, int cap)
+{
+    if (!e || cap < 0 || (cap > 0 && !out)) { orbx_set_error("orbx_debug_fast_cells: invalid argument"); return ORBX_E_INVALID; }
+    if (e->geom.w == 0) return 0;
+    Geom G = e->geom;
+    std::vector<CellRec> cells;
+    std::vector<uint8_t> pairs;
+    orbx_fast_plan(e, G, cells, pairs);
+    if (cap < G.total_cells) return G.total_cells;
+    for (int i = 0; i < G.total_cells; i++) {
+        const CellRec &c = cells[i];
+        const int32_t v[8] = { c.level & 0xF, c.skip, c.ini_x, c.ini_y, c.tw, c.th, c.pitch, (c.level >> 4) & 0x7FF };
+        memcpy(out + 8 * i, v, sizeof v);
+    }
+    return G.total_cells;
 }
 
 void orbx_fast_launch(orbx_extractor *e, const PyrRef &pr, int batch, hipStream_t s)
@@ -950,6 +1060,7 @@ void orbx_fast_launch(orbx_extractor *e, const PyrRef &pr, int batch, hipStream_
         FastArgs fa;
         fa.total_cells = G.total_cells; fa.lds_sc = G.fast_lds_sc; fa.lds_list = G.fast_lds_list; fa.lds_bm = G.fast_lds_bm;
         fa.bm_rows = G.fast_bm_rows; fa.ini_th = e->ini_th; fa.min_th = e->min_th; fa.cand_total = G.cand_total; fa.list_cap = ORBX_FAST_LIST_CAP;
+        fa.lane_tab_off = G.fast_lane_tab_off;
         const dim3 grid((G.total_cells + 8 * FAST_XG - 1) / (8 * FAST_XG) * (8 * FAST_XG), batch);
         if (G.fast_small)
         {

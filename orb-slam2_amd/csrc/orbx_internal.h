@@ -59,6 +59,7 @@ struct Geom {
     int fast_lds_sc, fast_lds_list, fast_lds_bm, fast_bm_rows, fast_lds_bytes; // LDS carve of k_fast
     int fast_small;         // 1: k_fast<48,40> (every cell <= 38 px wide), 0: k_fast<80,64>
     int fast_list_cap_big, fast_lds_bm_big, fast_lds_bytes_big;   // the carve with a candidate list that holds a whole cell (several waves per cell)
+    int fast_lane_tab_off;  // k_fast's lane table (one block of 64 x 16 bytes per detect shape): byte offset behind the first cell record
     int fast2_ok, total_pairs;   // k_fast2 (a wave per pair of adjacent cells) is usable for this geometry; pair records per image
     int fast2_first[2], fast2_count[2];   // two launches: levels whose detect areas have at most 32 rows, then the taller ones
     int fast2_lds_sc[2], fast2_lds_list[2], fast2_lds_bm[2], fast2_bm_rows[2], fast2_lds_bytes[2];

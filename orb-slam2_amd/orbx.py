@@ -348,6 +348,8 @@ def lib():
     L.orbx_debug_level_counts.argtypes = [vp, i, vp]
     L.orbx_debug_fast_form.argtypes = [vp]
     L.orbx_debug_launch_forms.argtypes = [vp, vp, i]
+    L.orbx_debug_fast_lane_table.argtypes = [i, i, i, vp, vp]
+    L.orbx_debug_fast_cells.argtypes = [vp, vp, i]
     L.orbx_debug_bow_last_form.argtypes = [vp]
     L.orbx_debug_set_bow_form.argtypes = [i]
     L.orbx_debug_set_match_items.argtypes = [i]
@@ -405,6 +407,14 @@ def desc_rowpass_matrix(profile):
     acc0 = C.c_int(0)
     _check(lib().orbx_desc_rowpass_matrix(profile, _p(b), C.byref(acc0)))
     return b, acc0.value
+
+
+def debug_fast_lane_table(tile_pitch, dw, dh):
+    """k_fast's host-built lane table of one detect shape (orbx_debug_fast_lane_table): (entries uint32 [64, 4], rpi, half_mode); no device needed"""
+    out = np.zeros((64, 4), np.uint32)
+    uni = np.zeros(2, np.int32)
+    _check(lib().orbx_debug_fast_lane_table(int(tile_pitch), int(dw), int(dh), _p(out), _p(uni)))
+    return out, int(uni[0]), bool(uni[1])
 
 
 def debug_set_bow_form(form):
@@ -505,6 +515,17 @@ class ORBextractor:
     def debug_fast_form(self):
         """1 = k_fast, 2 = k_fast2 (a pair of cells per wave) ran in the most recent extraction"""
         return self._L.orbx_debug_fast_form(self._h)
+
+    FAST_CELL_FIELDS = ("level", "skip", "ini_x", "ini_y", "tw", "th", "pitch", "shape_class")
+
+    def debug_fast_cells(self):
+        """the FAST cell records of the current geometry (orbx_debug_fast_cells): int32 [cells, 8], columns FAST_CELL_FIELDS"""
+        n = self._L.orbx_debug_fast_cells(self._h, None, 0)
+        _check(min(n, 0))
+        out = np.zeros((n, 8), np.int32)
+        if n:
+            _check(min(self._L.orbx_debug_fast_cells(self._h, _p(out), n), 0))
+        return out
 
     LAUNCH_FORM_FIELDS = ("pyramid_regime", "fast_waves", "fast_image_major", "tree_threads", "tree_tab_lds", "tree_reg",
                           "desc_levels", "stereo_kpw", "stereo_xcd_grid", "desc_rowpass")

@@ -99,6 +99,46 @@ KERNEL(k_lshl_b16, "v_lshlrev_b16 %0, 1, %0", "v"(b))
 KERNEL(k_ballot_like, "v_cmp_ne_u32 vcc, 0, %0", "v"(b) : "vcc")
 KERNEL(k_readlane, "v_readfirstlane_b32 s20, %0", "v"(b) : "s20")
 
+// 64-bit address arithmetic: what a flat-pointer LDS-direct load costs in front of it when its address is "scalar base + lane offset"
+// (v_lshl_add_u64 with the base in an SGPR pair is what the compiler emits there), against the carry pair it replaced on older targets.
+// Same 32 statements per iteration: the figure printed is per v_lshl_add_u64, and per PAIR for k_add64_pair.
+#define KERNEL64(NAME, ASM, ...)                                                                                \
+    __global__ __launch_bounds__(64) void NAME(unsigned *out)                                                   \
+    {                                                                                                           \
+        unsigned long long a[16];                                                                               \
+        _Pragma("unroll") for (int i = 0; i < 16; i++) a[i] = threadIdx.x * 17 + i * 3 + blockIdx.x;            \
+        unsigned long long b = threadIdx.x ^ 5;                                                                 \
+        const unsigned long long s = (unsigned long long)blockIdx.x * 4099u + 7u;                               \
+        for (int it = 0; it < ITERS; it++) {                                                                    \
+            _Pragma("unroll") for (int r = 0; r < 2; r++)                                                       \
+            _Pragma("unroll") for (int i = 0; i < 16; i++) asm volatile(ASM : "+v"(a[i]) : __VA_ARGS__);        \
+        }                                                                                                       \
+        unsigned long long t = 0;                                                                               \
+        _Pragma("unroll") for (int i = 0; i < 16; i++) t += a[i];                                               \
+        out[blockIdx.x * 64 + threadIdx.x] = (unsigned)(t + b + s) + (unsigned)((t + b + s) >> 32);             \
+    }
+KERNEL64(k_lshl_add_u64, "v_lshl_add_u64 %0, %0, 0, %1", "v"(b))
+KERNEL64(k_lshl_add_u64_s, "v_lshl_add_u64 %0, %0, 0, %1", "s"(s))
+KERNEL64(k_lshl_add_u64_sh, "v_lshl_add_u64 %0, %0, 2, %1", "v"(b))
+__global__ __launch_bounds__(64) void k_add64_pair(unsigned *out)
+{
+    unsigned lo[16], hi[16];
+#pragma unroll
+    for (int i = 0; i < 16; i++) { lo[i] = threadIdx.x * 17 + i * 3 + blockIdx.x; hi[i] = i; }
+    unsigned b = threadIdx.x ^ 5, c = threadIdx.x * 3 + 1;
+    for (int it = 0; it < ITERS; it++) {
+#pragma unroll
+        for (int r = 0; r < 2; r++)
+#pragma unroll
+            for (int i = 0; i < 16; i++)
+                asm volatile("v_add_co_u32 %0, vcc, %0, %2\n\tv_addc_co_u32 %1, vcc, %1, %3, vcc" : "+v"(lo[i]), "+v"(hi[i]) : "v"(b), "v"(c) : "vcc");
+    }
+    unsigned s = 0;
+#pragma unroll
+    for (int i = 0; i < 16; i++) s += lo[i] + hi[i];
+    out[blockIdx.x * 64 + threadIdx.x] = s + b + c;
+}
+
 typedef void (*kern_t)(unsigned *);
 static double clock_ghz = 2.3;
 
@@ -150,5 +190,6 @@ int main()
     R(k_max_u32); R(k_max_i32); R(k_min_i32); R(k_add_f32); R(k_mul_f32); R(k_add_f16); R(k_max_f16); R(k_or3); R(k_lshl_or); R(k_xad); R(k_cvt_ub0); R(k_cndmask_s);
     R(k_add_vop3); R(k_add_co); R(k_min_u16_sdwa); R(k_add_sdwa); R(k_mul_u16); R(k_lshl_b16); R(k_ballot_like); R(k_readlane);
     R(k_fma); R(k_pk_fma); R(k_max_f32); R(k_max3_f32); R(k_pk_max_f16); R(k_cmp); R(k_cmp_s);
+    R(k_lshl_add_u64); R(k_lshl_add_u64_s); R(k_lshl_add_u64_sh); R(k_add64_pair);
     return 0;
 }
