@@ -59,36 +59,28 @@ def test_oracle_reproduces_stereo_and_bow_fixtures(oracle):
     assert (p == b["tri_pairs"]).all()
 
 
-def _search_by_bow_python(kf, f, ratio):
-    """independent plain-Python restatement of SearchByBoW(KF,F) (reference src/ORBmatcher.cc:171-303)
-    without the orientation filter, with dicts standing in for std::map"""
-    pop = np.array([bin(i).count("1") for i in range(256)])
-    fv_kf = {int(i): kf["feat"][kf["node_off"][j]:kf["node_off"][j + 1]] for j, i in enumerate(kf["node_id"])}
-    fv_f = {int(i): f["feat"][f["node_off"][j]:f["node_off"][j + 1]] for j, i in enumerate(f["node_id"])}
-    match = np.full(len(f["desc"]), -1, np.int32)
-    for node in sorted(set(fv_kf) & set(fv_f)):
-        for i_kf in fv_kf[node]:
-            if not kf["flag"][i_kf]:
-                continue
-            b1, b2, bi = 256, 256, -1
-            for i_f in fv_f[node]:
-                if match[i_f] >= 0:
-                    continue
-                dist = int(pop[kf["desc"][i_kf] ^ f["desc"][i_f]].sum())
-                if dist < b1:
-                    b2, b1, bi = b1, dist, i_f
-                elif dist < b2:
-                    b2 = dist
-            if b1 <= 50 and np.float32(b1) < np.float32(ratio) * np.float32(b2):
-                match[bi] = i_kf
+def _search_by_bow_python(kf, f, ratio, check_ori=False):
+    """independent plain-Python restatement of SearchByBoW(KF,F) (reference src/ORBmatcher.cc:171-303), dicts standing in for std::map:
+    tests/matcher_model.py, which never touches the oracle"""
+    import matcher_model
+    match, n, _ = matcher_model.search_by_bow_kf_f(kf, f, ratio, check_ori)
+    assert n == (match >= 0).sum()
     return match
 
 
 def test_bow_oracle_vs_plain_python(oracle):
     b = _load(os.path.join(GOLD, "bow_s105.npz"))
     kf, fr = _featset(b, "kf"), _featset(b, "fr")
-    m, n = oracle.search_by_bow_kf_f(kf, fr, 0.75, False)
-    assert (m == _search_by_bow_python(kf, fr, 0.75)).all() and n == (m >= 0).sum()
+    for ori in (False, True):
+        m, n = oracle.search_by_bow_kf_f(kf, fr, 0.75, ori)
+        assert (m == _search_by_bow_python(kf, fr, 0.75, ori)).all() and n == (m >= 0).sum()
+    assert n == int(b["n_kf_f"])
+    import matcher_model
+    m, n, _ = matcher_model.search_by_bow_kf_kf(kf, fr, 0.75, True)
+    assert n == int(b["n_kf_kf"]) and (m == b["m_kf_kf"]).all()
+    p, _ = matcher_model.search_for_triangulation(_featset(b, "kf", b["tri_flag_kf"]), _featset(b, "fr", b["tri_flag_fr"]), b["F12"], 300.0, 200.0,
+                                                  b["sf"], b["sig2"], False, False)
+    assert (p == b["tri_pairs"]).all()
 
 
 # ---------------------------------------------------------------------------------- GPU vs fixtures
