@@ -5,13 +5,20 @@
 #include "orb_pattern.inc"
 
 #include <limits.h>
+#include <stddef.h>
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
 
-__constant__ uint32_t c_pat4[256];        // x0 | y0<<8 | x1<<16 | y1<<24, signed bytes (src/ORBextractor.cc:160-418, data)
-__constant__ uint4 c_omask[64];           // IC_Angle: per lane (row, half) the byte mask of its 16-pixel window inside the circular patch
-__constant__ uint4 c_rowB[2][3][64];      // row pass on the matrix cores: per tap profile and column tile the lane's B fragment (orbx_desc_rowpass_matrix)
+// k_desc's constant tables as ONE symbol: the wave forms one base address (one s_getpc_b64) and reaches every table as base + lane offset +
+// immediate; a symbol per table cost an s_getpc_b64 / s_add_u32 / s_addc_u32 triple per table and load
+struct DescTab {
+    uint32_t pat4[256];         // x0 | y0<<8 | x1<<16 | y1<<24, signed bytes (src/ORBextractor.cc:160-418, data)
+    uint4 omask[64];            // IC_Angle: per lane (row, half) the byte mask of its 16-pixel window inside the circular patch
+    uint4 rowB[2][3][64];       // row pass on the matrix cores: per tap profile and column tile the lane's B fragment (orbx_desc_rowpass_matrix)
+};
+__constant__ DescTab c_desc;
+static_assert(offsetof(DescTab, omask) + sizeof(uint4[64]) <= 4096 && sizeof(uint4[3][64]) <= 4096, "every table load is base + lane offset + a 12-bit immediate");
 
 #ifdef ORBX_DIAG
 __device__ unsigned long long g_desc_stamp[4096 * 8]; // diagnostic build only: summed phase cycles of k_desc, 4096 slots
@@ -37,14 +44,32 @@ __device__ uint2 g_span_1[SPAN_SLOTS];                // SPAN_END(1): slot 1 of 
 // found by comparing against kp_off[] in registers, and only then one dependent fetch (the level's record) remains before the
 // patch address is known.  Fetching them through the Geom pointer was a chain of dependent scalar loads at the start of every
 // wave, during which the wave already holds its LDS.
-struct DescLevel { int w, h, pitch, kp_off; long long pyr_off; float scale; int patch_size; };
+// The start of a wave is two scalar round trips:
+//   1. the head of DescArgs, everything up to kp_off[]: adjacent fields, fetched as wide loads that depend on nothing;
+//   2. everything that depends on (b, slot, l), requested in one batch: the level's record lv[l] (one 32-byte load), the image's
+//      row of level counts, the slot's packed keypoint, and the PyrRef fields.
+// The compiler sinks scalar loads to their first use, behind branches and behind other waits (it makes six to eight dependent rounds of
+// these two): DESC_PIN names the values of a round as inputs of one empty asm statement, which puts all their loads in front of one wait.
+// Measured (profiles/r18_desc_start.txt): the rounds themselves are worth 0.5 % of the kernel at most; what the start
+// gained over its predecessor (2.7 %) came with its shorter scalar instruction stream and its registers.
+struct DescLevel { int w, h, pitch, kp_off; long long pyr_off; float scale; int patch_size; };     // 32 bytes
 struct DescArgs {
-    int nlevels, kp_total;
+    int kp_total, nimg, cap, rt_on;   // per-image staging slots; images of the launch; output capacity per image; 1: slot "-1" is the row-table wave
+    unsigned xg;                      // image columns of the grid: min(8, images) -- blockIdx.x = xg * slot + image column
+    int rowb_off;                     // matrix-core row pass: byte offset of the tap profile's rowB table in c_desc
+    int acc0;                         // ... and 128 * sum(g), where its accumulators start
     unsigned gauss;                   // taps g0 | g1 << 8 | g2 << 16 | g3 << 24 of the handle's 7-tap kernel (symmetric; orbx_gaussian_taps)
-    int rowb, acc0;                   // matrix-core row pass: which c_rowB table (the tap profile), and 128 * sum(g), where its accumulators start
+    const int *lvl_cnt;               // [image][ORBX_MAX_LEVELS] keypoints kept per level, zero beyond nlevels
+    const uint32_t *lvl_kp;           // [image][kp_total] packed keypoints
     int kp_off[ORBX_MAX_LEVELS];      // first staging slot of level i; INT_MAX for i >= nlevels
     DescLevel lv[ORBX_MAX_LEVELS];
 };
+static_assert(offsetof(DescArgs, kp_off) == 48 && sizeof(DescLevel) == 32, "the head of DescArgs is three 16-byte loads in front of kp_off[]");
+#ifdef ORBX_DESC_NO_PIN     // A/B timing: the same start with its loads left where the compiler puts them
+#define DESC_PIN(...) do { } while (0)
+#else
+#define DESC_PIN(...) asm volatile("" :: __VA_ARGS__)
+#endif
 
 // NL = 8 or ORBX_MAX_LEVELS: the level search and the count sums below are unrolled over NL levels (ORB-SLAM2 uses 8)
 // The row table of Frame::ComputeStereoMatches (vRowIndices, src/Frame.cc:584-604) as a by-product of the extraction: it depends only
@@ -130,9 +155,8 @@ __device__ __forceinline__ void desc_rowtab(const DescArgs &da, const int *__res
 }
 
 template <int NL, bool MF>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(64))) void k_desc(const DescArgs da, PyrRef pr, const int *__restrict__ lvl_cnt,
-                                             const uint32_t *__restrict__ lvl_kp, orbx_keypoint *__restrict__ out_kps,
-                                             uint8_t *__restrict__ out_desc, int *__restrict__ out_n, int cap, int nimg, const RowTabArgs rt,
+__global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(64))) void k_desc(const DescArgs da, PyrRef pr, orbx_keypoint *__restrict__ out_kps,
+                                             uint8_t *__restrict__ out_desc, int *__restrict__ out_n, const RowTabArgs rt,
                                              const int *__restrict__ err_flag, int *__restrict__ flag_out)
 {
     // LDS pitches: raw bytes (11 dwords per row), row-pass u16 (column-major, 43 rows per column, 37 columns).  1908 + 3188 bytes
@@ -161,57 +185,113 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(64))) void k_des
     // A launch of fewer than eight images (a single stereo frame: two) has no empty XCD columns in its grid: blockIdx.x = xg * slot +
     // image, xg = min(8, images) -- dispatching the 6 800 empty workgroups of an 8-wide grid took longer than the 2 000 waves that
     // had work (their starts spread over 6.5 us).
-    const unsigned xg = gridDim.y == 1 && nimg < 8 ? (unsigned)nimg : 8u;
-    const unsigned sx = xg == 8 ? blockIdx.x >> 3 : blockIdx.x / xg;
-    const int slot = (int)sx - rt.on, b = (int)(blockIdx.y * 8u + (blockIdx.x - sx * xg));
-    if (b >= nimg) return;
-    if (slot < 0) {
-        desc_rowtab<NL>(da, lvl_cnt + (long long)b * ORBX_MAX_LEVELS, lvl_kp + (long long)b * da.kp_total, cap, rt, b,
-                        reinterpret_cast<int *>(desc_smem) + 4 * ORBX_MAX_LEVELS, reinterpret_cast<int *>(desc_smem) + 4 * ORBX_MAX_LEVELS + ((rt.rows + 4) & ~3),
-                        reinterpret_cast<int4 *>(desc_smem));
-        return;
-    }
-    int l = 0;
-#pragma unroll
-    for (int i = 1; i < NL; i++) l += slot >= da.kp_off[i];
-    const DescLevel L = da.lv[l];
-    const int *lc = lvl_cnt + (long long)b * ORBX_MAX_LEVELS;   // rows of ORBX_MAX_LEVELS counts, zero beyond nlevels
-    // the slot's packed keypoint is fetched together with the level counts (its address does not depend on them):
-    // one global round trip less on the critical path of every wave; slots past the level's count hold stale data
-    // that is never used
+    // ---- round 1: the head of the kernel arguments (three 16-byte loads and kp_off[], nothing depends on anything)
 #ifdef ORBX_DIAG
     unsigned long long _t_prev = __builtin_amdgcn_s_memtime();
 #endif
     SPAN_BEGIN();
-    const uint32_t p = lvl_kp[(long long)b * da.kp_total + slot];
-    // the lane's four pattern words (lane-indexed constant data = vector loads) are requested here, with the first
-    // memory round trip, not in the sampling phase where they would cost a round trip of their own
+    const unsigned xg = da.xg;
+    const int cap = da.cap;
+    if constexpr (NL == 8)
+        DESC_PIN("s"(da.kp_total), "s"(da.nimg), "s"(da.rt_on), "s"(xg), "s"(da.rowb_off), "s"(da.lvl_cnt), "s"(da.lvl_kp), "s"(da.kp_off[1]), "s"(da.kp_off[2]), "s"(da.kp_off[3]),
+                 "s"(da.kp_off[4]), "s"(da.kp_off[5]), "s"(da.kp_off[6]), "s"(da.kp_off[7]));
+    else
+        DESC_PIN("s"(da.kp_total), "s"(da.nimg), "s"(da.rt_on), "s"(xg), "s"(da.rowb_off), "s"(da.lvl_cnt), "s"(da.lvl_kp), "s"(da.kp_off[1]), "s"(da.kp_off[2]), "s"(da.kp_off[3]),
+                 "s"(da.kp_off[4]), "s"(da.kp_off[5]), "s"(da.kp_off[6]), "s"(da.kp_off[7]), "s"(da.kp_off[8]), "s"(da.kp_off[9]), "s"(da.kp_off[10]),
+                 "s"(da.kp_off[11]), "s"(da.kp_off[12]), "s"(da.kp_off[13]), "s"(da.kp_off[14]), "s"(da.kp_off[15]));
+    unsigned sx = blockIdx.x >> 3;
+    if (xg != 8) sx = blockIdx.x / xg;      // (fewer than eight images: the division stays behind its condition)
+    const int slot = (int)sx - da.rt_on, b = (int)(blockIdx.y * 8u + (blockIdx.x - sx * xg));
+    if (b >= da.nimg) return;
+    // 32-bit byte offsets of the image's rows (scalar loads take base + a zero-extended 32-bit register): image * max(kp_total,
+    // ORBX_MAX_LEVELS) <= 2^30 for every image of a handle's largest batch, orbx_prepare_geometry refuses anything larger
+    const unsigned cnt_byte = (unsigned)b * (unsigned)(ORBX_MAX_LEVELS * sizeof(int)), kp_byte = ((unsigned)b * (unsigned)da.kp_total) * 4u;
+    if (slot < 0) {
+        desc_rowtab<NL>(da, reinterpret_cast<const int *>(reinterpret_cast<const uint8_t *>(da.lvl_cnt) + cnt_byte),
+                        reinterpret_cast<const uint32_t *>(reinterpret_cast<const uint8_t *>(da.lvl_kp) + kp_byte), cap, rt, b,
+                        reinterpret_cast<int *>(desc_smem) + 4 * ORBX_MAX_LEVELS, reinterpret_cast<int *>(desc_smem) + 4 * ORBX_MAX_LEVELS + ((rt.rows + 4) & ~3),
+                        reinterpret_cast<int4 *>(desc_smem));
+        return;
+    }
+    // level of the slot: kp_off[] ascends (INT_MAX beyond nlevels), one scalar compare and select per level
+    int l = 0;
+    asm("" : "+s"(l));      // (opaque: a select between the constants 0 and 1 is formed on the vector unit and read back)
+#pragma unroll
+    for (int i = 1; i < NL; i++) l = slot >= da.kp_off[i] ? i : l;
+    // ---- round 2, one batch: the level's record, the image's row of level counts (zero beyond nlevels), the slot's packed keypoint (slots
+    // past the level's count hold stale data that is never used) and the pyramid's addresses
+    // (k_desc only reads the counts and the staging slots: loads through constant-address-space pointers, which the compiler may issue on
+    // the scalar unit; through the plain pointers of DescArgs it made them vector loads and read the values back lane by lane)
+    const DescLevel L = da.lv[l];
+    typedef const __attribute__((address_space(4))) uint8_t *cptr_t;
+    typedef const __attribute__((address_space(4))) uint32_t *cptr32_t;
+    const cptr_t lc = reinterpret_cast<cptr_t>(reinterpret_cast<unsigned long long>(da.lvl_cnt)) + cnt_byte;
+    int cn[NL];
+#pragma unroll
+    for (int i = 0; i < NL; i++) cn[i] = (int)*reinterpret_cast<cptr32_t>(lc + 4 * i);
+    const uint32_t p = *reinterpret_cast<cptr32_t>(reinterpret_cast<cptr_t>(reinterpret_cast<unsigned long long>(da.lvl_kp)) + (kp_byte + 4u * (unsigned)slot));
+    const PyrRef P = pr;
+    // the lane's constant data (lane-indexed = vector loads) is requested here, with the wave's second round trip, not in the phases that
+    // use it, where each table would cost a round trip of its own: four pattern words, the orientation mask, the B fragments of the
+    // three column tiles (matrix-core form).  One base for all of them (opaque to the compiler, which otherwise forms every table's address
+    // from the program counter again).
+    unsigned long long tb_ = reinterpret_cast<unsigned long long>(&c_desc);
+    asm volatile("" : "+s"(tb_));
+    typedef const __attribute__((address_space(1))) uint8_t *gptr_t;
+    const gptr_t tb = reinterpret_cast<gptr_t>(tb_);
     uint32_t pat4[4];
 #pragma unroll
-    for (int jj = 0; jj < 4; jj++) pat4[jj] = c_pat4[lane + 64 * jj];
-    const uint4 omask = c_omask[lane];
+    for (int jj = 0; jj < 4; jj++) pat4[jj] = *reinterpret_cast<const __attribute__((address_space(1))) uint32_t *>(tb + offsetof(DescTab, pat4) + 256 * jj + 4 * lane);
+    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    typedef const __attribute__((address_space(1))) u32x4 *gptr4_t;
+    auto load16 = [](gptr_t a) { const u32x4 t = *reinterpret_cast<gptr4_t>(a); return make_uint4(t.x, t.y, t.z, t.w); };
+    const uint4 omask = load16(tb + offsetof(DescTab, omask) + 16 * lane);
     uint4 rowB[3] = {};     // (matrix-core form) the lane's B fragments of the three column tiles
     if constexpr (MF) {
+        const gptr_t tbB = tb + (unsigned)da.rowb_off;
 #pragma unroll
-        for (int nt = 0; nt < 3; nt++) rowB[nt] = c_rowB[da.rowb][nt][lane];
+        for (int nt = 0; nt < 3; nt++) rowB[nt] = load16(tbB + 1024 * nt + 16 * lane);
     }
-    int off = 0, total = 0;
+    if constexpr (NL == 8)
+        DESC_PIN("s"(L.w), "s"(L.h), "s"(L.pitch), "s"(L.kp_off), "s"(L.pyr_off), "s"(L.scale), "s"(L.patch_size), "s"(p),
+                 "s"(P.img0), "s"(P.img0_stride), "s"(P.img0_pitch), "s"(P.pyr), "s"(P.pyr_stride),
+                 "s"(cn[0]), "s"(cn[1]), "s"(cn[2]), "s"(cn[3]), "s"(cn[4]), "s"(cn[5]), "s"(cn[6]), "s"(cn[7]));
+    else
+        DESC_PIN("s"(L.w), "s"(L.h), "s"(L.pitch), "s"(L.kp_off), "s"(L.pyr_off), "s"(L.scale), "s"(L.patch_size), "s"(p),
+                 "s"(P.img0), "s"(P.img0_stride), "s"(P.img0_pitch), "s"(P.pyr), "s"(P.pyr_stride),
+                 "s"(cn[0]), "s"(cn[1]), "s"(cn[2]), "s"(cn[3]), "s"(cn[4]), "s"(cn[5]), "s"(cn[6]), "s"(cn[7]),
+                 "s"(cn[8]), "s"(cn[9]), "s"(cn[10]), "s"(cn[11]), "s"(cn[12]), "s"(cn[13]), "s"(cn[14]), "s"(cn[15]));
+    // prefix sums of the counts; the level's own count and the counts below it are S[l + 1] - S[l] and S[l], both selected from registers
+    // by the bits of l (a select tree: NL - 1 selects each, against a compare, a select and an add per level and a second fetch of lc[l])
+    int S[NL + 1];
+    S[0] = 0;
 #pragma unroll
-    for (int i = 0; i < NL; i++) { const int c = lc[i]; off += i < l ? c : 0; total += c; }
+    for (int i = 0; i < NL; i++) S[i + 1] = S[i] + cn[i];
     if (slot == 0 && lane == 0) {
-        out_n[b] = total < cap ? total : cap;
+        out_n[b] = S[NL] < cap ? S[NL] : cap;
         if (flag_out && b == 0) *flag_out = *err_flag;     // (pipelined frames: the quadtree's error flag rides in the frame's result block)
     }
+    int lo_[NL], hi_[NL];
+#pragma unroll
+    for (int i = 0; i < NL; i++) { lo_[i] = S[i]; hi_[i] = S[i + 1]; }
+#pragma unroll
+    for (int w = NL / 2, bit = 0; w >= 1; w >>= 1, bit++) {
+        const bool odd = (l >> bit) & 1;
+#pragma unroll
+        for (int k = 0; k < w; k++) { lo_[k] = odd ? lo_[2 * k + 1] : lo_[2 * k]; hi_[k] = odd ? hi_[2 * k + 1] : hi_[2 * k]; }
+    }
+    const int off = lo_[0];
     const int j = slot - L.kp_off;
-    if (j >= lc[l]) return;
+    if (j >= hi_[0] - off) return;
     const int idx = off + j;
     if (idx >= cap) return;
     const int x = p & 0xFFF, y = (p >> 12) & 0xFFF, resp = p >> 24;
-    const int pitch = l == 0 ? pr.img0_pitch : L.pitch;
-    const uint8_t *img = l == 0 ? pr.img0 + (long long)b * pr.img0_stride : pr.pyr + (long long)b * pr.pyr_stride + L.pyr_off;
+    const int pitch = l == 0 ? P.img0_pitch : L.pitch;
+    // (the pyramid block of one image is below 4 GB, orbx_prepare_geometry: image * stride is one 32 x 32 -> 64 bit product)
+    const uint8_t *img = l == 0 ? P.img0 + (long long)b * P.img0_stride : P.pyr + (unsigned long long)(unsigned)b * (unsigned)P.pyr_stride + L.pyr_off;
 #ifdef ORBX_DIAG
     asm volatile("" :: "v"(x), "s"(pitch));
-    DSTAMP(5); // prologue: level search, level counts, packed keypoint
+    DSTAMP(5); // prologue: both scalar rounds, level search, count prefix, patch address
 #endif
     // ---- stage the 43x43 patch at LDS column 0 of every row (unaligned dword loads: the window phase is a constant,
     // so the realignment shifts below are immediates and the row pass reads three dwords per item instead of four)
@@ -236,9 +316,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(64))) void k_des
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     } else { // image edge (BORDER_REFLECT_101 of the cloned level, :1312-1314)
-        // lane = patch column (its reflected source column computed once), rows walked on the scalar unit, eight byte loads in
-        // flight: ~2 vector instructions per row (an element-wise walk with a division and two reflections per byte cost more
-        // than the whole rest of the keypoint, for the ~6 % of the keypoints that lie within 21 px of an image edge)
+        // lane = patch column (its reflected source column computed once), rows walked on the scalar unit, sixteen byte loads in
+        // flight (three round trips for the 43 rows): ~2 vector instructions per row (an element-wise walk with a division and two
+        // reflections per byte cost more than the whole rest of the keypoint, for the ~6 % of the keypoints that lie within 21 px of an
+        // image edge).  Every load is scalar row base + the column as an unsigned 32-bit lane offset: written as img[ry * pitch + cx] the
+        // compiler adds the column to the image base first and forms every row's address with a 64-bit vector multiply-add.
+#ifdef ORBX_DESC_EDGE_VADDR     // A/B timing: that form, eight loads in flight
         const int cx = reflect101(x - 21 + min(lane, 42), L.w);
         if (lane < 43) {
 #pragma unroll 8
@@ -247,6 +330,26 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(64))) void k_des
                 raw[r * RP + lane] = img[(long long)ry * pitch + cx];
             }
         }
+#else
+        const unsigned cx = (unsigned)reflect101(x - 21 + min(lane, 42), L.w);
+        if (lane < 43) {
+            constexpr int G = 16;
+#pragma unroll 1
+            for (int r0 = 0; r0 < 43; r0 += G) {
+                uint8_t v[G];
+#pragma unroll
+                for (int k = 0; k < G; k++) {
+                    const int ry = reflect101(y - 21 + min(r0 + k, 42), L.h);      // (rows past the patch: row 42 again, not stored)
+                    unsigned long long rowp = reinterpret_cast<unsigned long long>(img + (long long)ry * pitch);
+                    asm("" : "+s"(rowp));   // (opaque: keeps the row base on the scalar unit)
+                    v[k] = reinterpret_cast<const __attribute__((address_space(1))) uint8_t *>(rowp)[cx];
+                }
+#pragma unroll
+                for (int k = 0; k < G; k++)
+                    if (r0 + k < 43) raw[(r0 + k) * RP + lane] = v[k];
+            }
+        }
+#endif
     }
     DSTAMP(6); // patch loads issued and consumed (the last LDS stores may still be in flight)
     __syncthreads();
@@ -416,12 +519,13 @@ int orbx_desc_upload_constants(orbx_extractor *e)
     for (int i = 0; i < 256; i++)
         pat[i] = (uint32_t)(uint8_t)ORB_PAT_X0[i] | ((uint32_t)(uint8_t)ORB_PAT_Y0[i] << 8) | ((uint32_t)(uint8_t)ORB_PAT_X1[i] << 16) |
                  ((uint32_t)(uint8_t)ORB_PAT_Y1[i] << 24);
-    ORBX_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_pat4), pat, sizeof pat));
-    {   // the banded tap matrices of the matrix-core row pass, one per tap profile (a launch names its profile's table: DescArgs::rowb)
+    ORBX_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_desc), pat, sizeof pat, offsetof(DescTab, pat4)));
+    {   // the banded tap matrices of the matrix-core row pass, one per tap profile (a launch names its profile's table: DescArgs::rowb_off)
         uint8_t rb[2][3 * 64 * 16];
         int acc0;
         for (int prof = 0; prof < 2; prof++) { const int rc = orbx_desc_rowpass_matrix(prof, rb[prof], &acc0); if (rc) return rc; }
-        ORBX_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_rowB), rb, sizeof rb));
+        static_assert(sizeof rb == sizeof(DescTab::rowB), "one table of three column tiles per tap profile");
+        ORBX_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_desc), rb, sizeof rb, offsetof(DescTab, rowB)));
     }
     {   // k_desc's orientation lanes: lane = (row v = lane/2 - 15, half = lane & 1); the left half covers u = -16..-1 and
         // keeps u >= -umax[|v|], the right half covers u = 0..15 and keeps u <= umax[|v|] (src/ORBextractor.cc:91-108)
@@ -434,7 +538,7 @@ int orbx_desc_upload_constants(orbx_extractor *e)
                 m[lane][k] = (u >= -d && u <= d) ? 0xFF : 0;
             }
         }
-        ORBX_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_omask), m, sizeof m));
+        ORBX_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_desc), m, sizeof m, offsetof(DescTab, omask)));
     }
     return ORBX_OK;
 }
@@ -511,9 +615,10 @@ void orbx_desc_launch(orbx_extractor *e, const PyrRef &pr, int batch, void *d_kp
     const Geom &G = e->geom;
     DescArgs da;
     memset(&da, 0, sizeof da);
-    da.nlevels = G.nlevels; da.kp_total = G.kp_total;
+    da.kp_total = G.kp_total; da.nimg = batch; da.cap = cap; da.xg = batch < 8 ? batch : 8;
+    da.lvl_cnt = e->d_lvl_cnt; da.lvl_kp = e->d_lvl_kp;
     da.gauss = (unsigned)e->gauss[0] | (unsigned)e->gauss[1] << 8 | (unsigned)e->gauss[2] << 16 | (unsigned)e->gauss[3] << 24;
-    da.rowb = e->cv_profile == ORBX_CV_PROFILE_3_4_2; da.acc0 = 128 * (2 * (e->gauss[0] + e->gauss[1] + e->gauss[2]) + e->gauss[3]);
+    da.rowb_off = (int)(offsetof(DescTab, rowB) + (e->cv_profile == ORBX_CV_PROFILE_3_4_2) * sizeof(uint4[3][64])); da.acc0 = 128 * (2 * (e->gauss[0] + e->gauss[1] + e->gauss[2]) + e->gauss[3]);
     for (int i = 0; i < ORBX_MAX_LEVELS; i++) {
         da.kp_off[i] = i < G.nlevels ? G.lv[i].kp_off : INT_MAX;
         if (i < G.nlevels) {
@@ -529,10 +634,11 @@ void orbx_desc_launch(orbx_extractor *e, const PyrRef &pr, int batch, void *d_kp
         rt.row_off = e->d_rt_off; rt.entries = (uint4 *)e->d_rt_entries; rt.ent_cap = e->rt_ent_cap; rt.rows = G.lv[0].h; rt.on = 1;
         e->rt_kps = d_kps; e->rt_cap = cap; e->rt_batch = batch;
     }
+    da.rt_on = rt.on;
     e->last_forms[6] = G.nlevels <= 8 ? 8 : ORBX_MAX_LEVELS;    // orbx_debug_launch_forms
     e->last_forms[9] = e->desc_valu_rowpass ? 1 : 2;
     const auto kern = e->desc_valu_rowpass ? (G.nlevels <= 8 ? k_desc<8, false> : k_desc<ORBX_MAX_LEVELS, false>)
                                            : (G.nlevels <= 8 ? k_desc<8, true> : k_desc<ORBX_MAX_LEVELS, true>);
-    hipLaunchKernelGGL(kern, dim3((batch < 8 ? batch : 8) * (G.kp_total + rt.on), (batch + 7) / 8), dim3(64), 0, s, da, pr, e->d_lvl_cnt, e->d_lvl_kp,
-                       (orbx_keypoint *)d_kps, (uint8_t *)d_desc, (int *)d_n_out, cap, batch, rt, (const int *)orbx_err_flag(e), e->flag_out);
+    hipLaunchKernelGGL(kern, dim3(da.xg * (G.kp_total + rt.on), (batch + 7) / 8), dim3(64), 0, s, da, pr,
+                       (orbx_keypoint *)d_kps, (uint8_t *)d_desc, (int *)d_n_out, rt, (const int *)orbx_err_flag(e), e->flag_out);
 }

@@ -91,6 +91,11 @@ int orbx_prepare_geometry(orbx_extractor *e, int w, int h)
         if (qrc) return qrc;
     }
     const size_t B = e->max_batch;
+    // k_desc addresses an image's count row and staging slots with 32-bit byte offsets and multiplies image * pyramid bytes as 32 x 32 bits
+    if ((long long)(G.kp_total > ORBX_MAX_LEVELS ? G.kp_total : ORBX_MAX_LEVELS) * (long long)B > (1ll << 30) || G.pyr_bytes >= (1ll << 32)) {
+        orbx_set_error("%dx%d with %d staging slots per image and batches of %d: beyond the descriptor stage's 32-bit offsets", w, h, G.kp_total, e->max_batch);
+        return ORBX_E_INVALID;
+    }
     if ((rc = ensure(&e->d_tabs, &e->tabs_cap, tabs.size() * 2))) return rc;
     if ((rc = ensure(&e->d_cells, &e->cells_cap, cells.size() * sizeof(CellRec)))) return rc;
     if (!pairs.empty() && (rc = ensure(&e->d_pairs, &e->pairs_cap, pairs.size()))) return rc;
