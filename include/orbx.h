@@ -1126,6 +1126,158 @@ int orbx_pnp_hypotheses(int device, orbx_pnp_job *job);
  * words in all (both masks counted). */
 int orbx_pnp_hypotheses_batch(int device, orbx_pnp_job *jobs, int njobs);
 
+/* ---- Initializer: Tracking::MonocularInitialization's H / F RANSAC and reconstruction (src/Initializer.cc:37-1026) --------
+ * Initializer::Initialize runs FindHomography and FindFundamental over the same 200 sample rows (mvSets), picks a model by the
+ * ratio of the two best scores and reconstructs the motion from it (ReconstructH / ReconstructF over CheckRT).  The device
+ * evaluates the WHOLE TABLE of both models in one launch (k_mono_hyp: one wave per (model, hypothesis), the ballot of the inlier
+ * test is the mask word), every motion hypothesis in a second (k_mono_reconstruct: one workgroup each, the arg-max of the table
+ * and the decomposition repeated in every wave) and the final choice in a third (k_mono_decide: one workgroup).  "mono_init":
+ * "init" alone names SearchForInitialization and the library's set-up.
+ * The arithmetic follows the C++ types of the reference text; every operation is rounded on its own (no fused multiply-add); float
+ * sums and products associate left to right as C parses them.  "dotd(a, b)" is ((double)a0*b0 + (double)a1*b1) + (double)a2*b2, and
+ * every cv::Mat product X*Y is mm(X, Y)[r][c] = (float)dotd(X.row(r), Y.col(c)), one cast from a double accumulation; a product of
+ * three is (X*Y)*Z with the middle result stored as float.  "1.0 / x" with a float x is (float)(1.0 / (double)x) wherever the text
+ * writes it: w2in1inv, w1in2inv, invSigmaSquare, invZ1, invZ2, sX, sY.
+ *   Normalize (:831-883) on the HOST half of the call, over ALL keypoints of a frame in index order: meanX, meanY = the serial
+ *            float sums from 0.0f divided by (float)N; meanDevX, meanDevY = the serial float sums of |x - meanX|, |y - meanY|
+ *            divided by (float)N; sX = 1.0 / meanDevX, sY likewise; T = (sX 0 (-meanX)*sX; 0 sY (-meanY)*sY; 0 0 1).  A normalised
+ *            point is ((x - meanX) * sX, (y - meanY) * sY), which the device evaluates for the eight matches of a sample row.
+ *   det, inv det(M) = (m00*(m11*m22 - m12*m21) - m01*(m10*m22 - m12*m20)) + m02*(m10*m21 - m11*m20) with every factor widened to
+ *            double (cv::determinant).  inv(M): d = det(M); d == 0: NINE ZEROS (cv::Mat::inv of a singular matrix); else d = 1.0 / d
+ *            and inv[r][c] = (float)(cof * d), cof = the difference of two double products of the adjugate, in the order
+ *            m11*m22 - m12*m21, m02*m21 - m01*m22, m01*m12 - m02*m11 / m12*m20 - m10*m22, m00*m22 - m02*m20, m02*m10 - m00*m12 /
+ *            m10*m21 - m11*m20, m01*m20 - m00*m21, m00*m11 - m01*m10.  T2inv = inv(T2) (:164), H12i = inv(H21i) (:194), invK (:654).
+ *   SVD      every cv::SVDecomp / cv::SVD::compute of the file (:305, :349, :353, :667, :1009) is ONE routine, a one-sided (Hestenes)
+ *            Jacobi on the n columns of an m x n FLOAT matrix A, n odd (9 or 3), V = I (n x n, float).  A sweep is the n rounds r =
+ *            0 .. n-1 of the round-robin schedule of the PnP block for N = n + 1: round r holds the pivots {(r + k) mod n, (r - k)
+ *            mod n}, k = 1 .. (n-1)/2, each taken as (p, q) with p < q (the pair of the schedule that holds the padding column N-1
+ *            does not exist); the pivots of a round touch disjoint columns, so their order is immaterial.  For a pivot, in DOUBLE:
+ *            a = SUM (double)A[i][p]*A[i][p], b = SUM (double)A[i][q]*A[i][q], g = SUM (double)A[i][p]*A[i][q], where SUM is a
+ *            STATED BUTTERFLY over 16 slots (m <= 16): slot i holds 0.0 + the product of row i (0.0 for i >= m), then v[i] = v[i] +
+ *            v[i ^ stride] for the strides 8, 4, 2, 1; every slot ends with the same bits.  (Measured against the serial sum in
+ *            rising i: profiles/r19_init.txt.)  The pivot is skipped when |g| <= (double)(2 * FLT_EPSILON) * sqrt(a * b) (false for NaN) --
+ *            the stopping test: a sweep that skipped every pivot ends the iteration, which runs 30 sweeps at most.  Otherwise g2 =
+ *            g * 2, beta = a - b, gamma = sqrt(g2*g2 + beta*beta), and in double, cast to float: beta < 0: s = sqrt(((gamma - beta) *
+ *            0.5) / gamma), c = g2 / ((gamma * s) * 2); else c = sqrt((gamma + beta) / (gamma * 2)), s = g2 / ((gamma * c) * 2) (s
+ *            resp. c re-widened from its float).  Every row (x, y) = (.[p], .[q]) of A and of V becomes (c*x + s*y, (-s)*x + c*y) in
+ *            float.  Afterwards W2[j] = the SERIAL sum over rising i, from 0.0, of (double)A[i][j]^2.  (The shape of OpenCV's float JacobiSVDImpl_, which
+ *            sweeps lexicographically, carries the norms along and calls hypot.)
+ *   null     vt.row(8) (:307, :351): column j of V for the SMALLEST W2[j], of equal ones the LATER (j = 0, then every j whose W2[j]
+ *            <= the kept one).  The sign cancels in everything that follows.
+ *   U w Vt   of a 3 x 3 matrix: order = descending W2, of equal values the earlier index first (selection: the r-th is the first
+ *            unused j whose W2 no later unused one exceeds); wd = sqrt(W2[j]) in double, w[r] = (float)wd, column r of U = the
+ *            rotated column j of A times (float)(1.0 / wd) -- times 0.0f when wd <= FLT_MIN: no completion of a zero singular
+ *            value -- and row r of Vt = column j of V.
+ *   H        A of ComputeH21 (:274-301) literally, in float ((-u2)*u1 for -u2*u1), m = 16; Hn = null reshaped 3 x 3; H21i =
+ *            mm(mm(T2inv, Hn), T1) (:193); H12i = inv(H21i).
+ *   F        A of ComputeF21 (:329-345), m = 8; Fpre = null reshaped; U w Vt of Fpre; Fn = mm(mm(U, diag(w0, w1, 0)), Vt) (:355-
+ *            357); F21i = mm(mm(T2^T, Fn), T1) (:253).
+ *   check    CheckHomography (:360-448) / CheckFundamental (:450-528) literally in float, th = 5.991f resp. th = 3.841f with thScore
+ *            = 5.991f, invSigmaSquare = 1.0 / (sigma*sigma).  The gate is `if (chi > th) bIn = false; else score += th - chi`: a
+ *            NaN chi takes the else -- the score becomes NaN and the match STAYS an inlier.  A singular H21i gives H12i = 0, hence
+ *            w2in1inv = inf, u2in1 = NaN, chiSquare1 = NaN and a NaN score with every first gate open.
+ *   score    a STATED DEVIATION from the reference's single serial float sum: lane l of 64 adds, from 0.0f and in rising i, the
+ *            two terms of every match i = l (mod 64) in the text's order, then a xor butterfly over the strides 32, 16, 8, 4, 2, 1
+ *            (v[l] = v[l] + v[l ^ stride]); every lane ends with the same bits.
+ *   choice   (:203, :257) best_h = the EARLIEST hypothesis whose score_h is strictly the greatest and > 0.0f (currentScore > score
+ *            from 0.0f: a NaN never wins), -1 if none, SH its score or 0.0f; best_f, SF likewise.  RH = SH / (SH + SF) in float;
+ *            (double)RH > 0.40 takes H, else F (:133-142).  A STATED DEVIATION: when the model taken has no winner -- SH == SF ==
+ *            0, RH is NaN -- the reference's F21 is an empty matrix and its mask has no element (FindFundamental sizes them from
+ *            the empty argument, :219) and ReconstructF reads out of range; here model = 0, ok = 0, nothing is reconstructed.
+ *   ReconstructH (:642-812) A = mm(mm(invK, H21), K); U w Vt of A; s = (float)(det(U) * det(Vt)); (d1, d2, d3) = w; `(double)(d1 /
+ *            d2) < 1.00001 || (double)(d2 / d3) < 1.00001` (float quotients): ok = 0 with every row zero.  aux1, aux3, aux_stheta,
+ *            ctheta, aux_sphi, cphi (:688-733) in float, sqrt correctly rounded; x1, x3, stheta, sphi by the four sign rows of the
+ *            text.  Hypothesis i < 4: Rp = (ctheta 0 -stheta[i]; 0 1 0; stheta[i] 0 ctheta), tp = (x1[i], 0, -x3[i]) each times (d1 -
+ *            d3) in float; 4 + i: Rp = (cphi 0 sphi[i]; 0 -1 0; sphi[i] 0 -cphi), tp = (x1[i], 0, x3[i]) each times (d1 + d3).  R =
+ *            mm(mm(sU, Rp), Vt) with sU = s * U in float; t = U*tp as a Mat product, then t[k] = (float)((double)t[k] * (1.0 /
+ *            sqrt(dotd(t, t)))) (t / cv::norm(t)).  The normals vn are never read.
+ *   ReconstructF (:533-640) E21 = mm(mm(K^T, F21), K); DecomposeE (:1006-1026): U w Vt of E21; t = U.col(2) normalised as above;
+ *            R1 = mm(mm(U, W), Vt), W = (0 -1 0; 1 0 0; 0 0 1), negated when det(R1) < 0; R2 likewise with W^T.  Rows: (R1, t),
+ *            (R2, t), (R1, -t), (R2, -t).  Which of R1 / R2 is which and the sign of t follow from the restated SVD; the SET of
+ *            four is the same.
+ *   CheckRT  (:886-1004) th2 = (float)(4.0 * (double)(sigma*sigma)).  P1 = K[I|0], P2 = mm(K, [R|t]) (3 x 4), O2[r] =
+ *            (float)(-dotd(R.col(r), t)).  Per match of the mask: A (:818-821) rows u1*P1.row(2) - P1.row(0), v1*P1.row(2) -
+ *            P1.row(1), u2*P2.row(2) - P2.row(0), v2*P2.row(2) - P2.row(1) in float; v = the 4x4 routine of the triangulation
+ *            block ("SVD" there, unchanged); p = v[0..2] / v[3], float divisions as there.  A non-finite p is skipped.  dist1 =
+ *            (float)sqrt(dotd(p, p)); n2 = p - O2 in float, dist2 likewise; cosParallax = (float)(dotd(p, n2) / (double)(dist1 *
+ *            dist2)).  `p.z <= 0 && (double)cosParallax < 0.99998` skips; p2[r] = (float)(dotd(R.row(r), p) + (double)t[r]); p2.z
+ *            likewise.  invZ1 = 1.0 / p.z; im1x = fx*p.x*invZ1 + cx, left to right; squareError1 > th2 skips (a NaN error does NOT
+ *            skip); view 2 likewise.  Every match that arrives here is ACCEPTED: it counts in n_good and its point is kept;
+ *            triangulated is true only where (double)cosParallax < 0.99998.
+ *   rank     cos_parallax of a row = the accepted cosine of rank min(50, n_good - 1) in ascending order, a NaN above every number
+ *            and returned as 0x7fc00000; 1.0f when n_good == 0 (the text's parallax = 0).
+ *   acos     parallax = acos(c)*180/CV_PI goes through the C library, which no device matches bit for bit.  The host bisects once
+ *            per call the float thresholds c_gt and c_ge with (float)(acos((double)c) * 180 / CV_PI) > min_parallax exactly when c
+ *            < c_gt, and >= min_parallax exactly when c < c_ge, over the floats of [-1, 1] (the float above 1 when every one
+ *            passes).  The device tests `c >= -1.0f && c < c_gt` (ReconstructF's `>`, :595) resp. c_ge (ReconstructH's `>=`,
+ *            :801); a NaN fails as in the text.  Degrees are formed from the returned cosine by the host's acos.
+ *   decide H (:769-811) literally over the eight rows in order: nGood > bestGood moves bestGood to secondBestGood and takes the
+ *            row; else nGood > secondBestGood takes its place.  ok = (double)secondBestGood < 0.75 * bestGood && parallax(best) >=
+ *            min_parallax && bestGood > min_triangulated && (double)bestGood > 0.9 * N, N = the bits of the mask.  winner =
+ *            bestSolutionIdx (-1 when no row has a point).
+ *   decide F (:569-639) maxGood = the largest of the four; nMinGood = max((int)(0.9 * N), min_triangulated); nsimilar = rows with
+ *            (double)nGood > 0.7 * maxGood; maxGood < nMinGood || nsimilar > 1: ok = 0, winner = -1.  Else winner = the FIRST row
+ *            whose nGood == maxGood (the else-if chain tries no other) and ok = parallax(winner) > min_parallax.
+ *   points   P3D[first] / triangulated[first] of the winner's accepted matches when ok; zero / false everywhere else.
+ *   NaN      every NaN among the returned floats (scores, H21, F21, R, t, cos_parallax, parallax) is the quiet NaN 0x7fc00000: the
+ *            sign and payload of an invalid operation's result differ between processors.
+ * Against OpenCV's own arithmetic (SVDecomp sweeps, rotates and sorts differently and completes zero singular values; its gemm,
+ * inv and determinant kernels differ by build) this restatement is unpinned: DESIGN.md. */
+typedef struct {
+    int n1, n2;                     /* keypoints of the reference / current frame: n .. 65535 each */
+    const float *xy1, *xy2;         /* [n1][2], [n2][2] mvKeys1 / mvKeys2 (undistorted): pt.x, pt.y */
+    int n;                          /* matches, mvMatches12.size(): 8 .. 8192 */
+    const int32_t *matches;         /* [n][2] mvMatches12: (first, second), first STRICTLY rising */
+    float sigma;                    /* mSigma */
+    float K[4];                     /* fx fy cx cy of mK; read by orbx_mono_init_reconstruct / _initialize */
+    float min_parallax;             /* minParallax (Initialize passes 1.0); read as K is */
+    int min_triangulated;           /* minTriangulated (Initialize passes 50); read as K is */
+    int n_hyp;                      /* mMaxIterations: 1 .. 1024; not read by orbx_mono_init_reconstruct */
+    const int32_t *samples;         /* [n_hyp][8] mvSets: indices into 0 .. n-1, the eight of a row distinct; as n_hyp */
+    /* out of orbx_mono_init_hypotheses alone */
+    float *score_h, *score_f;       /* [n_hyp] currentScore of CheckHomography / CheckFundamental */
+    float *H21, *F21;               /* [n_hyp][9] H21i / F21i row major */
+    uint64_t *bits_h, *bits_f;      /* [n_hyp][(n+63)/64] bit i%64 of word i/64 = vbCurrentInliers[i]; bits >= n are 0 */
+} orbx_mono_init_job;
+/* The whole table of FindHomography and FindFundamental.  One upload, one launch, one download.  ORBX_E_INVALID before any device
+ * work: a NULL job or array, n outside [8, 8192], n1 or n2 outside [n, 65535], n_hyp outside [1, 1024], a match index outside its
+ * frame, firsts not strictly rising, a sample index outside [0, n), a row of samples with two equal indices. */
+int orbx_mono_init_hypotheses(int device, orbx_mono_init_job *job);
+typedef struct {
+    int ok;                         /* the return value of ReconstructH / ReconstructF */
+    int winner;                     /* the row the decision settled on ("decide"), -1 none */
+    int32_t n_good[8];              /* nGood of CheckRT per motion hypothesis: 8 rows for H, 4 for F (the others 0) */
+    float cos_parallax[8];          /* "rank" above */
+    float R[8][9], t[8][3];         /* the motion hypotheses, R row major; zero for rows that do not exist */
+    float *P3D;                     /* [n1][3] vP3D */
+    uint8_t *triangulated;          /* [n1] vbTriangulated */
+} orbx_mono_init_recon;
+/* ReconstructH (model = 1, M = H21) or ReconstructF (model = 2, M = F21) on a model and an inlier mask[(n+63)/64] of the caller's
+ * choosing; job gives the keypoints, the matches, sigma, K, min_parallax and min_triangulated.  One upload, two launches on one
+ * stream, one download.  ORBX_E_INVALID before any device work: a NULL argument or array, model outside {1, 2}, a mask bit >= n, the
+ * refusals of orbx_mono_init_hypotheses that do not concern samples. */
+int orbx_mono_init_reconstruct(int device, const orbx_mono_init_job *job, int model, const float *M, const uint64_t *mask,
+                               orbx_mono_init_recon *out);
+typedef struct {
+    int ok;                         /* Initialize's return value */
+    int model;                      /* 0 none ("choice"), 1 H, 2 F */
+    int best_h, best_f;             /* -1: no hypothesis scored above 0 */
+    float SH, SF;
+    float M[9];                     /* H21 of best_h or F21 of best_f by model; zero for model 0 */
+    float R21[9], t21[3];           /* the winner's motion when ok, else zero */
+    float parallax;                 /* degrees, (float)(acos((double)cos_parallax[winner]) * 180 / CV_PI) on the host; 0 without a winner */
+    int winner;
+    int32_t n_good[8];
+    float cos_parallax[8];
+    float *P3D;                     /* [n1][3] */
+    uint8_t *triangulated;          /* [n1] */
+} orbx_mono_init_result;
+/* Initialize (:52-145) behind the drawing of mvSets: the table, the choice, the decomposition, CheckRT of every motion hypothesis
+ * and the decision as three launches chained on one stream with no host step between them; one upload, and only the result comes
+ * down.  Everything it returns is byte-equal to orbx_mono_init_reconstruct on the winner of orbx_mono_init_hypotheses.  The table
+ * outputs of job are not written.  ORBX_E_INVALID as orbx_mono_init_hypotheses, and for a NULL res or array of it. */
+int orbx_mono_init_initialize(int device, orbx_mono_init_job *job, orbx_mono_init_result *res);
+
 /* ORBmatcher::SearchByProjection(Frame &CurrentFrame, const Frame &LastFrame, th, bMono) (src/ORBmatcher.cc:1396-1553;
  * Tracking::TrackWithMotionModel).  direction: 0 none, 1 bForward, 2 bBackward (:1412-1413).  match_cur[cur->n] =
  * index of the point each current feature finally holds (-1 none); *nmatches = the reference's return value

@@ -159,6 +159,28 @@ class PnpJob(C.Structure):
                 ("n_refined", C.c_void_p), ("Rt_refined", C.c_void_p), ("refined_bits", C.c_void_p)]
 
 
+class MonoInitJob(C.Structure):
+    """orbx_mono_init_job (include/orbx.h)"""
+    _fields_ = [("n1", C.c_int), ("n2", C.c_int), ("xy1", C.c_void_p), ("xy2", C.c_void_p), ("n", C.c_int), ("matches", C.c_void_p),
+                ("sigma", C.c_float), ("K", C.c_float * 4), ("min_parallax", C.c_float), ("min_triangulated", C.c_int),
+                ("n_hyp", C.c_int), ("samples", C.c_void_p),
+                ("score_h", C.c_void_p), ("score_f", C.c_void_p), ("H21", C.c_void_p), ("F21", C.c_void_p),
+                ("bits_h", C.c_void_p), ("bits_f", C.c_void_p)]
+
+
+class MonoInitRecon(C.Structure):
+    """orbx_mono_init_recon (include/orbx.h)"""
+    _fields_ = [("ok", C.c_int), ("winner", C.c_int), ("n_good", C.c_int32 * 8), ("cos_parallax", C.c_float * 8),
+                ("R", C.c_float * 72), ("t", C.c_float * 24), ("P3D", C.c_void_p), ("triangulated", C.c_void_p)]
+
+
+class MonoInitResult(C.Structure):
+    """orbx_mono_init_result (include/orbx.h)"""
+    _fields_ = [("ok", C.c_int), ("model", C.c_int), ("best_h", C.c_int), ("best_f", C.c_int), ("SH", C.c_float), ("SF", C.c_float),
+                ("M", C.c_float * 9), ("R21", C.c_float * 9), ("t21", C.c_float * 3), ("parallax", C.c_float), ("winner", C.c_int),
+                ("n_good", C.c_int32 * 8), ("cos_parallax", C.c_float * 8), ("P3D", C.c_void_p), ("triangulated", C.c_void_p)]
+
+
 class Sim3OptObs(C.Structure):
     """orbx_sim3opt_obs (include/orbx.h)"""
     _fields_ = [("n", C.c_int), ("has_pair", C.c_void_p), ("P1c", C.c_void_p), ("P2c", C.c_void_p), ("x1", C.c_void_p), ("y1", C.c_void_p),
@@ -290,6 +312,9 @@ def lib():
     L.orbx_sim3_hypotheses_batch.argtypes = [i, C.POINTER(Sim3Job), i]
     L.orbx_pnp_hypotheses.argtypes = [i, C.POINTER(PnpJob)]
     L.orbx_pnp_hypotheses_batch.argtypes = [i, C.POINTER(PnpJob), i]
+    L.orbx_mono_init_hypotheses.argtypes = [i, C.POINTER(MonoInitJob)]
+    L.orbx_mono_init_reconstruct.argtypes = [i, C.POINTER(MonoInitJob), i, vp, vp, C.POINTER(MonoInitRecon)]
+    L.orbx_mono_init_initialize.argtypes = [i, C.POINTER(MonoInitJob), C.POINTER(MonoInitResult)]
     L.orbx_sim3_optimize.argtypes = [i, C.POINTER(Sim3OptObs), vp, vp, vp, f, i, vp, vp, ip, C.POINTER(Sim3OptReport)]
     L.orbx_sim3_optimize_batch.argtypes = [i, C.POINTER(Sim3OptJob), i]
     L.orbx_bow_frames_create.argtypes = [i, i, i, C.POINTER(vp)]
@@ -1347,6 +1372,121 @@ def pnp_hypotheses_batch(jobs, device=0):
         keep.append((J, k, out))
     _check(lib().orbx_pnp_hypotheses_batch(device, arr, nj))
     return [k[2] for k in keep]
+
+
+def _mono_init_job(job, who, table=True):
+    """dict(xy1[n1][2], xy2[n2][2], matches[n][2], K[4] = fx fy cx cy, sigma=1.0, min_parallax=1.0, min_triangulated=50, samples[n_hyp][8])
+    -> (MonoInitJob, inputs, table outputs); samples may be absent when table is False"""
+    xy1, xy2 = np.ascontiguousarray(job["xy1"], np.float32), np.ascontiguousarray(job["xy2"], np.float32)
+    ma = np.ascontiguousarray(job["matches"], np.int32)
+    sa = np.ascontiguousarray(job["samples"], np.int32) if job.get("samples") is not None else np.zeros((0, 8), np.int32)
+    k = np.asarray(job["K"], np.float32).reshape(-1)
+    if xy1.ndim != 2 or xy1.shape[1] != 2 or xy2.ndim != 2 or xy2.shape[1] != 2 or ma.ndim != 2 or ma.shape[1] != 2 or sa.ndim != 2 or \
+            sa.shape[1] != 8 or len(k) != 4:
+        raise OrbxError(-1, f"{who}: xy1 [n1][2], xy2 [n2][2], matches [n][2], samples [n_hyp][8], K [4]")
+    n, nh = len(ma), len(sa)
+    words = (n + 63) // 64
+    out = (np.zeros(nh, np.float32), np.zeros((nh, 9), np.float32), np.zeros((nh, words), np.uint64),
+           np.zeros(nh, np.float32), np.zeros((nh, 9), np.float32), np.zeros((nh, words), np.uint64))
+    J = MonoInitJob(len(xy1), len(xy2), _p(xy1), _p(xy2), n, _p(ma), float(job.get("sigma", 1.0)), (C.c_float * 4)(*k),
+                    float(job.get("min_parallax", 1.0)), int(job.get("min_triangulated", 50)), nh, _p(sa) if nh else None,
+                    _p(out[0]), _p(out[3]), _p(out[1]), _p(out[4]), _p(out[2]), _p(out[5]))
+    if not table:
+        J.score_h = J.score_f = J.H21 = J.F21 = J.bits_h = J.bits_f = None
+    return J, (xy1, xy2, ma, sa), out
+
+
+def mono_init_hypotheses(job, device=0):
+    """The table of Initializer::FindHomography and FindFundamental over the sample rows of one job (orbx_mono_init_hypotheses): job as
+    _mono_init_job -> (score_h[n_hyp] float32, H21[n_hyp][9], bits_h[n_hyp][(n+63)/64] uint64, score_f, F21, bits_f)"""
+    J, keep, out = _mono_init_job(job, "mono_init_hypotheses")
+    _check(lib().orbx_mono_init_hypotheses(device, C.byref(J)))
+    return out
+
+
+def _mono_points(n1):
+    return np.zeros((n1, 3), np.float32), np.zeros(n1, np.uint8)
+
+
+def mono_init_reconstruct(job, model, M, mask, device=0):
+    """ReconstructH (model 1) / ReconstructF (model 2) on the matrix M[9] and the inlier mask[(n+63)/64] uint64 (orbx_mono_init_reconstruct)
+    -> dict(ok, winner, n_good[8], cos_parallax[8], R[8][3][3], t[8][3], P3D[n1][3], triangulated[n1] bool)"""
+    J, keep, _ = _mono_init_job(job, "mono_init_reconstruct", table=False)
+    M = np.ascontiguousarray(M, np.float32).reshape(-1)
+    mask = np.ascontiguousarray(mask, np.uint64).reshape(-1)
+    if len(M) != 9 or len(mask) != (J.n + 63) // 64:
+        raise OrbxError(-1, "mono_init_reconstruct: M [9], mask [(n+63)/64]")
+    P3D, tri = _mono_points(J.n1)
+    R = MonoInitRecon(P3D=_p(P3D), triangulated=_p(tri))
+    _check(lib().orbx_mono_init_reconstruct(device, C.byref(J), int(model), _p(M), _p(mask), C.byref(R)))
+    return dict(ok=bool(R.ok), winner=R.winner, n_good=np.array(R.n_good, np.int32), cos_parallax=np.array(R.cos_parallax, np.float32),
+                R=np.array(R.R, np.float32).reshape(8, 3, 3), t=np.array(R.t, np.float32).reshape(8, 3), P3D=P3D, triangulated=tri.astype(bool))
+
+
+def mono_init_initialize(job, device=0):
+    """Initializer::Initialize behind the drawing of the sample rows, in one call (orbx_mono_init_initialize) -> dict(ok, model, best_h,
+    best_f, SH, SF, M[9], R21[3][3], t21[3], parallax, winner, n_good[8], cos_parallax[8], P3D[n1][3], triangulated[n1] bool)"""
+    J, keep, _ = _mono_init_job(job, "mono_init_initialize", table=False)
+    P3D, tri = _mono_points(J.n1)
+    R = MonoInitResult(P3D=_p(P3D), triangulated=_p(tri))
+    _check(lib().orbx_mono_init_initialize(device, C.byref(J), C.byref(R)))
+    return dict(ok=bool(R.ok), model=R.model, best_h=R.best_h, best_f=R.best_f, SH=np.float32(R.SH), SF=np.float32(R.SF),
+                M=np.array(R.M, np.float32), R21=np.array(R.R21, np.float32).reshape(3, 3), t21=np.array(R.t21, np.float32),
+                parallax=np.float32(R.parallax), winner=R.winner, n_good=np.array(R.n_good, np.int32),
+                cos_parallax=np.array(R.cos_parallax, np.float32), P3D=P3D, triangulated=tri.astype(bool))
+
+
+class DUtilsRandom:
+    """DUtils::Random::RandomInt over the C library's rand(), seeded as SeedRandOnce(0) seeds it (Thirdparty/DBoW2/DUtils/Random.cpp):
+    the stream Initializer::Initialize draws mvSets from.  seed = None keeps the process's stream (a second SeedRandOnce is a no-op)."""
+
+    def __init__(self, seed=0):
+        self._libc = C.CDLL(None)
+        if seed is not None:
+            self._libc.srand(C.c_uint(seed))
+
+    def random_int(self, lo, hi):
+        d = hi - lo + 1
+        return int((float(self._libc.rand()) / (2147483647.0 + 1.0)) * d) + lo
+
+
+def mono_init_draw_sets(n, iterations, rng):
+    """mvSets of Initializer::Initialize (:79-111): per iteration eight draws without replacement from 0 .. n-1 -> int32 [iterations][8]"""
+    sets = np.zeros((iterations, 8), np.int32)
+    for it in range(iterations):
+        avail = list(range(n))
+        for j in range(8):
+            r = rng.random_int(0, len(avail) - 1)
+            sets[it, j] = avail[r]
+            avail[r] = avail[-1]
+            avail.pop()
+    return sets
+
+
+class Initializer:
+    """Initializer (reference include/Initializer.h:36-46, src/Initializer.cc:37-145).  keys1 / keys2 = the undistorted keypoint positions
+    [n][2] of the reference / current frame, K = mK as 3 x 3 or (fx, fy, cx, cy).  Initialize(keys2, matches12) takes vMatches12 (per
+    keypoint of frame 1 the index in frame 2 or -1) and returns (ok, R21[3][3], t21[3], P3D[n1][3], triangulated[n1]); the sample rows are
+    drawn as the reference draws them unless `samples` gives them.  self.last keeps the whole result of the call."""
+
+    def __init__(self, keys1, K, sigma=1.0, iterations=200, device=0):
+        self.keys1 = np.ascontiguousarray(keys1, np.float32).reshape(-1, 2)
+        K = np.asarray(K, np.float32)
+        self.K = np.array([K[0, 0], K[1, 1], K[0, 2], K[1, 2]], np.float32) if K.shape == (3, 3) else K.reshape(4).copy()
+        self.sigma, self.iterations, self.device = float(sigma), int(iterations), device
+        self.sets = None
+        self.last = None
+
+    def Initialize(self, keys2, matches12, samples=None):
+        keys2 = np.ascontiguousarray(keys2, np.float32).reshape(-1, 2)
+        m12 = np.asarray(matches12, np.int64).reshape(-1)
+        first = np.nonzero(m12 >= 0)[0]
+        matches = np.stack([first, m12[first]], 1).astype(np.int32)
+        self.sets = mono_init_draw_sets(len(matches), self.iterations, DUtilsRandom(0)) if samples is None else np.asarray(samples, np.int32)
+        r = mono_init_initialize(dict(xy1=self.keys1, xy2=keys2, matches=matches, K=self.K, sigma=self.sigma, samples=self.sets),
+                                 self.device)
+        self.last = r
+        return r["ok"], r["R21"], r["t21"], r["P3D"], r["triangulated"]
 
 
 class PnPRansac:
