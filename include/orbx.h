@@ -816,6 +816,100 @@ int orbx_frame_pose_optimize(const orbx_frame *cur, const orbx_mappoints *m, con
                              const float *inv_level_sigma2, int nlevels, const float *cam, const float *Tcw, float *Tcw_out,
                              uint8_t *outlier, int *n_inliers, orbx_pose_report *report);
 
+/* ---- Optimizer::LocalBundleAdjustment (src/Optimizer.cc:528-862; LocalMapping::Run) ---------
+ * The optimisation of the local window behind SearchInNeighbors, which g2o solved on one host core per inserted keyframe: 6-DoF
+ * vertices for the local and the fixed keyframes, marginalised 3-D vertices for the local points, one binary edge per observation.
+ * Everything between :584 (the optimizer's set-up) and :825 (vToErase) is this call; the three lists before it and the map update
+ * behind it stay with the adaptor (adapter/lba/LocalBundleAdjustment.cc).  The host drives the Levenberg loop and polls the stop flag;
+ * a linearisation and a damping trial are short chains of launches (orbx_lba.hip), with one small status record read back after each.
+ * The arithmetic, in double unless a step says float, every operation rounded on its own (no fused multiply-add):
+ *   start    Converter::toSE3Quat(GetPose()) per keyframe as in orbx_pose_optimize: the float rotation block to a quaternion, w >= 0,
+ *            normalised.  Tcw_out of a FIXED keyframe is that quaternion turned back into a matrix and cast to float (:847-850 calls
+ *            SetPose with exactly that for the keyframe with mnId == 0); its bits can differ from the input.  Points: Xw widened.
+ *   edges    edge e joins point edge_point[e] (vertex 0) and keyframe edge_kf[e] (vertex 1); monocular (EdgeSE3ProjectXYZ, :675-701)
+ *            if u_right[e] < 0, else stereo (EdgeStereoSE3ProjectXYZ, :702-731).  Information = inv_sigma2[e] * I.  Error =
+ *            measurement - projection of Pc = q * X + t: monocular (Pc.x / Pc.z) * fx + cx, likewise y; stereo invz =
+ *            (double)(float)(1.0 / Pc.z) (types_six_dof_expmap.cpp:151), u = (Pc.x * invz) * fx + cx, v likewise, third row
+ *            u - mbf * invz.  chi2 = sum_r e_r * (inv_sigma2 * e_r).
+ *   Jacobians linearizeOplus (types_six_dof_expmap.cpp:103-139, :188-234), as written there (x*y/z_2 *fx, -1./z *fx, ...), with
+ *            R = the quaternion's rotation matrix.  _jacobianOplusXj is the 2/3 x 6 pose block Jp.  _jacobianOplusXi is the 2/3 x 3 point
+ *            block Jl: stereo entry by entry as :202-212; monocular (-1./z * tmp) * R with every sum ((t_i0 R_0c + t_i1 R_1c) + t_i2 R_2c),
+ *            the zero entries of tmp included.
+ *   Huber    delta = (float)sqrt(5.991) / (float)sqrt(7.815) (:650-651), robust_kernel_impl.cpp:78-91, in round 1 only.
+ *   quadratic form  base_binary_edge.hpp constructQuadraticForm: omega_r = -(inv_sigma2 e) * rho1; rw = rho1 * inv_sigma2 (rho2 is
+ *            ignored); per edge  Hll += Jl^T rw Jl, bl += Jl^T omega_r, and for a free keyframe  Hpp += Jp^T rw Jp, bp += Jp^T omega_r,
+ *            W = Jp^T rw Jl (6 x 3).  An entry of such a product is ((a_0 rw) b_0 + (a_1 rw) b_1) + (a_2 rw) b_2 over the edge's rows (two
+ *            for a monocular edge's non-zero rows; the third adds an exact zero).  No pose block and no b for a fixed keyframe.
+ *   system   per point, Hll and bl are summed over the point's active edges one after the other in edge order: that fixes them bit for
+ *            bit.  Per free keyframe, Hpp and bp are summed over its active edges, taken in point order, in a fixed order that is a function
+ *            of their count only.  setLambda adds lambda to the diagonals of every Hpp and every Hll block.  Dinv = (Hll + lambda I)^-1 is
+ *            the closed 3 x 3 cofactor inverse (Eigen's fixed-size inverse(): determinant along the first column), no singularity test.
+ *            S = Hpp + lambda I - sum_points sum_{i<=j} (W_i Dinv) W_j^T, b_S = bp - sum W_i (Dinv bl) (block_solver.hpp:372-439), the sums
+ *            in a fixed order; rows and columns of S are the active free keyframes in keyframe order.
+ *   solve    S x_p = b_S by a dense LDL^T without pivoting on the lower triangle (the mirror image of what the sums give for the upper one),
+ *            column by column: l_ij = s_ij / d_j, then s_ik -= (l_ij l_kj) d_j for i >= k > j; forward substitution y_i -= l_ij y_j in
+ *            ascending j, y_i / d_i, backward substitution x_i -= l_ji x_j in descending j.  A pivot <= 0 makes the trial's chi2 DBL_MAX
+ *            and leaves x as the previous trial left it (0 at the start).  THIS DENSE SOLVE IS THE STATED DEVIATION: g2o factors the same
+ *            matrix with Eigen's sparse SimplicialLDLT under an AMD ordering -- the same solution, with different rounding.
+ *            x_l = Dinv (bl - sum_edges W^T x_p), the edges of the point in order.
+ *   update   pose = SE3Quat::exp(x) * pose as in orbx_pose_optimize; point += x_l.
+ *   Levenberg optimization_algorithm_levenberg.cpp:61-189 as restated for orbx_pose_optimize.  computeLambdaInit takes the maximum over
+ *            the diagonals of ALL active vertices, poses and points; computeScale runs over the whole x and b (bp and bl, not b_S), poses
+ *            first, in a fixed order; ni and lambda are set anew at iteration 0 of each round; at most 10 trials per iteration; the
+ *            _nBad >= 3 stop and the rho == 0 stop are kept.  The active robust chi2 sums, in a fixed order over the points, each point's
+ *            sum of rho0 (chi2 in round 2) over its active edges in edge order.
+ *   rounds   (:740-825) round 1 = optimize(5) on all edges with Huber.  The classification sets level 1 where chi2 > 5.991 (7.815
+ *            stereo) or isDepthPositive fails, and removes every kernel.  initializeOptimization(0): a point with no level-0 edge, or a
+ *            free keyframe with no level-0 edge, leaves the active set and keeps its estimate; it has no row in the system and no share
+ *            in lambdaInit.  Round 2 = optimize(10) without a kernel; a round with no active edge does nothing (optimize returns -1).
+ *            The final check marks vToErase by the same test.  An active edge's chi2() is that of the LAST EVALUATED TRIAL -- after a
+ *            rejected last trial that is the rejected state (the pose-optimisation rule).  A level-1 edge is never re-evaluated in round 2:
+ *            in the final check it still carries its round-1 error.  isDepthPositive() (Pc.z > 0) is always evaluated at the current,
+ *            restored estimates.  The thresholds compare as the reference's doubles do, chi2 > 5.991: no float cast here, unlike
+ *            PoseOptimization.
+ *   stop     *stop (mbAbortBA) is read on entry (:736), before every iteration and between trials (terminate()), and after round 1
+ *            (:745).  debug_stop_at_trial = t behaves as if the flag rose when the running count of trials (both rounds) reaches t; it
+ *            exists so that the bDoMore = false path is testable, an adaptor never sets it.  stopped = 2: round 2 is skipped; bit 0 of
+ *            the flags then holds the test the skipped classification would have made (the reference sets no level there), and bit 1
+ *            equals it.  Stated deviation: if the stop comes before any evaluation, the errors are those at the start estimates (the
+ *            reference would read uninitialised memory there).
+ *   result   pose_out = [R | t] of the final quaternion, point_out the final points, in double; Tcw_out and Xw_out are their
+ *            Converter::toCvMat float casts (last row 0 0 0 1).  A point without edges returns Xw bit for bit.
+ * A call is byte-reproducible: no atomics, every reduction in a fixed order.  iterations / trials near convergence hang on the sign of
+ * rounding noise and are reported, not promised.  Outside the contract: a projection that is not finite at a state the solver visits.
+ * Against g2o's own arithmetic (SimplicialLDLT, Eigen's product evaluation order) this restatement is unpinned: DESIGN.md. */
+typedef struct {
+    int n_kf;                       /* local + fixed keyframes, 1 .. 1024; at most 256 with fixed[k] == 0 */
+    const float *Tcw;               /* [n_kf][16] GetPose(), row major */
+    const float *cam;               /* [n_kf][5] fx fy cx cy mbf */
+    const uint8_t *fixed;           /* [n_kf]: lFixedCameras, and the keyframe with mnId == 0 */
+    int n_points;                   /* 0 .. 2^20 */
+    const float *Xw;                /* [n_points][3] GetWorldPos() */
+    int n_edges;                    /* 0 .. 2^22; edges of one point are contiguous, points ascending */
+    const int32_t *edge_kf, *edge_point;
+    const float *x, *y, *u_right, *inv_sigma2;   /* mvKeysUn[idx].pt, mvuRight[idx] (< 0: monocular edge), mvInvLevelSigma2[octave] */
+} orbx_lba_problem;
+typedef struct { const volatile unsigned char *stop; int debug_stop_at_trial; } orbx_lba_options;   /* NULL / -1: never */
+typedef struct {
+    int stopped;                    /* 0 no, 1 on entry (nothing written), 2 in round 1 (round 2 skipped), 3 in round 2 */
+    int iterations[2], trials[2];   /* Levenberg iterations / damping trials of optimize(5) and optimize(10) */
+    int n_level1, n_erase;          /* edges set to level 1 after round 1; edges in vToErase */
+    int n_active_kf[2], n_active_points[2];
+    double chi2[2], lambda[2];      /* active robust chi2 and lambda each round ended with */
+} orbx_lba_report;
+/* One upload in front, one download behind; the device buffers are the calling thread's (orbx_thread_release).  Refusals before any
+ * device work.  ORBX_E_INVALID: a NULL argument or array that the sizes need (opt, pose_out, point_out, report may be NULL; Xw_out with
+ * n_points == 0 and edge_flags with n_edges == 0 too), n_kf < 1 or a negative size, an index out of range, edges of a point not
+ * contiguous or points not ascending, more than one edge between a point and a keyframe.  ORBX_E_CAPACITY: n_kf > 1024, n_points >
+ * 2^20, n_edges > 2^22, more than 256 keyframes with fixed[k] == 0.  stopped == 1: nothing but the report is written.
+ * The limits say what the buffers hold, not what runs well: the reduced system (6 x the free keyframes) is factored by one workgroup,
+ * which suits the tens of free keyframes of a covisibility window; at 256 a trial costs on the order of 0.1 s. */
+int orbx_local_bundle_adjustment(int device, const orbx_lba_problem *p, const orbx_lba_options *opt /* may be NULL */,
+                                 float *Tcw_out /* [n_kf][16] */, float *Xw_out /* [n_points][3] */,
+                                 uint8_t *edge_flags /* [n_edges]: bit 0 level 1 after round 1, bit 1 in vToErase */,
+                                 double *pose_out /* [n_kf][12], may be NULL */, double *point_out /* [n_points][3], may be NULL */,
+                                 orbx_lba_report *report /* may be NULL */);
+
 /* ---- Optimizer::OptimizeSim3: the Sim3 between two keyframes (src/Optimizer.cc:1164-1365) ------------------------------
  * Step 4 of LoopClosing::ComputeSim3 (src/LoopClosing.cc:282-460), between SearchBySim3 and the Sim3 SearchByProjection.  Every
  * VertexSBAPointXYZ of the function is fixed: the one free vertex is a 7-DoF VertexSim3Expmap, and the whole function -- two rounds
@@ -1407,6 +1501,13 @@ int orbx_debug_set_match_items(int in_memory);
 /* host phases of the calling thread's most recent per-call matcher search (orbx_match.hip), microseconds:
  * [0] prepare (node intersection, participation bytes, packing), [1] launch, [2] wait for the kernel's ticket, [3] copy-out */
 int orbx_debug_match_timing(double *out4);
+/* measurement hook (tools/bench_lba.py): enable = 1 makes every launch of the calling thread's later orbx_local_bundle_adjustment calls sit
+ * between two events and be waited for, its device time going to its kernel's slot; enable = 0 ends that, writes the milliseconds and
+ * launch counts gathered since (ms[12], launches[12], either may be NULL) and returns 12, the slot count.  Slots: 0 k_lba_init, 1 k_lba_active,
+ * 2 k_lba_points<true>, 3 k_lba_kf, 4 k_lba_reduce, 5 k_lba_prep, 6 k_lba_schur, 7 k_lba_solve, 8 k_lba_update, 9 k_lba_points<false>,
+ * 10 k_lba_classify, 11 k_lba_finish.  Results are the same bytes with and without it.  The events belong to the thread's context and go
+ * with it (orbx_thread_release, or the thread's end). */
+int orbx_debug_lba_profile(int enable, double *ms, int32_t *launches);
 /* process-wide: the per-thread search contexts (see orbx_thread_release) that are set up right now, over all threads, families and
  * devices.  A thread's share leaves the count when it calls orbx_thread_release or ends. */
 int orbx_debug_thread_contexts(void);

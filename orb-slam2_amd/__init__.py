@@ -13,6 +13,7 @@ sitting directly on the C ABI of liborbx.so (include/orbx.h):
   sim3_hypotheses / Sim3Ransac <- reference src/Sim3Solver.cc:117-433 (LoopClosing::ComputeSim3's RANSAC)
   sim3_optimize / sim3_optimize_batch <- reference src/Optimizer.cc:1164-1365 (Optimizer::OptimizeSim3)
   pnp_hypotheses / PnPRansac <- reference src/PnPsolver.cc:128-961 (Tracking::Relocalization's EPnP RANSAC)
+  local_bundle_adjustment <- reference src/Optimizer.cc:528-862 (Optimizer::LocalBundleAdjustment, LocalMapping's optimisation)
   mono_init_hypotheses / mono_init_reconstruct / Initializer <- reference src/Initializer.cc:37-1026 (Tracking::MonocularInitialization)
 
 There is NO CPU fallback: importing works without a GPU (so that the ABI can be inspected), but
@@ -25,11 +26,13 @@ from .orbx import (OrbxError, KP_DTYPE, lib, lib_path, ORBextractor, ORBmatcher,
                    RGBDParams, depth_map_factor, rgbd_depth_batch_device, DEPTH_U16, DEPTH_F32, pose_optimize, pose_optimize_batch,
                    triangulate_pairs, frame_set_depth, frame_triangulate, sim3_hypotheses, sim3_hypotheses_batch, sim3_max_error, Sim3Ransac,
                    sim3_optimize, sim3_optimize_batch, sim3opt_camera_points, pnp_hypotheses, pnp_hypotheses_batch, PnPRansac,
-                   mono_init_hypotheses, mono_init_reconstruct, mono_init_initialize, mono_init_draw_sets, DUtilsRandom, Initializer)
+                   mono_init_hypotheses, mono_init_reconstruct, mono_init_initialize, mono_init_draw_sets, DUtilsRandom, Initializer,
+                   local_bundle_adjustment)
 
 __all__ = ["OrbxError", "KP_DTYPE", "lib", "lib_path", "ORBextractor", "ORBmatcher", "ComputeStereoMatches",
            "FeatSet", "make_featset", "STAGES", "BowDatabase", "DeviceKeyFrame", "DeviceFrame", "MapPoints", "BowFrames", "KeyFrameDatabase", "ORBVocabulary", "ComputeDistinctiveDescriptors", "Rectifier", "UndistortKeyPoints",
            "RGBDParams", "depth_map_factor", "rgbd_depth_batch_device", "DEPTH_U16", "DEPTH_F32", "pose_optimize", "pose_optimize_batch",
            "triangulate_pairs", "frame_set_depth", "frame_triangulate", "sim3_hypotheses", "sim3_hypotheses_batch", "sim3_max_error", "Sim3Ransac",
            "sim3_optimize", "sim3_optimize_batch", "sim3opt_camera_points", "pnp_hypotheses", "pnp_hypotheses_batch", "PnPRansac",
-           "mono_init_hypotheses", "mono_init_reconstruct", "mono_init_initialize", "mono_init_draw_sets", "DUtilsRandom", "Initializer"]
+           "mono_init_hypotheses", "mono_init_reconstruct", "mono_init_initialize", "mono_init_draw_sets", "DUtilsRandom", "Initializer",
+           "local_bundle_adjustment"]

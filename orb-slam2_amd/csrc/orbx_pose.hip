@@ -33,7 +33,6 @@ struct PoseOut { double pose[12], chi2[4]; float Tcw[16]; int32_t n_corr, rounds
 
 namespace {
 
-struct Pose { double qx, qy, qz, qw, tx, ty, tz; };
 struct Edge { double mx, my, mr, X, Y, Z, w; bool stereo; };
 struct Cam { double fx, fy, cx, cy, bf; };
 
@@ -89,69 +88,7 @@ __device__ __forceinline__ double edge_chi2(const PoseJob &J, int i, const Pose 
 
 // huber, block_sum (its fixed order: header comment) and Eigen's Quaternion(Matrix3) are orbx_lm.h's, shared with k_sim3_opt
 
-// SE3Quat::normalizeRotation
-__device__ __forceinline__ void quat_normalize(double &qx, double &qy, double &qz, double &qw)
-{
-    if (qw < 0.0) { qx = -qx; qy = -qy; qz = -qz; qw = -qw; }
-    const double n = sqrt(((qx * qx + qy * qy) + qz * qz) + qw * qw);
-    qx /= n; qy /= n; qz /= n; qw /= n;
-}
-
-__device__ __forceinline__ void quat_to_matrix(const Pose &P, double R[9])
-{
-    const double tx = 2.0 * P.qx, ty = 2.0 * P.qy, tz = 2.0 * P.qz;
-    const double twx = tx * P.qw, twy = ty * P.qw, twz = tz * P.qw, txx = tx * P.qx, txy = ty * P.qx, txz = tz * P.qx;
-    const double tyy = ty * P.qy, tyz = tz * P.qy, tzz = tz * P.qz;
-    R[0] = 1.0 - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy;
-    R[3] = txy + twz; R[4] = 1.0 - (txx + tzz); R[5] = tyz - twx;
-    R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1.0 - (txx + tyy);
-}
-
-// VertexSE3Expmap::oplusImpl: SE3Quat::exp(x) * P (se3quat.h:223-257, :104-110); x[0..2] rotation, x[3..5] translation
-__device__ __forceinline__ Pose pose_update(const Pose &P, const double x[6])
-{
-    const double o0 = x[0], o1 = x[1], o2 = x[2];
-    const double theta = sqrt((o0 * o0 + o1 * o1) + o2 * o2);
-    const double O[9] = { 0.0, -o2, o1, o2, 0.0, -o0, -o1, o0, 0.0 };
-    double O2[9], R[9], V[9];
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-#pragma unroll
-        for (int c = 0; c < 3; c++) O2[3 * r + c] = (O[3 * r] * O[c] + O[3 * r + 1] * O[3 + c]) + O[3 * r + 2] * O[6 + c];
-    if (theta < 0.00001) {
-#pragma unroll
-        for (int k = 0; k < 9; k++) { R[k] = ((k % 4 == 0 ? 1.0 : 0.0) + O[k]) + O2[k]; V[k] = R[k]; }
-    } else {
-        const double s = sin(theta), c = cos(theta);
-        const double a = s / theta, b = (1.0 - c) / (theta * theta), cc = (theta - s) / ((theta * theta) * theta);
-#pragma unroll
-        for (int k = 0; k < 9; k++) {
-            const double id = k % 4 == 0 ? 1.0 : 0.0;
-            R[k] = (id + a * O[k]) + b * O2[k];
-            V[k] = (id + b * O[k]) + cc * O2[k];
-        }
-    }
-    Pose E;
-    quat_from_matrix(R, E.qx, E.qy, E.qz, E.qw);
-    quat_normalize(E.qx, E.qy, E.qz, E.qw);
-    E.tx = (V[0] * x[3] + V[1] * x[4]) + V[2] * x[5];
-    E.ty = (V[3] * x[3] + V[4] * x[4]) + V[5] * x[5];
-    E.tz = (V[6] * x[3] + V[7] * x[4]) + V[8] * x[5];
-    // E * P: t = E.t + E.q * P.t ; q = E.q * P.q, normalised
-    Pose N;
-    {
-        const double ux = 2.0 * (E.qy * P.tz - E.qz * P.ty), uy = 2.0 * (E.qz * P.tx - E.qx * P.tz), uz = 2.0 * (E.qx * P.ty - E.qy * P.tx);
-        N.tx = E.tx + ((P.tx + E.qw * ux) + (E.qy * uz - E.qz * uy));
-        N.ty = E.ty + ((P.ty + E.qw * uy) + (E.qz * ux - E.qx * uz));
-        N.tz = E.tz + ((P.tz + E.qw * uz) + (E.qx * uy - E.qy * ux));
-    }
-    N.qw = ((E.qw * P.qw - E.qx * P.qx) - E.qy * P.qy) - E.qz * P.qz;
-    N.qx = ((E.qw * P.qx + E.qx * P.qw) + E.qy * P.qz) - E.qz * P.qy;
-    N.qy = ((E.qw * P.qy + E.qy * P.qw) + E.qz * P.qx) - E.qx * P.qz;
-    N.qz = ((E.qw * P.qz + E.qz * P.qw) + E.qx * P.qy) - E.qy * P.qx;
-    quat_normalize(N.qx, N.qy, N.qz, N.qw);
-    return N;
-}
+// SE3Quat (Pose, quat_normalize, quat_to_matrix, pose_update) is orbx_lm.h's too, shared with the kernels of orbx_lba.hip
 
 // (H + lambda I) x = b by LDL^T without pivoting; H's upper triangle in row order (00 01 .. 05 11 12 ..).  false (x untouched) unless
 // every pivot is > 0 (linear_solver_dense.h:104-112)

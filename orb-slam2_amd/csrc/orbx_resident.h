@@ -30,6 +30,7 @@ struct CallCtx : ThreadCtx {
     uint32_t *d_entries = nullptr; size_t ent_cap = 0;   // the candidate pool of proj_search
     int32_t *h_out = nullptr; size_t out_cap = 0;
     int32_t *h_n = nullptr;    // pinned: the feature count a frame created from extraction outputs reads back
+    hipEvent_t ev_a = nullptr, ev_b = nullptr;   // the pair round a launch while orbx_debug_lba_profile is on (orbx_lba.hip); made on first use
     ORBX_LOCAL void release();
     ~CallCtx() { release(); }
 };

@@ -209,7 +209,10 @@ void CallCtx::release()
         if (d_entries) (void)hipFree(d_entries);
         if (h_out) (void)hipHostFree(h_out);
         if (h_n) (void)hipHostFree(h_n);
+        if (ev_a) (void)hipEventDestroy(ev_a);
+        if (ev_b) (void)hipEventDestroy(ev_b);
     }
+    ev_a = ev_b = nullptr;
     h_blob = d_blob = d_work = nullptr; d_entries = nullptr; h_out = h_n = nullptr;
     h_cap = d_cap = work_cap = ent_cap = out_cap = 0;
 }

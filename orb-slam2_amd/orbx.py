@@ -126,6 +126,24 @@ class PoseReport(C.Structure):
                 ("chi2", C.c_double * 4), ("pose", C.c_double * 12)]
 
 
+class LbaProblem(C.Structure):
+    """orbx_lba_problem (include/orbx.h)"""
+    _fields_ = [("n_kf", C.c_int), ("Tcw", C.c_void_p), ("cam", C.c_void_p), ("fixed", C.c_void_p), ("n_points", C.c_int), ("Xw", C.c_void_p),
+                ("n_edges", C.c_int), ("edge_kf", C.c_void_p), ("edge_point", C.c_void_p), ("x", C.c_void_p), ("y", C.c_void_p),
+                ("u_right", C.c_void_p), ("inv_sigma2", C.c_void_p)]
+
+
+class LbaOptions(C.Structure):
+    """orbx_lba_options (include/orbx.h)"""
+    _fields_ = [("stop", C.c_void_p), ("debug_stop_at_trial", C.c_int)]
+
+
+class LbaReport(C.Structure):
+    """orbx_lba_report (include/orbx.h)"""
+    _fields_ = [("stopped", C.c_int), ("iterations", C.c_int * 2), ("trials", C.c_int * 2), ("n_level1", C.c_int), ("n_erase", C.c_int),
+                ("n_active_kf", C.c_int * 2), ("n_active_points", C.c_int * 2), ("chi2", C.c_double * 2), ("lambda_", C.c_double * 2)]
+
+
 class PoseJob(C.Structure):
     """orbx_pose_job (include/orbx.h)"""
     _fields_ = [("obs", C.POINTER(PoseObs)), ("cam", C.c_void_p), ("Tcw", C.c_void_p), ("Tcw_out", C.c_void_p),
@@ -304,6 +322,8 @@ def lib():
     L.orbx_pose_optimize.argtypes = [i, C.POINTER(PoseObs), vp, vp, vp, vp, ip, C.POINTER(PoseReport)]
     L.orbx_pose_optimize_batch.argtypes = [i, C.POINTER(PoseJob), i]
     L.orbx_frame_pose_optimize.argtypes = [vp, vp, vp, vp, i, vp, vp, vp, vp, ip, C.POINTER(PoseReport)]
+    L.orbx_local_bundle_adjustment.argtypes = [i, C.POINTER(LbaProblem), C.POINTER(LbaOptions), vp, vp, vp, vp, vp, C.POINTER(LbaReport)]
+    L.orbx_debug_lba_profile.argtypes = [i, vp, vp]
     L.orbx_triangulate_pairs.argtypes = [i, C.POINTER(TriFeats), C.POINTER(TriView), C.POINTER(C.POINTER(TriFeats)), C.POINTER(TriView), i, vp, i, vp,
                                          vp, vp, i, f, vp, vp, ip]
     L.orbx_frame_set_depth.argtypes = [vp, vp, vp, vp]
@@ -1052,6 +1072,37 @@ def pose_optimize(obs, cam, Tcw, device=0):
     out = np.zeros(16, np.float32); fl = np.zeros(po.n, np.uint8); ni = C.c_int(); rep = PoseReport()
     _check(lib().orbx_pose_optimize(device, C.byref(po), _p(ca), _p(tc), _p(out), _p(fl), C.byref(ni), C.byref(rep)))
     return _pose_result(out, fl, ni.value, rep)
+
+
+def _lba_problem(problem, who):
+    """problem = dict(Tcw [K][4][4], cam [K][5], fixed [K], Xw [P][3], edge_kf, edge_point, x, y, u_right, inv_sigma2) -> (LbaProblem, arrays)"""
+    Tcw = np.ascontiguousarray(problem["Tcw"], np.float32).reshape(-1, 16)
+    K = len(Tcw)
+    cam = np.ascontiguousarray(problem["cam"], np.float32).reshape(-1, 5)
+    fixed = np.ascontiguousarray(problem["fixed"], np.uint8).reshape(-1)
+    Xw = np.ascontiguousarray(problem["Xw"], np.float32).reshape(-1, 3)
+    ek = np.ascontiguousarray(problem["edge_kf"], np.int32).reshape(-1)
+    ep = np.ascontiguousarray(problem["edge_point"], np.int32).reshape(-1)
+    obs = [np.ascontiguousarray(problem[k], np.float32).reshape(-1) for k in ("x", "y", "u_right", "inv_sigma2")]
+    if len(cam) != K or len(fixed) != K or any(len(a) != len(ek) for a in [ep] + obs):
+        raise OrbxError(-1, f"{who}: Tcw, cam and fixed need one entry per keyframe, the edge arrays one per edge")
+    keep = [Tcw, cam, fixed, Xw, ek, ep] + obs
+    return LbaProblem(K, _p(Tcw), _p(cam), _p(fixed), len(Xw), _p(Xw), len(ek), _p(ek), _p(ep), *[_p(a) for a in obs]), keep
+
+
+def local_bundle_adjustment(problem, stop_at_trial=-1, stop=None, device=0):
+    """Optimizer::LocalBundleAdjustment (orbx_local_bundle_adjustment): problem = dict(Tcw [K][4][4], cam [K][5] fx fy cx cy mbf, fixed [K],
+    Xw [P][3], edge_kf, edge_point, x, y, u_right, inv_sigma2 [E]); stop: a uint8 array of one element that is polled as mbAbortBA;
+    stop_at_trial: the debug_stop_at_trial hook -> dict(Tcw [K][4][4], Xw [P][3], edge_flags [E], pose [K][3][4], point [P][3], stopped,
+    iterations, trials, n_level1, n_erase, n_active_kf, n_active_points, chi2, lambda)"""
+    pr, keep = _lba_problem(problem, "local_bundle_adjustment")
+    opt = LbaOptions(stop.ctypes.data if stop is not None else None, int(stop_at_trial))
+    Tcw = np.zeros((pr.n_kf, 4, 4), np.float32); Xw = np.zeros((pr.n_points, 3), np.float32); fl = np.zeros(pr.n_edges, np.uint8)
+    pose = np.zeros((pr.n_kf, 3, 4), np.float64); point = np.zeros((pr.n_points, 3), np.float64); rep = LbaReport()
+    _check(lib().orbx_local_bundle_adjustment(device, C.byref(pr), C.byref(opt), _p(Tcw), _p(Xw), _p(fl), _p(pose), _p(point), C.byref(rep)))
+    return {"Tcw": Tcw, "Xw": Xw, "edge_flags": fl, "pose": pose, "point": point, "stopped": rep.stopped, "iterations": list(rep.iterations),
+            "trials": list(rep.trials), "n_level1": rep.n_level1, "n_erase": rep.n_erase, "n_active_kf": list(rep.n_active_kf),
+            "n_active_points": list(rep.n_active_points), "chi2": list(rep.chi2), "lambda": list(rep.lambda_)}
 
 
 def pose_optimize_batch(jobs, device=0):
