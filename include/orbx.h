@@ -910,6 +910,40 @@ int orbx_local_bundle_adjustment(int device, const orbx_lba_problem *p, const or
                                  double *pose_out /* [n_kf][12], may be NULL */, double *point_out /* [n_points][3], may be NULL */,
                                  orbx_lba_report *report /* may be NULL */);
 
+/* ---- Optimizer::BundleAdjustment (src/Optimizer.cc:48-281; Tracking::CreateInitialMapMonocular, LoopClosing::RunGlobalBundleAdjustment) ----
+ * The global bundle adjustment over a whole map: everything between :67 (the optimiser's set-up) and :232 (the recovery loops) is this
+ * call; the two lists in front and the recovery behind stay with the adaptor (adapter/ba/BundleAdjustment.cc).  It takes the problem of
+ * orbx_local_bundle_adjustment, and its start, edges, Jacobians, quadratic form, system, solve, update, Levenberg rules and result are that
+ * contract's, operation for operation (the block above; not repeated here).  What differs:
+ *   rounds   ONE round, optimize(iterations), on every edge.  robust != 0: Huber on every edge throughout, with thHuber2D =
+ *            (float)sqrt(5.99) for a monocular edge (:101 -- not LocalBundleAdjustment's 5.991) and thHuber3D = (float)sqrt(7.815) for a
+ *            stereo one; robust == 0: no kernel.  No classification, no levels: every edge is active for the whole call, and there are
+ *            no edge flags.
+ *   vertices a point without an edge is not a vertex (:215-219, vbNotIncludedMP): point_included = 0 and Xw_out = Xw bit for bit.  A free
+ *            keyframe without an edge has no row in the system and keeps its estimate (through the quaternion round trip, like a fixed one).
+ *   solve    the same dense LDL^T with the same per-entry operation order, computed in panels over many workgroups (orbx_ldlt.hip), so the
+ *            bytes of x are those the one-workgroup kernel of orbx_local_bundle_adjustment would give.
+ *   stop     there is no return on entry: the reference only hands the flag to setForceStopFlag (:64-65).  With *stop up on entry no
+ *            iteration runs and the outputs are the start estimates through the quaternion round trip, stopped = 1.  After that the flag is
+ *            polled before every iteration and between trials as in orbx_local_bundle_adjustment; stopped = 2 if it is up when the round
+ *            ends.  debug_stop_at_trial as there.
+ *   sizes    n_kf <= 4096, at most 2048 keyframes with fixed == 0, n_points <= 2^20, n_edges <= 2^22.  The reduced system is dense:
+ *            8 (6 F)^2 bytes for F free keyframes with an edge, 1.2 GB at 2048 (the thread's work area grows to twice its largest request).
+ * opt == NULL: no flag, 10 iterations, robust.  Refusals before any device work: ORBX_E_INVALID as for orbx_local_bundle_adjustment
+ * (point_included is needed when n_points > 0), and for iterations < 0; ORBX_E_CAPACITY beyond a size above. */
+typedef struct { const volatile unsigned char *stop; int debug_stop_at_trial; int iterations; int robust; } orbx_ba_options;
+typedef struct {
+    int stopped;                    /* 0 no, 1 the flag was up on entry (no iteration), 2 it rose during the round */
+    int iterations, trials;
+    int n_active_kf, n_active_points;   /* rows of the reduced system / 6; points with an edge */
+    double chi2, lambda, lambda_init;   /* active (robust) chi2 and lambda at the end, computeLambdaInit's value; 0 if no iteration ran */
+} orbx_ba_report;
+int orbx_bundle_adjustment(int device, const orbx_lba_problem *p, const orbx_ba_options *opt /* may be NULL */,
+                           float *Tcw_out /* [n_kf][16] */, float *Xw_out /* [n_points][3] */,
+                           uint8_t *point_included /* [n_points]: 0 = no edge, vbNotIncludedMP */,
+                           double *pose_out /* [n_kf][12], may be NULL */, double *point_out /* [n_points][3], may be NULL */,
+                           orbx_ba_report *report /* may be NULL */);
+
 /* ---- Optimizer::OptimizeSim3: the Sim3 between two keyframes (src/Optimizer.cc:1164-1365) ------------------------------
  * Step 4 of LoopClosing::ComputeSim3 (src/LoopClosing.cc:282-460), between SearchBySim3 and the Sim3 SearchByProjection.  Every
  * VertexSBAPointXYZ of the function is fixed: the one free vertex is a 7-DoF VertexSim3Expmap, and the whole function -- two rounds
@@ -1508,6 +1542,15 @@ int orbx_debug_match_timing(double *out4);
  * 10 k_lba_classify, 11 k_lba_finish.  Results are the same bytes with and without it.  The events belong to the thread's context and go
  * with it (orbx_thread_release, or the thread's end). */
 int orbx_debug_lba_profile(int enable, double *ms, int32_t *launches);
+/* test hooks for the dense LDL^T of the two bundle adjustments.  It exists in two forms that give the same bytes: 0, one workgroup
+ * (k_lba_solve, n <= 1536), and 1, panels of orbx_debug_ldlt_panel_width() columns over many workgroups (orbx_ldlt.hip, n <= 12288).
+ * orbx_debug_ldlt_solve uploads a dense system (S [n][n] row major, only its lower triangle is read; b [n]) and solves it with the named
+ * form: *ok = 1 and x = the solution, or *ok = 0 at a pivot that is not > 0, x as the caller left it.  orbx_debug_set_lba_solver makes the
+ * calling thread's later orbx_local_bundle_adjustment calls use the named form (default 0); orbx_bundle_adjustment always uses form 1.
+ * With orbx_debug_lba_profile on, slot 7 holds the whole solve in either form, and orbx_bundle_adjustment's two active-set kernels share slot 1. */
+int orbx_debug_ldlt_solve(int device, int n, const double *S, const double *b, double *x, int form, int *ok);
+int orbx_debug_set_lba_solver(int form);
+int orbx_debug_ldlt_panel_width(void);
 /* process-wide: the per-thread search contexts (see orbx_thread_release) that are set up right now, over all threads, families and
  * devices.  A thread's share leaves the count when it calls orbx_thread_release or ends. */
 int orbx_debug_thread_contexts(void);

@@ -19,8 +19,14 @@
 //                      k_lba_reduce       (chi2 and the scale sum)
 // Between the rounds:  k_lba_classify, k_lba_active (the level-0 edges of every keyframe compacted in point order, the rows, the active points).
 // The host reads one small status record back per linearisation and per trial and computes rho, lambda and ni in double.
+//
+// Optimizer::BundleAdjustment (src/Optimizer.cc:48-281, orbx_bundle_adjustment, model tests/gba_model.py) is the same staging, the same
+// linearisation and the same trial in ONE round over every edge: k_gba_active / k_gba_rows in place of k_lba_active (no edge ever leaves
+// level 0, the keyframes outnumber a workgroup), no k_lba_classify, and the solve in panels over many workgroups (orbx_ldlt.hip, the same
+// bytes as k_lba_solve), so n = 6 rows goes to 12 288.  orbx_debug_set_lba_solver puts the panels under the local call as well.
 #include "orbx_resident.h"
 #include "orbx_lm.h"
+#include "orbx_ldlt.h"
 #include <float.h>
 #include <algorithm>
 #include <cmath>
@@ -29,6 +35,8 @@ namespace {
 
 struct Lba {
     int K, P, E;
+    int nx;                            // the length of x: 6 x the free keyframes the entry point admits
+    double delta_mono;                 // Huber's delta of a monocular edge: the entry point's own thHuberMono / thHuber2D, a float widened
     // inputs (the uploaded blob)
     const float *Tcw, *cam, *Xw, *mx, *my, *mr, *isig;
     const uint8_t *fixed;
@@ -174,7 +182,7 @@ __global__ __launch_bounds__(256) void k_lba_init(Lba L)
         }
     }
     if (t < L.E) { L.flags[t] = 0; L.echi[t] = 0.0; }
-    if (t < 6 * 256) L.x[t] = 0.0;
+    if (t < L.nx) L.x[t] = 0.0;
 }
 
 __global__ __launch_bounds__(256) void k_lba_finish(Lba L, int cur)
@@ -252,6 +260,59 @@ __global__ __launch_bounds__(1024) void k_lba_active(Lba L)
     }
 }
 
+// The active set of orbx_bundle_adjustment, whose edges are all at level 0 for the whole call (kf_act is kf_edges itself) and whose
+// keyframes outnumber a workgroup.  k_gba_active, a thread per keyframe and per point: the edge count, whether the keyframe gets a row
+// (row = 0, else -1), whether the point is a vertex.  k_gba_rows, one workgroup, four consecutive keyframes per thread (n_kf <= 4096): the
+// rows 0, 1, .. in keyframe order, the counts.
+__global__ __launch_bounds__(256) void k_gba_active(Lba L)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t < L.K) {
+        const int m = L.kf_off[t + 1] - L.kf_off[t];
+        L.kf_cnt[t] = m;
+        L.row[t] = (!L.fixed[t] && m > 0) ? 0 : -1;
+    }
+    if (t < L.P) L.pactive[t] = (uint8_t)(L.point_off[t + 1] > L.point_off[t]);
+}
+
+__global__ __launch_bounds__(1024) void k_gba_rows(Lba L)
+{
+    __shared__ int sc[1024];
+    __shared__ int wsum[16];
+    const int t = threadIdx.x;
+    int act[4], mine = 0;
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const int k = 4 * t + q;
+        act[q] = (k < L.K && L.row[k] == 0) ? 1 : 0;
+        mine += act[q];
+    }
+    sc[t] = mine;
+    __syncthreads();
+    for (int d = 1; d < 1024; d <<= 1) {
+        const int v = t >= d ? sc[t - d] : 0;
+        __syncthreads();
+        sc[t] += v;
+        __syncthreads();
+    }
+    int r = sc[t] - mine;
+#pragma unroll
+    for (int q = 0; q < 4; q++)
+        if (act[q]) { L.row[4 * t + q] = r; L.rowkf[r] = 4 * t + q; r++; }
+    int np = 0;
+    for (int p = t; p < L.P; p += 1024) np += L.pactive[p];
+    for (int m = 32; m >= 1; m >>= 1) np += __shfl_xor(np, m, 64);
+    if ((t & 63) == 0) wsum[t >> 6] = np;
+    __syncthreads();
+    if (t == 0) {
+        int s = 0;
+        for (int w = 0; w < 16; w++) s += wsum[w];
+        L.counts[0] = sc[1023];
+        L.counts[1] = s;
+        L.status[3] = 1.0;
+    }
+}
+
 // ---------------------------------------------------------------- errors and linearisation
 
 // a thread per point, its level-0 edges one after the other in edge order.  LIN = false: computeActiveErrors (the edge's chi2, the point's
@@ -263,7 +324,7 @@ __global__ __launch_bounds__(256) void k_lba_points(Lba L, int st, int robust)
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= L.P) return;
     if (!L.pactive[p]) { L.chi_pt[p] = 0.0; return; }
-    const double delta_mono = (double)(float)sqrt(5.991), delta_stereo = (double)(float)sqrt(7.815);   // src/Optimizer.cc:650-651
+    const double delta_mono = L.delta_mono, delta_stereo = (double)(float)sqrt(7.815);   // src/Optimizer.cc:650-651, :101-102
     const double X[3] = { L.pts[st][3 * (size_t)p], L.pts[st][3 * (size_t)p + 1], L.pts[st][3 * (size_t)p + 2] };
     double H[6] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 }, b[3] = { 0.0, 0.0, 0.0 }, chi_sum = 0.0;
     for (int e = L.point_off[p]; e < L.point_off[p + 1]; e++) {
@@ -317,7 +378,7 @@ __global__ __launch_bounds__(256) void k_lba_kf(Lba L, int st, int robust)
 {
     __shared__ double red[4 * 27];
     const int r0 = blockIdx.x, k = L.rowkf[r0], tid = threadIdx.x;
-    const double delta_mono = (double)(float)sqrt(5.991), delta_stereo = (double)(float)sqrt(7.815);
+    const double delta_mono = L.delta_mono, delta_stereo = (double)(float)sqrt(7.815);
     const Pose T = pose_load(L.pose[st] + 7 * (size_t)k);
     const Cam C = cam_load(L.cam + 5 * (size_t)k);
     const int32_t *list = L.kf_act + L.kf_off[k];
@@ -630,16 +691,18 @@ extern "C" int orbx_debug_lba_profile(int enable, double *ms, int32_t *launches)
     return LBA_K_COUNT;
 }
 
-static int lba_check(const char *who, const orbx_lba_problem *p, const float *Tcw_out, const float *Xw_out, const uint8_t *edge_flags, int *n_free)
+// has_edge_out / has_point_out: the entry point's own per-edge (edge_flags) or per-point (point_included) output is there, or it has none
+static int lba_check(const char *who, const orbx_lba_problem *p, const float *Tcw_out, const float *Xw_out, bool has_edge_out,
+                     bool has_point_out, int max_kf, int max_free, int *n_free)
 {
     if (!p || !Tcw_out) { orbx_set_error("%s: NULL problem or Tcw_out", who); return ORBX_E_INVALID; }
     if (p->n_kf < 1 || p->n_points < 0 || p->n_edges < 0) { orbx_set_error("%s: n_kf = %d, n_points = %d, n_edges = %d", who, p->n_kf, p->n_points, p->n_edges); return ORBX_E_INVALID; }
-    if (p->n_kf > 1024 || p->n_points > (1 << 20) || p->n_edges > (1 << 22)) {
-        orbx_set_error("%s: n_kf = %d, n_points = %d, n_edges = %d beyond 1024, 2^20, 2^22", who, p->n_kf, p->n_points, p->n_edges);
+    if (p->n_kf > max_kf || p->n_points > (1 << 20) || p->n_edges > (1 << 22)) {
+        orbx_set_error("%s: n_kf = %d, n_points = %d, n_edges = %d beyond %d, 2^20, 2^22", who, p->n_kf, p->n_points, p->n_edges, max_kf);
         return ORBX_E_CAPACITY;
     }
-    if (!p->Tcw || !p->cam || !p->fixed || (p->n_points && (!p->Xw || !Xw_out)) ||
-        (p->n_edges && (!p->edge_kf || !p->edge_point || !p->x || !p->y || !p->u_right || !p->inv_sigma2 || !edge_flags))) {
+    if (!p->Tcw || !p->cam || !p->fixed || (p->n_points && (!p->Xw || !Xw_out || !has_point_out)) ||
+        (p->n_edges && (!p->edge_kf || !p->edge_point || !p->x || !p->y || !p->u_right || !p->inv_sigma2 || !has_edge_out))) {
         orbx_set_error("%s: a NULL array", who);
         return ORBX_E_INVALID;
     }
@@ -653,48 +716,52 @@ static int lba_check(const char *who, const orbx_lba_problem *p, const float *Tc
         if (seen[k] == q) { orbx_set_error("%s: edge %d: a second edge between point %d and keyframe %d", who, e, q, k); return ORBX_E_INVALID; }
         seen[k] = q;
     }
-    if (nf > 256) { orbx_set_error("%s: %d keyframes with fixed == 0, more than 256", who, nf); return ORBX_E_CAPACITY; }
+    if (nf > max_free) { orbx_set_error("%s: %d keyframes with fixed == 0, more than %d", who, nf, max_free); return ORBX_E_CAPACITY; }
     *n_free = nf;
     return ORBX_OK;
 }
 
-static inline unsigned lba_grid(int n) { return (unsigned)((n + 255) / 256 > 0 ? (n + 255) / 256 : 1); }
+// orbx_debug_set_lba_solver: the form of the dense solve in the calling thread's orbx_local_bundle_adjustment calls, 0 = k_lba_solve (one
+// workgroup), 1 = the panels of orbx_ldlt.hip.  Both give the same bytes.  orbx_bundle_adjustment always takes the panels.
+static thread_local int g_lba_solver = 0;
 
-extern "C" int orbx_local_bundle_adjustment(int device, const orbx_lba_problem *p, const orbx_lba_options *opt, float *Tcw_out, float *Xw_out,
-                                            uint8_t *edge_flags, double *pose_out, double *point_out, orbx_lba_report *report)
+extern "C" int orbx_debug_set_lba_solver(int form)
 {
-    const char *who = "orbx_local_bundle_adjustment";
-    int n_free = 0;
-    int rc = lba_check(who, p, Tcw_out, Xw_out, edge_flags, &n_free);
-    if (rc) return rc;
-    orbx_lba_report rep;
-    memset(&rep, 0, sizeof rep);
-    const volatile unsigned char *stop = opt ? opt->stop : nullptr;
-    const int dbg = opt ? opt->debug_stop_at_trial : -1;
-    if (stop && *stop) {   // :736-738
-        rep.stopped = 1;
-        if (report) *report = rep;
-        return ORBX_OK;
-    }
-    CallCtx *c;
-    if ((rc = orbx_call_ctx(device, &c))) return rc;
-    const size_t K = (size_t)p->n_kf, P = (size_t)p->n_points, E = (size_t)p->n_edges, F = (size_t)n_free, N = 6 * F;
+    if (form != 0 && form != 1) { orbx_set_error("orbx_debug_set_lba_solver: form = %d", form); return ORBX_E_INVALID; }
+    g_lba_solver = form;
+    return ORBX_OK;
+}
 
-    // the blob: the problem's arrays, the points' edge ranges, the keyframes' edge lists in point order
+extern "C" int orbx_debug_ldlt_panel_width(void) { return LDLT_W; }
+
+// what one call has staged: the kernels' argument block and where the download block of the work area holds what
+struct LbaStage {
+    Lba L;
+    size_t w_counts, w_pose, w_point, w_Tcw, w_Xw, w_flags, out;
+    const int32_t *point_off;   // the points' edge ranges, in the host blob
+};
+
+// the blob (the problem's arrays, the points' edge ranges, the keyframes' edge lists in point order) uploaded, the work area laid out:
+// [status | counts | pose_out point_out Tcw_out Xw_out flags] is what comes down, the state follows.  max_rows: the most rows the reduced
+// system can have, x_len: the entries of x, delta_mono: Lba::delta_mono.  own_lists: the keyframes' edge lists are compacted between rounds
+// (k_lba_active) and need an area of their own; without it kf_act is kf_edges itself, never written.
+static int lba_stage(CallCtx *c, const orbx_lba_problem *p, int max_rows, int x_len, double delta_mono, bool own_lists, LbaStage *st)
+{
+    int rc;
+    const size_t K = (size_t)p->n_kf, P = (size_t)p->n_points, E = (size_t)p->n_edges, F = (size_t)max_rows, N = 6 * F;
     BlobCursor b = { nullptr, nullptr, 0 };
     const size_t o_T = b.take(64 * K), o_cam = b.take(20 * K), o_fix = b.take(K), o_X = b.take(12 * P), o_ek = b.take(4 * E), o_ep = b.take(4 * E),
                  o_x = b.take(4 * E), o_y = b.take(4 * E), o_r = b.take(4 * E), o_w = b.take(4 * E), o_po = b.take(4 * (P + 1)), o_ko = b.take(4 * (K + 1)),
                  o_ke = b.take(4 * E);
     const size_t blob = b.o;
-    // the work area: [status | counts | pose_out point_out Tcw_out Xw_out flags] is what comes down, the state follows
     BlobCursor w = { nullptr, nullptr, 0 };
     const size_t w_status = w.take(64), w_counts = w.take(16), w_pose = w.take(96 * K), w_point = w.take(24 * P), w_Tcw = w.take(64 * K),
                  w_Xw = w.take(12 * P), w_flags = w.take(E);
     const size_t out = w.o;
     const size_t w_p0 = w.take(56 * K), w_p1 = w.take(56 * K), w_q0 = w.take(24 * P), w_q1 = w.take(24 * P), w_echi = w.take(8 * E), w_W = w.take(144 * E),
                  w_pact = w.take(P), w_Hll = w.take(48 * P), w_bl = w.take(24 * P), w_Dinv = w.take(48 * P), w_db = w.take(24 * P), w_xl = w.take(24 * P),
-                 w_chi = w.take(8 * P), w_kact = w.take(4 * E), w_kcnt = w.take(4 * K), w_row = w.take(4 * K), w_rowkf = w.take(4 * K),
-                 w_Hpp = w.take(168 * F), w_bp = w.take(48 * F), w_S = w.take(8 * N * N), w_bS = w.take(8 * N), w_xv = w.take(8 * 1536);
+                 w_chi = w.take(8 * P), w_kact = w.take(own_lists ? 4 * E : 0), w_kcnt = w.take(4 * K), w_row = w.take(4 * K), w_rowkf = w.take(4 * K),
+                 w_Hpp = w.take(168 * F), w_bp = w.take(48 * F), w_S = w.take(8 * N * N), w_bS = w.take(8 * N), w_xv = w.take(8 * (size_t)x_len);
     if ((rc = call_reserve(c, blob, w.o, out))) return rc;
     uint8_t *h = c->h_blob;
     memcpy(h + o_T, p->Tcw, 64 * K); memcpy(h + o_cam, p->cam, 20 * K); memcpy(h + o_fix, p->fixed, K);
@@ -714,9 +781,9 @@ extern "C" int orbx_local_bundle_adjustment(int device, const orbx_lba_problem *
     }
     if ((rc = call_upload(c, blob))) return rc;
 
-    Lba L;
+    Lba &L = st->L;
     memset(&L, 0, sizeof L);
-    L.K = p->n_kf; L.P = p->n_points; L.E = p->n_edges;
+    L.K = p->n_kf; L.P = p->n_points; L.E = p->n_edges; L.nx = x_len; L.delta_mono = delta_mono;
     uint8_t *d = c->d_blob, *wk = c->d_work;
     L.Tcw = (const float *)(d + o_T); L.cam = (const float *)(d + o_cam); L.fixed = d + o_fix; L.Xw = (const float *)(d + o_X);
     L.edge_kf = (const int32_t *)(d + o_ek); L.edge_point = (const int32_t *)(d + o_ep);
@@ -729,36 +796,36 @@ extern "C" int orbx_local_bundle_adjustment(int device, const orbx_lba_problem *
     L.echi = (double *)(wk + w_echi); L.W = (double *)(wk + w_W); L.pactive = wk + w_pact;
     L.Hll = (double *)(wk + w_Hll); L.bl = (double *)(wk + w_bl); L.Dinv = (double *)(wk + w_Dinv); L.db = (double *)(wk + w_db);
     L.xl = (double *)(wk + w_xl); L.chi_pt = (double *)(wk + w_chi);
-    L.kf_act = (int32_t *)(wk + w_kact); L.kf_cnt = (int32_t *)(wk + w_kcnt); L.row = (int32_t *)(wk + w_row); L.rowkf = (int32_t *)(wk + w_rowkf);
+    L.kf_act = own_lists ? (int32_t *)(wk + w_kact) : const_cast<int32_t *>(L.kf_edges); L.kf_cnt = (int32_t *)(wk + w_kcnt); L.row = (int32_t *)(wk + w_row); L.rowkf = (int32_t *)(wk + w_rowkf);
     L.Hpp = (double *)(wk + w_Hpp); L.bp = (double *)(wk + w_bp); L.S = (double *)(wk + w_S); L.bS = (double *)(wk + w_bS); L.x = (double *)(wk + w_xv);
+    st->w_counts = w_counts; st->w_pose = w_pose; st->w_point = w_point; st->w_Tcw = w_Tcw; st->w_Xw = w_Xw; st->w_flags = w_flags; st->out = out;
+    st->point_off = po;
+    return ORBX_OK;
+}
 
-    hipStream_t s = c->stream;
-    CallCtx *pc = nullptr;   // the context while orbx_debug_lba_profile is on
-    if (g_prof.on) {
-        if (!c->ev_a) ORBX_HIP(hipEventCreate(&c->ev_a));
-        if (!c->ev_b) ORBX_HIP(hipEventCreate(&c->ev_b));
-        pc = c;
-    }
-    const int most = (int)(K > P ? K : P);
-    const unsigned g_all = lba_grid(std::max(std::max(most, p->n_edges), 1536));
-    const unsigned g_vert = lba_grid(most), g_pts = lba_grid(p->n_points), g_edges = lba_grid(p->n_edges);
-    const double *hs = (const double *)c->h_out;
-    const int32_t *hc = (const int32_t *)((const uint8_t *)c->h_out + w_counts);
-    auto fetch_status = [&]() -> int { return call_fetch(c, w_counts + 16); };
-    int trials_total = 0;
-    auto stop_up = [&]() { return (stop && *stop) || (dbg >= 0 && trials_total >= dbg); };
+static inline unsigned lba_grid(int n) { return (unsigned)((n + 255) / 256 > 0 ? (n + 255) / 256 : 1); }
 
-    lba_launch(LBA_K_INIT, pc, [&] { hipLaunchKernelGGL(k_lba_init, dim3(g_all), dim3(256), 0, s, L); });
-    int cur = 0;
+// the Levenberg loop of one call: the state that outlives a round, and optimize() = SparseOptimizer::optimize(max_it) on the active set
+struct LbaRun {
+    CallCtx *c, *pc;       // pc: the context while orbx_debug_lba_profile is on, else nullptr
+    const Lba &L;
+    size_t w_counts;
+    const volatile unsigned char *stop;
+    int dbg, solver;
+    unsigned g_vert, g_pts;
+    int cur = 0, trials_total = 0;
     bool evaluated = false;
-    for (int round = 0; round < 2; round++) {
-        lba_launch(LBA_K_ACTIVE, pc, [&] { hipLaunchKernelGGL(k_lba_active, dim3(1), dim3(1024), 0, s, L); });
-        if ((rc = fetch_status())) return rc;
-        const int rows = hc[0], npts = hc[1], robust = round == 0;
-        rep.n_active_kf[round] = rows; rep.n_active_points[round] = npts;
+
+    bool stop_up() const { return (stop && *stop) || (dbg >= 0 && trials_total >= dbg); }
+    int fetch_status() { return call_fetch(c, w_counts + 16); }
+
+    int optimize(int rows, int npts, int max_it, int robust, int *iterations, int *trials, double *chi2, double *lambda_end, double *lambda_init)
+    {
+        int rc;
+        hipStream_t s = c->stream;
+        const double *hs = (const double *)c->h_out;
         double lambda = 0.0, ni = 2.0, cur_chi = 0.0;
         int n_bad = 0;
-        const int max_it = round == 0 ? 5 : 10;
         for (int it = 0; it < max_it && npts > 0 && !stop_up(); it++) {   // sparse_optimizer.cpp:356, :376
             lba_launch(LBA_K_LINEARIZE, pc, [&] { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lba_points<true>), dim3(g_pts), dim3(256), 0, s, L, cur, robust); });
             if (rows) lba_launch(LBA_K_KF, pc, [&] { hipLaunchKernelGGL(k_lba_kf, dim3(rows), dim3(256), 0, s, L, cur, robust); });
@@ -767,20 +834,26 @@ extern "C" int orbx_local_bundle_adjustment(int device, const orbx_lba_problem *
             evaluated = true;
             cur_chi = hs[0];
             const double ini_chi = cur_chi;
-            if (it == 0) { lambda = 1e-5 * hs[2]; ni = 2.0; n_bad = 0; }   // optimization_algorithm_levenberg.cpp:93-97, :166-180
+            if (it == 0) {   // optimization_algorithm_levenberg.cpp:93-97, :166-180
+                lambda = 1e-5 * hs[2]; ni = 2.0; n_bad = 0;
+                if (lambda_init) *lambda_init = lambda;
+            }
             double rho = 0.0;
             int qmax = 0;
             do {
                 lba_launch(LBA_K_PREP, pc, [&] { hipLaunchKernelGGL(k_lba_prep, dim3(g_pts), dim3(256), 0, s, L, lambda); });
                 if (rows) {
                     lba_launch(LBA_K_SCHUR, pc, [&] { hipLaunchKernelGGL(k_lba_schur, dim3(rows, rows), dim3(256), 0, s, L, lambda); });
-                    lba_launch(LBA_K_SOLVE, pc, [&] { hipLaunchKernelGGL(k_lba_solve, dim3(1), dim3(1024), 0, s, L); });
+                    lba_launch(LBA_K_SOLVE, pc, [&] {
+                        if (solver == 0) hipLaunchKernelGGL(k_lba_solve, dim3(1), dim3(1024), 0, s, L);
+                        else orbx_ldlt_panel_launch(L.S, L.bS, L.x, L.status + 3, 6 * rows, s);
+                    });
                 }
                 lba_launch(LBA_K_UPDATE, pc, [&] { hipLaunchKernelGGL(k_lba_update, dim3(g_vert), dim3(256), 0, s, L, cur); });
                 lba_launch(LBA_K_ERRORS, pc, [&] { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lba_points<false>), dim3(g_pts), dim3(256), 0, s, L, 1 - cur, robust); });
                 lba_launch(LBA_K_REDUCE, pc, [&] { hipLaunchKernelGGL(k_lba_reduce, dim3(1), dim3(1024), 0, s, L, 1, lambda); });
                 if ((rc = fetch_status())) return rc;
-                trials_total++; rep.trials[round]++;
+                trials_total++; (*trials)++;
                 const double temp_chi = hs[3] != 0.0 ? hs[0] : DBL_MAX;
                 const double scale = hs[1] + 1e-3;
                 rho = (cur_chi - temp_chi) / scale;
@@ -797,35 +870,194 @@ extern "C" int orbx_local_bundle_adjustment(int device, const orbx_lba_problem *
                 }
                 qmax++;
             } while (rho < 0.0 && qmax < 10 && !stop_up());
-            rep.iterations[round]++;
+            (*iterations)++;
             if (qmax == 10 || rho == 0.0) break;
             if ((ini_chi - cur_chi) * 1e3 < ini_chi) n_bad++; else n_bad = 0;
             if (n_bad >= 3) break;
         }
-        rep.chi2[round] = cur_chi; rep.lambda[round] = lambda;
-        if (round == 0) {
-            if (stop_up()) rep.stopped = 2;   // :745-747
-            if (!evaluated && E) {   // stopped before any evaluation: the errors at the start estimates (the reference reads uninitialised memory)
-                lba_launch(LBA_K_ERRORS, pc, [&] { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lba_points<false>), dim3(g_pts), dim3(256), 0, s, L, cur, 1); });
-                evaluated = true;
-            }
-            if (E) lba_launch(LBA_K_CLASSIFY, pc, [&] { hipLaunchKernelGGL(k_lba_classify, dim3(g_edges), dim3(256), 0, s, L, cur, 1); });
-            if (rep.stopped) break;
-        } else if (stop_up()) rep.stopped = 3;
+        *chi2 = cur_chi; *lambda_end = lambda;
+        return ORBX_OK;
     }
-    if (E) lba_launch(LBA_K_CLASSIFY, pc, [&] { hipLaunchKernelGGL(k_lba_classify, dim3(g_edges), dim3(256), 0, s, L, cur, 2); });
-    lba_launch(LBA_K_FINISH, pc, [&] { hipLaunchKernelGGL(k_lba_finish, dim3(g_vert), dim3(256), 0, s, L, cur); });
-    if ((rc = call_fetch(c, out))) return rc;
+};
+
+// the events a profiled call needs -> the context to hand to lba_launch, or nullptr
+static int lba_profile_ctx(CallCtx *c, CallCtx **pc)
+{
+    *pc = nullptr;
+    if (!g_prof.on) return ORBX_OK;
+    if (!c->ev_a) ORBX_HIP(hipEventCreate(&c->ev_a));
+    if (!c->ev_b) ORBX_HIP(hipEventCreate(&c->ev_b));
+    *pc = c;
+    return ORBX_OK;
+}
+
+extern "C" int orbx_local_bundle_adjustment(int device, const orbx_lba_problem *p, const orbx_lba_options *opt, float *Tcw_out, float *Xw_out,
+                                            uint8_t *edge_flags, double *pose_out, double *point_out, orbx_lba_report *report)
+{
+    const char *who = "orbx_local_bundle_adjustment";
+    int n_free = 0;
+    int rc = lba_check(who, p, Tcw_out, Xw_out, edge_flags != nullptr, true, 1024, 256, &n_free);
+    if (rc) return rc;
+    orbx_lba_report rep;
+    memset(&rep, 0, sizeof rep);
+    const volatile unsigned char *stop = opt ? opt->stop : nullptr;
+    if (stop && *stop) {   // :736-738
+        rep.stopped = 1;
+        if (report) *report = rep;
+        return ORBX_OK;
+    }
+    CallCtx *c, *pc;
+    if ((rc = orbx_call_ctx(device, &c))) return rc;
+    LbaStage st;
+    if ((rc = lba_stage(c, p, n_free, 1536, (double)(float)sqrt(5.991), true, &st))) return rc;   // thHuberMono, :650
+    if ((rc = lba_profile_ctx(c, &pc))) return rc;
+    const Lba &L = st.L;
+    const size_t K = (size_t)p->n_kf, P = (size_t)p->n_points, E = (size_t)p->n_edges;
+    hipStream_t s = c->stream;
+    const int most = (int)(K > P ? K : P);
+    const unsigned g_all = lba_grid(std::max(std::max(most, p->n_edges), L.nx));
+    const unsigned g_vert = lba_grid(most), g_pts = lba_grid(p->n_points), g_edges = lba_grid(p->n_edges);
+    const int32_t *hc = (const int32_t *)((const uint8_t *)c->h_out + st.w_counts);
+    LbaRun run = { c, pc, L, st.w_counts, stop, opt ? opt->debug_stop_at_trial : -1, g_lba_solver, g_vert, g_pts };
+
+    lba_launch(LBA_K_INIT, pc, [&] { hipLaunchKernelGGL(k_lba_init, dim3(g_all), dim3(256), 0, s, L); });
+    for (int round = 0; round < 2; round++) {
+        lba_launch(LBA_K_ACTIVE, pc, [&] { hipLaunchKernelGGL(k_lba_active, dim3(1), dim3(1024), 0, s, L); });
+        if ((rc = run.fetch_status())) return rc;
+        const int rows = hc[0], npts = hc[1];
+        rep.n_active_kf[round] = rows; rep.n_active_points[round] = npts;
+        if ((rc = run.optimize(rows, npts, round == 0 ? 5 : 10, round == 0, &rep.iterations[round], &rep.trials[round], &rep.chi2[round],
+                               &rep.lambda[round], nullptr)))
+            return rc;
+        if (round == 0) {
+            if (run.stop_up()) rep.stopped = 2;   // :745-747
+            if (!run.evaluated && E) {   // stopped before any evaluation: the errors at the start estimates (the reference reads uninitialised memory)
+                lba_launch(LBA_K_ERRORS, pc, [&] { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lba_points<false>), dim3(g_pts), dim3(256), 0, s, L, run.cur, 1); });
+                run.evaluated = true;
+            }
+            if (E) lba_launch(LBA_K_CLASSIFY, pc, [&] { hipLaunchKernelGGL(k_lba_classify, dim3(g_edges), dim3(256), 0, s, L, run.cur, 1); });
+            if (rep.stopped) break;
+        } else if (run.stop_up()) rep.stopped = 3;
+    }
+    if (E) lba_launch(LBA_K_CLASSIFY, pc, [&] { hipLaunchKernelGGL(k_lba_classify, dim3(g_edges), dim3(256), 0, s, L, run.cur, 2); });
+    lba_launch(LBA_K_FINISH, pc, [&] { hipLaunchKernelGGL(k_lba_finish, dim3(g_vert), dim3(256), 0, s, L, run.cur); });
+    if ((rc = call_fetch(c, st.out))) return rc;
 
     const uint8_t *ho = (const uint8_t *)c->h_out;
-    memcpy(Tcw_out, ho + w_Tcw, 64 * K);
-    if (P) memcpy(Xw_out, ho + w_Xw, 12 * P);
-    if (pose_out) memcpy(pose_out, ho + w_pose, 96 * K);
-    if (point_out && P) memcpy(point_out, ho + w_point, 24 * P);
+    memcpy(Tcw_out, ho + st.w_Tcw, 64 * K);
+    if (P) memcpy(Xw_out, ho + st.w_Xw, 12 * P);
+    if (pose_out) memcpy(pose_out, ho + st.w_pose, 96 * K);
+    if (point_out && P) memcpy(point_out, ho + st.w_point, 24 * P);
     for (size_t e = 0; e < E; e++) {
-        const uint8_t f = ho[w_flags + e];
+        const uint8_t f = ho[st.w_flags + e];
         edge_flags[e] = f; rep.n_level1 += f & 1; rep.n_erase += (f >> 1) & 1;
     }
     if (report) *report = rep;
+    return ORBX_OK;
+}
+
+// ---------------------------------------------------------------- include/orbx.h: orbx_bundle_adjustment
+// Optimizer::BundleAdjustment (reference src/Optimizer.cc:48-281) between :67 and :232: the same staging, linearisation and trial as above,
+// ONE round on every edge, the reduced system solved in panels (orbx_ldlt.hip).  k_lba_schur runs on all row pairs: a pair of keyframes
+// without a common point costs a workgroup that walks row i's edges through a binary search each and writes 36 zeros twice.
+
+extern "C" int orbx_bundle_adjustment(int device, const orbx_lba_problem *p, const orbx_ba_options *opt, float *Tcw_out, float *Xw_out,
+                                      uint8_t *point_included, double *pose_out, double *point_out, orbx_ba_report *report)
+{
+    const char *who = "orbx_bundle_adjustment";
+    int n_free = 0;
+    int rc = lba_check(who, p, Tcw_out, Xw_out, true, point_included != nullptr, 4096, 2048, &n_free);
+    if (rc) return rc;
+    const int iterations = opt ? opt->iterations : 10, robust = opt ? opt->robust != 0 : 1;
+    if (iterations < 0) { orbx_set_error("%s: iterations = %d", who, iterations); return ORBX_E_INVALID; }
+    orbx_ba_report rep;
+    memset(&rep, 0, sizeof rep);
+    const volatile unsigned char *stop = opt ? opt->stop : nullptr;
+    const bool up_on_entry = stop && *stop;   // setForceStopFlag (:64-65): optimize() then runs no iteration, the recovery still does
+    CallCtx *c, *pc;
+    if ((rc = orbx_call_ctx(device, &c))) return rc;
+    int max_rows = 0;   // the free keyframes with an edge: S is dense and sized by the keyframes that get a row
+    {
+        std::vector<uint8_t> seen((size_t)p->n_kf, 0);
+        for (int e = 0; e < p->n_edges; e++) seen[p->edge_kf[e]] = 1;
+        for (int k = 0; k < p->n_kf; k++) max_rows += seen[k] && !p->fixed[k];
+    }
+    LbaStage st;
+    // thHuber2D is sqrt(5.99) here (:101), not LocalBundleAdjustment's 5.991; every edge stays at level 0, so the edge lists are the uploaded ones
+    if ((rc = lba_stage(c, p, max_rows, std::max(6 * max_rows, 1), (double)(float)sqrt(5.99), false, &st))) return rc;
+    if ((rc = lba_profile_ctx(c, &pc))) return rc;
+    const Lba &L = st.L;
+    const size_t K = (size_t)p->n_kf, P = (size_t)p->n_points;
+    hipStream_t s = c->stream;
+    const int most = (int)(K > P ? K : P);
+    const unsigned g_all = lba_grid(std::max(std::max(most, p->n_edges), L.nx));
+    const unsigned g_vert = lba_grid(most), g_pts = lba_grid(p->n_points);
+    const int32_t *hc = (const int32_t *)((const uint8_t *)c->h_out + st.w_counts);
+    LbaRun run = { c, pc, L, st.w_counts, stop, opt ? opt->debug_stop_at_trial : -1, 1, g_vert, g_pts };
+
+    lba_launch(LBA_K_INIT, pc, [&] { hipLaunchKernelGGL(k_lba_init, dim3(g_all), dim3(256), 0, s, L); });
+    lba_launch(LBA_K_ACTIVE, pc, [&] {
+        hipLaunchKernelGGL(k_gba_active, dim3(g_vert), dim3(256), 0, s, L);
+        hipLaunchKernelGGL(k_gba_rows, dim3(1), dim3(1024), 0, s, L);
+    });
+    if ((rc = run.fetch_status())) return rc;
+    rep.n_active_kf = hc[0]; rep.n_active_points = hc[1];
+    if (up_on_entry) rep.stopped = 1;
+    else {
+        if ((rc = run.optimize(rep.n_active_kf, rep.n_active_points, iterations, robust, &rep.iterations, &rep.trials, &rep.chi2, &rep.lambda,
+                               &rep.lambda_init)))
+            return rc;
+        if (run.stop_up()) rep.stopped = 2;
+    }
+    lba_launch(LBA_K_FINISH, pc, [&] { hipLaunchKernelGGL(k_lba_finish, dim3(g_vert), dim3(256), 0, s, L, run.cur); });
+    if ((rc = call_fetch(c, st.out))) return rc;
+
+    const uint8_t *ho = (const uint8_t *)c->h_out;
+    memcpy(Tcw_out, ho + st.w_Tcw, 64 * K);
+    if (P) memcpy(Xw_out, ho + st.w_Xw, 12 * P);
+    if (pose_out) memcpy(pose_out, ho + st.w_pose, 96 * K);
+    if (point_out && P) memcpy(point_out, ho + st.w_point, 24 * P);
+    for (size_t q = 0; q < P; q++) point_included[q] = st.point_off[q + 1] > st.point_off[q];
+    if (report) *report = rep;
+    return ORBX_OK;
+}
+
+// ---------------------------------------------------------------- include/orbx.h: orbx_debug_ldlt_solve
+
+extern "C" int orbx_debug_ldlt_solve(int device, int n, const double *S, const double *b, double *x, int form, int *ok)
+{
+    const char *who = "orbx_debug_ldlt_solve";
+    if (!S || !b || !x || !ok) { orbx_set_error("%s: a NULL argument", who); return ORBX_E_INVALID; }
+    if (n < 1 || (form != 0 && form != 1)) { orbx_set_error("%s: n = %d, form = %d", who, n, form); return ORBX_E_INVALID; }
+    if (n > (form == 0 ? 1536 : 6 * 2048)) { orbx_set_error("%s: n = %d beyond %d", who, n, form == 0 ? 1536 : 6 * 2048); return ORBX_E_CAPACITY; }
+    int rc;
+    CallCtx *c;
+    if ((rc = orbx_call_ctx(device, &c))) return rc;
+    // k_lba_solve takes its size as 6 x a row count: form 0 solves diag(S, I) of the next multiple of 6.  The added rows of L are exact
+    // zeros and the added unknowns +0, so every operation on the first n rows has the operands it has without them.
+    const size_t N = (size_t)n, M = form == 0 ? (N + 5) / 6 * 6 : N;
+    BlobCursor bl = { nullptr, nullptr, 0 };
+    const size_t o_S = bl.take(8 * M * M), o_b = bl.take(8 * M), o_x = bl.take(8 * M), o_cnt = bl.take(16);
+    BlobCursor w = { nullptr, nullptr, 0 };
+    const size_t w_status = w.take(64), w_x = w.take(8 * M);
+    if ((rc = call_reserve(c, bl.o, w.o, w.o))) return rc;
+    uint8_t *h = c->h_blob;
+    double *hS = (double *)(h + o_S), *hb = (double *)(h + o_b), *hx = (double *)(h + o_x);
+    memset(hS, 0, 8 * M * M); memset(hb, 0, 8 * M); memset(hx, 0, 8 * M);
+    for (size_t i = 0; i < N; i++) memcpy(hS + i * M, S + i * N, 8 * N);
+    for (size_t i = N; i < M; i++) hS[i * M + i] = 1.0;
+    memcpy(hb, b, 8 * N); memcpy(hx, x, 8 * N);
+    ((int32_t *)(h + o_cnt))[0] = (int32_t)(M / 6);
+    if ((rc = call_upload(c, bl.o))) return rc;
+    Lba L;
+    memset(&L, 0, sizeof L);
+    L.S = (double *)(c->d_blob + o_S); L.bS = (double *)(c->d_blob + o_b); L.counts = (int32_t *)(c->d_blob + o_cnt);
+    L.status = (double *)(c->d_work + w_status); L.x = (double *)(c->d_work + w_x);
+    ORBX_HIP(hipMemcpyAsync(L.x, c->d_blob + o_x, 8 * M, hipMemcpyDeviceToDevice, c->stream));
+    if (form == 0) hipLaunchKernelGGL(k_lba_solve, dim3(1), dim3(1024), 0, c->stream, L);
+    else orbx_ldlt_panel_launch(L.S, L.bS, L.x, L.status + 3, n, c->stream);
+    if ((rc = call_fetch(c, w.o))) return rc;
+    *ok = ((const double *)c->h_out)[3] != 0.0;
+    memcpy(x, (const uint8_t *)c->h_out + w_x, 8 * N);
     return ORBX_OK;
 }

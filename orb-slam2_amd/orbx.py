@@ -144,6 +144,17 @@ class LbaReport(C.Structure):
                 ("n_active_kf", C.c_int * 2), ("n_active_points", C.c_int * 2), ("chi2", C.c_double * 2), ("lambda_", C.c_double * 2)]
 
 
+class BaOptions(C.Structure):
+    """orbx_ba_options (include/orbx.h)"""
+    _fields_ = [("stop", C.c_void_p), ("debug_stop_at_trial", C.c_int), ("iterations", C.c_int), ("robust", C.c_int)]
+
+
+class BaReport(C.Structure):
+    """orbx_ba_report (include/orbx.h)"""
+    _fields_ = [("stopped", C.c_int), ("iterations", C.c_int), ("trials", C.c_int), ("n_active_kf", C.c_int), ("n_active_points", C.c_int),
+                ("chi2", C.c_double), ("lambda_", C.c_double), ("lambda_init", C.c_double)]
+
+
 class PoseJob(C.Structure):
     """orbx_pose_job (include/orbx.h)"""
     _fields_ = [("obs", C.POINTER(PoseObs)), ("cam", C.c_void_p), ("Tcw", C.c_void_p), ("Tcw_out", C.c_void_p),
@@ -324,6 +335,10 @@ def lib():
     L.orbx_frame_pose_optimize.argtypes = [vp, vp, vp, vp, i, vp, vp, vp, vp, ip, C.POINTER(PoseReport)]
     L.orbx_local_bundle_adjustment.argtypes = [i, C.POINTER(LbaProblem), C.POINTER(LbaOptions), vp, vp, vp, vp, vp, C.POINTER(LbaReport)]
     L.orbx_debug_lba_profile.argtypes = [i, vp, vp]
+    L.orbx_bundle_adjustment.argtypes = [i, C.POINTER(LbaProblem), C.POINTER(BaOptions), vp, vp, vp, vp, vp, C.POINTER(BaReport)]
+    L.orbx_debug_ldlt_solve.argtypes = [i, i, vp, vp, vp, i, C.POINTER(C.c_int)]
+    L.orbx_debug_set_lba_solver.argtypes = [i]
+    L.orbx_debug_ldlt_panel_width.argtypes = []
     L.orbx_triangulate_pairs.argtypes = [i, C.POINTER(TriFeats), C.POINTER(TriView), C.POINTER(C.POINTER(TriFeats)), C.POINTER(TriView), i, vp, i, vp,
                                          vp, vp, i, f, vp, vp, ip]
     L.orbx_frame_set_depth.argtypes = [vp, vp, vp, vp]
@@ -1103,6 +1118,45 @@ def local_bundle_adjustment(problem, stop_at_trial=-1, stop=None, device=0):
     return {"Tcw": Tcw, "Xw": Xw, "edge_flags": fl, "pose": pose, "point": point, "stopped": rep.stopped, "iterations": list(rep.iterations),
             "trials": list(rep.trials), "n_level1": rep.n_level1, "n_erase": rep.n_erase, "n_active_kf": list(rep.n_active_kf),
             "n_active_points": list(rep.n_active_points), "chi2": list(rep.chi2), "lambda": list(rep.lambda_)}
+
+
+def bundle_adjustment(problem, iterations=10, robust=True, stop=None, stop_at_trial=-1, device=0):
+    """Optimizer::BundleAdjustment (orbx_bundle_adjustment): problem as for local_bundle_adjustment; iterations: 20 at map creation, 10
+    after a loop; stop: a uint8 array of one element polled as pbStopFlag; stop_at_trial: the debug_stop_at_trial hook -> dict(Tcw
+    [K][4][4], Xw [P][3], point_included [P], pose [K][3][4], point [P][3], stopped, iterations, trials, n_active_kf, n_active_points, chi2,
+    lambda, lambda_init)"""
+    pr, keep = _lba_problem(problem, "bundle_adjustment")
+    opt = BaOptions(stop.ctypes.data if stop is not None else None, int(stop_at_trial), int(iterations), int(bool(robust)))
+    Tcw = np.zeros((pr.n_kf, 4, 4), np.float32); Xw = np.zeros((pr.n_points, 3), np.float32); inc = np.zeros(pr.n_points, np.uint8)
+    pose = np.zeros((pr.n_kf, 3, 4), np.float64); point = np.zeros((pr.n_points, 3), np.float64); rep = BaReport()
+    _check(lib().orbx_bundle_adjustment(device, C.byref(pr), C.byref(opt), _p(Tcw), _p(Xw), _p(inc), _p(pose), _p(point), C.byref(rep)))
+    return {"Tcw": Tcw, "Xw": Xw, "point_included": inc, "pose": pose, "point": point, "stopped": rep.stopped, "iterations": rep.iterations,
+            "trials": rep.trials, "n_active_kf": rep.n_active_kf, "n_active_points": rep.n_active_points, "chi2": rep.chi2,
+            "lambda": rep.lambda_, "lambda_init": rep.lambda_init}
+
+
+def ldlt_solve(S, b, form, x0=None, device=0):
+    """orbx_debug_ldlt_solve: the dense LDL^T of the bundle adjustments on S x = b (S [n][n], its lower triangle read), form 0 = one
+    workgroup (n <= 1536), 1 = panels -> (x [n], ok); after a pivot that is not > 0, ok is False and x is x0 (zeros) untouched"""
+    S = np.ascontiguousarray(S, np.float64); b = np.ascontiguousarray(b, np.float64).reshape(-1)
+    n = len(b)
+    if S.shape != (n, n):
+        raise OrbxError(-1, "ldlt_solve: S must be [n][n] for b [n]")
+    x = np.zeros(n) if x0 is None else np.array(x0, np.float64).reshape(n)
+    ok = C.c_int(-1)
+    _check(lib().orbx_debug_ldlt_solve(device, n, _p(S), _p(b), _p(x), int(form), C.byref(ok)))
+    return x, bool(ok.value)
+
+
+def ldlt_panel_width():
+    """the panel width of form 1 of the dense LDL^T (orbx_debug_ldlt_panel_width)"""
+    return lib().orbx_debug_ldlt_panel_width()
+
+
+def set_lba_solver(form):
+    """orbx_debug_set_lba_solver: the calling thread's later local_bundle_adjustment calls solve with form 0 (one workgroup, the default)
+    or 1 (panels)"""
+    _check(lib().orbx_debug_set_lba_solver(int(form)))
 
 
 def pose_optimize_batch(jobs, device=0):

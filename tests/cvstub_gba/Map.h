@@ -1,0 +1,20 @@
+// overlay of tests/cvstub_lba/Map.h (same include guard): the members Optimizer::GlobalBundleAdjustemnt uses (include/Map.h:51-52:
+// GetAllKeyFrames, GetAllMapPoints, which copy the map's sets into vectors) beside mMutexMapUpdate
+#ifndef CVSTUB_MAP_H
+#define CVSTUB_MAP_H
+#include <mutex>
+#include <vector>
+namespace ORB_SLAM2 {
+class KeyFrame;
+class MapPoint;
+class Map
+{
+public:
+    std::vector<KeyFrame *> GetAllKeyFrames() { return mspKeyFrames; }
+    std::vector<MapPoint *> GetAllMapPoints() { return mspMapPoints; }
+    std::mutex mMutexMapUpdate;
+    std::vector<KeyFrame *> mspKeyFrames;      // std::set, protected, in the reference: the stand-in keeps the order it is given
+    std::vector<MapPoint *> mspMapPoints;
+};
+}
+#endif
