@@ -15,6 +15,7 @@
 // No atomics, no scratch.  The arithmetic is restated in include/orbx.h (orbx_mono_init_hypotheses) and, in numpy, in tests/init_model.py.
 // Behind the kernels: the refusals, Normalize and the acos thresholds (the host half), the staging and the three entry points.
 #include "orbx_resident.h"
+#include "orbx_wave.h"
 #include <float.h>
 #include <math.h>
 
@@ -60,18 +61,6 @@ struct MonoLds {
     float pad;
     double w2[9];
 };
-
-__device__ __forceinline__ void wsync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ double dotd(float a0, float a1, float a2, float b0, float b1, float b2)
-{
-    return ((double)a0 * (double)b0 + (double)a1 * (double)b1) + (double)a2 * (double)b2;
-}
 
 // the correctly rounded float square root (through double: the second rounding is innocuous for a square root)
 __device__ __forceinline__ float fsqrt(float x) { return (float)sqrt((double)x); }

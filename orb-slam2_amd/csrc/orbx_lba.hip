@@ -56,12 +56,8 @@ struct Lba {
     float *Tcw_out, *Xw_out;
 };
 
-struct Cam { double fx, fy, cx, cy, bf; };
-struct Obs { double mx, my, mr, w; bool stereo; };
-
 __device__ __forceinline__ Pose pose_load(const double *p) { return Pose{ p[0], p[1], p[2], p[3], p[4], p[5], p[6] }; }
 __device__ __forceinline__ void pose_store(double *p, const Pose &P) { p[0] = P.qx; p[1] = P.qy; p[2] = P.qz; p[3] = P.qw; p[4] = P.tx; p[5] = P.ty; p[6] = P.tz; }
-__device__ __forceinline__ Cam cam_load(const float *c) { return Cam{ (double)c[0], (double)c[1], (double)c[2], (double)c[3], (double)c[4] }; }
 
 __device__ __forceinline__ Obs obs_load(const Lba &L, int e)
 {
@@ -70,28 +66,6 @@ __device__ __forceinline__ Obs obs_load(const Lba &L, int e)
     o.mx = (double)L.mx[e]; o.my = (double)L.my[e]; o.mr = (double)ur; o.w = (double)L.isig[e];
     o.stereo = !(ur < 0.f);   // src/Optimizer.cc:675
     return o;
-}
-
-// SE3Quat::map: Eigen's Quaternion * vector, then + t
-__device__ __forceinline__ void se3_map(const Pose &P, const double X[3], double &x, double &y, double &z)
-{
-    const double ux = 2.0 * (P.qy * X[2] - P.qz * X[1]), uy = 2.0 * (P.qz * X[0] - P.qx * X[2]), uz = 2.0 * (P.qx * X[1] - P.qy * X[0]);
-    x = ((X[0] + P.qw * ux) + (P.qy * uz - P.qz * uy)) + P.tx;
-    y = ((X[1] + P.qw * uy) + (P.qz * ux - P.qx * uz)) + P.ty;
-    z = ((X[2] + P.qw * uz) + (P.qx * uy - P.qy * ux)) + P.tz;
-}
-
-// computeError of EdgeSE3ProjectXYZ / EdgeStereoSE3ProjectXYZ (types_six_dof_expmap.h, cam_project :141-157); returns chi2 = e . (Omega e)
-__device__ __forceinline__ double edge_error(const Obs &o, const Cam &C, double x, double y, double z, double err[3])
-{
-    if (o.stereo) {
-        const double invz = (double)(float)(1.0 / z);   // :151 `const float invz = 1.0f/trans_xyz[2]`
-        const double u = (x * invz) * C.fx + C.cx, v = (y * invz) * C.fy + C.cy;
-        err[0] = o.mx - u; err[1] = o.my - v; err[2] = o.mr - (u - C.bf * invz);
-        return (err[0] * (o.w * err[0]) + err[1] * (o.w * err[1])) + err[2] * (o.w * err[2]);
-    }
-    err[0] = o.mx - ((x / z) * C.fx + C.cx); err[1] = o.my - ((y / z) * C.fy + C.cy); err[2] = 0.0;
-    return err[0] * (o.w * err[0]) + err[1] * (o.w * err[1]);
 }
 
 // _jacobianOplusXj, the 2/3 x 6 pose block (types_six_dof_expmap.cpp:126-138, :214-233); the third row only for a stereo edge
@@ -132,28 +106,6 @@ __device__ __forceinline__ void jac_point(const Cam &C, bool stereo, const doubl
         A[1][c] = (t10 * R[c] + t11 * R[3 + c]) + t12 * R[6 + c];
         A[2][c] = 0.0;
     }
-}
-
-// a[k] summed over a workgroup of 1024 threads, for every thread: the xor butterfly across each wave, then a balanced tree over the 16 waves
-template <int K>
-__device__ __forceinline__ void block_sum16(double (&a)[K], double *red)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < K; k++) a[k] = wave_sum(a[k]);
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < K; k++) red[wave * K + k] = a[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; k++) {
-        double q[4];
-#pragma unroll
-        for (int g = 0; g < 4; g++) q[g] = (red[(4 * g) * K + k] + red[(4 * g + 1) * K + k]) + (red[(4 * g + 2) * K + k] + red[(4 * g + 3) * K + k]);
-        a[k] = (q[0] + q[1]) + (q[2] + q[3]);
-    }
-    __syncthreads();
 }
 
 // ---------------------------------------------------------------- start and finish
@@ -248,7 +200,7 @@ __global__ __launch_bounds__(1024) void k_lba_active(Lba L)
         L.pactive[p] = (uint8_t)a;
         np += a;
     }
-    for (int m = 32; m >= 1; m >>= 1) np += __shfl_xor(np, m, 64);
+    np = wave_sum(np);
     if ((t & 63) == 0) wsum[t >> 6] = np;
     __syncthreads();
     if (t == 0) {
@@ -301,7 +253,7 @@ __global__ __launch_bounds__(1024) void k_gba_rows(Lba L)
         if (act[q]) { L.row[4 * t + q] = r; L.rowkf[r] = 4 * t + q; r++; }
     int np = 0;
     for (int p = t; p < L.P; p += 1024) np += L.pactive[p];
-    for (int m = 32; m >= 1; m >>= 1) np += __shfl_xor(np, m, 64);
+    np = wave_sum(np);
     if ((t & 63) == 0) wsum[t >> 6] = np;
     __syncthreads();
     if (t == 0) {
@@ -334,7 +286,7 @@ __global__ __launch_bounds__(256) void k_lba_points(Lba L, int st, int robust)
         const Cam C = cam_load(L.cam + 5 * (size_t)k);
         const Obs o = obs_load(L, e);
         double x, y, z, err[3];
-        se3_map(T, X, x, y, z);
+        se3_map(T, X[0], X[1], X[2], x, y, z);
         const double chi = edge_error(o, C, x, y, z, err);
         L.echi[e] = chi;
         double rho0 = chi, rho1 = 1.0;
@@ -391,7 +343,7 @@ __global__ __launch_bounds__(256) void k_lba_kf(Lba L, int st, int robust)
         const double X[3] = { L.pts[st][3 * (size_t)p], L.pts[st][3 * (size_t)p + 1], L.pts[st][3 * (size_t)p + 2] };
         const Obs o = obs_load(L, e);
         double x, y, z, err[3], B[3][6];
-        se3_map(T, X, x, y, z);
+        se3_map(T, X[0], X[1], X[2], x, y, z);
         const double chi = edge_error(o, C, x, y, z, err);
         double rho0 = chi, rho1 = 1.0;
         if (robust) huber(chi, o.stereo ? delta_stereo : delta_mono, rho0, rho1);
@@ -445,8 +397,8 @@ __global__ __launch_bounds__(1024) void k_lba_reduce(Lba L, int what, double lam
             md = fmax(fabs(L.Hll[6 * (size_t)p]), md); md = fmax(fabs(L.Hll[6 * (size_t)p + 3]), md); md = fmax(fabs(L.Hll[6 * (size_t)p + 5]), md);
         }
     }
-    block_sum16(a, red);
-    for (int m = 32; m >= 1; m >>= 1) md = fmax(md, __shfl_xor(md, m, 64));
+    block_sum<16>(a, red);
+    md = wave_max(md);
     if ((t & 63) == 0) mx[t >> 6] = md;
     __syncthreads();
     if (t == 0) {
@@ -647,7 +599,7 @@ __global__ __launch_bounds__(256) void k_lba_classify(Lba L, int cur, int bit)
     const Pose T = pose_load(L.pose[cur] + 7 * (size_t)k);
     const double X[3] = { L.pts[cur][3 * (size_t)p], L.pts[cur][3 * (size_t)p + 1], L.pts[cur][3 * (size_t)p + 2] };
     double x, y, z;
-    se3_map(T, X, x, y, z);
+    se3_map(T, X[0], X[1], X[2], x, y, z);
     const bool stereo = !(L.mr[e] < 0.f);
     const bool bad = L.echi[e] > (stereo ? 7.815 : 5.991) || !(z > 0.0);
     if (bad) L.flags[e] = (uint8_t)(L.flags[e] | bit);
@@ -812,12 +764,21 @@ struct LbaRun {
     size_t w_counts;
     const volatile unsigned char *stop;
     int dbg, solver;
-    unsigned g_vert, g_pts;
     int cur = 0, trials_total = 0;
     bool evaluated = false;
 
+    // a thread per keyframe and point, per point, per edge, per anything k_lba_init clears
+    unsigned g_vert() const { return lba_grid(std::max(L.K, L.P)); }
+    unsigned g_pts() const { return lba_grid(L.P); }
+    unsigned g_edges() const { return lba_grid(L.E); }
+    unsigned g_all() const { return lba_grid(std::max(std::max(L.K, L.P), std::max(L.E, L.nx))); }
+
     bool stop_up() const { return (stop && *stop) || (dbg >= 0 && trials_total >= dbg); }
     int fetch_status() { return call_fetch(c, w_counts + 16); }
+    const int32_t *counts() const { return (const int32_t *)((const uint8_t *)c->h_out + w_counts); }   // rows, active points, behind fetch_status
+
+    void init() { lba_launch(LBA_K_INIT, pc, [&] { hipLaunchKernelGGL(k_lba_init, dim3(g_all()), dim3(256), 0, c->stream, L); }); }
+    void finish() { lba_launch(LBA_K_FINISH, pc, [&] { hipLaunchKernelGGL(k_lba_finish, dim3(g_vert()), dim3(256), 0, c->stream, L, cur); }); }
 
     int optimize(int rows, int npts, int max_it, int robust, int *iterations, int *trials, double *chi2, double *lambda_end, double *lambda_init)
     {
@@ -825,23 +786,23 @@ struct LbaRun {
         hipStream_t s = c->stream;
         const double *hs = (const double *)c->h_out;
         double lambda = 0.0, ni = 2.0, cur_chi = 0.0;
-        int n_bad = 0;
+        int stop_bad = 0;
         for (int it = 0; it < max_it && npts > 0 && !stop_up(); it++) {   // sparse_optimizer.cpp:356, :376
-            lba_launch(LBA_K_LINEARIZE, pc, [&] { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lba_points<true>), dim3(g_pts), dim3(256), 0, s, L, cur, robust); });
+            lba_launch(LBA_K_LINEARIZE, pc, [&] { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lba_points<true>), dim3(g_pts()), dim3(256), 0, s, L, cur, robust); });
             if (rows) lba_launch(LBA_K_KF, pc, [&] { hipLaunchKernelGGL(k_lba_kf, dim3(rows), dim3(256), 0, s, L, cur, robust); });
             lba_launch(LBA_K_REDUCE, pc, [&] { hipLaunchKernelGGL(k_lba_reduce, dim3(1), dim3(1024), 0, s, L, 0, 0.0); });
             if ((rc = fetch_status())) return rc;
             evaluated = true;
             cur_chi = hs[0];
             const double ini_chi = cur_chi;
-            if (it == 0) {   // optimization_algorithm_levenberg.cpp:93-97, :166-180
-                lambda = 1e-5 * hs[2]; ni = 2.0; n_bad = 0;
+            if (it == 0) {
+                lm_start(hs[2], lambda, ni, stop_bad);
                 if (lambda_init) *lambda_init = lambda;
             }
             double rho = 0.0;
             int qmax = 0;
             do {
-                lba_launch(LBA_K_PREP, pc, [&] { hipLaunchKernelGGL(k_lba_prep, dim3(g_pts), dim3(256), 0, s, L, lambda); });
+                lba_launch(LBA_K_PREP, pc, [&] { hipLaunchKernelGGL(k_lba_prep, dim3(g_pts()), dim3(256), 0, s, L, lambda); });
                 if (rows) {
                     lba_launch(LBA_K_SCHUR, pc, [&] { hipLaunchKernelGGL(k_lba_schur, dim3(rows, rows), dim3(256), 0, s, L, lambda); });
                     lba_launch(LBA_K_SOLVE, pc, [&] {
@@ -849,31 +810,22 @@ struct LbaRun {
                         else orbx_ldlt_panel_launch(L.S, L.bS, L.x, L.status + 3, 6 * rows, s);
                     });
                 }
-                lba_launch(LBA_K_UPDATE, pc, [&] { hipLaunchKernelGGL(k_lba_update, dim3(g_vert), dim3(256), 0, s, L, cur); });
-                lba_launch(LBA_K_ERRORS, pc, [&] { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lba_points<false>), dim3(g_pts), dim3(256), 0, s, L, 1 - cur, robust); });
+                lba_launch(LBA_K_UPDATE, pc, [&] { hipLaunchKernelGGL(k_lba_update, dim3(g_vert()), dim3(256), 0, s, L, cur); });
+                lba_launch(LBA_K_ERRORS, pc, [&] { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lba_points<false>), dim3(g_pts()), dim3(256), 0, s, L, 1 - cur, robust); });
                 lba_launch(LBA_K_REDUCE, pc, [&] { hipLaunchKernelGGL(k_lba_reduce, dim3(1), dim3(1024), 0, s, L, 1, lambda); });
                 if ((rc = fetch_status())) return rc;
                 trials_total++; (*trials)++;
                 const double temp_chi = hs[3] != 0.0 ? hs[0] : DBL_MAX;
-                const double scale = hs[1] + 1e-3;
-                rho = (cur_chi - temp_chi) / scale;
-                if (rho > 0.0 && std::isfinite(temp_chi)) {
-                    const double t = 2.0 * rho - 1.0;
-                    double alpha = 1.0 - (t * t) * t;
-                    alpha = alpha < 2.0 / 3.0 ? alpha : 2.0 / 3.0;
-                    lambda *= (1.0 / 3.0 > alpha ? 1.0 / 3.0 : alpha);
-                    ni = 2.0;
+                rho = lm_gain(cur_chi, temp_chi, hs[1]);
+                if (lm_accepts(rho, temp_chi)) {
+                    lm_accept(rho, lambda, ni);
                     cur_chi = temp_chi;
                     cur = 1 - cur;   // discardTop(): the trial copy is the estimate
-                } else {
-                    lambda *= ni; ni *= 2.0;   // pop(): the estimates go back, the edges keep the errors of the rejected state
-                }
+                } else lm_reject(lambda, ni);   // pop(): the estimates go back, the edges keep the errors of the rejected state
                 qmax++;
             } while (rho < 0.0 && qmax < 10 && !stop_up());
             (*iterations)++;
-            if (qmax == 10 || rho == 0.0) break;
-            if ((ini_chi - cur_chi) * 1e3 < ini_chi) n_bad++; else n_bad = 0;
-            if (n_bad >= 3) break;
+            if (lm_done(qmax, rho, ini_chi, cur_chi, stop_bad)) break;
         }
         *chi2 = cur_chi; *lambda_end = lambda;
         return ORBX_OK;
@@ -888,6 +840,20 @@ static int lba_profile_ctx(CallCtx *c, CallCtx **pc)
     if (!c->ev_a) ORBX_HIP(hipEventCreate(&c->ev_a));
     if (!c->ev_b) ORBX_HIP(hipEventCreate(&c->ev_b));
     *pc = c;
+    return ORBX_OK;
+}
+
+// the download block fetched, and what both entry points hand back from it
+static int lba_deliver(CallCtx *c, const LbaStage &st, float *Tcw_out, float *Xw_out, double *pose_out, double *point_out)
+{
+    const int rc = call_fetch(c, st.out);
+    if (rc) return rc;
+    const size_t K = (size_t)st.L.K, P = (size_t)st.L.P;
+    const uint8_t *ho = (const uint8_t *)c->h_out;
+    memcpy(Tcw_out, ho + st.w_Tcw, 64 * K);
+    if (P) memcpy(Xw_out, ho + st.w_Xw, 12 * P);
+    if (pose_out) memcpy(pose_out, ho + st.w_pose, 96 * K);
+    if (point_out && P) memcpy(point_out, ho + st.w_point, 24 * P);
     return ORBX_OK;
 }
 
@@ -912,19 +878,16 @@ extern "C" int orbx_local_bundle_adjustment(int device, const orbx_lba_problem *
     if ((rc = lba_stage(c, p, n_free, 1536, (double)(float)sqrt(5.991), true, &st))) return rc;   // thHuberMono, :650
     if ((rc = lba_profile_ctx(c, &pc))) return rc;
     const Lba &L = st.L;
-    const size_t K = (size_t)p->n_kf, P = (size_t)p->n_points, E = (size_t)p->n_edges;
+    const size_t E = (size_t)p->n_edges;
     hipStream_t s = c->stream;
-    const int most = (int)(K > P ? K : P);
-    const unsigned g_all = lba_grid(std::max(std::max(most, p->n_edges), L.nx));
-    const unsigned g_vert = lba_grid(most), g_pts = lba_grid(p->n_points), g_edges = lba_grid(p->n_edges);
-    const int32_t *hc = (const int32_t *)((const uint8_t *)c->h_out + st.w_counts);
-    LbaRun run = { c, pc, L, st.w_counts, stop, opt ? opt->debug_stop_at_trial : -1, g_lba_solver, g_vert, g_pts };
+    LbaRun run = { c, pc, L, st.w_counts, stop, opt ? opt->debug_stop_at_trial : -1, g_lba_solver };
+    const unsigned g_pts = run.g_pts(), g_edges = run.g_edges();
 
-    lba_launch(LBA_K_INIT, pc, [&] { hipLaunchKernelGGL(k_lba_init, dim3(g_all), dim3(256), 0, s, L); });
+    run.init();
     for (int round = 0; round < 2; round++) {
         lba_launch(LBA_K_ACTIVE, pc, [&] { hipLaunchKernelGGL(k_lba_active, dim3(1), dim3(1024), 0, s, L); });
         if ((rc = run.fetch_status())) return rc;
-        const int rows = hc[0], npts = hc[1];
+        const int rows = run.counts()[0], npts = run.counts()[1];
         rep.n_active_kf[round] = rows; rep.n_active_points[round] = npts;
         if ((rc = run.optimize(rows, npts, round == 0 ? 5 : 10, round == 0, &rep.iterations[round], &rep.trials[round], &rep.chi2[round],
                                &rep.lambda[round], nullptr)))
@@ -940,16 +903,11 @@ extern "C" int orbx_local_bundle_adjustment(int device, const orbx_lba_problem *
         } else if (run.stop_up()) rep.stopped = 3;
     }
     if (E) lba_launch(LBA_K_CLASSIFY, pc, [&] { hipLaunchKernelGGL(k_lba_classify, dim3(g_edges), dim3(256), 0, s, L, run.cur, 2); });
-    lba_launch(LBA_K_FINISH, pc, [&] { hipLaunchKernelGGL(k_lba_finish, dim3(g_vert), dim3(256), 0, s, L, run.cur); });
-    if ((rc = call_fetch(c, st.out))) return rc;
-
-    const uint8_t *ho = (const uint8_t *)c->h_out;
-    memcpy(Tcw_out, ho + st.w_Tcw, 64 * K);
-    if (P) memcpy(Xw_out, ho + st.w_Xw, 12 * P);
-    if (pose_out) memcpy(pose_out, ho + st.w_pose, 96 * K);
-    if (point_out && P) memcpy(point_out, ho + st.w_point, 24 * P);
+    run.finish();
+    if ((rc = lba_deliver(c, st, Tcw_out, Xw_out, pose_out, point_out))) return rc;
+    const uint8_t *flags = (const uint8_t *)c->h_out + st.w_flags;
     for (size_t e = 0; e < E; e++) {
-        const uint8_t f = ho[st.w_flags + e];
+        const uint8_t f = flags[e];
         edge_flags[e] = f; rep.n_level1 += f & 1; rep.n_erase += (f >> 1) & 1;
     }
     if (report) *report = rep;
@@ -987,21 +945,16 @@ extern "C" int orbx_bundle_adjustment(int device, const orbx_lba_problem *p, con
     if ((rc = lba_stage(c, p, max_rows, std::max(6 * max_rows, 1), (double)(float)sqrt(5.99), false, &st))) return rc;
     if ((rc = lba_profile_ctx(c, &pc))) return rc;
     const Lba &L = st.L;
-    const size_t K = (size_t)p->n_kf, P = (size_t)p->n_points;
     hipStream_t s = c->stream;
-    const int most = (int)(K > P ? K : P);
-    const unsigned g_all = lba_grid(std::max(std::max(most, p->n_edges), L.nx));
-    const unsigned g_vert = lba_grid(most), g_pts = lba_grid(p->n_points);
-    const int32_t *hc = (const int32_t *)((const uint8_t *)c->h_out + st.w_counts);
-    LbaRun run = { c, pc, L, st.w_counts, stop, opt ? opt->debug_stop_at_trial : -1, 1, g_vert, g_pts };
+    LbaRun run = { c, pc, L, st.w_counts, stop, opt ? opt->debug_stop_at_trial : -1, 1 };
 
-    lba_launch(LBA_K_INIT, pc, [&] { hipLaunchKernelGGL(k_lba_init, dim3(g_all), dim3(256), 0, s, L); });
+    run.init();
     lba_launch(LBA_K_ACTIVE, pc, [&] {
-        hipLaunchKernelGGL(k_gba_active, dim3(g_vert), dim3(256), 0, s, L);
+        hipLaunchKernelGGL(k_gba_active, dim3(run.g_vert()), dim3(256), 0, s, L);
         hipLaunchKernelGGL(k_gba_rows, dim3(1), dim3(1024), 0, s, L);
     });
     if ((rc = run.fetch_status())) return rc;
-    rep.n_active_kf = hc[0]; rep.n_active_points = hc[1];
+    rep.n_active_kf = run.counts()[0]; rep.n_active_points = run.counts()[1];
     if (up_on_entry) rep.stopped = 1;
     else {
         if ((rc = run.optimize(rep.n_active_kf, rep.n_active_points, iterations, robust, &rep.iterations, &rep.trials, &rep.chi2, &rep.lambda,
@@ -1009,15 +962,9 @@ extern "C" int orbx_bundle_adjustment(int device, const orbx_lba_problem *p, con
             return rc;
         if (run.stop_up()) rep.stopped = 2;
     }
-    lba_launch(LBA_K_FINISH, pc, [&] { hipLaunchKernelGGL(k_lba_finish, dim3(g_vert), dim3(256), 0, s, L, run.cur); });
-    if ((rc = call_fetch(c, st.out))) return rc;
-
-    const uint8_t *ho = (const uint8_t *)c->h_out;
-    memcpy(Tcw_out, ho + st.w_Tcw, 64 * K);
-    if (P) memcpy(Xw_out, ho + st.w_Xw, 12 * P);
-    if (pose_out) memcpy(pose_out, ho + st.w_pose, 96 * K);
-    if (point_out && P) memcpy(point_out, ho + st.w_point, 24 * P);
-    for (size_t q = 0; q < P; q++) point_included[q] = st.point_off[q + 1] > st.point_off[q];
+    run.finish();
+    if ((rc = lba_deliver(c, st, Tcw_out, Xw_out, pose_out, point_out))) return rc;
+    for (size_t q = 0; q < (size_t)p->n_points; q++) point_included[q] = st.point_off[q + 1] > st.point_off[q];
     if (report) *report = rep;
     return ORBX_OK;
 }

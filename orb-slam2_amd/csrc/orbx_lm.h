@@ -1,8 +1,22 @@
-// orbx_lm.h — what the Levenberg kernels share (k_pose_opt of orbx_pose.hip, k_sim3_opt of orbx_sim3opt.hip, the k_lba_* of orbx_lba.hip): the
-// fixed-order workgroup sum that hands every thread of a 256-thread workgroup the same bits, g2o's Huber kernel and Eigen's
-// Quaternion(Matrix3), and g2o's SE3Quat with its exponential update (k_pose_opt, k_lba_*).  Device code only; every function is inlined into its kernel.
+// orbx_lm.h — g2o's small pieces, one copy each, for the Levenberg kernels (k_pose_opt of orbx_pose.hip, k_sim3_opt of orbx_sim3opt.hip,
+// the k_lba_* of orbx_lba.hip) and for the host loop of the bundle adjustments (LbaRun::optimize):
+//   sums      block_sum: the fixed-order workgroup sum that hands every thread of a 4- or 16-wave workgroup the same bits
+//   solver    ldlt_small<N>: the dense (H + lambda I) x = b of the one-vertex problems; hu_max_diag<N>
+//   damping   lm_*: the rule of optimization_algorithm_levenberg.cpp (rho, lambda, ni, the two stops), host and device
+//   robust    huber
+//   geometry  Eigen's Quaternion(Matrix3), quaternion * vector and quaternion product; g2o's SE3Quat (Pose) with map and the exponential
+//             update; Cam, Obs and computeError of the mono / stereo reprojection edges
+// Two things are NOT here.  The pose Jacobians: k_pose_opt's (EdgeSE3ProjectXYZOnlyPose, products with invz) and jac_pose of orbx_lba.hip
+// (EdgeSE3ProjectXYZ, divisions) are different reference expressions with different bits.  And the Omega, Omega^2, R = (I + a Omega) + b
+// Omega^2 of the exponentials: pose_update below and sim3_exp of orbx_sim3opt.hip each keep their own.  Each fuses R with its own
+// theta < 1e-5 branch (pose_update fills V there, sim3_exp selects per entry next to its A, B, C), and a helper for Omega and Omega^2
+// alone lets the compiler take -(o o) from the o o of theta: the same bits, one multiplication fewer, and so not the instructions these
+// kernels were measured with.
+// Everything but lm_* is device code; every function is inlined into its kernel.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cmath>
+#include "orbx_wave.h"
 
 // robust_kernel_impl.cpp:78-91 (rho[2] is never used: base_edge.h:96-102)
 static __device__ __forceinline__ void huber(double e, double delta, double &rho0, double &rho1)
@@ -14,17 +28,12 @@ static __device__ __forceinline__ void huber(double e, double delta, double &rho
     rho1 = delta / sqrte;
 }
 
-static __device__ __forceinline__ double wave_sum(double v)
-{
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
-// a[k] summed over the workgroup's 256 threads, for every thread: the xor butterfly across the wave (both partners add the same two
-// numbers, so all 64 lanes hold the same bits), then ((w0 + w1) + (w2 + w3)) over the four waves through red[4 * K]
-template <int K>
+// a[k] summed over the workgroup's WAVES x 64 threads, for every thread: the xor butterfly across the wave (all 64 lanes hold the same
+// bits), then through red[WAVES * K] ((w0 + w1) + (w2 + w3)) over each four waves and, of 16 waves, the same tree over the four fours
+template <int WAVES = 4, int K>
 static __device__ __forceinline__ void block_sum(double (&a)[K], double *red)
 {
+    static_assert(WAVES == 4 || WAVES == 16, "a tree of fours");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int k = 0; k < K; k++) a[k] = wave_sum(a[k]);
@@ -34,8 +43,112 @@ static __device__ __forceinline__ void block_sum(double (&a)[K], double *red)
     }
     __syncthreads();
 #pragma unroll
-    for (int k = 0; k < K; k++) a[k] = (red[k] + red[K + k]) + (red[2 * K + k] + red[3 * K + k]);
+    for (int k = 0; k < K; k++) {
+        double q[WAVES / 4];
+#pragma unroll
+        for (int g = 0; g < WAVES / 4; g++) q[g] = (red[(4 * g) * K + k] + red[(4 * g + 1) * K + k]) + (red[(4 * g + 2) * K + k] + red[(4 * g + 3) * K + k]);
+        if constexpr (WAVES == 4) a[k] = q[0];
+        else a[k] = (q[0] + q[1]) + (q[2] + q[3]);
+    }
     __syncthreads();
+}
+
+// (H + lambda I) x = b by LDL^T without pivoting; H's upper triangle in row order (00 01 .. 0(N-1) 11 12 ..).  false (x untouched) unless
+// every pivot is > 0 (linear_solver_dense.h:104-112)
+template <int N>
+static __device__ __forceinline__ bool ldlt_small(const double *Hu, const double *b, double lambda, double *x)
+{
+    double A[N][N], L[N][N], d[N];
+    int k = 0;
+#pragma unroll
+    for (int r = 0; r < N; r++)
+#pragma unroll
+        for (int c = r; c < N; c++) { A[r][c] = A[c][r] = Hu[k++]; }
+#pragma unroll
+    for (int r = 0; r < N; r++) A[r][r] += lambda;
+#pragma unroll
+    for (int j = 0; j < N; j++) {
+        double dj = A[j][j];
+#pragma unroll
+        for (int m = 0; m < j; m++) dj -= (L[j][m] * L[j][m]) * d[m];
+        if (!(dj > 0.0)) return false;
+        d[j] = dj;
+#pragma unroll
+        for (int i = j + 1; i < N; i++) {
+            double v = A[i][j];
+#pragma unroll
+            for (int m = 0; m < j; m++) v -= (L[i][m] * L[j][m]) * d[m];
+            L[i][j] = v / dj;
+        }
+    }
+    double y[N];
+#pragma unroll
+    for (int i = 0; i < N; i++) {
+        double v = b[i];
+#pragma unroll
+        for (int m = 0; m < i; m++) v -= L[i][m] * y[m];
+        y[i] = v;
+    }
+#pragma unroll
+    for (int i = 0; i < N; i++) y[i] = y[i] / d[i];
+#pragma unroll
+    for (int i = N - 1; i >= 0; i--) {
+        double v = y[i];
+#pragma unroll
+        for (int m = i + 1; m < N; m++) v -= L[m][i] * x[m];
+        x[i] = v;
+    }
+    return true;
+}
+
+// the largest |diagonal entry| of H, its upper triangle in row order (optimization_algorithm_levenberg.cpp:166-180)
+template <int N>
+static __device__ __forceinline__ double hu_max_diag(const double *Hu)
+{
+    double md = 0.0;
+#pragma unroll
+    for (int k = 0; k < N; k++) md = fmax(fabs(Hu[k * N - k * (k - 1) / 2]), md);
+    return md;
+}
+
+// The damping of optimization_algorithm_levenberg.cpp:66-164, on the host and in a kernel, over the caller's own lambda, ni (2 at the
+// start) and stop_bad.  One outer iteration of its callers:
+//   linearise -> ini_chi = cur_chi; the first time lm_start(max |diagonal|, ..)
+//   do { solve with lambda, evaluate the trial; rho = lm_gain(..); where lm_accepts(rho, temp_chi): lm_accept(..), cur_chi = temp_chi, the
+//        trial is the estimate; else lm_reject(..), the estimate goes back; qmax++ } while (rho < 0 && qmax < 10 [&& not stopped])
+//   if (lm_done(qmax, rho, ini_chi, cur_chi, stop_bad)) break
+// (The accept branch stays with the caller: its two sides are where the estimate is kept or restored.)
+static __host__ __device__ __forceinline__ void lm_start(double max_diag, double &lambda, double &ni, int &stop_bad)   // :93-97
+{
+    lambda = 1e-5 * max_diag; ni = 2.0; stop_bad = 0;
+}
+
+// scale: computeScale's sum of x_j (lambda x_j + b_j)
+static __host__ __device__ __forceinline__ double lm_gain(double cur_chi, double temp_chi, double scale)
+{
+    scale += 1e-3;
+    return (cur_chi - temp_chi) / scale;
+}
+
+static __host__ __device__ __forceinline__ bool lm_accepts(double rho, double temp_chi) { return rho > 0.0 && std::isfinite(temp_chi); }
+
+static __host__ __device__ __forceinline__ void lm_accept(double rho, double &lambda, double &ni)
+{
+    const double t = 2.0 * rho - 1.0;
+    double alpha = 1.0 - (t * t) * t;
+    alpha = fmin(alpha, 2.0 / 3.0);
+    lambda *= fmax(1.0 / 3.0, alpha);
+    ni = 2.0;
+}
+
+static __host__ __device__ __forceinline__ void lm_reject(double &lambda, double &ni) { lambda *= ni; ni *= 2.0; }
+
+// the end of an outer iteration: the trials ran out or the step was exactly useless, or three iterations in a row gained under 1e-3
+static __host__ __device__ __forceinline__ bool lm_done(int qmax, double rho, double ini_chi, double cur_chi, int &stop_bad)
+{
+    if (qmax == 10 || rho == 0.0) return true;
+    if ((ini_chi - cur_chi) * 1e3 < ini_chi) stop_bad++; else stop_bad = 0;
+    return stop_bad >= 3;
 }
 
 // Eigen's Quaternion(Matrix3): m row-major
@@ -68,6 +181,25 @@ static __device__ __forceinline__ void quat_from_matrix(const double m[9], doubl
     }
 }
 
+// Eigen's Quaternion * vector: uv = 2 (q.vec x v); v + w uv + q.vec x uv (the quaternion need not be a unit one)
+static __device__ __forceinline__ void quat_rot(double qx, double qy, double qz, double qw, double X, double Y, double Z, double &x, double &y, double &z)
+{
+    const double ux = 2.0 * (qy * Z - qz * Y), uy = 2.0 * (qz * X - qx * Z), uz = 2.0 * (qx * Y - qy * X);
+    x = (X + qw * ux) + (qy * uz - qz * uy);
+    y = (Y + qw * uy) + (qz * ux - qx * uz);
+    z = (Z + qw * uz) + (qx * uy - qy * ux);
+}
+
+// Eigen's quaternion product a * b, not normalised
+static __device__ __forceinline__ void quat_mul(double ax, double ay, double az, double aw, double bx, double by, double bz, double bw,
+                                                double &qx, double &qy, double &qz, double &qw)
+{
+    qw = ((aw * bw - ax * bx) - ay * by) - az * bz;
+    qx = ((aw * bx + ax * bw) + ay * bz) - az * by;
+    qy = ((aw * by + ay * bw) + az * bx) - ax * bz;
+    qz = ((aw * bz + az * bw) + ax * by) - ay * bx;
+}
+
 // g2o's SE3Quat: a unit quaternion and a translation
 struct Pose { double qx, qy, qz, qw, tx, ty, tz; };
 
@@ -87,6 +219,13 @@ static __device__ __forceinline__ void quat_to_matrix(const Pose &P, double R[9]
     R[0] = 1.0 - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy;
     R[3] = txy + twz; R[4] = 1.0 - (txx + tzz); R[5] = tyz - twx;
     R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1.0 - (txx + tyy);
+}
+
+// SE3Quat::map
+static __device__ __forceinline__ void se3_map(const Pose &P, double X, double Y, double Z, double &x, double &y, double &z)
+{
+    quat_rot(P.qx, P.qy, P.qz, P.qw, X, Y, Z, x, y, z);
+    x = x + P.tx; y = y + P.ty; z = z + P.tz;
 }
 
 // VertexSE3Expmap::oplusImpl: SE3Quat::exp(x) * P (se3quat.h:223-257, :104-110); x[0..2] rotation, x[3..5] translation
@@ -121,16 +260,30 @@ static __device__ __forceinline__ Pose pose_update(const Pose &P, const double x
     E.tz = (V[6] * x[3] + V[7] * x[4]) + V[8] * x[5];
     // E * P: t = E.t + E.q * P.t ; q = E.q * P.q, normalised
     Pose N;
-    {
-        const double ux = 2.0 * (E.qy * P.tz - E.qz * P.ty), uy = 2.0 * (E.qz * P.tx - E.qx * P.tz), uz = 2.0 * (E.qx * P.ty - E.qy * P.tx);
-        N.tx = E.tx + ((P.tx + E.qw * ux) + (E.qy * uz - E.qz * uy));
-        N.ty = E.ty + ((P.ty + E.qw * uy) + (E.qz * ux - E.qx * uz));
-        N.tz = E.tz + ((P.tz + E.qw * uz) + (E.qx * uy - E.qy * ux));
-    }
-    N.qw = ((E.qw * P.qw - E.qx * P.qx) - E.qy * P.qy) - E.qz * P.qz;
-    N.qx = ((E.qw * P.qx + E.qx * P.qw) + E.qy * P.qz) - E.qz * P.qy;
-    N.qy = ((E.qw * P.qy + E.qy * P.qw) + E.qz * P.qx) - E.qx * P.qz;
-    N.qz = ((E.qw * P.qz + E.qz * P.qw) + E.qx * P.qy) - E.qy * P.qx;
+    double rx, ry, rz;
+    quat_rot(E.qx, E.qy, E.qz, E.qw, P.tx, P.ty, P.tz, rx, ry, rz);
+    N.tx = E.tx + rx; N.ty = E.ty + ry; N.tz = E.tz + rz;
+    quat_mul(E.qx, E.qy, E.qz, E.qw, P.qx, P.qy, P.qz, P.qw, N.qx, N.qy, N.qz, N.qw);
     quat_normalize(N.qx, N.qy, N.qz, N.qw);
     return N;
+}
+
+// a camera (fx fy cx cy mbf) and one observation of the mono / stereo reprojection edges: stereo where u_right is not negative
+struct Cam { double fx, fy, cx, cy, bf; };
+struct Obs { double mx, my, mr, w; bool stereo; };
+
+static __device__ __forceinline__ Cam cam_load(const float *c) { return Cam{ (double)c[0], (double)c[1], (double)c[2], (double)c[3], (double)c[4] }; }
+
+// computeError of EdgeSE3ProjectXYZ[OnlyPose] / EdgeStereoSE3ProjectXYZ[OnlyPose] at the mapped point (types_six_dof_expmap.h, cam_project
+// :141-157): error = measurement - projection; returns chi2 = e . (w e)
+static __device__ __forceinline__ double edge_error(const Obs &o, const Cam &C, double x, double y, double z, double err[3])
+{
+    if (o.stereo) {
+        const double invz = (double)(float)(1.0 / z);   // types_six_dof_expmap.cpp:300: `const float invz = 1.0f/trans_xyz[2]`
+        const double u = (x * invz) * C.fx + C.cx, v = (y * invz) * C.fy + C.cy;
+        err[0] = o.mx - u; err[1] = o.my - v; err[2] = o.mr - (u - C.bf * invz);
+        return (err[0] * (o.w * err[0]) + err[1] * (o.w * err[1])) + err[2] * (o.w * err[2]);
+    }
+    err[0] = o.mx - ((x / z) * C.fx + C.cx); err[1] = o.my - ((y / z) * C.fy + C.cy); err[2] = 0.0;
+    return err[0] * (o.w * err[0]) + err[1] * (o.w * err[1]);
 }

@@ -9,6 +9,7 @@
 // The arithmetic is restated in include/orbx.h (orbx_pnp_hypotheses) and, in numpy, in tests/pnp_model.py.  Behind the kernel: the
 // refusals, the staging (one blob up, one block down) and the delivery of the two calls (pnp_check, pnp_run and the entry points).
 #include "orbx_resident.h"
+#include "orbx_wave.h"
 
 // One job of k_pnp.  Every pointer is a device address.  first = the number of this job's first wave, as in k_sim3.
 struct PnpJob {
@@ -36,21 +37,6 @@ struct PnpLds {
     int order[12];
     int pad[4];
 };
-
-__device__ __forceinline__ void wsync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// the xor butterfly over strides 32 .. 1: every lane ends with the same bits (a + b == b + a)
-__device__ __forceinline__ double wred(double v)
-{
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) v = v + __shfl_xor(v, s, 64);
-    return v;
-}
 
 __device__ __forceinline__ double dot3(double a0, double a1, double a2, double b0, double b1, double b2)
 {
@@ -260,7 +246,7 @@ __device__ __forceinline__ void compute_pose(const PnpJob &J, const Members &M, 
         c0[0] = c0[0] + c.p0; c0[1] = c0[1] + c.p1; c0[2] = c0[2] + c.p2;
     });
 #pragma unroll
-    for (int j = 0; j < 3; j++) { if (!M.serial) c0[j] = wred(c0[j]); c0[j] = c0[j] / nc; }
+    for (int j = 0; j < 3; j++) { if (!M.serial) c0[j] = wave_sum(c0[j]); c0[j] = c0[j] / nc; }
     double ptp[6] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };   // 00 01 02 11 12 22
     for_members(M, lane, [&](int i) {
         const Corr c = corr_load(J, i);
@@ -270,7 +256,7 @@ __device__ __forceinline__ void compute_pose(const PnpJob &J, const Members &M, 
     });
     if (!M.serial) {
 #pragma unroll
-        for (int j = 0; j < 6; j++) ptp[j] = wred(ptp[j]);
+        for (int j = 0; j < 6; j++) ptp[j] = wave_sum(ptp[j]);
     }
     wsync();
     if (lane == 0) {
@@ -340,7 +326,7 @@ __device__ __forceinline__ void compute_pose(const PnpJob &J, const Members &M, 
         for (int j = 0; j < 3; j++)
 #pragma unroll
             for (int k = 3 * blk + j; k < 12; k++) {
-                const double v = M.serial ? acc[j][k] : wred(acc[j][k]);
+                const double v = M.serial ? acc[j][k] : wave_sum(acc[j][k]);
                 if (lane == 0) { B[(3 * blk + j) * PNP_LD + k] = v; B[k * PNP_LD + 3 * blk + j] = v; }
             }
     }
@@ -471,7 +457,7 @@ __device__ __forceinline__ void compute_pose(const PnpJob &J, const Members &M, 
             for (int j = 0; j < 3; j++) pc0[j] = pc0[j] + (((a[0] * ccs[0][j] + a[1] * ccs[1][j]) + a[2] * ccs[2][j]) + a[3] * ccs[3][j]);
         });
 #pragma unroll
-        for (int j = 0; j < 3; j++) { if (!M.serial) pc0[j] = wred(pc0[j]); pc0[j] = pc0[j] / nc; }
+        for (int j = 0; j < 3; j++) { if (!M.serial) pc0[j] = wave_sum(pc0[j]); pc0[j] = pc0[j] / nc; }
         double abt[9];
 #pragma unroll
         for (int j = 0; j < 9; j++) abt[j] = 0.0;
@@ -488,7 +474,7 @@ __device__ __forceinline__ void compute_pose(const PnpJob &J, const Members &M, 
         });
         if (!M.serial) {
 #pragma unroll
-            for (int j = 0; j < 9; j++) abt[j] = wred(abt[j]);
+            for (int j = 0; j < 9; j++) abt[j] = wave_sum(abt[j]);
         }
         wsync();
         if (lane == 0) {
@@ -521,7 +507,7 @@ __device__ __forceinline__ void compute_pose(const PnpJob &J, const Members &M, 
             const double eu = c.u - ue, ev = c.v - ve;
             sum2 = sum2 + sqrt(eu * eu + ev * ev);
         });
-        if (!M.serial) sum2 = wred(sum2);
+        if (!M.serial) sum2 = wave_sum(sum2);
         const double err = sum2 / nc;
         if (ap == 0 || err < err_best) {
             err_best = err;

@@ -33,8 +33,7 @@ struct PoseOut { double pose[12], chi2[4]; float Tcw[16]; int32_t n_corr, rounds
 
 namespace {
 
-struct Edge { double mx, my, mr, X, Y, Z, w; bool stereo; };
-struct Cam { double fx, fy, cx, cy, bf; };
+struct Edge : Obs { double X, Y, Z; };   // an observation and its map point
 
 __device__ __forceinline__ bool edge_present(const PoseJob &J, int i) { return J.slot ? J.slot[i] >= 0 : J.has_point[i] != 0; }
 
@@ -55,86 +54,13 @@ __device__ __forceinline__ Edge edge_load(const PoseJob &J, int i)
     return e;
 }
 
-// Eigen's Quaternion * vector: uv = 2 (q.vec x v); v + w uv + q.vec x uv; then + t (SE3Quat::map)
-__device__ __forceinline__ void pose_map(const Pose &P, const Edge &e, double &x, double &y, double &z)
-{
-    const double ux = 2.0 * (P.qy * e.Z - P.qz * e.Y), uy = 2.0 * (P.qz * e.X - P.qx * e.Z), uz = 2.0 * (P.qx * e.Y - P.qy * e.X);
-    x = ((e.X + P.qw * ux) + (P.qy * uz - P.qz * uy)) + P.tx;
-    y = ((e.Y + P.qw * uy) + (P.qz * ux - P.qx * uz)) + P.ty;
-    z = ((e.Z + P.qw * uz) + (P.qx * uy - P.qy * ux)) + P.tz;
-}
-
-// error = measurement - projection (types_six_dof_expmap.h computeError); returns chi2 = e . (w e)
-__device__ __forceinline__ double edge_error(const Edge &e, const Cam &K, double x, double y, double z, double err[3])
-{
-    if (e.stereo) {
-        const double invz = (double)(float)(1.0 / z);   // types_six_dof_expmap.cpp:300: `const float invz = 1.0f/trans_xyz[2]`
-        const double u = (x * invz) * K.fx + K.cx, v = (y * invz) * K.fy + K.cy;
-        err[0] = e.mx - u; err[1] = e.my - v; err[2] = e.mr - (u - K.bf * invz);
-        return (err[0] * (e.w * err[0]) + err[1] * (e.w * err[1])) + err[2] * (e.w * err[2]);
-    }
-    err[0] = e.mx - ((x / z) * K.fx + K.cx); err[1] = e.my - ((y / z) * K.fy + K.cy); err[2] = 0.0;
-    return err[0] * (e.w * err[0]) + err[1] * (e.w * err[1]);
-}
-
 __device__ __forceinline__ double edge_chi2(const PoseJob &J, int i, const Pose &P, const Cam &K, bool *stereo)
 {
     const Edge e = edge_load(J, i);
     double x, y, z, err[3];
-    pose_map(P, e, x, y, z);
+    se3_map(P, e.X, e.Y, e.Z, x, y, z);
     *stereo = e.stereo;
     return edge_error(e, K, x, y, z, err);
-}
-
-// huber, block_sum (its fixed order: header comment) and Eigen's Quaternion(Matrix3) are orbx_lm.h's, shared with k_sim3_opt
-
-// SE3Quat (Pose, quat_normalize, quat_to_matrix, pose_update) is orbx_lm.h's too, shared with the kernels of orbx_lba.hip
-
-// (H + lambda I) x = b by LDL^T without pivoting; H's upper triangle in row order (00 01 .. 05 11 12 ..).  false (x untouched) unless
-// every pivot is > 0 (linear_solver_dense.h:104-112)
-__device__ __forceinline__ bool solve6(const double *Hu, const double *b, double lambda, double x[6])
-{
-    double A[6][6], L[6][6], d[6];
-    int k = 0;
-#pragma unroll
-    for (int r = 0; r < 6; r++)
-#pragma unroll
-        for (int c = r; c < 6; c++) { A[r][c] = A[c][r] = Hu[k++]; }
-#pragma unroll
-    for (int r = 0; r < 6; r++) A[r][r] += lambda;
-#pragma unroll
-    for (int j = 0; j < 6; j++) {
-        double dj = A[j][j];
-#pragma unroll
-        for (int m = 0; m < j; m++) dj -= (L[j][m] * L[j][m]) * d[m];
-        if (!(dj > 0.0)) return false;
-        d[j] = dj;
-#pragma unroll
-        for (int i = j + 1; i < 6; i++) {
-            double v = A[i][j];
-#pragma unroll
-            for (int m = 0; m < j; m++) v -= (L[i][m] * L[j][m]) * d[m];
-            L[i][j] = v / dj;
-        }
-    }
-    double y[6];
-#pragma unroll
-    for (int i = 0; i < 6; i++) {
-        double v = b[i];
-#pragma unroll
-        for (int m = 0; m < i; m++) v -= L[i][m] * y[m];
-        y[i] = v;
-    }
-#pragma unroll
-    for (int i = 0; i < 6; i++) y[i] = y[i] / d[i];
-#pragma unroll
-    for (int i = 5; i >= 0; i--) {
-        double v = y[i];
-#pragma unroll
-        for (int m = i + 1; m < 6; m++) v -= L[m][i] * x[m];
-        x[i] = v;
-    }
-    return true;
 }
 
 __global__ __launch_bounds__(256) void k_pose_opt(const PoseJob *__restrict__ jobs, PoseOut *__restrict__ outs)
@@ -143,7 +69,7 @@ __global__ __launch_bounds__(256) void k_pose_opt(const PoseJob *__restrict__ jo
     const PoseJob &J = jobs[blockIdx.x];
     PoseOut &out = outs[blockIdx.x];
     const int tid = threadIdx.x, n = J.n;
-    const Cam K = { (double)J.cam[0], (double)J.cam[1], (double)J.cam[2], (double)J.cam[3], (double)J.cam[4] };
+    const Cam K = cam_load(J.cam);
     const double delta_mono = (double)(float)sqrt(5.991), delta_stereo = (double)(float)sqrt(7.815);   // src/Optimizer.cc:322-323
 
     double cnt[2] = { 0.0, 0.0 };   // correspondences; those whose octave names no level (resident form)
@@ -200,7 +126,7 @@ __global__ __launch_bounds__(256) void k_pose_opt(const PoseJob *__restrict__ jo
                 if (!edge_present(J, i) || J.outlier[i]) continue;
                 const Edge e = edge_load(J, i);
                 double X, Y, Z, err[3];
-                pose_map(P, e, X, Y, Z);
+                se3_map(P, e.X, e.Y, e.Z, X, Y, Z);
                 const double chi = edge_error(e, K, X, Y, Z, err);
                 double rho0 = chi, rho1 = 1.0;
                 if (robust) huber(chi, e.stereo ? delta_stereo : delta_mono, rho0, rho1);
@@ -234,18 +160,12 @@ __global__ __launch_bounds__(256) void k_pose_opt(const PoseJob *__restrict__ jo
             block_sum(acc, red);
             cur_chi = acc[27];
             const double ini_chi = cur_chi;
-            if (iter == 0) {   // optimization_algorithm_levenberg.cpp:93-97, :166-180
-                double md = 0.0;
-                const int diag[6] = { 0, 6, 11, 15, 18, 20 };
-#pragma unroll
-                for (int k = 0; k < 6; k++) md = fmax(fabs(acc[diag[k]]), md);
-                lambda = 1e-5 * md; ni = 2.0; stop_bad = 0;
-            }
+            if (iter == 0) lm_start(hu_max_diag<6>(acc), lambda, ni, stop_bad);
             double rho = 0.0;
             int qmax = 0;
             do {
                 const Pose backup = P;
-                const bool ok = solve6(acc, acc + 21, lambda, x);
+                const bool ok = ldlt_small<6>(acc, acc + 21, lambda, x);
                 P = pose_update(P, x);
                 Ptrial = P;
                 double tc[1] = { 0.0 };
@@ -262,25 +182,18 @@ __global__ __launch_bounds__(256) void k_pose_opt(const PoseJob *__restrict__ jo
                 double scale = 0.0;
 #pragma unroll
                 for (int j = 0; j < 6; j++) scale += x[j] * (lambda * x[j] + acc[21 + j]);
-                scale += 1e-3;
-                rho = (cur_chi - temp_chi) / scale;
-                if (rho > 0.0 && isfinite(temp_chi)) {
-                    const double t = 2.0 * rho - 1.0;
-                    double alpha = 1.0 - (t * t) * t;
-                    alpha = fmin(alpha, 2.0 / 3.0);
-                    lambda *= fmax(1.0 / 3.0, alpha);
-                    ni = 2.0;
+                rho = lm_gain(cur_chi, temp_chi, scale);
+                if (lm_accepts(rho, temp_chi)) {
+                    lm_accept(rho, lambda, ni);
                     cur_chi = temp_chi;
                 } else {
-                    lambda *= ni; ni *= 2.0;
+                    lm_reject(lambda, ni);
                     P = backup;   // pop(): the vertex goes back, the edges keep the errors of the rejected pose
                 }
                 qmax++;
             } while (rho < 0.0 && qmax < 10);
             iters++;
-            if (qmax == 10 || rho == 0.0) break;
-            if ((ini_chi - cur_chi) * 1e3 < ini_chi) stop_bad++; else stop_bad = 0;
-            if (stop_bad >= 3) break;
+            if (lm_done(qmax, rho, ini_chi, cur_chi, stop_bad)) break;
         }
         // :441-502: an outlier gets a fresh error at the round's pose, an active edge keeps the error of the last evaluated trial
         double bad[1] = { 0.0 };

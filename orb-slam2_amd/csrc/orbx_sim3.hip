@@ -8,6 +8,7 @@
 // The arithmetic is restated in include/orbx.h (orbx_sim3_hypotheses) and, in numpy, in tests/sim3_model.py.  Behind the kernel: the
 // refusals, the staging (one blob up, one block down) and the delivery of the two calls (sim3_check, sim3_run and the entry points).
 #include "orbx_resident.h"
+#include "orbx_wave.h"
 
 // One job of k_sim3.  Every pointer is a device address.  first = the number of this job's
 // first wave: wave first + h evaluates hypothesis h; the jobs of a call are in rising order of it.
@@ -20,12 +21,6 @@ struct Sim3Job {
 };
 
 namespace {
-
-// (double) a . b, left to right
-__device__ __forceinline__ double dotd(float a0, float a1, float a2, float b0, float b1, float b2)
-{
-    return ((double)a0 * (double)b0 + (double)a1 * (double)b1) + (double)a2 * (double)b2;
-}
 
 // where OpenCV calls hypot
 __device__ __forceinline__ float hyp(float a, float b)

@@ -53,16 +53,7 @@ __device__ __forceinline__ Pair pair_load(const Sim3OptJob &J, int i)
     return p;
 }
 
-// Eigen's Quaternion * vector: uv = 2 (q.vec x v); v + w uv + q.vec x uv (the quaternion is NOT a unit one here)
-__device__ __forceinline__ void quat_rot(double qx, double qy, double qz, double qw, double X, double Y, double Z, double &x, double &y, double &z)
-{
-    const double ux = 2.0 * (qy * Z - qz * Y), uy = 2.0 * (qz * X - qx * Z), uz = 2.0 * (qx * Y - qy * X);
-    x = (X + qw * ux) + (qy * uz - qz * uy);
-    y = (Y + qw * uy) + (qz * ux - qx * uz);
-    z = (Z + qw * uz) + (qx * uy - qy * ux);
-}
-
-// sim3.h:144-146: s * (r * xyz) + t
+// sim3.h:144-146: s * (r * xyz) + t (r is NOT a unit quaternion here)
 __device__ __forceinline__ void sim3_map(const Sim3 &S, double X, double Y, double Z, double &x, double &y, double &z)
 {
     quat_rot(S.qx, S.qy, S.qz, S.qw, X, Y, Z, x, y, z);
@@ -84,10 +75,7 @@ __device__ __forceinline__ Sim3 sim3_inverse(const Sim3 &S)
 __device__ __forceinline__ Sim3 sim3_mul(const Sim3 &a, const Sim3 &b)
 {
     Sim3 N;
-    N.qw = ((a.qw * b.qw - a.qx * b.qx) - a.qy * b.qy) - a.qz * b.qz;
-    N.qx = ((a.qw * b.qx + a.qx * b.qw) + a.qy * b.qz) - a.qz * b.qy;
-    N.qy = ((a.qw * b.qy + a.qy * b.qw) + a.qz * b.qx) - a.qx * b.qz;
-    N.qz = ((a.qw * b.qz + a.qz * b.qw) + a.qx * b.qy) - a.qy * b.qx;
+    quat_mul(a.qx, a.qy, a.qz, a.qw, b.qx, b.qy, b.qz, b.qw, N.qx, N.qy, N.qz, N.qw);
     double x, y, z;
     quat_rot(a.qx, a.qy, a.qz, a.qw, b.tx, b.ty, b.tz, x, y, z);
     N.tx = a.s * x + a.tx; N.ty = a.s * y + a.ty; N.tz = a.s * z + a.tz;
@@ -217,53 +205,6 @@ __device__ __forceinline__ void edge_accumulate(double (&acc)[36], const double 
     }
 }
 
-// (H + lambda I) x = b by LDL^T without pivoting; H's upper triangle in row order (00 01 .. 06 11 12 ..).  false (x untouched) unless
-// every pivot is > 0 (linear_solver_dense.h:104-112)
-__device__ __forceinline__ bool solve7(const double *Hu, const double *b, double lambda, double x[7])
-{
-    double A[7][7], L[7][7], d[7];
-    int k = 0;
-#pragma unroll
-    for (int r = 0; r < 7; r++)
-#pragma unroll
-        for (int c = r; c < 7; c++) { A[r][c] = A[c][r] = Hu[k++]; }
-#pragma unroll
-    for (int r = 0; r < 7; r++) A[r][r] += lambda;
-#pragma unroll
-    for (int j = 0; j < 7; j++) {
-        double dj = A[j][j];
-#pragma unroll
-        for (int m = 0; m < j; m++) dj -= (L[j][m] * L[j][m]) * d[m];
-        if (!(dj > 0.0)) return false;
-        d[j] = dj;
-#pragma unroll
-        for (int i = j + 1; i < 7; i++) {
-            double v = A[i][j];
-#pragma unroll
-            for (int m = 0; m < j; m++) v -= (L[i][m] * L[j][m]) * d[m];
-            L[i][j] = v / dj;
-        }
-    }
-    double y[7];
-#pragma unroll
-    for (int i = 0; i < 7; i++) {
-        double v = b[i];
-#pragma unroll
-        for (int m = 0; m < i; m++) v -= L[i][m] * y[m];
-        y[i] = v;
-    }
-#pragma unroll
-    for (int i = 0; i < 7; i++) y[i] = y[i] / d[i];
-#pragma unroll
-    for (int i = 6; i >= 0; i--) {
-        double v = y[i];
-#pragma unroll
-        for (int m = i + 1; m < 7; m++) v -= L[m][i] * x[m];
-        x[i] = v;
-    }
-    return true;
-}
-
 __global__ __launch_bounds__(256) void k_sim3_opt(const Sim3OptJob *__restrict__ jobs, Sim3OptOut *__restrict__ outs)
 {
     __shared__ double red[4 * 36];
@@ -319,17 +260,13 @@ __global__ __launch_bounds__(256) void k_sim3_opt(const Sim3OptJob *__restrict__
             cur_chi = acc[35];
             const double ini_chi = cur_chi;
             if (iter == 0) {   // optimization_algorithm_levenberg.cpp:93-97, :166-180
-                double md = 0.0;
-                const int diag[7] = { 0, 7, 13, 18, 22, 25, 27 };
-#pragma unroll
-                for (int k = 0; k < 7; k++) md = fmax(fabs(acc[diag[k]]), md);
-                lambda = 1e-5 * md; ni = 2.0; stop_bad = 0;
+                lm_start(hu_max_diag<7>(acc), lambda, ni, stop_bad);
             }
             double rho = 0.0;
             int qmax = 0;
             do {
                 const Sim3 backup = S;
-                const bool ok = solve7(acc, acc + 28, lambda, x);
+                const bool ok = ldlt_small<7>(acc, acc + 28, lambda, x);
                 if (fix) x[6] = 0.0;
                 S = sim3_mul(sim3_exp(x), S);
                 Strial = S;
@@ -348,25 +285,18 @@ __global__ __launch_bounds__(256) void k_sim3_opt(const Sim3OptJob *__restrict__
                 double scale = 0.0;
 #pragma unroll
                 for (int j = 0; j < 7; j++) scale += x[j] * (lambda * x[j] + acc[28 + j]);
-                scale += 1e-3;
-                rho = (cur_chi - temp_chi) / scale;
-                if (rho > 0.0 && isfinite(temp_chi)) {
-                    const double t = 2.0 * rho - 1.0;
-                    double alpha = 1.0 - (t * t) * t;
-                    alpha = fmin(alpha, 2.0 / 3.0);
-                    lambda *= fmax(1.0 / 3.0, alpha);
-                    ni = 2.0;
+                rho = lm_gain(cur_chi, temp_chi, scale);
+                if (lm_accepts(rho, temp_chi)) {
+                    lm_accept(rho, lambda, ni);
                     cur_chi = temp_chi;
                 } else {
-                    lambda *= ni; ni *= 2.0;
+                    lm_reject(lambda, ni);
                     S = backup;   // pop(): the vertex goes back, the edges keep the errors of the rejected estimate
                 }
                 qmax++;
             } while (rho < 0.0 && qmax < 10);
             iters++;
-            if (qmax == 10 || rho == 0.0) break;
-            if ((ini_chi - cur_chi) * 1e3 < ini_chi) stop_bad++; else stop_bad = 0;
-            if (stop_bad >= 3) break;
+            if (lm_done(qmax, rho, ini_chi, cur_chi, stop_bad)) break;
         }
         // :1308-1327 / :1343-1358: every pair still in the graph, at the errors of the last evaluated trial
         const Sim3 Ti = sim3_inverse(Strial);

@@ -9,6 +9,7 @@
 // The arithmetic is restated in include/orbx.h (orbx_triangulate_pairs) and, in numpy, in tests/triangulate_model.py.  Behind the kernels:
 // the refusals, the staging and the delivery of the two calls (tri_check, tri_run and the entry points).
 #include "orbx_resident.h"
+#include "orbx_wave.h"
 #include <stddef.h>
 
 // What k_triangulate reads besides the pair list.  Every pointer is a device address; raw_x / raw_y are x / y and
@@ -27,12 +28,6 @@ struct TriHead {
 namespace {
 
 struct V3 { float x, y, z; };
-
-// (double) a . b, left to right
-__device__ __forceinline__ double dotd(float a0, float a1, float a2, float b0, float b1, float b2)
-{
-    return ((double)a0 * (double)b0 + (double)a1 * (double)b1) + (double)a2 * (double)b2;
-}
 
 // Rwc * v (+ add): Rwc is the transpose of the rotation block of Tcw[3][4]; one cast per row
 __device__ __forceinline__ V3 rot_wc(const float *T, float v0, float v1, float v2, double a0, double a1, double a2)
