@@ -1,7 +1,7 @@
 // adapter/ba/BundleAdjustment.cc -- ORB_SLAM2::Optimizer::GlobalBundleAdjustemnt and ORB_SLAM2::Optimizer::BundleAdjustment (reference
 // src/Optimizer.cc:48-281) on the device.  The problem is gathered as :85-224 adds vertices and edges; ONE call of orbx_bundle_adjustment
 // replaces g2o between :67 and :232 (it polls pbStopFlag as optimizer.setForceStopFlag makes g2o do); then the recovery loops of :236-279.
-// It replaces these two functions only: OptimizeEssentialGraph and g2o stay as they are.  Its own sub-directory, like
+// It replaces these two functions only: OptimizeEssentialGraph has its own adaptor, adapter/essential/ (INTEGRATION.md).  Its own sub-directory, like
 // adapter/lba/: it needs Optimizer.h and Map.h.
 // Stated deviation: an observation in a good keyframe that is not in vpKFs but has mnId <= maxKFid makes the reference attach the edge to a
 // vertex that does not exist (optimizer.vertex() returns NULL); here that observation is skipped.

@@ -2,8 +2,8 @@
 // (reference src/Optimizer.cc:528-862) on the device.  The three lists of :530-582 and their marks are built statement for statement; the
 // problem is gathered as :602-734 adds vertices and edges; ONE call of orbx_local_bundle_adjustment replaces g2o between :584 and :825
 // (it polls pbStopFlag as optimizer.setForceStopFlag makes g2o do); then vToErase in the reference's order, the erasures and the
-// write-back under Map::mMutexMapUpdate (:827-861).  It replaces that one function only: BundleAdjustment, OptimizeEssentialGraph and g2o
-// stay as they are.  Its own sub-directory, like adapter/pose/: it needs Optimizer.h and Map.h.
+// write-back under Map::mMutexMapUpdate (:827-861).  It replaces that one function only: BundleAdjustment and OptimizeEssentialGraph
+// have adaptors of their own, adapter/ba/ and adapter/essential/ (INTEGRATION.md).  Its own sub-directory, like adapter/pose/: it needs Optimizer.h and Map.h.
 #include "Optimizer.h"
 
 #include <list>

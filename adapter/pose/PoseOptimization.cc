@@ -1,8 +1,8 @@
 // adapter/pose/PoseOptimization.cc -- int ORB_SLAM2::Optimizer::PoseOptimization(Frame *pFrame) (reference src/Optimizer.cc:286-513) on the
 // device: the gather of :326-420 under MapPoint::mGlobalMutex, ONE call of orbx_pose_optimize (one upload, one launch, one download:
 // the four rounds of Levenberg iterations and the classifications between them run in the kernel), then mvbOutlier, SetPose and the return
-// value.  It replaces that one function only: the rest of src/Optimizer.cc -- the bundle adjustments, the essential graph (OptimizeSim3: orbx_sim3_optimize) --
-// and g2o stay as they are.  Its own sub-directory, like adapter/localmap/: it needs Optimizer.h and Frame::SetPose.
+// value.  It replaces that one function only: the rest of src/Optimizer.cc -- the bundle adjustments, the essential graph, OptimizeSim3 --
+// has adaptors of its own (adapter/lba/, adapter/ba/, adapter/essential/, adapter/sim3opt/).  Its own sub-directory, like adapter/localmap/: it needs Optimizer.h and Frame::SetPose.
 #include "Optimizer.h"
 
 #include <mutex>

@@ -739,7 +739,8 @@ int orbx_frame_search_local_points(orbx_frame *cur, const uint8_t *occupied, con
  * Relocalization up to three times per candidate, src/Tracking.cc:1730-1800): one 6-DoF vertex, one unary edge per feature that
  * holds a map point.  The whole function -- four rounds of at most ten Levenberg iterations with at most ten damping trials each,
  * and the inlier / outlier classification between the rounds -- is ONE kernel launch, one workgroup per job.  Only this function:
- * the bundle adjustments and the essential graph stay with g2o (OptimizeSim3, the other single-vertex problem: orbx_sim3_optimize).
+ * the other functions of src/Optimizer.cc have calls of their own below (orbx_local_bundle_adjustment, orbx_bundle_adjustment,
+ * orbx_sim3_optimize, orbx_optimize_essential_graph).
  * The arithmetic, in double unless a step says float, every operation rounded on its own (no fused multiply-add):
  *   edges    feature i with has_point[i] is a monocular edge (src/Optimizer.cc:335-377) if u_right[i] < 0, else a stereo edge
  *            (:378-416).  Measurement, Xw, cam and inv_sigma2 are floats widened to double; information = inv_sigma2[i] * I.
@@ -943,6 +944,87 @@ int orbx_bundle_adjustment(int device, const orbx_lba_problem *p, const orbx_ba_
                            uint8_t *point_included /* [n_points]: 0 = no edge, vbNotIncludedMP */,
                            double *pose_out /* [n_kf][12], may be NULL */, double *point_out /* [n_points][3], may be NULL */,
                            orbx_ba_report *report /* may be NULL */);
+
+/* ---- Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:885-1153; LoopClosing::CorrectLoop) ----------------------------------
+ * The pose graph over the essential graph behind a loop closure, between ComputeSim3 and the global bundle adjustment: one 7-DoF
+ * VertexSim3Expmap per good keyframe (pLoopKF fixed), binary EdgeSim3 edges, no points; then the correction of every map point by its
+ * reference keyframe.  Graph selection stays with the adaptor (adapter/essential/OptimizeEssentialGraph.cc): GetWeight < minFeat, parents,
+ * GetLoopEdges, GetCovisiblesByWeight, sInsertedEdges walk KeyFrame pointers.  Everything arithmetic is this call, in double, every
+ * operation rounded on its own (no fused multiply-add), a Sim3 as qx qy qz qw tx ty tz s with the quaternion NEVER normalised:
+ *   vScw     vScw[k] = S_corrected[corrected[k]] where corrected[k] >= 0 (:923-929), else Sim3(Matrix3d(Rcw), tcw, 1.0) of the float pose
+ *            (:933-937): Eigen's Quaternion(Matrix3) on the doubles of the floats, not normalised (sim3.h:64-67).  It is the start estimate.
+ *   edges    edge e joins vertex 0 = edge_i[e] and vertex 1 = edge_j[e] with the measurement Sji = Sjw * Swi, Swi = Siw.inverse()
+ *            (sim3.h:233-236, :266-272).  edge_kind 0 (:958-989): Siw = vScw[i], Sjw = vScw[j].  edge_kind 1 (:992-1092): each end's
+ *            S_noncorrected[noncorrected[.]] where it has one, else its vScw.  information = I, no robust kernel.
+ *   error    log(C * Si * Sj^-1) = ((C * Si) * Sj.inverse()).log() (types_seven_dof_expmap.h:106-114).  Sim3::log (sim3.h:148-230): sigma =
+ *            log(s); R = r.toRotationMatrix() of the quaternion as it stands; d = 0.5 * (((R00 + R11) + R22) - 1); eps = 1e-5; the four
+ *            branches on fabs(sigma) < eps and d > 1 - eps, omega = 0.5 deltaR(R) or acos(d) / (2 sqrt(1 - d d)) deltaR(R), A B C as the
+ *            text has them; W = (A Omega + (B Omega) Omega) + C I with B Omega rounded first and each product entry summed (p0 + p1) + p2;
+ *            upsilon = W.lu().solve(t): Eigen's 3 x 3 PartialPivLU -- in column k the FIRST row >= k of the largest magnitude is the pivot,
+ *            rows exchanged, the entries below divided by the pivot (a division, not a product with its reciprocal), the trailing block
+ *            updated entry by entry; forward y1 = t1 - l10 y0, y2 = t2 - (l20 y0 + l21 y1); backward x2 = y2 / u22, x1 = (y1 - u12 x2) /
+ *            u11, x0 = (y0 - (u01 x1 + u02 x2)) / u00.  chi2 of an edge = ((((((e0 e0 + e1 e1) + e2 e2) + e3 e3) + e4 e4) + e5 e5) + e6 e6.
+ *   jacobian base_binary_edge.hpp:131-205 for each end that is not fixed: column d = (1 / (2 delta)) * (e(+delta) - e(-delta)), delta = 1e-9,
+ *            the end's estimate replaced by Sim3(+-delta e_d) * estimate (VertexSim3Expmap::oplusImpl); with fix_scale oplusImpl zeroes
+ *            update[6], both sides of column 6 are the same evaluation and the column is an exact zero.  The 14 transforms Sim3(+-delta
+ *            e_d) do not depend on the vertex and are computed once per call.
+ *   system   constructQuadraticForm (:55-120) without a kernel: for a free vertex 0, b_i += A^T (-e), H_ii += A^T A; for a free vertex 1
+ *            likewise with B; both free: the pair's off-diagonal block += A^T B, read transposed where the row order asks for it.  A
+ *            product entry is the sum over the 7 error rows in ascending order.  FIXED ORDERS: a vertex's H_ii and b are summed over its
+ *            incident edges in edge order; a pair's block over that pair's edges in edge order (several edges may join one pair; g2o maps
+ *            them to one block); chi2 = the edges strided over 256 partial sums (edge e to partial e % 256, ascending), the partials summed
+ *            by a butterfly over 64 and ((w0 + w1) + (w2 + w3)) -- a function of n_edges alone.  Rows: the free keyframes in keyframe order.
+ *   damping  optimization_algorithm_levenberg.cpp:61-189 as in orbx_local_bundle_adjustment, with setUserLambdaInit(1e-16) (:899):
+ *            computeLambdaInit returns 1e-16, not 1e-5 * the largest diagonal entry.  setLambda adds lambda to every diagonal entry;
+ *            computeScale = sum of x_j (lambda x_j + b_j) over the whole x, per vertex in ascending j, the vertices' sums in the chi2 order,
+ *            after oplus has zeroed x[6] of every vertex under fix_scale; rho = (chi2 - trial chi2) / (scale + 1e-3); the qmax == 10,
+ *            rho == 0 and _nBad >= 3 stops.  The function has no stop flag, and neither has this call.
+ *   solve    the dense 7F x 7F matrix zeroed, its lower triangle filled, factored by the panel LDL^T of orbx_bundle_adjustment
+ *            (orbx_ldlt.hip).  A pivot that is not > 0: the trial's chi2 is DBL_MAX and x is what the previous trial left (0 at the start).
+ *            THIS DENSE SOLVE IS THE STATED DEVIATION, the bundle adjustments' own: g2o solves the same matrix with Eigen's sparse Cholesky;
+ *            the same solution, other rounding.  A vertex without an edge has the block lambda I and b = 0, hence x = 0 and exp(0) * S = S
+ *            bit for bit; under fix_scale every scale row has the pivot lambda and x = 0.
+ *   update   trial estimate = Sim3(x_k) * S_k (sim3.h:70-142).
+ *   result   (:1101-1152) S_out[k] = the final estimate; Tcw_out[k] = [R | t * (1. / s)], R = rotation().toRotationMatrix(), cast to float
+ *            as Converter::toCvSE3 does, last row 0 0 0 1; the fixed keyframe goes through the same recovery.  point_out[p] =
+ *            S_out[ref].inverse().map(vScw[ref].map(Xw[p])), ref = point_ref[p]; Xw_out = its float cast.
+ * sizes: n_kf 1 .. 4096 with EXACTLY ONE fixed[k] != 0 and at most 1536 free; n_edges 0 .. 2^18; n_points 0 .. 2^20; n_corrected and
+ * n_noncorrected 0 .. 4096.  1536 is the round
+ * number below the 1755 that the panel solver's n <= 12288 allows; the dense matrix is 0.92 GB there (the thread's work area grows to
+ * twice its largest request).  The limits say what the buffers hold, not what runs well: the factorisation is dense and dominates above
+ * a few hundred keyframes.  A call is byte-reproducible: no atomics, no cooperative launch.
+ * opt == NULL: 20 iterations (:1096).  One upload in front, one download behind; the device buffers are the calling thread's.  Refusals
+ * before any device work.  ORBX_E_INVALID: a NULL argument or array that the sizes need (opt, S_out, point_out, report may be NULL; Xw_out
+ * with n_points == 0 too; S_corrected / S_noncorrected where no index names them), n_kf < 1 or a negative size, an index out of range
+ * (edge_i, edge_j, point_ref; corrected / noncorrected below -1), edge_i == edge_j, edge_kind above 1, not exactly one fixed keyframe,
+ * iterations < 0.  ORBX_E_CAPACITY: a size beyond those above.
+ * Against g2o's own arithmetic (Eigen's sparse Cholesky, its product evaluation order, the PartialPivLU of the Eigen version at hand)
+ * this restatement is unpinned: DESIGN.md. */
+typedef struct {
+    int n_kf;                       /* good keyframes of the map, 1 .. 4096; exactly one with fixed[k] != 0 (pLoopKF); at most 1536 free */
+    const float *Tcw;               /* [n_kf][16] GetPose(), row major */
+    const uint8_t *fixed;           /* [n_kf] */
+    const int32_t *corrected;       /* [n_kf] index into S_corrected or -1 (CorrectedSim3.find) */
+    const int32_t *noncorrected;    /* [n_kf] index into S_noncorrected or -1 (NonCorrectedSim3.find) */
+    int n_corrected, n_noncorrected;   /* entries of the two arrays below */
+    const double *S_corrected, *S_noncorrected;   /* [.][8] qx qy qz qw tx ty tz s */
+    int n_edges;                    /* 0 .. 2^18 */
+    const int32_t *edge_i, *edge_j; /* vertex 0 and vertex 1 of the EdgeSim3, i != j */
+    const uint8_t *edge_kind;       /* 0: loop-connection edge (:958-989), 1: normal edge (:992-1092) */
+    int n_points;                   /* 0 .. 2^20 */
+    const float *Xw;                /* [n_points][3] GetWorldPos() */
+    const int32_t *point_ref;       /* [n_points] nIDr's keyframe index (:1129-1138) */
+    int fix_scale;
+} orbx_eg_problem;
+typedef struct { int iterations; } orbx_eg_options;
+typedef struct {
+    int iterations, trials, n_free, n_solve_failed;
+    double chi2_start, chi2, lambda;   /* chi2 at the start estimates and at the end, lambda at the end; 0 if no iteration ran */
+} orbx_eg_report;
+int orbx_optimize_essential_graph(int device, const orbx_eg_problem *p, const orbx_eg_options *opt /* may be NULL */,
+                                  float *Tcw_out /* [n_kf][16] */, float *Xw_out /* [n_points][3] */,
+                                  double *S_out /* [n_kf][8], may be NULL */, double *point_out /* [n_points][3], may be NULL */,
+                                  orbx_eg_report *report /* may be NULL */);
 
 /* ---- Optimizer::OptimizeSim3: the Sim3 between two keyframes (src/Optimizer.cc:1164-1365) ------------------------------
  * Step 4 of LoopClosing::ComputeSim3 (src/LoopClosing.cc:282-460), between SearchBySim3 and the Sim3 SearchByProjection.  Every
@@ -1542,6 +1624,10 @@ int orbx_debug_match_timing(double *out4);
  * 10 k_lba_classify, 11 k_lba_finish.  Results are the same bytes with and without it.  The events belong to the thread's context and go
  * with it (orbx_thread_release, or the thread's end). */
 int orbx_debug_lba_profile(int enable, double *ms, int32_t *launches);
+/* the same hook for the calling thread's orbx_optimize_essential_graph calls (tools/bench_eg.py): ms[10], launches[10], returns 10.  Slots:
+ * 0 k_eg_setup, 1 k_eg_edges<true>, 2 k_eg_rows, 3 k_eg_reduce, 4 k_eg_fill (both phases), 5 the panel solve, 6 k_eg_update,
+ * 7 k_eg_edges<false>, 8 k_eg_finish, 9 k_eg_points. */
+int orbx_debug_eg_profile(int enable, double *ms, int32_t *launches);
 /* test hooks for the dense LDL^T of the two bundle adjustments.  It exists in two forms that give the same bytes: 0, one workgroup
  * (k_lba_solve, n <= 1536), and 1, panels of orbx_debug_ldlt_panel_width() columns over many workgroups (orbx_ldlt.hip, n <= 12288).
  * orbx_debug_ldlt_solve uploads a dense system (S [n][n] row major, only its lower triangle is read; b [n]) and solves it with the named

@@ -15,6 +15,7 @@ sitting directly on the C ABI of liborbx.so (include/orbx.h):
   pnp_hypotheses / PnPRansac <- reference src/PnPsolver.cc:128-961 (Tracking::Relocalization's EPnP RANSAC)
   local_bundle_adjustment <- reference src/Optimizer.cc:528-862 (Optimizer::LocalBundleAdjustment, LocalMapping's optimisation)
   bundle_adjustment <- reference src/Optimizer.cc:48-281 (Optimizer::BundleAdjustment, the global bundle adjustment)
+  optimize_essential_graph <- reference src/Optimizer.cc:885-1153 (Optimizer::OptimizeEssentialGraph, LoopClosing::CorrectLoop)
   mono_init_hypotheses / mono_init_reconstruct / Initializer <- reference src/Initializer.cc:37-1026 (Tracking::MonocularInitialization)
 
 There is NO CPU fallback: importing works without a GPU (so that the ABI can be inspected), but
@@ -28,7 +29,7 @@ from .orbx import (OrbxError, KP_DTYPE, lib, lib_path, ORBextractor, ORBmatcher,
                    triangulate_pairs, frame_set_depth, frame_triangulate, sim3_hypotheses, sim3_hypotheses_batch, sim3_max_error, Sim3Ransac,
                    sim3_optimize, sim3_optimize_batch, sim3opt_camera_points, pnp_hypotheses, pnp_hypotheses_batch, PnPRansac,
                    mono_init_hypotheses, mono_init_reconstruct, mono_init_initialize, mono_init_draw_sets, DUtilsRandom, Initializer,
-                   local_bundle_adjustment, bundle_adjustment)
+                   local_bundle_adjustment, bundle_adjustment, optimize_essential_graph)
 
 __all__ = ["OrbxError", "KP_DTYPE", "lib", "lib_path", "ORBextractor", "ORBmatcher", "ComputeStereoMatches",
            "FeatSet", "make_featset", "STAGES", "BowDatabase", "DeviceKeyFrame", "DeviceFrame", "MapPoints", "BowFrames", "KeyFrameDatabase", "ORBVocabulary", "ComputeDistinctiveDescriptors", "Rectifier", "UndistortKeyPoints",
@@ -36,4 +37,4 @@ __all__ = ["OrbxError", "KP_DTYPE", "lib", "lib_path", "ORBextractor", "ORBmatch
            "triangulate_pairs", "frame_set_depth", "frame_triangulate", "sim3_hypotheses", "sim3_hypotheses_batch", "sim3_max_error", "Sim3Ransac",
            "sim3_optimize", "sim3_optimize_batch", "sim3opt_camera_points", "pnp_hypotheses", "pnp_hypotheses_batch", "PnPRansac",
            "mono_init_hypotheses", "mono_init_reconstruct", "mono_init_initialize", "mono_init_draw_sets", "DUtilsRandom", "Initializer",
-           "local_bundle_adjustment", "bundle_adjustment"]
+           "local_bundle_adjustment", "bundle_adjustment", "optimize_essential_graph"]

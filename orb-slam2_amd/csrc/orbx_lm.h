@@ -1,5 +1,6 @@
 // orbx_lm.h — g2o's small pieces, one copy each, for the Levenberg kernels (k_pose_opt of orbx_pose.hip, k_sim3_opt of orbx_sim3opt.hip,
-// the k_lba_* of orbx_lba.hip) and for the host loop of the bundle adjustments (LbaRun::optimize):
+// the k_lba_* of orbx_lba.hip, the k_eg_* of orbx_essential.hip) and for the host loops of the bundle adjustments (LbaRun::optimize) and of
+// the essential graph:
 //   sums      block_sum: the fixed-order workgroup sum that hands every thread of a 4- or 16-wave workgroup the same bits
 //   solver    ldlt_small<N>: the dense (H + lambda I) x = b of the one-vertex problems; hu_max_diag<N>
 //   damping   lm_*: the rule of optimization_algorithm_levenberg.cpp (rho, lambda, ni, the two stops), host and device
@@ -8,7 +9,7 @@
 //             update; Cam, Obs and computeError of the mono / stereo reprojection edges
 // Two things are NOT here.  The pose Jacobians: k_pose_opt's (EdgeSE3ProjectXYZOnlyPose, products with invz) and jac_pose of orbx_lba.hip
 // (EdgeSE3ProjectXYZ, divisions) are different reference expressions with different bits.  And the Omega, Omega^2, R = (I + a Omega) + b
-// Omega^2 of the exponentials: pose_update below and sim3_exp of orbx_sim3opt.hip each keep their own.  Each fuses R with its own
+// Omega^2 of the exponentials: pose_update below and sim3_exp of orbx_sim3.h each keep their own.  Each fuses R with its own
 // theta < 1e-5 branch (pose_update fills V there, sim3_exp selects per entry next to its A, B, C), and a helper for Omega and Omega^2
 // alone lets the compiler take -(o o) from the o o of theta: the same bits, one multiplication fewer, and so not the instructions these
 // kernels were measured with.
@@ -118,9 +119,10 @@ static __device__ __forceinline__ double hu_max_diag(const double *Hu)
 //        trial is the estimate; else lm_reject(..), the estimate goes back; qmax++ } while (rho < 0 && qmax < 10 [&& not stopped])
 //   if (lm_done(qmax, rho, ini_chi, cur_chi, stop_bad)) break
 // (The accept branch stays with the caller: its two sides are where the estimate is kept or restored.)
-static __host__ __device__ __forceinline__ void lm_start(double max_diag, double &lambda, double &ni, int &stop_bad)   // :93-97
+// user_lambda_init: setUserLambdaInit's value; computeLambdaInit (:166-180) returns it where it is > 0, else tau * the largest diagonal
+static __host__ __device__ __forceinline__ void lm_start(double max_diag, double &lambda, double &ni, int &stop_bad, double user_lambda_init = 0.0)   // :93-97
 {
-    lambda = 1e-5 * max_diag; ni = 2.0; stop_bad = 0;
+    lambda = user_lambda_init > 0.0 ? user_lambda_init : 1e-5 * max_diag; ni = 2.0; stop_bad = 0;
 }
 
 // scale: computeScale's sum of x_j (lambda x_j + b_j)

@@ -1,5 +1,5 @@
 // orbx_resident.h — what the files that work on resident handles share (orbx_resident.hip, orbx_proj.hip, orbx_pose.hip,
-// orbx_triangulate.hip, orbx_sim3.hip, orbx_sim3opt.hip, orbx_pnp.hip; not part of orbx_internal.h): the frame and map-point handles, the per-thread staging of one call
+// orbx_triangulate.hip, orbx_sim3.hip, orbx_sim3opt.hip, orbx_pnp.hip, orbx_lba.hip, orbx_essential.hip; not part of orbx_internal.h): the frame and map-point handles, the per-thread staging of one call
 // (CallCtx: reserve, upload, fetch, the blob cursor), the stream ordering behind a handle's last writer, and the launches of the two
 // kernels of orbx_resident.hip that the searches of orbx_proj.hip need.
 #pragma once

@@ -21,6 +21,7 @@
 // The arithmetic is restated in include/orbx.h (orbx_sim3_optimize) and, in numpy, in tests/sim3opt_model.py.
 #include "orbx_resident.h"
 #include "orbx_lm.h"
+#include "orbx_sim3.h"
 #include <float.h>
 #include <math.h>
 
@@ -38,7 +39,6 @@ struct Sim3OptOut { double S12[8], chi2[2]; int32_t n_corr, rounds, n_bad, more_
 
 namespace {
 
-struct Sim3 { double qx, qy, qz, qw, tx, ty, tz, s; };
 struct Cam4 { double fx, fy, cx, cy; };
 struct Pair { double p1x, p1y, p1z, p2x, p2y, p2z, m1x, m1y, w1, m2x, m2y, w2; };
 
@@ -51,94 +51,6 @@ __device__ __forceinline__ Pair pair_load(const Sim3OptJob &J, int i)
     p.m1x = (double)J.x1[i]; p.m1y = (double)J.y1[i]; p.w1 = (double)J.w1[i];
     p.m2x = (double)J.x2[i]; p.m2y = (double)J.y2[i]; p.w2 = (double)J.w2[i];
     return p;
-}
-
-// sim3.h:144-146: s * (r * xyz) + t (r is NOT a unit quaternion here)
-__device__ __forceinline__ void sim3_map(const Sim3 &S, double X, double Y, double Z, double &x, double &y, double &z)
-{
-    quat_rot(S.qx, S.qy, S.qz, S.qw, X, Y, Z, x, y, z);
-    x = S.s * x + S.tx; y = S.s * y + S.ty; z = S.s * z + S.tz;
-}
-
-// sim3.h:233-236: Sim3(r.conjugate(), r.conjugate() * ((-1. / s) * t), 1. / s)
-__device__ __forceinline__ Sim3 sim3_inverse(const Sim3 &S)
-{
-    Sim3 I;
-    I.qx = -S.qx; I.qy = -S.qy; I.qz = -S.qz; I.qw = S.qw;
-    const double k = -1.0 / S.s;
-    quat_rot(I.qx, I.qy, I.qz, I.qw, k * S.tx, k * S.ty, k * S.tz, I.tx, I.ty, I.tz);
-    I.s = 1.0 / S.s;
-    return I;
-}
-
-// sim3.h:266-272: r = a.r * b.r (no normalisation, unlike SE3Quat), t = a.s * (a.r * b.t) + a.t, s = a.s * b.s
-__device__ __forceinline__ Sim3 sim3_mul(const Sim3 &a, const Sim3 &b)
-{
-    Sim3 N;
-    quat_mul(a.qx, a.qy, a.qz, a.qw, b.qx, b.qy, b.qz, b.qw, N.qx, N.qy, N.qz, N.qw);
-    double x, y, z;
-    quat_rot(a.qx, a.qy, a.qz, a.qw, b.tx, b.ty, b.tz, x, y, z);
-    N.tx = a.s * x + a.tx; N.ty = a.s * y + a.ty; N.tz = a.s * z + a.tz;
-    N.s = a.s * b.s;
-    return N;
-}
-
-// sim3.h:70-142: Sim3(Vector7d), u[0..2] rotation, u[3..5] translation, u[6] log scale; r = Quaterniond(R) is not normalised
-__device__ __forceinline__ Sim3 sim3_exp(const double u[7])
-{
-    const double o0 = u[0], o1 = u[1], o2 = u[2], sigma = u[6];
-    const double theta = sqrt((o0 * o0 + o1 * o1) + o2 * o2);
-    const double O[9] = { 0.0, -o2, o1, o2, 0.0, -o0, -o1, o0, 0.0 };
-    double O2[9], R[9];
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-#pragma unroll
-        for (int c = 0; c < 3; c++) O2[3 * r + c] = (O[3 * r] * O[c] + O[3 * r + 1] * O[3 + c]) + O[3 * r + 2] * O[6 + c];
-    Sim3 E;
-    E.s = exp(sigma);
-    const double eps = 0.00001;
-    const bool small_theta = theta < eps;
-    double A, B, C, ra = 1.0, rb = 1.0;   // R = (I + ra Omega) + rb Omega2; ra = rb = 1 written without the products when theta < eps
-    if (!small_theta) {
-        ra = sin(theta) / theta;
-        rb = (1.0 - cos(theta)) / (theta * theta);
-    }
-    if (fabs(sigma) < eps) {
-        C = 1.0;
-        if (small_theta) {
-            A = 1.0 / 2.0; B = 1.0 / 6.0;
-        } else {
-            const double theta2 = theta * theta;
-            A = (1.0 - cos(theta)) / theta2;
-            B = (theta - sin(theta)) / (theta2 * theta);
-        }
-    } else {
-        C = (E.s - 1.0) / sigma;
-        if (small_theta) {
-            const double sigma2 = sigma * sigma;
-            A = ((sigma - 1.0) * E.s + 1.0) / sigma2;
-            B = ((0.5 * sigma2 - sigma + 1.0) * E.s) / (sigma2 * sigma);
-        } else {
-            const double a = E.s * sin(theta), b = E.s * cos(theta);
-            const double theta2 = theta * theta, sigma2 = sigma * sigma;
-            const double c = theta2 + sigma2;
-            A = (a * sigma + (1.0 - b) * theta) / (theta * c);
-            B = (C - ((b - 1.0) * sigma + a * theta) / c) * 1.0 / theta2;
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 9; k++) {
-        const double id = k % 4 == 0 ? 1.0 : 0.0;
-        R[k] = small_theta ? (id + O[k]) + O2[k] : (id + ra * O[k]) + rb * O2[k];
-    }
-    quat_from_matrix(R, E.qx, E.qy, E.qz, E.qw);
-    double W[9];   // W = A Omega + B Omega2 + C I
-#pragma unroll
-    for (int k = 0; k < 9; k++) W[k] = (A * O[k] + B * O2[k]) + (k % 4 == 0 ? C : 0.0);
-    E.tx = (W[0] * u[3] + W[1] * u[4]) + W[2] * u[5];
-    E.ty = (W[3] * u[3] + W[4] * u[4]) + W[5] * u[5];
-    E.tz = (W[6] * u[3] + W[7] * u[4]) + W[8] * u[5];
-    return E;
 }
 
 // error = obs - cam_map(project(T.map(P))) (types_seven_dof_expmap.h:138-167); returns chi2 = e . (w e)
@@ -157,18 +69,6 @@ __device__ __forceinline__ void pair_chi2(const Pair &p, const Sim3 &S, const Si
     double e0, e1;
     c12 = edge_err(S, K1, p.p2x, p.p2y, p.p2z, p.m1x, p.m1y, p.w1, e0, e1);
     c21 = edge_err(Si, K2, p.p1x, p.p1y, p.p1z, p.m2x, p.m2y, p.w2, e0, e1);
-}
-
-__device__ __forceinline__ Sim3 xf_load(const double *xf)
-{
-    Sim3 T;
-    T.qx = xf[0]; T.qy = xf[1]; T.qz = xf[2]; T.qw = xf[3]; T.tx = xf[4]; T.ty = xf[5]; T.tz = xf[6]; T.s = xf[7];
-    return T;
-}
-
-__device__ __forceinline__ void xf_store(double *xf, const Sim3 &T)
-{
-    xf[0] = T.qx; xf[1] = T.qy; xf[2] = T.qz; xf[3] = T.qw; xf[4] = T.tx; xf[5] = T.ty; xf[6] = T.tz; xf[7] = T.s;
 }
 
 // one edge into the system: its error and chi2 at T0, the central-difference Jacobian from the 14 transforms at xf (xf[16 * d] is

@@ -155,6 +155,25 @@ class BaReport(C.Structure):
                 ("chi2", C.c_double), ("lambda_", C.c_double), ("lambda_init", C.c_double)]
 
 
+class EgProblem(C.Structure):
+    """orbx_eg_problem (include/orbx.h)"""
+    _fields_ = [("n_kf", C.c_int), ("Tcw", C.c_void_p), ("fixed", C.c_void_p), ("corrected", C.c_void_p), ("noncorrected", C.c_void_p),
+                ("n_corrected", C.c_int), ("n_noncorrected", C.c_int), ("S_corrected", C.c_void_p), ("S_noncorrected", C.c_void_p),
+                ("n_edges", C.c_int), ("edge_i", C.c_void_p), ("edge_j", C.c_void_p), ("edge_kind", C.c_void_p),
+                ("n_points", C.c_int), ("Xw", C.c_void_p), ("point_ref", C.c_void_p), ("fix_scale", C.c_int)]
+
+
+class EgOptions(C.Structure):
+    """orbx_eg_options (include/orbx.h)"""
+    _fields_ = [("iterations", C.c_int)]
+
+
+class EgReport(C.Structure):
+    """orbx_eg_report (include/orbx.h)"""
+    _fields_ = [("iterations", C.c_int), ("trials", C.c_int), ("n_free", C.c_int), ("n_solve_failed", C.c_int),
+                ("chi2_start", C.c_double), ("chi2", C.c_double), ("lambda_", C.c_double)]
+
+
 class PoseJob(C.Structure):
     """orbx_pose_job (include/orbx.h)"""
     _fields_ = [("obs", C.POINTER(PoseObs)), ("cam", C.c_void_p), ("Tcw", C.c_void_p), ("Tcw_out", C.c_void_p),
@@ -336,6 +355,8 @@ def lib():
     L.orbx_local_bundle_adjustment.argtypes = [i, C.POINTER(LbaProblem), C.POINTER(LbaOptions), vp, vp, vp, vp, vp, C.POINTER(LbaReport)]
     L.orbx_debug_lba_profile.argtypes = [i, vp, vp]
     L.orbx_bundle_adjustment.argtypes = [i, C.POINTER(LbaProblem), C.POINTER(BaOptions), vp, vp, vp, vp, vp, C.POINTER(BaReport)]
+    L.orbx_optimize_essential_graph.argtypes = [i, C.POINTER(EgProblem), C.POINTER(EgOptions), vp, vp, vp, vp, C.POINTER(EgReport)]
+    L.orbx_debug_eg_profile.argtypes = [i, vp, vp]
     L.orbx_debug_ldlt_solve.argtypes = [i, i, vp, vp, vp, i, C.POINTER(C.c_int)]
     L.orbx_debug_set_lba_solver.argtypes = [i]
     L.orbx_debug_ldlt_panel_width.argtypes = []
@@ -1133,6 +1154,42 @@ def bundle_adjustment(problem, iterations=10, robust=True, stop=None, stop_at_tr
     return {"Tcw": Tcw, "Xw": Xw, "point_included": inc, "pose": pose, "point": point, "stopped": rep.stopped, "iterations": rep.iterations,
             "trials": rep.trials, "n_active_kf": rep.n_active_kf, "n_active_points": rep.n_active_points, "chi2": rep.chi2,
             "lambda": rep.lambda_, "lambda_init": rep.lambda_init}
+
+
+def _eg_problem(problem, who):
+    """problem = dict(Tcw [K][4][4], fixed [K], corrected [K], noncorrected [K], S_corrected [.][8], S_noncorrected [.][8], edge_i, edge_j,
+    edge_kind [E], Xw [P][3], point_ref [P], fix_scale) -> (EgProblem, arrays)"""
+    Tcw = np.ascontiguousarray(problem["Tcw"], np.float32).reshape(-1, 16)
+    K = len(Tcw)
+    fixed = np.ascontiguousarray(problem["fixed"], np.uint8).reshape(-1)
+    cor = np.ascontiguousarray(problem["corrected"], np.int32).reshape(-1)
+    non = np.ascontiguousarray(problem["noncorrected"], np.int32).reshape(-1)
+    Sc = np.ascontiguousarray(problem["S_corrected"], np.float64).reshape(-1, 8)
+    Sn = np.ascontiguousarray(problem["S_noncorrected"], np.float64).reshape(-1, 8)
+    ei = np.ascontiguousarray(problem["edge_i"], np.int32).reshape(-1)
+    ej = np.ascontiguousarray(problem["edge_j"], np.int32).reshape(-1)
+    kind = np.ascontiguousarray(problem["edge_kind"], np.uint8).reshape(-1)
+    Xw = np.ascontiguousarray(problem["Xw"], np.float32).reshape(-1, 3)
+    ref = np.ascontiguousarray(problem["point_ref"], np.int32).reshape(-1)
+    if len(fixed) != K or len(cor) != K or len(non) != K or len(ej) != len(ei) or len(kind) != len(ei) or len(ref) != len(Xw):
+        raise OrbxError(-1, f"{who}: Tcw, fixed, corrected and noncorrected need one entry per keyframe, the edge arrays one per edge, point_ref one per point")
+    keep = [Tcw, fixed, cor, non, Sc, Sn, ei, ej, kind, Xw, ref]
+    return EgProblem(K, _p(Tcw), _p(fixed), _p(cor), _p(non), len(Sc), len(Sn), _p(Sc), _p(Sn), len(ei), _p(ei), _p(ej), _p(kind), len(Xw), _p(Xw),
+                     _p(ref), int(bool(problem["fix_scale"]))), keep
+
+
+def optimize_essential_graph(problem, iterations=20, device=0):
+    """Optimizer::OptimizeEssentialGraph (orbx_optimize_essential_graph): problem = dict(Tcw [K][4][4], fixed [K] (exactly one set: pLoopKF),
+    corrected / noncorrected [K] (index into S_corrected / S_noncorrected [.][8] qx qy qz qw tx ty tz s, or -1), edge_i, edge_j, edge_kind [E]
+    (0 loop-connection edge, 1 normal edge), Xw [P][3], point_ref [P], fix_scale) -> dict(Tcw [K][4][4], Xw [P][3], S [K][8], point [P][3],
+    iterations, trials, n_free, n_solve_failed, chi2_start, chi2, lambda)"""
+    pr, keep = _eg_problem(problem, "optimize_essential_graph")
+    opt = EgOptions(int(iterations))
+    Tcw = np.zeros((pr.n_kf, 4, 4), np.float32); Xw = np.zeros((pr.n_points, 3), np.float32)
+    S = np.zeros((pr.n_kf, 8), np.float64); point = np.zeros((pr.n_points, 3), np.float64); rep = EgReport()
+    _check(lib().orbx_optimize_essential_graph(device, C.byref(pr), C.byref(opt), _p(Tcw), _p(Xw), _p(S), _p(point), C.byref(rep)))
+    return {"Tcw": Tcw, "Xw": Xw, "S": S, "point": point, "iterations": rep.iterations, "trials": rep.trials, "n_free": rep.n_free,
+            "n_solve_failed": rep.n_solve_failed, "chi2_start": rep.chi2_start, "chi2": rep.chi2, "lambda": rep.lambda_}
 
 
 def ldlt_solve(S, b, form, x0=None, device=0):

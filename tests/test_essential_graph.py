@@ -1,0 +1,145 @@
+"""orbx_optimize_essential_graph (Optimizer::OptimizeEssentialGraph, reference src/Optimizer.cc:885-1153) against tests/eg_model.py on the
+scenes of tests/eg_scene.py.
+
+Exact: n_free; Tcw == float32 of the double recovery of the returned S, Xw == float32(point); the fixed keyframe and a keyframe without an
+edge bit for bit; under fix_scale every scale; a second call returns the same bytes.  iterations and trials are printed, not compared:
+the central difference with delta = 1e-9 multiplies last-bit noise by 5e8, and a (1 - cos theta) in front of it by more, so whether a
+trial is accepted is often rounding.  S, point and chi2 are compared in double under a MEASURED bound:
+
+    python tools/eg_spread.py
+    SPREAD_S = 1.476e-04  SPREAD_POINT = 1.919e-04  SPREAD_CHI2 = 9.938e-06  (x 64: 9.446e-03, 1.228e-02, 6.360e-04)
+
+is the largest disagreement of the model with itself across its variants (three summation orders, two seeded one-ulp nudges of sin, cos,
+exp, log and acos, the closed-form Jacobian where it applies: eg_scene.variants) over all the scenes.  The GPU gets 64 x that spread, the
+project's margin (tests/test_lba.py, tests/test_sim3opt.py): it differs from the model in several of those variants at once.  The spread is
+LARGE, and it is the function's, not the model's: with a free scale the reference's Sim3::log is wrong by a factor of the order 1 / sigma^3
+in one of its four branches (eg_scene.make), Levenberg then rejects ten steps in a row and the call ends where it happens to stand.  What
+the bound can and cannot tell from the truth:
+
+    python tools/eg_spread.py --mutations
+    MUTATION lambda_diag smallest change 8.834e-11 over 24 scenes       (above the bound in 6 of them, largest 0.53)
+    MUTATION x6_not_zeroed smallest change 1.691e-08 over 10 scenes     (above the bound in 4, largest 0.29)
+    MUTATION normal_from_vscw smallest change 5.165e-03 over 24 scenes  (above the bound in 19, above 16 x the bound in 13, largest 1.3)
+    MUTATION normalise smallest change 7.793e-15 over 24 scenes         (above the bound in none, largest 4.8e-05: the quaternions are unit
+                                                                         ones to rounding, so normalising them is no visible error)
+    MUTATION t_not_divided smallest change 6.567e-16 over 16 scenes     (above the bound in 14, largest 0.20)
+    MUTATION bta_untransposed smallest change 1.798e+308 over 1 scenes  (the system is no longer symmetric, every solve fails)
+
+The test asserts BOUND <= SMALLEST_VISIBLE_MUTATION / 16 over the mutations listed as visible below; the others are NOT told from the
+truth by the comparison with the model and are named here and in DESIGN.md: lambda_diag, x6_not_zeroed,
+normal_from_vscw (seen in most scenes, not in all), normalise, t_not_divided.  Two of them are
+held by exact checks instead: t_not_divided by Tcw == float32(recover(S)), x6_not_zeroed by the scale bits under fix_scale."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import eg_model as em
+import eg_scene as es
+from tools.eg_spread import s_diff
+from tools.lba_spread import points_diff
+from tools.pose_spread import chi2_diff
+
+f32 = np.float32
+SPREAD_S = 1.476e-04    # python tools/eg_spread.py (rounded up in the fourth digit)
+SPREAD_POINT = 1.919e-04
+SPREAD_CHI2 = 9.938e-06
+BOUND_S, BOUND_POINT, BOUND_CHI2 = 64 * SPREAD_S, 64 * SPREAD_POINT, 64 * SPREAD_CHI2
+VISIBLE_MUTATIONS = {"bta_untransposed": 1.798e+308}  # python tools/eg_spread.py --mutations: the smallest change of each mutation the bound can see
+SMALLEST_VISIBLE_MUTATION = min(VISIBLE_MUTATIONS.values())
+assert max(BOUND_S, BOUND_POINT, BOUND_CHI2) <= SMALLEST_VISIBLE_MUTATION / 16, "the bound could hide one of the errors listed as visible"
+
+_cache = {}
+
+
+def world(tag):
+    """a scene, its options and the model's answer (ascending order), computed once"""
+    if tag not in _cache:
+        pr, opts = es.case(tag)
+        _cache[tag] = (pr, opts, em.optimize(pr, order="asc", **opts))
+    return _cache[tag]
+
+
+def same_bytes(a, b):
+    return all(np.asarray(a[k]).tobytes() == np.asarray(b[k]).tobytes() for k in a)
+
+
+def edgeless(pr):
+    has = np.zeros(len(pr["fixed"]), bool)
+    has[pr["edge_i"]] = True
+    has[pr["edge_j"]] = True
+    return np.nonzero(~has)[0]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("tag", es.all_tags())
+def test_matches_the_model(pkg, tag):
+    pr, opts, exp = world(tag)
+    got = pkg.optimize_essential_graph(pr, **opts)
+    ds, dx, dc = s_diff(exp["S"], got["S"]), points_diff(exp["point"], got["point"]), chi2_diff(exp["chi2"], got["chi2"])
+    print(f"{tag}: free {got['n_free']} iterations {got['iterations']} model {exp['iterations']} trials {got['trials']} model {exp['trials']} "
+          f"failed solves {got['n_solve_failed']} chi2 {got['chi2_start']:.6g} -> {got['chi2']:.6g} model {exp['chi2']:.6g} lambda {got['lambda']:.3g} "
+          f"S {ds:.3e} (bound {BOUND_S:.3e}) point {dx:.3e} (bound {BOUND_POINT:.3e}) chi2 {dc:.3e} (bound {BOUND_CHI2:.3e})")
+    assert got["n_free"] == exp["n_free"] == len(pr["fixed"]) - 1
+    assert got["Tcw"][:, :3].tobytes() == em.recover(got["S"]).astype(f32).tobytes()
+    assert (got["Tcw"][:, 3] == np.array([0, 0, 0, 1], f32)).all()
+    assert got["Xw"].tobytes() == got["point"].astype(f32).tobytes()
+    k0 = int(np.nonzero(pr["fixed"])[0][0])
+    assert got["S"][k0].tobytes() == exp["vscw"][k0].tobytes()                 # the fixed keyframe: its vScw, bit for bit
+    for k in edgeless(pr):                                                     # exp(0) * S is exact
+        assert got["S"][k].tobytes() == exp["vscw"][k].tobytes(), k
+    if len(pr["edge_i"]) == 0 or opts["iterations"] == 0:
+        assert got["S"].tobytes() == exp["vscw"].tobytes() and (got["iterations"], got["trials"]) == (0, 0)
+    elif got["n_free"]:
+        assert got["chi2"] < got["chi2_start"]
+    if pr["fix_scale"]:
+        assert got["S"][:, 7].tobytes() == exp["vscw"][:, 7].tobytes()
+    assert ds <= BOUND_S and dx <= BOUND_POINT and dc <= BOUND_CHI2
+    if tag != es.tag_of(es.BIG, 0) and tag != es.tag_of(es.BIG, 1):
+        assert same_bytes(got, pkg.optimize_essential_graph(pr, **opts))       # a call is byte-reproducible
+
+
+@pytest.mark.gpu
+def test_refusals(pkg):
+    L = pkg.lib()
+    base = world("5-free")[0]
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+
+    def call(problem=base, null=(), drop=(), fields=None, iterations=20):
+        pr, keep = pkg.orbx._eg_problem(problem, "test")
+        for k, v in (fields or {}).items():
+            setattr(pr, k, v)
+        for k in null:
+            setattr(pr, k, None)
+        T = np.zeros((max(pr.n_kf, 1), 16), f32); X = np.zeros((max(pr.n_points, 1), 3), f32)
+        outs = dict(T=p(T), X=p(X))
+        for k in drop:
+            outs[k] = None
+        opt = pkg.orbx.EgOptions(iterations)
+        return L.orbx_optimize_essential_graph(0, None if "problem" in drop else C.byref(pr), None if "opt" in drop else C.byref(opt), outs["T"],
+                                               outs["X"], None, None, None)
+
+    before = L.orbx_debug_thread_contexts()
+    for d in ("problem", "T", "X"):
+        assert call(drop=(d,)) == -1, d
+    for f in ("Tcw", "fixed", "corrected", "noncorrected", "S_corrected", "S_noncorrected", "edge_i", "edge_j", "edge_kind", "Xw", "point_ref"):
+        assert call(null=(f,)) == -1, f
+    assert call(iterations=-1) == -1 and "iterations" in L.orbx_last_error().decode()
+    assert call(fields=dict(n_kf=0)) == -1 and call(fields=dict(n_points=-1)) == -1 and call(fields=dict(n_edges=-1)) == -1
+    assert call(fields=dict(n_kf=4097)) == -2 and call(fields=dict(n_points=(1 << 20) + 1)) == -2 and call(fields=dict(n_edges=(1 << 18) + 1)) == -2
+    E, K = len(base["edge_i"]), len(base["fixed"])
+    for key, val in (("edge_i", K), ("edge_i", -1), ("edge_j", K), ("edge_j", -1), ("point_ref", K), ("point_ref", -1), ("corrected", -2),
+                     ("corrected", len(base["S_corrected"])), ("noncorrected", len(base["S_noncorrected"])), ("edge_kind", 2)):
+        bad = dict(base); bad[key] = base[key].copy(); bad[key][len(bad[key]) // 2] = val
+        assert call(bad) == -1, (key, val)
+    bad = dict(base); bad["edge_i"] = base["edge_i"].copy(); bad["edge_i"][E // 2] = base["edge_j"][E // 2]     # edge_i == edge_j
+    assert call(bad) == -1 and "equal" in L.orbx_last_error().decode()
+    for fx in (np.zeros(K, np.uint8), np.array([1, 1] + [0] * (K - 2), np.uint8)):                               # none fixed, two fixed
+        bad = dict(base); bad["fixed"] = fx
+        assert call(bad) == -1 and "exactly one" in L.orbx_last_error().decode()
+    many = dict(base)                                                                                            # 1537 free keyframes
+    for k in ("Tcw", "fixed", "corrected", "noncorrected"):
+        many[k] = np.concatenate([base[k]] + [base[k][1:2]] * (1538 - K))
+    assert call(many) == -2 and "1536" in L.orbx_last_error().decode()
+    assert L.orbx_debug_thread_contexts() == before                            # refused before any device work: nothing was set up
+    assert call() == 0 and call(drop=("opt",)) == 0                            # the arguments are good (opt, S_out, point_out, report NULL)
