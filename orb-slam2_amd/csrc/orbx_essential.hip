@@ -1,7 +1,7 @@
 // orbx_essential.hip — Optimizer::OptimizeEssentialGraph (reference src/Optimizer.cc:885-1153) between :907 and :1152: a pose graph of 7-DoF
 // VertexSim3Expmap vertices and binary EdgeSim3 edges, no points, then the correction of the map points.  The contract, operation by
 // operation, is include/orbx.h (orbx_optimize_essential_graph); the numpy restatement is tests/eg_model.py.  The Levenberg loop runs on the
-// host as LbaRun::optimize does (orbx_lba.hip), one status record per linearisation and per trial, the rule itself from orbx_lm.h; the
+// host as the bundle adjustments' does (lm_host_loop of orbx_lm.h), one status record per linearisation and per trial; the
 // system is dense, 7 x the free keyframes, and is solved by the panels of orbx_ldlt.hip.  fp64 on the plain VALU, no atomics.
 //
 //   k_eg_setup        vScw of every keyframe (the start estimates), the measurement of every edge, the 14 transforms Sim3(+-delta e_d)
@@ -318,34 +318,9 @@ __global__ __launch_bounds__(256) void k_eg_points(Eg G)
 
 // orbx_debug_eg_profile: as orbx_debug_lba_profile, for the calling thread's orbx_optimize_essential_graph calls (tools/bench_eg.py)
 enum { EG_K_SETUP, EG_K_LINEARIZE, EG_K_ROWS, EG_K_REDUCE, EG_K_FILL, EG_K_SOLVE, EG_K_UPDATE, EG_K_ERRORS, EG_K_FINISH, EG_K_POINTS, EG_K_COUNT };
-struct EgProf { bool on = false; double ms[EG_K_COUNT] = {}; int n[EG_K_COUNT] = {}; };
-static thread_local EgProf g_eg_prof;
+static thread_local LaunchProfile<EG_K_COUNT> g_eg_prof;
 
-template <class F>
-static inline void eg_launch(int slot, CallCtx *c, F launch)
-{
-    if (!c) { launch(); return; }
-    float ms = 0.f;
-    (void)hipEventRecord(c->ev_a, c->stream);
-    launch();
-    (void)hipEventRecord(c->ev_b, c->stream);
-    if (hipEventSynchronize(c->ev_b) == hipSuccess && hipEventElapsedTime(&ms, c->ev_a, c->ev_b) == hipSuccess) { g_eg_prof.ms[slot] += ms; g_eg_prof.n[slot]++; }
-}
-
-extern "C" int orbx_debug_eg_profile(int enable, double *ms, int32_t *launches)
-{
-    if (enable) {
-        g_eg_prof = EgProf();
-        g_eg_prof.on = true;
-        return ORBX_OK;
-    }
-    g_eg_prof.on = false;
-    for (int k = 0; k < EG_K_COUNT; k++) {
-        if (ms) ms[k] = g_eg_prof.ms[k];
-        if (launches) launches[k] = g_eg_prof.n[k];
-    }
-    return EG_K_COUNT;
-}
+extern "C" int orbx_debug_eg_profile(int enable, double *ms, int32_t *launches) { return g_eg_prof.entry(enable, ms, launches); }
 
 static int eg_check(const char *who, const orbx_eg_problem *p, const orbx_eg_options *opt, const float *Tcw_out, const float *Xw_out, int *n_free)
 {
@@ -388,8 +363,6 @@ static int eg_check(const char *who, const orbx_eg_problem *p, const orbx_eg_opt
     *n_free = p->n_kf - 1;
     return ORBX_OK;
 }
-
-static inline unsigned eg_grid(int n) { return (unsigned)((n + 255) / 256 > 0 ? (n + 255) / 256 : 1); }
 
 extern "C" int orbx_optimize_essential_graph(int device, const orbx_eg_problem *p, const orbx_eg_options *opt, float *Tcw_out, float *Xw_out,
                                              double *S_out, double *point_out, orbx_eg_report *report)
@@ -442,7 +415,7 @@ extern "C" int orbx_optimize_essential_graph(int device, const orbx_eg_problem *
     if (pedge.empty()) pedge.push_back(0);
     if (pair.empty()) { pair.push_back(0); pair.push_back(0); }
 
-    CallCtx *c, *pc = nullptr;
+    CallCtx *c, *pc;
     if ((rc = orbx_call_ctx(device, &c))) return rc;
     BlobCursor b = { nullptr, nullptr, 0 };
     const size_t o_T = b.take(64 * K), o_fix = b.take(K), o_cor = b.take(4 * K), o_non = b.take(4 * K), o_Sc = b.take(64 * NC), o_Sn = b.take(64 * NN),
@@ -467,11 +440,7 @@ extern "C" int orbx_optimize_essential_graph(int device, const orbx_eg_problem *
     memcpy(h + o_vedge, vedge.data(), 4 * vedge.size()); memcpy(h + o_poff, poff.data(), 4 * poff.size());
     memcpy(h + o_pedge, pedge.data(), 4 * pedge.size()); memcpy(h + o_pair, pair.data(), 4 * pair.size());
     if ((rc = call_upload(c, blob))) return rc;
-    if (g_eg_prof.on) {
-        if (!c->ev_a) ORBX_HIP(hipEventCreate(&c->ev_a));
-        if (!c->ev_b) ORBX_HIP(hipEventCreate(&c->ev_b));
-        pc = c;
-    }
+    if ((rc = g_eg_prof.ctx(c, &pc))) return rc;
 
     Eg G;
     memset(&G, 0, sizeof G);
@@ -496,55 +465,36 @@ extern "C" int orbx_optimize_essential_graph(int device, const orbx_eg_problem *
     rep.n_free = n_free;
     ORBX_HIP(hipMemsetAsync(G.status, 0, 64, s));
     if (N) ORBX_HIP(hipMemsetAsync(G.x, 0, 8 * N, s));   // the solver's x before the first solve: zeros, as in the other solvers
-    eg_launch(EG_K_SETUP, pc, [&] { hipLaunchKernelGGL(k_eg_setup, dim3(eg_grid((int)std::max(std::max(K, E), (size_t)14))), dim3(256), 0, s, G); });
+    g_eg_prof.launch(EG_K_SETUP, pc, [&] { hipLaunchKernelGGL(k_eg_setup, dim3(grid256((int)std::max(std::max(K, E), (size_t)14))), dim3(256), 0, s, G); });
 
     int cur = 0;
-    const double *hs = (const double *)c->h_out;
-    double lambda = 0.0, ni = 2.0, cur_chi = 0.0;
-    int stop_bad = 0;
     // no edge, or no free vertex: optimize() finds no active vertex and returns before the first iteration (sparse_optimizer.cpp:341-345)
-    for (int it = 0; it < iterations && E > 0 && F > 0; it++) {
-        eg_launch(EG_K_LINEARIZE, pc, [&] { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_eg_edges<true>), dim3((unsigned)((E + 7) / 8)), dim3(256), 0, s, G, cur); });
-        eg_launch(EG_K_ROWS, pc, [&] { hipLaunchKernelGGL(k_eg_rows, dim3((unsigned)(F + NP)), dim3(64), 0, s, G); });
-        eg_launch(EG_K_REDUCE, pc, [&] { hipLaunchKernelGGL(k_eg_reduce, dim3(1), dim3(256), 0, s, G, 0); });
-        if ((rc = call_fetch(c, 64))) return rc;
-        cur_chi = hs[0];
-        const double ini_chi = cur_chi;
-        if (it == 0) {
-            rep.chi2_start = cur_chi;
-            lm_start(hs[2], lambda, ni, stop_bad, 1e-16);   // setUserLambdaInit(1e-16), :899
-        }
-        double rho = 0.0;
-        int qmax = 0;
-        do {
-            eg_launch(EG_K_FILL, pc, [&] {
-                hipLaunchKernelGGL(k_eg_fill, dim3(eg_grid((int)N), (unsigned)N), dim3(256), 0, s, G, lambda, 0);
+    const LmRun r = lm_host_loop(
+        E > 0 && F > 0 ? iterations : 0, 1e-16,   // setUserLambdaInit(1e-16), :899
+        [&] {
+            g_eg_prof.launch(EG_K_LINEARIZE, pc, [&] { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_eg_edges<true>), dim3((unsigned)((E + 7) / 8)), dim3(256), 0, s, G, cur); });
+            g_eg_prof.launch(EG_K_ROWS, pc, [&] { hipLaunchKernelGGL(k_eg_rows, dim3((unsigned)(F + NP)), dim3(64), 0, s, G); });
+            g_eg_prof.launch(EG_K_REDUCE, pc, [&] { hipLaunchKernelGGL(k_eg_reduce, dim3(1), dim3(256), 0, s, G, 0); });
+            return call_fetch(c, 64);
+        },
+        [&](double lambda) {
+            g_eg_prof.launch(EG_K_FILL, pc, [&] {
+                hipLaunchKernelGGL(k_eg_fill, dim3(grid256((int)N), (unsigned)N), dim3(256), 0, s, G, lambda, 0);
                 hipLaunchKernelGGL(k_eg_fill, dim3((unsigned)(F + NP)), dim3(64), 0, s, G, lambda, 1);
             });
-            eg_launch(EG_K_SOLVE, pc, [&] { orbx_ldlt_panel_launch(G.S, G.y, G.x, G.status + 3, (int)N, s); });
-            eg_launch(EG_K_UPDATE, pc, [&] { hipLaunchKernelGGL(k_eg_update, dim3(eg_grid((int)K)), dim3(256), 0, s, G, cur, lambda); });
-            eg_launch(EG_K_ERRORS, pc, [&] { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_eg_edges<false>), dim3(eg_grid((int)E)), dim3(256), 0, s, G, 1 - cur); });
-            eg_launch(EG_K_REDUCE, pc, [&] { hipLaunchKernelGGL(k_eg_reduce, dim3(1), dim3(256), 0, s, G, 1); });
-            if ((rc = call_fetch(c, 64))) return rc;
-            rep.trials++;
-            const bool ok = hs[3] != 0.0;
-            rep.n_solve_failed += !ok;
-            const double temp_chi = ok ? hs[0] : DBL_MAX;
-            rho = lm_gain(cur_chi, temp_chi, hs[1]);
-            if (lm_accepts(rho, temp_chi)) {
-                lm_accept(rho, lambda, ni);
-                cur_chi = temp_chi;
-                cur = 1 - cur;   // discardTop(): the trial copy is the estimate
-            } else lm_reject(lambda, ni);   // pop()
-            qmax++;
-        } while (rho < 0.0 && qmax < 10);
-        rep.iterations++;
-        if (lm_done(qmax, rho, ini_chi, cur_chi, stop_bad)) break;
-    }
-    rep.chi2 = cur_chi; rep.lambda = lambda;
+            g_eg_prof.launch(EG_K_SOLVE, pc, [&] { orbx_ldlt_panel_launch(G.S, G.y, G.x, G.status + 3, (int)N, s); });
+            g_eg_prof.launch(EG_K_UPDATE, pc, [&] { hipLaunchKernelGGL(k_eg_update, dim3(grid256((int)K)), dim3(256), 0, s, G, cur, lambda); });
+            g_eg_prof.launch(EG_K_ERRORS, pc, [&] { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_eg_edges<false>), dim3(grid256((int)E)), dim3(256), 0, s, G, 1 - cur); });
+            g_eg_prof.launch(EG_K_REDUCE, pc, [&] { hipLaunchKernelGGL(k_eg_reduce, dim3(1), dim3(256), 0, s, G, 1); });
+            return call_fetch(c, 64);
+        },
+        [&] { return (const double *)c->h_out; }, [] { return false; }, [&] { cur = 1 - cur; });
+    if (r.rc) return r.rc;
+    rep.iterations = r.iterations; rep.trials = r.trials; rep.n_solve_failed = r.n_solve_failed;
+    rep.chi2_start = r.chi2_start; rep.chi2 = r.chi2; rep.lambda = r.lambda;
 
-    eg_launch(EG_K_FINISH, pc, [&] { hipLaunchKernelGGL(k_eg_finish, dim3(eg_grid((int)K)), dim3(256), 0, s, G, cur); });
-    if (P) eg_launch(EG_K_POINTS, pc, [&] { hipLaunchKernelGGL(k_eg_points, dim3(eg_grid((int)P)), dim3(256), 0, s, G); });
+    g_eg_prof.launch(EG_K_FINISH, pc, [&] { hipLaunchKernelGGL(k_eg_finish, dim3(grid256((int)K)), dim3(256), 0, s, G, cur); });
+    if (P) g_eg_prof.launch(EG_K_POINTS, pc, [&] { hipLaunchKernelGGL(k_eg_points, dim3(grid256((int)P)), dim3(256), 0, s, G); });
     if ((rc = call_fetch(c, out))) return rc;
     const uint8_t *ho = (const uint8_t *)c->h_out;
     memcpy(Tcw_out, ho + w_Tcw, 64 * K);

@@ -609,39 +609,13 @@ __global__ __launch_bounds__(256) void k_lba_classify(Lba L, int cur, int bit)
 
 // ---------------------------------------------------------------- host side (include/orbx.h: orbx_local_bundle_adjustment)
 
-// orbx_debug_lba_profile: while it is on for the calling thread, every launch of a call sits between two events and is waited for, and its
-// device time goes to its kernel's slot (tools/bench_lba.py: the per-kernel time per trial).  Slots: LBA_K_*.
+// orbx_debug_lba_profile: the LaunchProfile (orbx_resident.h) of the calling thread's bundle adjustments (tools/bench_lba.py: the per-kernel
+// time per trial).  Slots: LBA_K_*.
 enum { LBA_K_INIT, LBA_K_ACTIVE, LBA_K_LINEARIZE, LBA_K_KF, LBA_K_REDUCE, LBA_K_PREP, LBA_K_SCHUR, LBA_K_SOLVE, LBA_K_UPDATE, LBA_K_ERRORS,
        LBA_K_CLASSIFY, LBA_K_FINISH, LBA_K_COUNT };
-struct LbaProf { bool on = false; double ms[LBA_K_COUNT] = {}; int n[LBA_K_COUNT] = {}; };
-static thread_local LbaProf g_prof;
+static thread_local LaunchProfile<LBA_K_COUNT> g_prof;
 
-// the events are the context's (CallCtx::release gives them back with the thread's buffers); c == nullptr: not profiling
-template <class F>
-static inline void lba_launch(int slot, CallCtx *c, F launch)
-{
-    if (!c) { launch(); return; }
-    float ms = 0.f;
-    (void)hipEventRecord(c->ev_a, c->stream);
-    launch();
-    (void)hipEventRecord(c->ev_b, c->stream);
-    if (hipEventSynchronize(c->ev_b) == hipSuccess && hipEventElapsedTime(&ms, c->ev_a, c->ev_b) == hipSuccess) { g_prof.ms[slot] += ms; g_prof.n[slot]++; }
-}
-
-extern "C" int orbx_debug_lba_profile(int enable, double *ms, int32_t *launches)
-{
-    if (enable) {
-        g_prof = LbaProf();
-        g_prof.on = true;
-        return ORBX_OK;
-    }
-    g_prof.on = false;
-    for (int k = 0; k < LBA_K_COUNT; k++) {
-        if (ms) ms[k] = g_prof.ms[k];
-        if (launches) launches[k] = g_prof.n[k];
-    }
-    return LBA_K_COUNT;
-}
+extern "C" int orbx_debug_lba_profile(int enable, double *ms, int32_t *launches) { return g_prof.entry(enable, ms, launches); }
 
 // has_edge_out / has_point_out: the entry point's own per-edge (edge_flags) or per-point (point_included) output is there, or it has none
 static int lba_check(const char *who, const orbx_lba_problem *p, const float *Tcw_out, const float *Xw_out, bool has_edge_out,
@@ -755,8 +729,6 @@ static int lba_stage(CallCtx *c, const orbx_lba_problem *p, int max_rows, int x_
     return ORBX_OK;
 }
 
-static inline unsigned lba_grid(int n) { return (unsigned)((n + 255) / 256 > 0 ? (n + 255) / 256 : 1); }
-
 // the Levenberg loop of one call: the state that outlives a round, and optimize() = SparseOptimizer::optimize(max_it) on the active set
 struct LbaRun {
     CallCtx *c, *pc;       // pc: the context while orbx_debug_lba_profile is on, else nullptr
@@ -768,80 +740,51 @@ struct LbaRun {
     bool evaluated = false;
 
     // a thread per keyframe and point, per point, per edge, per anything k_lba_init clears
-    unsigned g_vert() const { return lba_grid(std::max(L.K, L.P)); }
-    unsigned g_pts() const { return lba_grid(L.P); }
-    unsigned g_edges() const { return lba_grid(L.E); }
-    unsigned g_all() const { return lba_grid(std::max(std::max(L.K, L.P), std::max(L.E, L.nx))); }
+    unsigned g_vert() const { return grid256(std::max(L.K, L.P)); }
+    unsigned g_pts() const { return grid256(L.P); }
+    unsigned g_edges() const { return grid256(L.E); }
+    unsigned g_all() const { return grid256(std::max(std::max(L.K, L.P), std::max(L.E, L.nx))); }
 
     bool stop_up() const { return (stop && *stop) || (dbg >= 0 && trials_total >= dbg); }
     int fetch_status() { return call_fetch(c, w_counts + 16); }
     const int32_t *counts() const { return (const int32_t *)((const uint8_t *)c->h_out + w_counts); }   // rows, active points, behind fetch_status
 
-    void init() { lba_launch(LBA_K_INIT, pc, [&] { hipLaunchKernelGGL(k_lba_init, dim3(g_all()), dim3(256), 0, c->stream, L); }); }
-    void finish() { lba_launch(LBA_K_FINISH, pc, [&] { hipLaunchKernelGGL(k_lba_finish, dim3(g_vert()), dim3(256), 0, c->stream, L, cur); }); }
+    void init() { g_prof.launch(LBA_K_INIT, pc, [&] { hipLaunchKernelGGL(k_lba_init, dim3(g_all()), dim3(256), 0, c->stream, L); }); }
+    void finish() { g_prof.launch(LBA_K_FINISH, pc, [&] { hipLaunchKernelGGL(k_lba_finish, dim3(g_vert()), dim3(256), 0, c->stream, L, cur); }); }
 
-    int optimize(int rows, int npts, int max_it, int robust, int *iterations, int *trials, double *chi2, double *lambda_end, double *lambda_init)
+    // the launches of one linearisation and of one trial under lm_host_loop (orbx_lm.h); without an active point no iteration runs
+    LmRun optimize(int rows, int npts, int max_it, int robust)
     {
-        int rc;
         hipStream_t s = c->stream;
-        const double *hs = (const double *)c->h_out;
-        double lambda = 0.0, ni = 2.0, cur_chi = 0.0;
-        int stop_bad = 0;
-        for (int it = 0; it < max_it && npts > 0 && !stop_up(); it++) {   // sparse_optimizer.cpp:356, :376
-            lba_launch(LBA_K_LINEARIZE, pc, [&] { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lba_points<true>), dim3(g_pts()), dim3(256), 0, s, L, cur, robust); });
-            if (rows) lba_launch(LBA_K_KF, pc, [&] { hipLaunchKernelGGL(k_lba_kf, dim3(rows), dim3(256), 0, s, L, cur, robust); });
-            lba_launch(LBA_K_REDUCE, pc, [&] { hipLaunchKernelGGL(k_lba_reduce, dim3(1), dim3(1024), 0, s, L, 0, 0.0); });
-            if ((rc = fetch_status())) return rc;
-            evaluated = true;
-            cur_chi = hs[0];
-            const double ini_chi = cur_chi;
-            if (it == 0) {
-                lm_start(hs[2], lambda, ni, stop_bad);
-                if (lambda_init) *lambda_init = lambda;
-            }
-            double rho = 0.0;
-            int qmax = 0;
-            do {
-                lba_launch(LBA_K_PREP, pc, [&] { hipLaunchKernelGGL(k_lba_prep, dim3(g_pts()), dim3(256), 0, s, L, lambda); });
+        const LmRun r = lm_host_loop(
+            npts > 0 ? max_it : 0, 0.0,
+            [&] {
+                g_prof.launch(LBA_K_LINEARIZE, pc, [&] { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lba_points<true>), dim3(g_pts()), dim3(256), 0, s, L, cur, robust); });
+                if (rows) g_prof.launch(LBA_K_KF, pc, [&] { hipLaunchKernelGGL(k_lba_kf, dim3(rows), dim3(256), 0, s, L, cur, robust); });
+                g_prof.launch(LBA_K_REDUCE, pc, [&] { hipLaunchKernelGGL(k_lba_reduce, dim3(1), dim3(1024), 0, s, L, 0, 0.0); });
+                return fetch_status();
+            },
+            [&](double lambda) {
+                g_prof.launch(LBA_K_PREP, pc, [&] { hipLaunchKernelGGL(k_lba_prep, dim3(g_pts()), dim3(256), 0, s, L, lambda); });
                 if (rows) {
-                    lba_launch(LBA_K_SCHUR, pc, [&] { hipLaunchKernelGGL(k_lba_schur, dim3(rows, rows), dim3(256), 0, s, L, lambda); });
-                    lba_launch(LBA_K_SOLVE, pc, [&] {
+                    g_prof.launch(LBA_K_SCHUR, pc, [&] { hipLaunchKernelGGL(k_lba_schur, dim3(rows, rows), dim3(256), 0, s, L, lambda); });
+                    g_prof.launch(LBA_K_SOLVE, pc, [&] {
                         if (solver == 0) hipLaunchKernelGGL(k_lba_solve, dim3(1), dim3(1024), 0, s, L);
                         else orbx_ldlt_panel_launch(L.S, L.bS, L.x, L.status + 3, 6 * rows, s);
                     });
                 }
-                lba_launch(LBA_K_UPDATE, pc, [&] { hipLaunchKernelGGL(k_lba_update, dim3(g_vert()), dim3(256), 0, s, L, cur); });
-                lba_launch(LBA_K_ERRORS, pc, [&] { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lba_points<false>), dim3(g_pts()), dim3(256), 0, s, L, 1 - cur, robust); });
-                lba_launch(LBA_K_REDUCE, pc, [&] { hipLaunchKernelGGL(k_lba_reduce, dim3(1), dim3(1024), 0, s, L, 1, lambda); });
-                if ((rc = fetch_status())) return rc;
-                trials_total++; (*trials)++;
-                const double temp_chi = hs[3] != 0.0 ? hs[0] : DBL_MAX;
-                rho = lm_gain(cur_chi, temp_chi, hs[1]);
-                if (lm_accepts(rho, temp_chi)) {
-                    lm_accept(rho, lambda, ni);
-                    cur_chi = temp_chi;
-                    cur = 1 - cur;   // discardTop(): the trial copy is the estimate
-                } else lm_reject(lambda, ni);   // pop(): the estimates go back, the edges keep the errors of the rejected state
-                qmax++;
-            } while (rho < 0.0 && qmax < 10 && !stop_up());
-            (*iterations)++;
-            if (lm_done(qmax, rho, ini_chi, cur_chi, stop_bad)) break;
-        }
-        *chi2 = cur_chi; *lambda_end = lambda;
-        return ORBX_OK;
+                g_prof.launch(LBA_K_UPDATE, pc, [&] { hipLaunchKernelGGL(k_lba_update, dim3(g_vert()), dim3(256), 0, s, L, cur); });
+                g_prof.launch(LBA_K_ERRORS, pc, [&] { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lba_points<false>), dim3(g_pts()), dim3(256), 0, s, L, 1 - cur, robust); });
+                g_prof.launch(LBA_K_REDUCE, pc, [&] { hipLaunchKernelGGL(k_lba_reduce, dim3(1), dim3(1024), 0, s, L, 1, lambda); });
+                const int rc = fetch_status();
+                if (!rc) trials_total++;
+                return rc;
+            },
+            [&] { return (const double *)c->h_out; }, [&] { return stop_up(); }, [&] { cur = 1 - cur; });   // discardTop(): the trial copy is the estimate
+        evaluated = evaluated || r.evaluated;
+        return r;
     }
 };
-
-// the events a profiled call needs -> the context to hand to lba_launch, or nullptr
-static int lba_profile_ctx(CallCtx *c, CallCtx **pc)
-{
-    *pc = nullptr;
-    if (!g_prof.on) return ORBX_OK;
-    if (!c->ev_a) ORBX_HIP(hipEventCreate(&c->ev_a));
-    if (!c->ev_b) ORBX_HIP(hipEventCreate(&c->ev_b));
-    *pc = c;
-    return ORBX_OK;
-}
 
 // the download block fetched, and what both entry points hand back from it
 static int lba_deliver(CallCtx *c, const LbaStage &st, float *Tcw_out, float *Xw_out, double *pose_out, double *point_out)
@@ -876,7 +819,7 @@ extern "C" int orbx_local_bundle_adjustment(int device, const orbx_lba_problem *
     if ((rc = orbx_call_ctx(device, &c))) return rc;
     LbaStage st;
     if ((rc = lba_stage(c, p, n_free, 1536, (double)(float)sqrt(5.991), true, &st))) return rc;   // thHuberMono, :650
-    if ((rc = lba_profile_ctx(c, &pc))) return rc;
+    if ((rc = g_prof.ctx(c, &pc))) return rc;
     const Lba &L = st.L;
     const size_t E = (size_t)p->n_edges;
     hipStream_t s = c->stream;
@@ -885,24 +828,24 @@ extern "C" int orbx_local_bundle_adjustment(int device, const orbx_lba_problem *
 
     run.init();
     for (int round = 0; round < 2; round++) {
-        lba_launch(LBA_K_ACTIVE, pc, [&] { hipLaunchKernelGGL(k_lba_active, dim3(1), dim3(1024), 0, s, L); });
+        g_prof.launch(LBA_K_ACTIVE, pc, [&] { hipLaunchKernelGGL(k_lba_active, dim3(1), dim3(1024), 0, s, L); });
         if ((rc = run.fetch_status())) return rc;
         const int rows = run.counts()[0], npts = run.counts()[1];
         rep.n_active_kf[round] = rows; rep.n_active_points[round] = npts;
-        if ((rc = run.optimize(rows, npts, round == 0 ? 5 : 10, round == 0, &rep.iterations[round], &rep.trials[round], &rep.chi2[round],
-                               &rep.lambda[round], nullptr)))
-            return rc;
+        const LmRun r = run.optimize(rows, npts, round == 0 ? 5 : 10, round == 0);
+        if (r.rc) return r.rc;
+        rep.iterations[round] = r.iterations; rep.trials[round] = r.trials; rep.chi2[round] = r.chi2; rep.lambda[round] = r.lambda;
         if (round == 0) {
             if (run.stop_up()) rep.stopped = 2;   // :745-747
             if (!run.evaluated && E) {   // stopped before any evaluation: the errors at the start estimates (the reference reads uninitialised memory)
-                lba_launch(LBA_K_ERRORS, pc, [&] { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lba_points<false>), dim3(g_pts), dim3(256), 0, s, L, run.cur, 1); });
+                g_prof.launch(LBA_K_ERRORS, pc, [&] { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lba_points<false>), dim3(g_pts), dim3(256), 0, s, L, run.cur, 1); });
                 run.evaluated = true;
             }
-            if (E) lba_launch(LBA_K_CLASSIFY, pc, [&] { hipLaunchKernelGGL(k_lba_classify, dim3(g_edges), dim3(256), 0, s, L, run.cur, 1); });
+            if (E) g_prof.launch(LBA_K_CLASSIFY, pc, [&] { hipLaunchKernelGGL(k_lba_classify, dim3(g_edges), dim3(256), 0, s, L, run.cur, 1); });
             if (rep.stopped) break;
         } else if (run.stop_up()) rep.stopped = 3;
     }
-    if (E) lba_launch(LBA_K_CLASSIFY, pc, [&] { hipLaunchKernelGGL(k_lba_classify, dim3(g_edges), dim3(256), 0, s, L, run.cur, 2); });
+    if (E) g_prof.launch(LBA_K_CLASSIFY, pc, [&] { hipLaunchKernelGGL(k_lba_classify, dim3(g_edges), dim3(256), 0, s, L, run.cur, 2); });
     run.finish();
     if ((rc = lba_deliver(c, st, Tcw_out, Xw_out, pose_out, point_out))) return rc;
     const uint8_t *flags = (const uint8_t *)c->h_out + st.w_flags;
@@ -943,13 +886,13 @@ extern "C" int orbx_bundle_adjustment(int device, const orbx_lba_problem *p, con
     LbaStage st;
     // thHuber2D is sqrt(5.99) here (:101), not LocalBundleAdjustment's 5.991; every edge stays at level 0, so the edge lists are the uploaded ones
     if ((rc = lba_stage(c, p, max_rows, std::max(6 * max_rows, 1), (double)(float)sqrt(5.99), false, &st))) return rc;
-    if ((rc = lba_profile_ctx(c, &pc))) return rc;
+    if ((rc = g_prof.ctx(c, &pc))) return rc;
     const Lba &L = st.L;
     hipStream_t s = c->stream;
     LbaRun run = { c, pc, L, st.w_counts, stop, opt ? opt->debug_stop_at_trial : -1, 1 };
 
     run.init();
-    lba_launch(LBA_K_ACTIVE, pc, [&] {
+    g_prof.launch(LBA_K_ACTIVE, pc, [&] {
         hipLaunchKernelGGL(k_gba_active, dim3(run.g_vert()), dim3(256), 0, s, L);
         hipLaunchKernelGGL(k_gba_rows, dim3(1), dim3(1024), 0, s, L);
     });
@@ -957,9 +900,9 @@ extern "C" int orbx_bundle_adjustment(int device, const orbx_lba_problem *p, con
     rep.n_active_kf = run.counts()[0]; rep.n_active_points = run.counts()[1];
     if (up_on_entry) rep.stopped = 1;
     else {
-        if ((rc = run.optimize(rep.n_active_kf, rep.n_active_points, iterations, robust, &rep.iterations, &rep.trials, &rep.chi2, &rep.lambda,
-                               &rep.lambda_init)))
-            return rc;
+        const LmRun r = run.optimize(rep.n_active_kf, rep.n_active_points, iterations, robust);
+        if (r.rc) return r.rc;
+        rep.iterations = r.iterations; rep.trials = r.trials; rep.chi2 = r.chi2; rep.lambda = r.lambda; rep.lambda_init = r.lambda_init;
         if (run.stop_up()) rep.stopped = 2;
     }
     run.finish();

@@ -1,6 +1,6 @@
 // orbx_lm.h — g2o's small pieces, one copy each, for the Levenberg kernels (k_pose_opt of orbx_pose.hip, k_sim3_opt of orbx_sim3opt.hip,
-// the k_lba_* of orbx_lba.hip, the k_eg_* of orbx_essential.hip) and for the host loops of the bundle adjustments (LbaRun::optimize) and of
-// the essential graph:
+// the k_lba_* of orbx_lba.hip, the k_eg_* of orbx_essential.hip) and the one host loop of the bundle adjustments and the essential graph
+// (lm_host_loop):
 //   sums      block_sum: the fixed-order workgroup sum that hands every thread of a 4- or 16-wave workgroup the same bits
 //   solver    ldlt_small<N>: the dense (H + lambda I) x = b of the one-vertex problems; hu_max_diag<N>
 //   damping   lm_*: the rule of optimization_algorithm_levenberg.cpp (rho, lambda, ni, the two stops), host and device
@@ -13,9 +13,10 @@
 // theta < 1e-5 branch (pose_update fills V there, sim3_exp selects per entry next to its A, B, C), and a helper for Omega and Omega^2
 // alone lets the compiler take -(o o) from the o o of theta: the same bits, one multiplication fewer, and so not the instructions these
 // kernels were measured with.
-// Everything but lm_* is device code; every function is inlined into its kernel.
+// Everything but lm_* is device code; every device function is inlined into its kernel.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cfloat>
 #include <cmath>
 #include "orbx_wave.h"
 
@@ -151,6 +152,59 @@ static __host__ __device__ __forceinline__ bool lm_done(int qmax, double rho, do
     if (qmax == 10 || rho == 0.0) return true;
     if ((ini_chi - cur_chi) * 1e3 < ini_chi) stop_bad++; else stop_bad = 0;
     return stop_bad >= 3;
+}
+
+// ---- host only: SparseOptimizer::optimize(max_it) for the solvers whose kernels run one step per launch (LbaRun::optimize of orbx_lba.hip,
+// orbx_optimize_essential_graph): the sequence above driven over a fetched status record of doubles, [0] chi2, [1] computeScale's sum,
+// [2] the largest diagonal entry (behind linearise), [3] != 0 where the solve succeeded (behind a trial; a failed one counts as chi2 DBL_MAX).
+struct LmRun {
+    int rc;                                            // the first failure of linearise() / trial(); the rest is then not to be read
+    int iterations, trials, n_solve_failed;
+    bool evaluated;                                    // linearise() ran at least once
+    double chi2, lambda, lambda_init, chi2_start;      // at the end (0 if no iteration ran); lm_start's lambda, the first linearisation's chi2
+};
+
+// linearise() and trial(lambda) launch their kernels and fetch the record (ORBX_OK or the failure); status() is where it was fetched to.  A
+// trial evaluates into the copy that is not the estimate: swap() makes that copy the estimate (discardTop()), a rejected trial leaves it
+// (pop()).  stop_up(): the caller's stop flag, asked before every iteration and behind every trial (sparse_optimizer.cpp:356, :376).
+template <class Linearise, class Trial, class Status, class StopUp, class Swap>
+static inline LmRun lm_host_loop(int max_it, double user_lambda_init, Linearise linearise, Trial trial, Status status, StopUp stop_up, Swap swap)
+{
+    LmRun r = {};
+    double lambda = 0.0, ni = 2.0, cur_chi = 0.0;
+    int stop_bad = 0;
+    for (int it = 0; it < max_it && !stop_up(); it++) {
+        if ((r.rc = linearise())) return r;
+        const double *hs = status();
+        r.evaluated = true;
+        cur_chi = hs[0];
+        const double ini_chi = cur_chi;
+        if (it == 0) {
+            r.chi2_start = cur_chi;
+            lm_start(hs[2], lambda, ni, stop_bad, user_lambda_init);
+            r.lambda_init = lambda;
+        }
+        double rho = 0.0;
+        int qmax = 0;
+        do {
+            if ((r.rc = trial(lambda))) return r;
+            r.trials++;
+            const bool ok = hs[3] != 0.0;
+            r.n_solve_failed += !ok;
+            const double temp_chi = ok ? hs[0] : DBL_MAX;
+            rho = lm_gain(cur_chi, temp_chi, hs[1]);
+            if (lm_accepts(rho, temp_chi)) {
+                lm_accept(rho, lambda, ni);
+                cur_chi = temp_chi;
+                swap();
+            } else lm_reject(lambda, ni);   // the edges keep the errors of the rejected state
+            qmax++;
+        } while (rho < 0.0 && qmax < 10 && !stop_up());
+        r.iterations++;
+        if (lm_done(qmax, rho, ini_chi, cur_chi, stop_bad)) break;
+    }
+    r.chi2 = cur_chi; r.lambda = lambda;
+    return r;
 }
 
 // Eigen's Quaternion(Matrix3): m row-major

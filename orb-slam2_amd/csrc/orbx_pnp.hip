@@ -635,6 +635,15 @@ static int pnp_check(const char *who, int j, const orbx_pnp_job &J)
     return ORBX_OK;
 }
 
+// a job's arrays, stated once (JobArrays, orbx_resident.h): what goes up, and the results, which lie in the work area
+static void pnp_arrays(JobArrays &w, const orbx_pnp_job &in, PnpJob &J)
+{
+    const size_t n = (size_t)in.n, nh = (size_t)in.n_hyp, wb = 8 * nh * ((n + 63) / 64);
+    w.in(J.P3Dw, in.P3Dw, 12 * n); w.in(J.P2D, in.P2D, 8 * n); w.in(J.max_err, in.max_err, 4 * n); w.in(J.samples, in.samples, 16 * nh);
+    w.out(J.n_inliers, in.n_inliers, 4 * nh); w.out(J.Rt, in.Rt, 96 * nh); w.out(J.bits, in.inlier_bits, wb);
+    w.out(J.n_refined, in.n_refined, 4 * nh); w.out(J.Rt_refined, in.Rt_refined, 96 * nh); w.out(J.refined_bits, in.refined_bits, wb);
+}
+
 static int pnp_run(const char *who, int device, orbx_pnp_job *jobs, int njobs)
 {
     if (!jobs || njobs < 1 || njobs > 64) { orbx_set_error("%s: invalid argument (jobs, 1 <= njobs <= 64)", who); return ORBX_E_INVALID; }
@@ -650,47 +659,27 @@ static int pnp_run(const char *who, int device, orbx_pnp_job *jobs, int njobs)
     int rc = orbx_call_ctx(device, &c);
     if (rc) return rc;
     const size_t jobs_b = a16(sizeof(PnpJob) * (size_t)njobs);
-    size_t blob = jobs_b, out = 0;
-    for (int j = 0; j < njobs; j++) {
-        const size_t n = (size_t)jobs[j].n, nh = (size_t)jobs[j].n_hyp;
-        blob += a16(12 * n) + a16(8 * n) + a16(4 * n) + a16(16 * nh);
-        out += 2 * (a16(4 * nh) + a16(96 * nh) + a16(8 * nh * ((n + 63) / 64)));
-    }
+    PnpJob none = {};
+    JobArrays size(JobArrays::MEASURE, c, jobs_b, 0);
+    for (int j = 0; j < njobs; j++) pnp_arrays(size, jobs[j], none);
+    const size_t blob = size.up.o, out = size.down.o;
     if ((rc = call_reserve(c, blob, out, out))) return rc;
-    PnpJob *hj = (PnpJob *)c->h_blob;
-    BlobCursor b = { c->h_blob, c->d_blob, jobs_b }, res = { nullptr, c->d_work, 0 };   // the arrays up; the results in the work area
+    JobArrays stage(JobArrays::STAGE, c, jobs_b, 0);
     int first = 0;
     for (int j = 0; j < njobs; j++) {
         const orbx_pnp_job &in = jobs[j];
-        const size_t n = (size_t)in.n, nh = (size_t)in.n_hyp, wb = 8 * nh * ((n + 63) / 64);
-        PnpJob &J = hj[j];
+        PnpJob &J = ((PnpJob *)c->h_blob)[j];
         memset(&J, 0, sizeof J);
         J.n = in.n; J.n_hyp = in.n_hyp; J.min_inliers = in.min_inliers; J.first = first;
         first += in.n_hyp;
-        J.P3Dw = (const float *)b.put(in.P3Dw, 12 * n); J.P2D = (const float *)b.put(in.P2D, 8 * n);
-        J.max_err = (const float *)b.put(in.max_err, 4 * n);
-        J.samples = (const int32_t *)b.put(in.samples, 16 * nh);
-        J.n_inliers = (int32_t *)(res.d + res.take(4 * nh)); J.Rt = (double *)(res.d + res.take(96 * nh));
-        J.bits = (uint64_t *)(res.d + res.take(wb));
-        J.n_refined = (int32_t *)(res.d + res.take(4 * nh)); J.Rt_refined = (double *)(res.d + res.take(96 * nh));
-        J.refined_bits = (uint64_t *)(res.d + res.take(wb));
+        pnp_arrays(stage, in, J);
         memcpy(J.K, in.K, sizeof J.K);
     }
     if ((rc = call_upload(c, blob))) return rc;
     hipLaunchKernelGGL(k_pnp, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, c->stream, (const PnpJob *)c->d_blob, njobs, (int)total);   // one wave per hypothesis
     if ((rc = call_fetch(c, out))) return rc;
-    const uint8_t *ho = (const uint8_t *)c->h_out;
-    size_t oo = 0;
-    for (int j = 0; j < njobs; j++) {
-        const orbx_pnp_job &in = jobs[j];
-        const size_t nh = (size_t)in.n_hyp, wb = 8 * nh * (((size_t)in.n + 63) / 64);
-        memcpy(in.n_inliers, ho + oo, 4 * nh); oo += a16(4 * nh);
-        memcpy(in.Rt, ho + oo, 96 * nh); oo += a16(96 * nh);
-        memcpy(in.inlier_bits, ho + oo, wb); oo += a16(wb);
-        memcpy(in.n_refined, ho + oo, 4 * nh); oo += a16(4 * nh);
-        memcpy(in.Rt_refined, ho + oo, 96 * nh); oo += a16(96 * nh);
-        memcpy(in.refined_bits, ho + oo, wb); oo += a16(wb);
-    }
+    JobArrays deliver(JobArrays::DELIVER, c, jobs_b, 0);
+    for (int j = 0; j < njobs; j++) pnp_arrays(deliver, jobs[j], none);
     return ORBX_OK;
 }
 

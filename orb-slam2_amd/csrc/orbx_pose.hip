@@ -270,6 +270,16 @@ static int pose_launch_and_fetch(CallCtx *c, size_t blob, size_t out, int njobs)
     return call_fetch(c, out);
 }
 
+// a job's arrays, stated once (JobArrays, orbx_resident.h): what goes up, then the flag bytes that come down behind the PoseOuts.  Returns
+// where the flags were fetched to (DELIVER)
+static const uint8_t *pose_arrays(JobArrays &w, const orbx_pose_obs &ob, PoseJob &J)
+{
+    const size_t n = (size_t)ob.n;
+    w.in(J.x, ob.x, 4 * n); w.in(J.y, ob.y, 4 * n); w.in(J.u_right, ob.u_right, 4 * n); w.in(J.inv_sigma2, ob.inv_sigma2, 4 * n);
+    w.in(J.Xw, ob.Xw, 12 * n); w.in(J.has_point, ob.has_point, n);
+    return w.out(J.outlier, nullptr, n);
+}
+
 static int pose_run(const char *who, int device, const PoseArgs *a, int njobs)
 {
     size_t total = 0;
@@ -283,36 +293,24 @@ static int pose_run(const char *who, int device, const PoseArgs *a, int njobs)
     int rc = orbx_call_ctx(device, &c);
     if (rc) return rc;
     const size_t jobs_b = a16(sizeof(PoseJob) * (size_t)njobs), outs_b = a16(sizeof(PoseOut) * (size_t)njobs);
-    size_t blob = jobs_b, out = outs_b;
-    for (int j = 0; j < njobs; j++) {
-        const size_t n = (size_t)a[j].obs->n;
-        blob += 4 * a16(4 * n) + a16(12 * n) + a16(n);
-        out += a16(n);
-    }
+    PoseJob none = {};
+    JobArrays size(JobArrays::MEASURE, c, jobs_b, outs_b);
+    for (int j = 0; j < njobs; j++) pose_arrays(size, *a[j].obs, none);
+    const size_t blob = size.up.o, out = size.down.o;
     if ((rc = call_reserve(c, blob, out, out))) return rc;
-    PoseJob *hj = (PoseJob *)c->h_blob;
-    BlobCursor b = { c->h_blob, c->d_blob, jobs_b };
-    size_t fo = outs_b;
+    JobArrays stage(JobArrays::STAGE, c, jobs_b, outs_b);
     for (int j = 0; j < njobs; j++) {
-        const orbx_pose_obs &ob = *a[j].obs;
-        const size_t n = (size_t)ob.n;
-        PoseJob &J = hj[j];
+        PoseJob &J = ((PoseJob *)c->h_blob)[j];
         memset(&J, 0, sizeof J);
-        J.n = ob.n;
-        J.x = (const float *)b.put(ob.x, 4 * n); J.y = (const float *)b.put(ob.y, 4 * n); J.u_right = (const float *)b.put(ob.u_right, 4 * n);
-        J.inv_sigma2 = (const float *)b.put(ob.inv_sigma2, 4 * n); J.Xw = (const float *)b.put(ob.Xw, 12 * n);
-        J.has_point = b.put(ob.has_point, n);
-        J.outlier = c->d_work + fo;
-        fo += a16(n);
+        J.n = a[j].obs->n;
+        pose_arrays(stage, *a[j].obs, J);
         memcpy(J.cam, a[j].cam, sizeof J.cam); memcpy(J.Tcw, a[j].Tcw, sizeof J.Tcw);
     }
     if ((rc = pose_launch_and_fetch(c, blob, out, njobs))) return rc;
-    const uint8_t *ho = (const uint8_t *)c->h_out;
-    fo = outs_b;
+    JobArrays deliver(JobArrays::DELIVER, c, jobs_b, outs_b);
     for (int j = 0; j < njobs; j++) {
         const orbx_pose_obs &ob = *a[j].obs;
-        pose_deliver(((const PoseOut *)ho)[j], ho + fo, ob.n, a[j], [&](int i) { return ob.has_point[i] != 0; });
-        fo += a16((size_t)ob.n);
+        pose_deliver(((const PoseOut *)c->h_out)[j], pose_arrays(deliver, ob, none), ob.n, a[j], [&](int i) { return ob.has_point[i] != 0; });
     }
     return ORBX_OK;
 }

@@ -30,7 +30,7 @@ struct CallCtx : ThreadCtx {
     uint32_t *d_entries = nullptr; size_t ent_cap = 0;   // the candidate pool of proj_search
     int32_t *h_out = nullptr; size_t out_cap = 0;
     int32_t *h_n = nullptr;    // pinned: the feature count a frame created from extraction outputs reads back
-    hipEvent_t ev_a = nullptr, ev_b = nullptr;   // the pair round a launch while orbx_debug_lba_profile is on (orbx_lba.hip); made on first use
+    hipEvent_t ev_a = nullptr, ev_b = nullptr;   // the pair round a launch while a LaunchProfile (below) is on; made on first use
     ORBX_LOCAL void release();
     ~CallCtx() { release(); }
 };
@@ -60,7 +60,8 @@ static inline int call_fetch(CallCtx *c, size_t out)
     return ORBX_OK;
 }
 
-// a cursor over a blob: sub-blocks at 16-byte boundaries, `h` where the host writes them and `d` where the device will find them
+// a cursor over a blob: sub-blocks at 16-byte boundaries, `h` where the host writes them and `d` where the device will find them.  Without
+// `h` it only counts: put() touches no memory and gives no address.
 struct BlobCursor {
     uint8_t *h, *d;
     size_t o;
@@ -68,10 +69,83 @@ struct BlobCursor {
     uint8_t *put(const void *src, size_t bytes, int absent = 0)   // src == NULL: `bytes` bytes of `absent`
     {
         const size_t at = take(bytes);
+        if (!h) return nullptr;
         if (bytes) { if (src) memcpy(h + at, src, bytes); else memset(h + at, absent, bytes); }
         return d + at;
     }
 };
+
+// ---- the arrays of the jobs of a batch call (orbx_pose.hip, orbx_sim3opt.hip, orbx_sim3.hip, orbx_pnp.hip).  A solver states a job's arrays
+// ONCE, in a function that calls in() for every array that goes up and out() for every array that comes down, in the order they lie in the
+// blob and in the download block.  The call walks that function over its jobs three times: to MEASURE (cursors that only count: call_reserve
+// gets the sizes the staging will use), to STAGE (the uploads into the blob, the job table's fields set to the device addresses) and, behind
+// call_fetch, to DELIVER.  up0 / down0: the bytes in front of the first job's arrays (the job table; the out-records, if any).
+struct JobArrays {
+    enum Mode { MEASURE, STAGE, DELIVER };
+    BlobCursor up, down;   // what a cursor has a base for is what the walk does
+    JobArrays(Mode m, CallCtx *c, size_t up0, size_t down0) : up{ nullptr, nullptr, up0 }, down{ nullptr, nullptr, down0 }
+    {
+        if (m == STAGE) { up.h = c->h_blob; up.d = c->d_blob; down.d = c->d_work; }
+        if (m == DELIVER) down.h = (uint8_t *)c->h_out;
+    }
+    // `field` is written in STAGE alone: only there has `up` a host base (h_blob, never null behind call_reserve), and put() gives an
+    // address only from a cursor that has one.  MEASURE and DELIVER count past the array and leave the job they are handed untouched.
+    template <class T>
+    void in(const T *&field, const void *src, size_t bytes)
+    {
+        uint8_t *d = up.put(src, bytes);
+        if (d) field = (const T *)d;
+    }
+    // DELIVER: the array goes to dst, where there is one, and the return value is where it was fetched to (else nullptr)
+    template <class T>
+    const uint8_t *out(T *&field, void *dst, size_t bytes)
+    {
+        const size_t at = down.take(bytes);
+        if (down.d) field = (T *)(down.d + at);
+        if (down.h && dst) memcpy(dst, down.h + at, bytes);
+        return down.h ? down.h + at : nullptr;
+    }
+};
+
+// ---- the per-kernel launch profile of a host-driven solver (orbx_debug_lba_profile, orbx_debug_eg_profile; one thread_local object each, N
+// its slots): while it is on, every launch of the thread's calls sits between the context's two events and is waited for, and its device
+// time goes to its kernel's slot.
+template <int N>
+struct ORBX_LOCAL LaunchProfile {
+    bool on = false;
+    double ms[N] = {};
+    int32_t n[N] = {};
+    // pc, the context to hand to launch(): c with its events made (CallCtx::release gives them back), or nullptr while the profile is off
+    int ctx(CallCtx *c, CallCtx **pc) const
+    {
+        *pc = on ? c : nullptr;
+        if (on && !c->ev_a) ORBX_HIP(hipEventCreate(&c->ev_a));
+        if (on && !c->ev_b) ORBX_HIP(hipEventCreate(&c->ev_b));
+        return ORBX_OK;
+    }
+    template <class F>
+    void launch(int slot, CallCtx *pc, F f)
+    {
+        if (!pc) { f(); return; }
+        float t = 0.f;
+        (void)hipEventRecord(pc->ev_a, pc->stream);
+        f();
+        (void)hipEventRecord(pc->ev_b, pc->stream);
+        if (hipEventSynchronize(pc->ev_b) == hipSuccess && hipEventElapsedTime(&t, pc->ev_a, pc->ev_b) == hipSuccess) { ms[slot] += t; n[slot]++; }
+    }
+    // the entry point: enable != 0 clears and switches on; 0 switches off, hands back what was gathered and returns N
+    int entry(int enable, double *ms_out, int32_t *launches)
+    {
+        if (enable) { *this = LaunchProfile(); on = true; return ORBX_OK; }
+        on = false;
+        if (ms_out) memcpy(ms_out, ms, sizeof ms);
+        if (launches) memcpy(launches, n, sizeof n);
+        return N;
+    }
+};
+
+// workgroups of 256 threads for n items, one at the least
+static inline unsigned grid256(int n) { return (unsigned)((n + 255) / 256 > 0 ? (n + 255) / 256 : 1); }
 
 // ---- the arrays of a frame, as they lie in a resident frame's block and, up to o_coff, at the head of a host-pointer call's staging
 // blob: x[n] y[n] octave[n] angle[n] u_right[n] desc[n][32] | cell_off[3073] cell_idx[n]

@@ -264,6 +264,15 @@ static int sim3_check(const char *who, int j, const orbx_sim3_job &J)
     return ORBX_OK;
 }
 
+// a job's arrays, stated once (JobArrays, orbx_resident.h): what goes up, and the results, which lie in the work area
+static void sim3_arrays(JobArrays &w, const orbx_sim3_job &in, Sim3Job &J)
+{
+    const size_t n = (size_t)in.n, nh = (size_t)in.n_hyp;
+    w.in(J.X1, in.X1, 12 * n); w.in(J.X2, in.X2, 12 * n); w.in(J.max_err1, in.max_err1, 4 * n); w.in(J.max_err2, in.max_err2, 4 * n);
+    w.in(J.samples, in.samples, 12 * nh);
+    w.out(J.n_inliers, in.n_inliers, 4 * nh); w.out(J.srt, in.srt, 52 * nh); w.out(J.inlier_bits, in.inlier_bits, 8 * nh * ((n + 63) / 64));
+}
+
 static int sim3_run(const char *who, int device, orbx_sim3_job *jobs, int njobs)
 {
     if (!jobs || njobs < 1 || njobs > 64) { orbx_set_error("%s: invalid argument (jobs, 1 <= njobs <= 64)", who); return ORBX_E_INVALID; }
@@ -279,42 +288,27 @@ static int sim3_run(const char *who, int device, orbx_sim3_job *jobs, int njobs)
     int rc = orbx_call_ctx(device, &c);
     if (rc) return rc;
     const size_t jobs_b = a16(sizeof(Sim3Job) * (size_t)njobs);
-    size_t blob = jobs_b, out = 0;
-    for (int j = 0; j < njobs; j++) {
-        const size_t n = (size_t)jobs[j].n, nh = (size_t)jobs[j].n_hyp;
-        blob += 2 * a16(12 * n) + 2 * a16(4 * n) + a16(12 * nh);
-        out += a16(4 * nh) + a16(52 * nh) + a16(8 * nh * ((n + 63) / 64));
-    }
+    Sim3Job none = {};
+    JobArrays size(JobArrays::MEASURE, c, jobs_b, 0);
+    for (int j = 0; j < njobs; j++) sim3_arrays(size, jobs[j], none);
+    const size_t blob = size.up.o, out = size.down.o;
     if ((rc = call_reserve(c, blob, out, out))) return rc;
-    Sim3Job *hj = (Sim3Job *)c->h_blob;
-    BlobCursor b = { c->h_blob, c->d_blob, jobs_b }, res = { nullptr, c->d_work, 0 };   // the arrays up; the results in the work area
+    JobArrays stage(JobArrays::STAGE, c, jobs_b, 0);
     int first = 0;
     for (int j = 0; j < njobs; j++) {
         const orbx_sim3_job &in = jobs[j];
-        const size_t n = (size_t)in.n, nh = (size_t)in.n_hyp;
-        Sim3Job &J = hj[j];
+        Sim3Job &J = ((Sim3Job *)c->h_blob)[j];
         memset(&J, 0, sizeof J);
         J.n = in.n; J.n_hyp = in.n_hyp; J.fix_scale = in.fix_scale ? 1 : 0; J.first = first;
         first += in.n_hyp;
-        J.X1 = (const float *)b.put(in.X1, 12 * n); J.X2 = (const float *)b.put(in.X2, 12 * n);
-        J.max_err1 = (const float *)b.put(in.max_err1, 4 * n); J.max_err2 = (const float *)b.put(in.max_err2, 4 * n);
-        J.samples = (const int32_t *)b.put(in.samples, 12 * nh);
-        J.n_inliers = (int32_t *)(res.d + res.take(4 * nh)); J.srt = (float *)(res.d + res.take(52 * nh));
-        J.inlier_bits = (uint64_t *)(res.d + res.take(8 * nh * ((n + 63) / 64)));
+        sim3_arrays(stage, in, J);
         memcpy(J.K1, in.K1, sizeof J.K1); memcpy(J.K2, in.K2, sizeof J.K2);
     }
     if ((rc = call_upload(c, blob))) return rc;
     hipLaunchKernelGGL(k_sim3, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, c->stream, (const Sim3Job *)c->d_blob, njobs, (int)total);   // one wave per hypothesis
     if ((rc = call_fetch(c, out))) return rc;
-    const uint8_t *ho = (const uint8_t *)c->h_out;
-    size_t oo = 0;
-    for (int j = 0; j < njobs; j++) {
-        const orbx_sim3_job &in = jobs[j];
-        const size_t nh = (size_t)in.n_hyp, wb = 8 * nh * (((size_t)in.n + 63) / 64);
-        memcpy(in.n_inliers, ho + oo, 4 * nh); oo += a16(4 * nh);
-        memcpy(in.srt, ho + oo, 52 * nh); oo += a16(52 * nh);
-        memcpy(in.inlier_bits, ho + oo, wb); oo += a16(wb);
-    }
+    JobArrays deliver(JobArrays::DELIVER, c, jobs_b, 0);
+    for (int j = 0; j < njobs; j++) sim3_arrays(deliver, jobs[j], none);
     return ORBX_OK;
 }
 

@@ -287,6 +287,17 @@ static bool sim3opt_has_pairs(const orbx_sim3opt_obs &o)
     return false;
 }
 
+// a job's arrays, stated once (JobArrays, orbx_resident.h): what goes up, then the flag bytes that come down behind the Sim3OptOuts.
+// Returns where the flags were fetched to (DELIVER)
+static const uint8_t *sim3opt_arrays(JobArrays &w, const orbx_sim3opt_obs &ob, Sim3OptJob &J)
+{
+    const size_t n = (size_t)ob.n;
+    w.in(J.has_pair, ob.has_pair, n); w.in(J.P1c, ob.P1c, 12 * n); w.in(J.P2c, ob.P2c, 12 * n);
+    w.in(J.x1, ob.x1, 4 * n); w.in(J.y1, ob.y1, 4 * n); w.in(J.w1, ob.inv_sigma2_1, 4 * n);
+    w.in(J.x2, ob.x2, 4 * n); w.in(J.y2, ob.y2, 4 * n); w.in(J.w2, ob.inv_sigma2_2, 4 * n);
+    return w.out(J.inlier, nullptr, n);
+}
+
 // staging: up [Sim3OptJob x njobs | the jobs' arrays], down [Sim3OptOut x njobs | the jobs' flag bytes]
 static int sim3opt_run(const char *who, int device, const Sim3OptArgs *a, int njobs)
 {
@@ -304,40 +315,25 @@ static int sim3opt_run(const char *who, int device, const Sim3OptArgs *a, int nj
     int rc = orbx_call_ctx(device, &c);
     if (rc) return rc;
     const size_t jobs_b = a16(sizeof(Sim3OptJob) * (size_t)njobs), outs_b = a16(sizeof(Sim3OptOut) * (size_t)njobs);
-    size_t blob = jobs_b, out = outs_b;
-    for (int j = 0; j < njobs; j++) {
-        const size_t n = (size_t)a[j].obs->n;
-        blob += a16(n) + 2 * a16(12 * n) + 6 * a16(4 * n);
-        out += a16(n);
-    }
+    Sim3OptJob none = {};
+    JobArrays size(JobArrays::MEASURE, c, jobs_b, outs_b);
+    for (int j = 0; j < njobs; j++) sim3opt_arrays(size, *a[j].obs, none);
+    const size_t blob = size.up.o, out = size.down.o;
     if ((rc = call_reserve(c, blob, out, out))) return rc;
-    Sim3OptJob *hj = (Sim3OptJob *)c->h_blob;
-    BlobCursor b = { c->h_blob, c->d_blob, jobs_b };
-    size_t fo = outs_b;
+    JobArrays stage(JobArrays::STAGE, c, jobs_b, outs_b);
     for (int j = 0; j < njobs; j++) {
-        const orbx_sim3opt_obs &ob = *a[j].obs;
-        const size_t n = (size_t)ob.n;
-        Sim3OptJob &J = hj[j];
+        Sim3OptJob &J = ((Sim3OptJob *)c->h_blob)[j];
         memset(&J, 0, sizeof J);
-        J.n = ob.n; J.fix_scale = a[j].fix_scale ? 1 : 0;
+        J.n = a[j].obs->n; J.fix_scale = a[j].fix_scale ? 1 : 0;
         J.th2 = a[j].th2; J.delta = sqrtf(a[j].th2);
-        J.has_pair = b.put(ob.has_pair, n);
-        J.P1c = (const float *)b.put(ob.P1c, 12 * n); J.P2c = (const float *)b.put(ob.P2c, 12 * n);
-        J.x1 = (const float *)b.put(ob.x1, 4 * n); J.y1 = (const float *)b.put(ob.y1, 4 * n); J.w1 = (const float *)b.put(ob.inv_sigma2_1, 4 * n);
-        J.x2 = (const float *)b.put(ob.x2, 4 * n); J.y2 = (const float *)b.put(ob.y2, 4 * n); J.w2 = (const float *)b.put(ob.inv_sigma2_2, 4 * n);
-        J.inlier = c->d_work + fo;
-        fo += a16(n);
+        sim3opt_arrays(stage, *a[j].obs, J);
         memcpy(J.cam1, a[j].cam1, sizeof J.cam1); memcpy(J.cam2, a[j].cam2, sizeof J.cam2); memcpy(J.S12, a[j].S12, sizeof J.S12);
     }
     if ((rc = call_upload(c, blob))) return rc;
     hipLaunchKernelGGL(k_sim3_opt, dim3(njobs), dim3(256), 0, c->stream, (const Sim3OptJob *)c->d_blob, (Sim3OptOut *)c->d_work);
     if ((rc = call_fetch(c, out))) return rc;
-    const uint8_t *ho = (const uint8_t *)c->h_out;
-    fo = outs_b;
-    for (int j = 0; j < njobs; j++) {
-        sim3opt_deliver(((const Sim3OptOut *)ho)[j], ho + fo, a[j]);
-        fo += a16((size_t)a[j].obs->n);
-    }
+    JobArrays deliver(JobArrays::DELIVER, c, jobs_b, outs_b);
+    for (int j = 0; j < njobs; j++) sim3opt_deliver(((const Sim3OptOut *)c->h_out)[j], sim3opt_arrays(deliver, *a[j].obs, none), a[j]);
     return ORBX_OK;
 }
 

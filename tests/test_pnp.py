@@ -94,6 +94,17 @@ def test_batch_equals_single_calls(pkg, size):
 
 
 @pytest.mark.gpu
+def test_three_unequal_jobs_in_one_batch(pkg):
+    """n and n_hyp that are no multiple of the 16 bytes the staging pads to: every job's arrays lie where its own sizes put them"""
+    jobs = [sc.job(500 + i, n, nh, sc.min_inliers_of(n)) for i, (n, nh) in enumerate(((5, 1), (33, 3), (100, 7)))]
+    got = pkg.pnp_hypotheses_batch(jobs)
+    guarded = _guarded_call(pkg, jobs, batch=True)
+    for j, g, gg in zip(jobs, got, guarded):
+        assert _same(g, pkg.pnp_hypotheses(j)), (len(j["P3Dw"]), len(j["samples"]))
+        assert _same(g, gg)
+
+
+@pytest.mark.gpu
 def test_special_rows(pkg):
     """four coplanar samples, two samples with the same 3-D point, a correspondence behind the camera, one with z == 0 at a row's pose
     (to float rounding: tests/pnp_scene.py), and min_inliers > n, for which no row refines"""

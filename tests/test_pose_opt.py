@@ -99,6 +99,19 @@ def test_batch_equals_the_single_calls(pkg, count):
         assert same_bytes(got[j], _cache[key]), j
 
 
+@pytest.mark.gpu
+def test_three_unequal_jobs_in_one_batch(pkg):
+    """sizes that are no multiple of the 16 bytes the staging pads to, an empty job between them: every job's arrays lie where its own
+    sizes put them"""
+    scs = [ps.scene(81000 + n, n, mix) for n, mix in ((33, "mixed"), (0, "mono"), (100, "stereo"))]
+    scs[1]["obs"] = {k: v[:0] for k, v in scs[1]["obs"].items()}                        # n = 0: no feature at all
+    assert [len(sc["obs"]["x"]) for sc in scs] == [52, 0, 153]
+    got = pkg.pose_optimize_batch([(sc["obs"], sc["cam"], sc["Tcw"]) for sc in scs])
+    assert len(got) == 3 and got[1]["n_corr"] == 0 and got[0]["n_corr"] > 3 and got[2]["n_corr"] > 3
+    for j, sc in enumerate(scs):
+        assert same_bytes(got[j], pkg.pose_optimize(sc["obs"], sc["cam"], sc["Tcw"])), j
+
+
 def _frame_dict(sc):
     n = len(sc["octave"])
     rng = np.random.Generator(np.random.PCG64(n))

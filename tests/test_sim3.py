@@ -90,6 +90,17 @@ def test_batch_equals_single_calls(pkg, size):
 
 
 @pytest.mark.gpu
+def test_three_unequal_jobs_in_one_batch(pkg):
+    """n and n_hyp that are no multiple of the 16 bytes the staging pads to: every job's arrays lie where its own sizes put them"""
+    jobs = [sc.job(400 + i, n, nh, bool(i & 1)) for i, (n, nh) in enumerate(((5, 1), (33, 3), (100, 7)))]
+    got = pkg.sim3_hypotheses_batch(jobs)
+    guarded = _guarded_call(pkg, jobs, batch=True)
+    for j, g, gg in zip(jobs, got, guarded):
+        assert all(a.tobytes() == b.tobytes() for a, b in zip(g, pkg.sim3_hypotheses(j))), (len(j["X1"]), len(j["samples"]))
+        assert all(a.tobytes() == b.tobytes() for a, b in zip(g, gg))
+
+
+@pytest.mark.gpu
 def test_degenerate_hypothesis_and_special_points(pkg):
     """three coincident correspondences, a point behind camera 1 and a point with z == 0 in camera 2, for both fix_scale values"""
     for fix in (False, True):

@@ -89,6 +89,19 @@ def test_batch_equals_the_single_calls(pkg, count):
 
 
 @pytest.mark.gpu
+def test_three_unequal_jobs_in_one_batch(pkg):
+    """sizes that are no multiple of the 16 bytes the staging pads to, an empty job between them: every job's arrays lie where its own
+    sizes put them"""
+    scs = [ss.scene(82000 + n, n, kind) for n, kind in ((33, "outliers"), (0, "clean"), (100, "clean"))]
+    scs[1]["obs"] = {k: v[:0] for k, v in scs[1]["obs"].items()}                        # n = 0: no feature at all
+    assert [len(sc["obs"]["x1"]) for sc in scs] == [52, 0, 153]
+    got = pkg.sim3_optimize_batch([ss.args(sc) for sc in scs])
+    assert len(got) == 3 and got[1]["n_corr"] == 0 and got[0]["n_corr"] > 10 and got[2]["n_corr"] > 10
+    for j, sc in enumerate(scs):
+        assert same_bytes(got[j], pkg.sim3_optimize(*ss.args(sc))), j
+
+
+@pytest.mark.gpu
 def test_refusals(pkg):
     L = pkg.lib()
     sc, _ = world(10, "clean")
