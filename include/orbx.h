@@ -1628,6 +1628,44 @@ int orbx_debug_lba_profile(int enable, double *ms, int32_t *launches);
  * 0 k_eg_setup, 1 k_eg_edges<true>, 2 k_eg_rows, 3 k_eg_reduce, 4 k_eg_fill (both phases), 5 the panel solve, 6 k_eg_update,
  * 7 k_eg_edges<false>, 8 k_eg_finish, 9 k_eg_points. */
 int orbx_debug_eg_profile(int enable, double *ms, int32_t *launches);
+/* test hook (tests/test_eg_stages.py): what every kernel of orbx_optimize_essential_graph leaves in device memory.  The problem is checked,
+ * staged and set up as in that call and taken through ONE linearisation at the start estimates and, with trial != 0, ONE Levenberg trial
+ * from them with the given lambda, by the same launch sequences.  With x_in ([7 F], F = n_kf - 1 free keyframes in keyframe order = the
+ * rows) the solve is skipped and x_in is what the update reads.  n = 7 F, E = n_edges, K = n_kf.  Every array may be NULL (not wanted):
+ *   behind the setup          vS [K][8] the start estimates; meas [E][8] Sjw * Swi; xf [14][8], xf[2 d] = Sim3(+delta e_d), xf[2 d + 1] =
+ *                             Sim3(-delta e_d) (e_6 zeroed under fix_scale).  Every Sim3 is qx qy qz qw tx ty tz s.
+ *   behind the linearisation  rec [E][120]: with J = [A | B] (7 x 14, columns 0 .. 6 vertex 0 = edge_i, 7 .. 13 vertex 1 = edge_j; the
+ *                             columns of a fixed end are zeros), rec[0 .. 104] = the upper triangle of J^T J in row order (entry (r, c),
+ *                             r <= c, at 14 r - r (r - 1) / 2 + (c - r)), rec[105 .. 118] = -J^T e, rec[119] = chi2;  echi [E] = chi2;
+ *                             Hd [F][28] the upper triangle of a row's diagonal block in row order (entry (r, c) at 7 r - r (r - 1) / 2 +
+ *                             (c - r)); bv [F][7]; *n_pairs = NP, pair [NP][2] = (higher row, lower row) of every pair of free vertices
+ *                             an edge joins, sorted by (higher, lower), each once; Off [NP][49], entry [a][c] for dof a of the higher row
+ *                             and dof c of the lower one (pair and Off need room for E pairs); status_lin [4] = chi2, 0, the largest
+ *                             |diagonal entry|, 0.
+ *   err [E][29][7]            from a kernel of this call alone (k_eg_probe), a thread per evaluation, on the same stored estimates,
+ *                             measurements and xf: evaluation 0 is the error, 1 + 2 c and 2 + 2 c the plus and the minus side of column c
+ *                             of J.  The evaluations of a fixed end, which the linearisation does not make, are zeros.
+ *   behind the trial          S [n][n] row major as the fill left it, in front of the solve that factors it in place (lower triangle
+ *                             and diagonal; above the diagonal the memory is not written); y [n]; *solve_ok = 1 / 0, or -1 with x_in;
+ *                             x [n] behind the update (which zeroes x[7 r + 6] under fix_scale); trial [K][8] the trial estimates;
+ *                             sc [F] the rows' x (lambda x + b); echi_trial [E]; status_trial [4] = trial chi2, the sum of sc, the
+ *                             largest diagonal entry, solve ok.
+ * A graph without an edge or without a free keyframe gets vS, meas, xf and *n_pairs only: the full call runs no iteration on it.
+ * Refusals before any device work: those of orbx_optimize_essential_graph for the problem; ORBX_E_INVALID for a NULL dump or a lambda
+ * that is negative or not finite; ORBX_E_CAPACITY for S with n > ORBX_EG_STAGES_MAX_N or err with E > ORBX_EG_STAGES_MAX_PROBED. */
+#define ORBX_EG_STAGES_MAX_N 1024
+#define ORBX_EG_STAGES_MAX_PROBED 4096
+typedef struct {
+    double *vS, *meas, *xf;
+    double *rec, *echi, *Hd, *bv;
+    int32_t *n_pairs, *pair;
+    double *Off, *status_lin, *err;
+    double *S, *y;
+    int32_t *solve_ok;
+    double *x, *trial, *sc, *echi_trial, *status_trial;
+} orbx_eg_stages;
+int orbx_debug_eg_stages(int device, const orbx_eg_problem *p, double lambda, const double *x_in /* [7 F], may be NULL */, int trial,
+                         orbx_eg_stages *dump);
 /* test hooks for the dense LDL^T of the two bundle adjustments.  It exists in two forms that give the same bytes: 0, one workgroup
  * (k_lba_solve, n <= 1536), and 1, panels of orbx_debug_ldlt_panel_width() columns over many workgroups (orbx_ldlt.hip, n <= 12288).
  * orbx_debug_ldlt_solve uploads a dense system (S [n][n] row major, only its lower triangle is read; b [n]) and solves it with the named

@@ -16,6 +16,7 @@
 //   k_eg_fill         phase 0 zeroes the lower triangle of S; phase 1 scatters the blocks, adds lambda, copies b to y
 //   k_eg_update       trial estimate = Sim3(x_k) * S_k, and the vertex's part of x (lambda x + b)
 //   k_eg_finish       S_out and the SE3 recovery;  k_eg_points: a thread per map point
+//   k_eg_probe        orbx_debug_eg_stages only: the 29 evaluations of every edge, a thread each, for the stage tests
 #include "orbx_resident.h"
 #include "orbx_lm.h"
 #include "orbx_sim3.h"
@@ -312,6 +313,32 @@ __global__ __launch_bounds__(256) void k_eg_points(Eg G)
     f[0] = (float)cx; f[1] = (float)cy; f[2] = (float)cz;
 }
 
+// orbx_debug_eg_stages only: a thread per (edge, evaluation), err[e][v][7].  Evaluation 0 is the error at the estimates; evaluation
+// 1 + 2 c is column c's plus side and 2 + 2 c its minus side, column c = dof c of vertex 0 for c < 7 and dof c - 7 of vertex 1 above:
+// that vertex's estimate goes through Sim3(+delta e_dof) (xf[2 dof]) or Sim3(-delta e_dof) (xf[2 dof + 1]), the other one stays.  The
+// evaluations of a fixed end, which the linearisation never makes, are written as zeros.  Stated from the column, not from a lane.
+__global__ __launch_bounds__(256) void k_eg_probe(Eg G, int cur, double *err)
+{
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= 29 * (size_t)G.E) return;
+    const int e = (int)(t / 29), v = (int)(t % 29);
+    const int i = G.edge_i[e], j = G.edge_j[e];
+    Sim3 Si = xf_load(G.est[cur] + 8 * (size_t)i), Sj = xf_load(G.est[cur] + 8 * (size_t)j);
+    bool made = true;
+    if (v > 0) {
+        const int col = (v - 1) >> 1, minus = (v - 1) & 1;
+        const bool second = col >= 7;
+        const int dof = second ? col - 7 : col;
+        const Sim3 T = xf_load(G.xf + 8 * (2 * dof + minus));
+        if (second) { Sj = sim3_mul(T, Sj); made = G.row[j] >= 0; }
+        else { Si = sim3_mul(T, Si); made = G.row[i] >= 0; }
+    }
+    double r[7];
+    eg_error(xf_load(G.meas + 8 * (size_t)e), Si, Sj, r);
+#pragma unroll
+    for (int m = 0; m < 7; m++) err[7 * t + m] = made ? r[m] : 0.0;
+}
+
 }   // namespace
 
 // ---------------------------------------------------------------- host side (include/orbx.h: orbx_optimize_essential_graph)
@@ -364,19 +391,64 @@ static int eg_check(const char *who, const orbx_eg_problem *p, const orbx_eg_opt
     return ORBX_OK;
 }
 
-extern "C" int orbx_optimize_essential_graph(int device, const orbx_eg_problem *p, const orbx_eg_options *opt, float *Tcw_out, float *Xw_out,
-                                             double *S_out, double *point_out, orbx_eg_report *report)
+// A checked problem on the device, and the launch sequences over it: what orbx_optimize_essential_graph and orbx_debug_eg_stages share.
+// stage() builds the row and pair lists, uploads the problem and lays out the work area (the download head first: the status record, then
+// the four outputs); setup(), linearise() and trial() are the launches of the start, of a linearisation and of a Levenberg trial.
+struct EgCall {
+    CallCtx *c = nullptr, *pc = nullptr;
+    hipStream_t s = nullptr;
+    Eg G;
+    size_t K = 0, E = 0, P = 0, F = 0, N = 0, NP = 0;
+    size_t out = 0, w_Sout = 0, w_Tcw = 0, w_point = 0, w_Xw = 0;   // the download head and the outputs in it
+    uint8_t *extra = nullptr;                                         // `extra_bytes` of device memory behind the work area (the probe's)
+    std::vector<int32_t> pair;                                        // hi row, lo row of every unique pair, as the device has them
+
+    int stage(int device, const orbx_eg_problem *p, int n_free, size_t extra_bytes);
+
+    int setup()
+    {
+        ORBX_HIP(hipMemsetAsync(G.status, 0, 64, s));
+        if (N) ORBX_HIP(hipMemsetAsync(G.x, 0, 8 * N, s));   // the solver's x before the first solve: zeros, as in the other solvers
+        g_eg_prof.launch(EG_K_SETUP, pc, [&] { hipLaunchKernelGGL(k_eg_setup, dim3(grid256((int)std::max(std::max(K, E), (size_t)14))), dim3(256), 0, s, G); });
+        return ORBX_OK;
+    }
+
+    // the system at est[cur]: the records, the rows and pairs, chi2 and the largest diagonal entry; the status record fetched
+    int linearise(int cur)
+    {
+        g_eg_prof.launch(EG_K_LINEARIZE, pc, [&] { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_eg_edges<true>), dim3((unsigned)((E + 7) / 8)), dim3(256), 0, s, G, cur); });
+        g_eg_prof.launch(EG_K_ROWS, pc, [&] { hipLaunchKernelGGL(k_eg_rows, dim3((unsigned)(F + NP)), dim3(64), 0, s, G); });
+        g_eg_prof.launch(EG_K_REDUCE, pc, [&] { hipLaunchKernelGGL(k_eg_reduce, dim3(1), dim3(256), 0, s, G, 0); });
+        return call_fetch(c, 64);
+    }
+
+    // a trial from est[cur] into est[1 - cur]; the status record fetched.  filled() runs between the fill and the solve, which factors S
+    // in place; solve == false leaves x as it stands (orbx_debug_eg_stages with x_in).  A hook's failure ends the trial.
+    template <class Filled>
+    int trial(int cur, double lambda, bool solve, Filled filled)
+    {
+        g_eg_prof.launch(EG_K_FILL, pc, [&] {
+            hipLaunchKernelGGL(k_eg_fill, dim3(grid256((int)N), (unsigned)N), dim3(256), 0, s, G, lambda, 0);
+            hipLaunchKernelGGL(k_eg_fill, dim3((unsigned)(F + NP)), dim3(64), 0, s, G, lambda, 1);
+        });
+        if (const int rc = filled()) return rc;
+        if (solve) g_eg_prof.launch(EG_K_SOLVE, pc, [&] { orbx_ldlt_panel_launch(G.S, G.y, G.x, G.status + 3, (int)N, s); });
+        g_eg_prof.launch(EG_K_UPDATE, pc, [&] { hipLaunchKernelGGL(k_eg_update, dim3(grid256((int)K)), dim3(256), 0, s, G, cur, lambda); });
+        g_eg_prof.launch(EG_K_ERRORS, pc, [&] { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_eg_edges<false>), dim3(grid256((int)E)), dim3(256), 0, s, G, 1 - cur); });
+        g_eg_prof.launch(EG_K_REDUCE, pc, [&] { hipLaunchKernelGGL(k_eg_reduce, dim3(1), dim3(256), 0, s, G, 1); });
+        return call_fetch(c, 64);
+    }
+};
+
+int EgCall::stage(int device, const orbx_eg_problem *p, int n_free, size_t extra_bytes)
 {
-    const char *who = "orbx_optimize_essential_graph";
-    int n_free = 0;
-    int rc = eg_check(who, p, opt, Tcw_out, Xw_out, &n_free);
-    if (rc) return rc;
-    const int iterations = opt ? opt->iterations : 20;   // :1096
-    const size_t K = (size_t)p->n_kf, E = (size_t)p->n_edges, P = (size_t)p->n_points, F = (size_t)n_free, N = 7 * F;
+    int rc;
+    K = (size_t)p->n_kf; E = (size_t)p->n_edges; P = (size_t)p->n_points; F = (size_t)n_free; N = 7 * F;
     const size_t NC = (size_t)p->n_corrected, NN = (size_t)p->n_noncorrected;
 
     // rows: the free keyframes in keyframe order; a vertex's incident edges and a pair's edges in edge order
-    std::vector<int32_t> row(K), rowkf(F ? F : 1), voff(F + 1, 0), vedge, poff, pedge, pair;
+    std::vector<int32_t> row(K), rowkf(F ? F : 1), voff(F + 1, 0), vedge, poff, pedge;
+    pair.clear();
     {
         int r = 0;
         for (size_t k = 0; k < K; k++) { row[k] = p->fixed[k] ? -1 : r; if (!p->fixed[k]) rowkf[r++] = (int32_t)k; }
@@ -411,11 +483,10 @@ extern "C" int orbx_optimize_essential_graph(int device, const orbx_eg_problem *
         pedge.push_back(pe[q].second);
     }
     poff.push_back((int32_t)pe.size());
-    const size_t NP = pair.size() / 2;
+    NP = pair.size() / 2;
     if (pedge.empty()) pedge.push_back(0);
     if (pair.empty()) { pair.push_back(0); pair.push_back(0); }
 
-    CallCtx *c, *pc;
     if ((rc = orbx_call_ctx(device, &c))) return rc;
     BlobCursor b = { nullptr, nullptr, 0 };
     const size_t o_T = b.take(64 * K), o_fix = b.take(K), o_cor = b.take(4 * K), o_non = b.take(4 * K), o_Sc = b.take(64 * NC), o_Sn = b.take(64 * NN),
@@ -424,11 +495,13 @@ extern "C" int orbx_optimize_essential_graph(int device, const orbx_eg_problem *
                  o_pedge = b.take(4 * pedge.size()), o_pair = b.take(4 * pair.size());
     const size_t blob = b.o;
     BlobCursor w = { nullptr, nullptr, 0 };
-    const size_t w_status = w.take(64), w_Sout = w.take(64 * K), w_Tcw = w.take(64 * K), w_point = w.take(24 * P), w_Xw = w.take(12 * P);
-    const size_t out = w.o;
+    const size_t w_status = w.take(64);
+    w_Sout = w.take(64 * K); w_Tcw = w.take(64 * K); w_point = w.take(24 * P); w_Xw = w.take(12 * P);
+    out = w.o;
     const size_t w_e0 = w.take(64 * K), w_e1 = w.take(64 * K), w_vS = w.take(64 * K), w_meas = w.take(64 * E), w_xf = w.take(14 * 64),
                  w_rec = w.take(8 * EG_REC * E), w_echi = w.take(8 * E), w_Hd = w.take(224 * F), w_bv = w.take(56 * F), w_Off = w.take(392 * NP),
                  w_sc = w.take(8 * F), w_S = w.take(8 * N * N), w_y = w.take(8 * N), w_x = w.take(8 * N);
+    const size_t w_extra = w.take(extra_bytes);
     if ((rc = call_reserve(c, blob, w.o, out))) return rc;
     uint8_t *h = c->h_blob;
     memcpy(h + o_T, p->Tcw, 64 * K); memcpy(h + o_fix, p->fixed, K); memcpy(h + o_cor, p->corrected, 4 * K); memcpy(h + o_non, p->noncorrected, 4 * K);
@@ -442,7 +515,6 @@ extern "C" int orbx_optimize_essential_graph(int device, const orbx_eg_problem *
     if ((rc = call_upload(c, blob))) return rc;
     if ((rc = g_eg_prof.ctx(c, &pc))) return rc;
 
-    Eg G;
     memset(&G, 0, sizeof G);
     uint8_t *d = c->d_blob, *wk = c->d_work;
     G.K = (int)K; G.E = (int)E; G.P = (int)P; G.F = (int)F; G.NP = (int)NP; G.fix = p->fix_scale ? 1 : 0;
@@ -459,48 +531,108 @@ extern "C" int orbx_optimize_essential_graph(int device, const orbx_eg_problem *
     G.bv = (double *)(wk + w_bv); G.Off = (double *)(wk + w_Off); G.sc = (double *)(wk + w_sc); G.S = (double *)(wk + w_S);
     G.y = (double *)(wk + w_y); G.x = (double *)(wk + w_x);
 
-    hipStream_t s = c->stream;
+    extra = wk + w_extra;
+    s = c->stream;
+    return ORBX_OK;
+}
+
+extern "C" int orbx_optimize_essential_graph(int device, const orbx_eg_problem *p, const orbx_eg_options *opt, float *Tcw_out, float *Xw_out,
+                                             double *S_out, double *point_out, orbx_eg_report *report)
+{
+    const char *who = "orbx_optimize_essential_graph";
+    int n_free = 0;
+    int rc = eg_check(who, p, opt, Tcw_out, Xw_out, &n_free);
+    if (rc) return rc;
+    const int iterations = opt ? opt->iterations : 20;   // :1096
+    EgCall q;
+    if ((rc = q.stage(device, p, n_free, 0))) return rc;
+    const size_t K = q.K, E = q.E, P = q.P, F = q.F;
+    CallCtx *c = q.c;
     orbx_eg_report rep;
     memset(&rep, 0, sizeof rep);
     rep.n_free = n_free;
-    ORBX_HIP(hipMemsetAsync(G.status, 0, 64, s));
-    if (N) ORBX_HIP(hipMemsetAsync(G.x, 0, 8 * N, s));   // the solver's x before the first solve: zeros, as in the other solvers
-    g_eg_prof.launch(EG_K_SETUP, pc, [&] { hipLaunchKernelGGL(k_eg_setup, dim3(grid256((int)std::max(std::max(K, E), (size_t)14))), dim3(256), 0, s, G); });
+    if ((rc = q.setup())) return rc;
 
     int cur = 0;
     // no edge, or no free vertex: optimize() finds no active vertex and returns before the first iteration (sparse_optimizer.cpp:341-345)
     const LmRun r = lm_host_loop(
         E > 0 && F > 0 ? iterations : 0, 1e-16,   // setUserLambdaInit(1e-16), :899
-        [&] {
-            g_eg_prof.launch(EG_K_LINEARIZE, pc, [&] { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_eg_edges<true>), dim3((unsigned)((E + 7) / 8)), dim3(256), 0, s, G, cur); });
-            g_eg_prof.launch(EG_K_ROWS, pc, [&] { hipLaunchKernelGGL(k_eg_rows, dim3((unsigned)(F + NP)), dim3(64), 0, s, G); });
-            g_eg_prof.launch(EG_K_REDUCE, pc, [&] { hipLaunchKernelGGL(k_eg_reduce, dim3(1), dim3(256), 0, s, G, 0); });
-            return call_fetch(c, 64);
-        },
-        [&](double lambda) {
-            g_eg_prof.launch(EG_K_FILL, pc, [&] {
-                hipLaunchKernelGGL(k_eg_fill, dim3(grid256((int)N), (unsigned)N), dim3(256), 0, s, G, lambda, 0);
-                hipLaunchKernelGGL(k_eg_fill, dim3((unsigned)(F + NP)), dim3(64), 0, s, G, lambda, 1);
-            });
-            g_eg_prof.launch(EG_K_SOLVE, pc, [&] { orbx_ldlt_panel_launch(G.S, G.y, G.x, G.status + 3, (int)N, s); });
-            g_eg_prof.launch(EG_K_UPDATE, pc, [&] { hipLaunchKernelGGL(k_eg_update, dim3(grid256((int)K)), dim3(256), 0, s, G, cur, lambda); });
-            g_eg_prof.launch(EG_K_ERRORS, pc, [&] { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_eg_edges<false>), dim3(grid256((int)E)), dim3(256), 0, s, G, 1 - cur); });
-            g_eg_prof.launch(EG_K_REDUCE, pc, [&] { hipLaunchKernelGGL(k_eg_reduce, dim3(1), dim3(256), 0, s, G, 1); });
-            return call_fetch(c, 64);
-        },
+        [&] { return q.linearise(cur); }, [&](double lambda) { return q.trial(cur, lambda, true, [] { return ORBX_OK; }); },
         [&] { return (const double *)c->h_out; }, [] { return false; }, [&] { cur = 1 - cur; });
     if (r.rc) return r.rc;
     rep.iterations = r.iterations; rep.trials = r.trials; rep.n_solve_failed = r.n_solve_failed;
     rep.chi2_start = r.chi2_start; rep.chi2 = r.chi2; rep.lambda = r.lambda;
 
-    g_eg_prof.launch(EG_K_FINISH, pc, [&] { hipLaunchKernelGGL(k_eg_finish, dim3(grid256((int)K)), dim3(256), 0, s, G, cur); });
-    if (P) g_eg_prof.launch(EG_K_POINTS, pc, [&] { hipLaunchKernelGGL(k_eg_points, dim3(grid256((int)P)), dim3(256), 0, s, G); });
-    if ((rc = call_fetch(c, out))) return rc;
+    g_eg_prof.launch(EG_K_FINISH, q.pc, [&] { hipLaunchKernelGGL(k_eg_finish, dim3(grid256((int)K)), dim3(256), 0, q.s, q.G, cur); });
+    if (P) g_eg_prof.launch(EG_K_POINTS, q.pc, [&] { hipLaunchKernelGGL(k_eg_points, dim3(grid256((int)P)), dim3(256), 0, q.s, q.G); });
+    if ((rc = call_fetch(c, q.out))) return rc;
     const uint8_t *ho = (const uint8_t *)c->h_out;
-    memcpy(Tcw_out, ho + w_Tcw, 64 * K);
-    if (S_out) memcpy(S_out, ho + w_Sout, 64 * K);
-    if (P) memcpy(Xw_out, ho + w_Xw, 12 * P);
-    if (P && point_out) memcpy(point_out, ho + w_point, 24 * P);
+    memcpy(Tcw_out, ho + q.w_Tcw, 64 * K);
+    if (S_out) memcpy(S_out, ho + q.w_Sout, 64 * K);
+    if (P) memcpy(Xw_out, ho + q.w_Xw, 12 * P);
+    if (P && point_out) memcpy(point_out, ho + q.w_point, 24 * P);
     if (report) *report = rep;
+    return ORBX_OK;
+}
+
+// orbx_debug_eg_stages (include/orbx.h): ONE linearisation at the start estimates and, where asked, ONE trial from them, through the
+// launch sequences of the call above; what each kernel left in device memory is copied out between them.
+extern "C" int orbx_debug_eg_stages(int device, const orbx_eg_problem *p, double lambda, const double *x_in, int trial, orbx_eg_stages *d)
+{
+    const char *who = "orbx_debug_eg_stages";
+    if (!d) { orbx_set_error("%s: NULL dump", who); return ORBX_E_INVALID; }
+    int n_free = 0;
+    static const float none = 0.f;   // this call has no Tcw_out and no Xw_out for eg_check to ask for
+    int rc = eg_check(who, p, nullptr, &none, &none, &n_free);
+    if (rc) return rc;
+    if (!(lambda >= 0.0) || !std::isfinite(lambda)) { orbx_set_error("%s: lambda = %g", who, lambda); return ORBX_E_INVALID; }
+    if (d->S && 7 * n_free > ORBX_EG_STAGES_MAX_N) {
+        orbx_set_error("%s: S asked for with n = %d, more than %d", who, 7 * n_free, ORBX_EG_STAGES_MAX_N);
+        return ORBX_E_CAPACITY;
+    }
+    if (d->err && p->n_edges > ORBX_EG_STAGES_MAX_PROBED) {
+        orbx_set_error("%s: err asked for with %d edges, more than %d", who, p->n_edges, ORBX_EG_STAGES_MAX_PROBED);
+        return ORBX_E_CAPACITY;
+    }
+    EgCall q;
+    if ((rc = q.stage(device, p, n_free, d->err ? 8 * 29 * 7 * (size_t)p->n_edges : 0))) return rc;
+    const size_t K = q.K, E = q.E, F = q.F, N = q.N, NP = q.NP;
+    const Eg &G = q.G;
+    // device memory -> the caller's array, where there is one
+    auto copy = [&](void *dst, const void *src, size_t bytes) -> int {
+        if (!dst || !bytes) return ORBX_OK;
+        ORBX_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, q.s));
+        ORBX_HIP(hipStreamSynchronize(q.s));
+        return ORBX_OK;
+    };
+    if ((rc = q.setup())) return rc;
+    if ((rc = copy(d->vS, G.vS, 64 * K)) || (rc = copy(d->meas, G.meas, 64 * E)) || (rc = copy(d->xf, G.xf, 14 * 64))) return rc;
+    if (d->n_pairs) *d->n_pairs = (int32_t)NP;
+    if (E == 0 || F == 0) { ORBX_HIP(hipStreamSynchronize(q.s)); return ORBX_OK; }   // the full call runs no iteration on such a graph
+
+    if ((rc = q.linearise(0))) return rc;
+    if (d->status_lin) memcpy(d->status_lin, q.c->h_out, 32);
+    if (d->pair && NP) memcpy(d->pair, q.pair.data(), 8 * NP);
+    if ((rc = copy(d->rec, G.rec, 8 * EG_REC * E)) || (rc = copy(d->echi, G.echi, 8 * E)) || (rc = copy(d->Hd, G.Hd, 224 * F)) ||
+        (rc = copy(d->bv, G.bv, 56 * F)) || (rc = copy(d->Off, G.Off, 392 * NP))) return rc;
+    if (d->err) {
+        double *err = (double *)q.extra;
+        hipLaunchKernelGGL(k_eg_probe, dim3(grid256((int)(29 * E))), dim3(256), 0, q.s, G, 0, err);
+        ORBX_HIP(hipGetLastError());
+        if ((rc = copy(d->err, err, 8 * 29 * 7 * E))) return rc;
+    }
+    if (!trial) return ORBX_OK;
+
+    rc = q.trial(0, lambda, x_in == nullptr, [&]() -> int {
+        int r;
+        if ((r = copy(d->S, G.S, 8 * N * N)) || (r = copy(d->y, G.y, 8 * N))) return r;   // above S's diagonal: whatever the memory held
+        if (x_in) ORBX_HIP(hipMemcpyAsync(G.x, x_in, 8 * N, hipMemcpyHostToDevice, q.s));
+        return ORBX_OK;
+    });
+    if (rc) return rc;
+    if (d->status_trial) memcpy(d->status_trial, q.c->h_out, 32);
+    if (d->solve_ok) *d->solve_ok = x_in ? -1 : (((const double *)q.c->h_out)[3] != 0.0);
+    if ((rc = copy(d->x, G.x, 8 * N)) || (rc = copy(d->trial, G.est[1], 64 * K)) || (rc = copy(d->sc, G.sc, 8 * F)) ||
+        (rc = copy(d->echi_trial, G.echi, 8 * E))) return rc;
     return ORBX_OK;
 }

@@ -174,6 +174,12 @@ class EgReport(C.Structure):
                 ("chi2_start", C.c_double), ("chi2", C.c_double), ("lambda_", C.c_double)]
 
 
+class EgStages(C.Structure):
+    """orbx_eg_stages (include/orbx.h)"""
+    _fields_ = [(k, C.c_void_p) for k in ("vS", "meas", "xf", "rec", "echi", "Hd", "bv", "n_pairs", "pair", "Off", "status_lin", "err", "S", "y",
+                                          "solve_ok", "x", "trial", "sc", "echi_trial", "status_trial")]
+
+
 class PoseJob(C.Structure):
     """orbx_pose_job (include/orbx.h)"""
     _fields_ = [("obs", C.POINTER(PoseObs)), ("cam", C.c_void_p), ("Tcw", C.c_void_p), ("Tcw_out", C.c_void_p),
@@ -357,6 +363,7 @@ def lib():
     L.orbx_bundle_adjustment.argtypes = [i, C.POINTER(LbaProblem), C.POINTER(BaOptions), vp, vp, vp, vp, vp, C.POINTER(BaReport)]
     L.orbx_optimize_essential_graph.argtypes = [i, C.POINTER(EgProblem), C.POINTER(EgOptions), vp, vp, vp, vp, C.POINTER(EgReport)]
     L.orbx_debug_eg_profile.argtypes = [i, vp, vp]
+    L.orbx_debug_eg_stages.argtypes = [i, C.POINTER(EgProblem), C.c_double, vp, i, C.POINTER(EgStages)]
     L.orbx_debug_ldlt_solve.argtypes = [i, i, vp, vp, vp, i, C.POINTER(C.c_int)]
     L.orbx_debug_set_lba_solver.argtypes = [i]
     L.orbx_debug_ldlt_panel_width.argtypes = []
@@ -1190,6 +1197,50 @@ def optimize_essential_graph(problem, iterations=20, device=0):
     _check(lib().orbx_optimize_essential_graph(device, C.byref(pr), C.byref(opt), _p(Tcw), _p(Xw), _p(S), _p(point), C.byref(rep)))
     return {"Tcw": Tcw, "Xw": Xw, "S": S, "point": point, "iterations": rep.iterations, "trials": rep.trials, "n_free": rep.n_free,
             "n_solve_failed": rep.n_solve_failed, "chi2_start": rep.chi2_start, "chi2": rep.chi2, "lambda": rep.lambda_}
+
+
+EG_STAGES = ("vS", "meas", "xf", "rec", "echi", "Hd", "bv", "pair", "Off", "status_lin", "err", "S", "y", "solve_ok", "x", "trial", "sc",
+             "echi_trial", "status_trial")
+EG_STAGES_MAX_N, EG_STAGES_MAX_PROBED = 1024, 4096
+
+
+def eg_stages(problem, lam, x=None, trial=True, want=None, device=0):
+    """orbx_debug_eg_stages: one linearisation of the essential graph at its start estimates and, with trial, one Levenberg trial with
+    lambda = lam, through the launch sequences of optimize_essential_graph; x [7 F]: the solve is skipped and the update reads x.
+    want: names of EG_STAGES (default all but "S" and "err"; without trial, those of the linearisation) -> dict of the arrays as
+    include/orbx.h lays them out: vS, trial [K][8], meas [E][8], xf [14][8], rec [E][120], echi, echi_trial [E], Hd [F][28], bv [F][7],
+    pair [NP][2] (with n_pairs), Off [NP][49], status_lin, status_trial [4], err [E][29][7], S [n][n], y, x [n], sc [F], solve_ok"""
+    pr, keep = _eg_problem(problem, "eg_stages")
+    K, E, F = pr.n_kf, pr.n_edges, pr.n_kf - 1
+    n = 7 * F
+    want = [k for k in EG_STAGES if k not in ("S", "err")] if want is None else list(want)
+    for k in want:
+        if k not in EG_STAGES:
+            raise OrbxError(-1, f"eg_stages: no stage {k!r}")
+    ran = E > 0 and F > 0
+    if not trial or not ran:
+        want = [k for k in want if k not in EG_STAGES[11:]]
+    if not ran:
+        want = [k for k in want if k in ("vS", "meas", "xf", "pair")]
+    shapes = dict(vS=(K, 8), meas=(E, 8), xf=(14, 8), rec=(E, 120), echi=(E,), Hd=(F, 28), bv=(F, 7), pair=(E, 2), Off=(E, 49), status_lin=(4,),
+                  err=(E, 29, 7), S=(n, n), y=(n,), solve_ok=(1,), x=(n,), trial=(K, 8), sc=(F,), echi_trial=(E,), status_trial=(4,))
+    out = {k: np.zeros(shapes[k], np.int32 if k in ("pair", "solve_ok") else np.float64) for k in want}
+    if "Off" in out and "pair" not in out:
+        out["pair"] = np.zeros(shapes["pair"], np.int32)
+    npairs = np.zeros(1, np.int32)
+    d = EgStages(**{k: _p(v) for k, v in out.items()}, n_pairs=_p(npairs))
+    xin = None if x is None else np.ascontiguousarray(x, np.float64).reshape(-1)
+    if xin is not None and len(xin) != n:
+        raise OrbxError(-1, f"eg_stages: x has {len(xin)} entries, not 7 x {F}")
+    _check(lib().orbx_debug_eg_stages(device, C.byref(pr), float(lam), None if xin is None else _p(xin), int(bool(trial)), C.byref(d)))
+    NP = int(npairs[0])
+    for k in ("pair", "Off"):
+        if k in out:
+            out[k] = out[k][:NP].copy()
+    if "solve_ok" in out:
+        out["solve_ok"] = int(out["solve_ok"][0])
+    out["n_pairs"] = NP
+    return out
 
 
 def ldlt_solve(S, b, form, x0=None, device=0):

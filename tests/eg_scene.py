@@ -9,7 +9,8 @@ corrected one.  Edges, in the order the function adds them: the LoopConnections 
 spanning-tree edge (some parents are not the predecessor), one earlier loop edge, and its covisibility edges that are neither of those nor in
 sInsertedEdges (kind 1).  Map points hang on reference keyframes all over the list.
 
-case(tag) -> (problem, options).  Tags: "<F>-free" / "<F>-fix" for F free keyframes, and the SPECIAL ones."""
+case(tag) -> (problem, options).  Tags: "<F>-free" / "<F>-fix" for F free keyframes, and the SPECIAL ones.
+stage_case(name) -> the small designed inputs of the stage tests (STAGE_CASES, at the end of the file)."""
 import math
 
 import numpy as np
@@ -233,3 +234,184 @@ def variants(pr, opts):
     base = em.optimize(pr, **opts, **VARIANTS[0])
     rest = [v for v in VARIANTS[1:] if not (v.get("jacobian") == "closed" and base["branches"][2])]
     return [base] + [em.optimize(pr, **opts, **v) for v in rest]
+
+
+# ---------------------------------------------------------------- the inputs of the stage tests (tests/test_eg_stages.py, tests/test_eg_stages_model.py)
+
+THETA_EDGE = math.acos(1.0 - 1e-5)            # the rotation angle at which Sim3::log's d = 1 - eps
+LOG_ANGLES = (0.0, 3e-6, THETA_EDGE - 1e-6, THETA_EDGE + 1e-6, 0.3, 3.0, 3.1)
+LOG_AXES = ((1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 0), (1, 2, 3))
+LOG_SIGMAS = (0.0, 3e-6, 1e-5 - 1e-9, 1e-5 + 1e-9, -(1e-5 - 1e-9), -(1e-5 + 1e-9), 0.2, -0.2)
+STAGE_LAMBDA = 0.25                           # a lambda that no diagonal entry swallows in rounding, exact in binary
+IDENTITY = np.array([0, 0, 0, 1, 0, 0, 0, 1], np.float64)
+
+
+def _quat(axis, angle):
+    a = np.asarray(axis, np.float64)
+    a = a / np.linalg.norm(a)
+    return np.concatenate([a * math.sin(0.5 * angle), [math.cos(0.5 * angle)]]) if angle != 0.0 else np.array([0.0, 0.0, 0.0, 1.0])
+
+
+def log_rows(fix_scale=1):
+    """the designed start residuals (label, Sim3 [8]) of the log table: every angle x axis x scale, each with its own nonzero translation,
+    then a row whose quaternion is -q and one whose quaternion has the norm 1 + 1e-3.  The four scales 1e-9 from eps are rows of the
+    fix_scale table alone: with a free scale the central difference moves sigma by delta = 1e-9 itself, one of the two evaluations of
+    columns 6 and 13 then has |sigma| = eps to the last bit, and which branch it takes is decided by the rounding of exp(1e-9) -- the
+    model disagrees with itself there by 2e-6 across its nudges in every such row, so the rows would only test the last bit of exp."""
+    rows = []
+    n = 0
+    for th in LOG_ANGLES:
+        for ax in LOG_AXES:
+            for sg in LOG_SIGMAS:
+                if not fix_scale and abs(abs(sg) - 1e-5) < 1e-8:
+                    continue
+                t = np.array([0.3 + 0.07 * (n % 5), -0.2 + 0.11 * (n % 7), 0.5 - 0.13 * (n % 3)])
+                t = np.roll(t, n % 3) * (-1.0 if n % 4 == 3 else 1.0)
+                rows.append((f"theta {th:.9g} axis {ax} sigma {sg:.9g}", np.concatenate([_quat(ax, th), t, [math.exp(sg) if sg else 1.0]])))
+                n += 1
+    rows.append(("-q", np.concatenate([-_quat((1, 2, 3), 0.3), [0.4, -0.1, 0.2], [math.exp(0.2)]])))
+    rows.append(("norm 1 + 1e-3", np.concatenate([(1.0 + 1e-3) * _quat((1, 2, 3), 0.3), [0.4, -0.1, 0.2], [math.exp(0.2)]])))
+    return rows
+
+
+def log_table(fix_scale=0):
+    """one edge per designed residual D_r (log_rows): keyframe 0 is fixed and an identity, free keyframe 1 + r starts at S_corrected = D_r
+    and is vertex 0 of edge r, whose vertex 1 is the fixed keyframe (r % 3 == 0) or the free identity keyframe FAR + r // 24.  All edges
+    are normal edges and every keyframe's NonCorrectedSim3 is the identity, so every measurement is the identity exactly and the start
+    error of edge r is log(D_r), the product with an identity being exact.  -> (problem, labels)"""
+    rows = log_rows(fix_scale)
+    R = len(rows)
+    n_far = (R + 23) // 24
+    K = 1 + R + n_far
+    Tcw = np.tile(np.eye(4, dtype=f32), (K, 1, 1))
+    fixed = np.zeros(K, np.uint8); fixed[0] = 1
+    corrected = -np.ones(K, np.int32); corrected[1:1 + R] = np.arange(R)
+    noncorrected = np.zeros(K, np.int32)
+    Sc = np.array([d for _, d in rows])
+    ei = 1 + np.arange(R, dtype=np.int32)
+    ej = np.array([0 if r % 3 == 0 else 1 + R + r // 24 for r in range(R)], np.int32)
+    return dict(Tcw=Tcw, fixed=fixed, corrected=corrected, noncorrected=noncorrected, S_corrected=Sc, S_noncorrected=IDENTITY[None].copy(),
+                edge_i=ei, edge_j=ej, edge_kind=np.ones(R, np.uint8), Xw=np.zeros((0, 3), f32), point_ref=np.zeros(0, np.int32),
+                fix_scale=int(bool(fix_scale))), [l for l, _ in rows]
+
+
+EXP_OMEGAS = (("0", (0.0, 0.0, 0.0)), ("3e-6", (0.0, 3e-6, 0.0)), ("1e-5 - 1e-9", (1e-5 - 1e-9, 0.0, 0.0)), ("1e-5 + 1e-9", (0.0, 0.0, 1e-5 + 1e-9)),
+              ("0.3", tuple(0.3 * np.array([1.0, 2.0, 3.0]) / math.sqrt(14.0))), ("3.0 x", (3.0, 0.0, 0.0)), ("3.0 y", (0.0, 3.0, 0.0)),
+              ("3.0 z", (0.0, 0.0, 3.0)))
+EXP_SIGMAS = (0.0, 3e-6, 0.2, -0.2)
+
+
+def _turned(k):
+    """keyframe rotations for Quaternion(Matrix3): k % 4 == 0 the trace > 0, else a turn of 3 rad about axis k % 4 - 1 (that diagonal entry
+    the largest, the trace below 0)"""
+    return _rot([0.2, -0.1, 1.0], 0.4 + 0.1 * k) if k % 4 == 0 else _rot(np.eye(3)[k % 4 - 1] + 0.02 * np.array([1.0, -2.0, 1.5]), 3.0)
+
+
+def chain(F, fix_scale, seed, fixed_at=0, extra=0):
+    """F + 1 keyframes in a row joined by F spanning edges (keyframe k to k - 1, every third one written the other way round) and `extra`
+    chords (k to k - 2).  The float poses turn through all four branches of Quaternion(Matrix3) (_turned); every fifth keyframe has a
+    CorrectedSim3 with a scale of its own, every seventh a NonCorrectedSim3.  The edges alternate between the two kinds."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    K = F + 1
+    Tcw = np.zeros((K, 4, 4), f32)
+    Sc, Sn = [], []
+    corrected, noncorrected = -np.ones(K, np.int32), -np.ones(K, np.int32)
+    for k in range(K):
+        R = _turned(k)
+        t = np.array([0.5 * k, 0.3 * math.sin(k), 0.1 * k]) + 0.05 * rng.normal(size=3)
+        Tcw[k, :3, :3] = R; Tcw[k, :3, 3] = t; Tcw[k, 3, 3] = 1
+        if k % 5 == 4:
+            corrected[k] = len(Sc)
+            Sc.append(_sim3(_rot(rng.normal(size=3), 0.02) @ R, t + 0.02 * rng.normal(size=3), 1.0 if fix_scale else 1.0 + 0.1 * rng.uniform(-1, 1)))
+        if k % 7 == 3:
+            noncorrected[k] = len(Sn)
+            Sn.append(_sim3(_rot(rng.normal(size=3), 0.01) @ R, t + 0.01 * rng.normal(size=3), 1.0))
+    fixed = np.zeros(K, np.uint8); fixed[fixed_at] = 1
+    ei, ej = [], []
+    for k in range(1, K):
+        a, b = (k, k - 1) if k % 3 else (k - 1, k)
+        ei.append(a); ej.append(b)
+    for n in range(extra):
+        k = 2 + n % max(K - 2, 1)
+        ei.append(k); ej.append(k - 2)
+    E = len(ei)
+    return dict(Tcw=Tcw, fixed=fixed, corrected=corrected, noncorrected=noncorrected, S_corrected=np.array(Sc).reshape(-1, 8),
+                S_noncorrected=np.array(Sn).reshape(-1, 8), edge_i=np.array(ei, np.int32), edge_j=np.array(ej, np.int32),
+                edge_kind=(np.arange(E) % 2).astype(np.uint8), Xw=np.zeros((0, 3), f32), point_ref=np.zeros(0, np.int32), fix_scale=int(bool(fix_scale)))
+
+
+def exp_table(fix_scale):
+    """a chain with one free keyframe per (omega, sigma) of EXP_OMEGAS x EXP_SIGMAS and the update x_in that holds them, each with a nonzero
+    upsilon -> (problem, x_in [7 F], labels [F])"""
+    labels, xs = [], []
+    n = 0
+    for name, om in EXP_OMEGAS:
+        for sg in EXP_SIGMAS:
+            ups = np.roll(np.array([0.05 + 0.01 * (n % 4), -0.03, 0.02 * (1 + n % 3)]), n % 3)
+            xs.append(np.concatenate([om, ups, [sg]])); labels.append(f"omega {name} sigma {sg:.9g}")
+            n += 1
+    return chain(len(xs), fix_scale, 9900 + int(bool(fix_scale))), np.concatenate(xs), labels
+
+
+SHAPES = ("edges-1", "edges-7", "edges-8", "edges-9", "edges-17", "fixed-is-i", "fixed-has-no-edge", "two_edges_one_pair", "vertex_without_edge",
+          "fixed_in_middle", "fixed_at_both_ends")
+
+
+def shape(tag):
+    """the small graphs of the stage tests.  edges-E: E edges, so that k_eg_edges<true>'s workgroups of eight are a single slot, part
+    filled, exactly full, full and one more, and two and one more; the fixed keyframe is vertex 1 of its edges (vertex 0 of both
+    its edges in fixed-is-i, and of no edge in fixed-has-no-edge).  The named special
+    scenes are case()'s.  The odd ones are fix_scale scenes."""
+    if tag.startswith("edges-"):
+        E = int(tag[6:])
+        F = min(E, 5)
+        return chain(F, E % 2, 9800 + E, extra=E - F)
+    if tag == "fixed-is-i":
+        return chain(6, 0, 9850, fixed_at=5, extra=3)
+    if tag == "fixed-has-no-edge":
+        pr = chain(6, 1, 9851, extra=4)
+        pr2 = {k: (np.concatenate([v, v[:1]]) if k in ("Tcw", "fixed", "corrected", "noncorrected") else v) for k, v in pr.items()}
+        pr2["fixed"] = pr2["fixed"].copy(); pr2["fixed"][:] = 0; pr2["fixed"][-1] = 1     # a copy of keyframe 0 behind the list, fixed, without an edge
+        return pr2
+    return case(tag)[0]
+
+
+def long_chain(fix_scale=0):
+    """260 free keyframes and 300 edges: more than one stride of 256 in k_eg_reduce's sums over the edges and the rows and in the update"""
+    return chain(260, fix_scale, 9870, fixed_at=130, extra=40)
+
+
+def long_chain_x(F=260):
+    """an update for long_chain: small, every dof nonzero"""
+    rng = np.random.Generator(np.random.PCG64(9871))
+    return 0.01 * rng.normal(size=7 * F)
+
+
+STAGE_CASES = ("log-free", "log-fix", "exp-free", "exp-fix", "long-free") + tuple("shape-" + t for t in SHAPES)
+_stage_cache = {}
+
+
+def stage_case(name):
+    """-> dict(problem, lam, x (None: the device solves), labels (of the rows of err, or of trial for an exp table), S (whether the n x n
+    matrix is worth dumping))"""
+    if name.startswith("log-"):
+        pr, labels = log_table(name == "log-fix")
+        return dict(problem=pr, lam=STAGE_LAMBDA, x=None, labels=labels, S=False)
+    if name.startswith("exp-"):
+        pr, x, labels = exp_table(name == "exp-fix")
+        return dict(problem=pr, lam=STAGE_LAMBDA, x=x, labels=["fixed"] + labels, S=True)
+    if name == "long-free":
+        pr = long_chain(0)
+        return dict(problem=pr, lam=STAGE_LAMBDA, x=long_chain_x(), labels=[f"edge {e}" for e in range(len(pr["edge_i"]))], S=False)
+    pr = shape(name[6:])
+    return dict(problem=pr, lam=STAGE_LAMBDA, x=None, labels=[f"edge {e}" for e in range(len(pr["edge_i"]))], S=True)
+
+
+def stage_models(name, mutation=None):
+    """the model's stages of a case at the nudge settings None, 1, 2 (computed once), or under a mutation without a nudge"""
+    key = (name, mutation)
+    if key not in _stage_cache:
+        c = stage_case(name)
+        nudges = (None, 1, 2) if mutation is None else (None,)
+        _stage_cache[key] = [em.stages(c["problem"], c["lam"], c["x"], nudge=n, mutation=mutation) for n in nudges]
+    return _stage_cache[key]

@@ -26,9 +26,14 @@ the bound can and cannot tell from the truth:
     MUTATION bta_untransposed smallest change 1.798e+308 over 1 scenes  (the system is no longer symmetric, every solve fails)
 
 The test asserts BOUND <= SMALLEST_VISIBLE_MUTATION / 16 over the mutations listed as visible below; the others are NOT told from the
-truth by the comparison with the model and are named here and in DESIGN.md: lambda_diag, x6_not_zeroed,
-normal_from_vscw (seen in most scenes, not in all), normalise, t_not_divided.  Two of them are
-held by exact checks instead: t_not_divided by Tcw == float32(recover(S)), x6_not_zeroed by the scale bits under fix_scale."""
+truth by THIS comparison, which is of a whole Levenberg run.  Each is held by a test of one stage instead (tests/test_eg_stages.py on
+orbx_debug_eg_stages, the checks of tests/eg_stage_checks.py; DESIGN.md has the table):
+    lambda_diag       test_one_iteration_leaves_lambda_from_1e_16: lambda after one iteration of the public call
+    x6_not_zeroed     test_equal_bytes, the update check (x[6::7] == 0 and the trial's scale bits, on a designed x), and the scale bits here
+    normal_from_vscw  test_equal_bytes, the setup check: meas equals the model's in bytes
+    normalise         the same check: a normalised product differs from the model's in the last bits
+    t_not_divided     here: Tcw == float32(recover(S))
+    bta_untransposed  test_equal_bytes, the rows check: Off equals the ordered sum of the device's own records; and the bound here"""
 import ctypes as C
 
 import numpy as np
@@ -45,7 +50,9 @@ SPREAD_S = 1.476e-04    # python tools/eg_spread.py (rounded up in the fourth di
 SPREAD_POINT = 1.919e-04
 SPREAD_CHI2 = 9.938e-06
 BOUND_S, BOUND_POINT, BOUND_CHI2 = 64 * SPREAD_S, 64 * SPREAD_POINT, 64 * SPREAD_CHI2
-VISIBLE_MUTATIONS = {"bta_untransposed": 1.798e+308}  # python tools/eg_spread.py --mutations: the smallest change of each mutation the bound can see
+# python tools/eg_spread.py --mutations: the smallest change of each mutation THIS bound can see; the stage tests of tests/test_eg_stages.py
+# see it and the other five by equal bytes (the list is in this file's docstring)
+VISIBLE_MUTATIONS = {"bta_untransposed": 1.798e+308}
 SMALLEST_VISIBLE_MUTATION = min(VISIBLE_MUTATIONS.values())
 assert max(BOUND_S, BOUND_POINT, BOUND_CHI2) <= SMALLEST_VISIBLE_MUTATION / 16, "the bound could hide one of the errors listed as visible"
 

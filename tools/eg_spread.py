@@ -5,7 +5,11 @@ points in tools/lba_spread.py's points_diff, chi2 in tools/pose_spread.py's chi2
 this spread.
     python tools/eg_spread.py              SPREAD_S, SPREAD_POINT, SPREAD_CHI2 over the scenes as they are
     python tools/eg_spread.py --mutations  the smallest output change of each deliberate error in the model (eg_model.MUTATIONS), over the
-                                           scenes the error can touch"""
+                                           scenes the error can touch
+    python tools/eg_spread.py --stages     per case of eg_scene.STAGE_CASES and per row of err (of the trial estimates for an exp table) the
+                                           model's spread across nudge None, 1, 2 (tests/eg_stage_checks.py: row_bounds), the floor, the
+                                           rows whose bound exceeds 1e-10, the paths the case visits; then per mutation the check that
+                                           sees it and, for those seen under the bound, the smallest change over the rows it can touch"""
 import math
 import os
 import sys
@@ -69,9 +73,42 @@ def mutations(tags):
     return 0 if all(math.isfinite(v) for v in worst.values()) else 1
 
 
+def stages():
+    import eg_stage_checks as ck
+    ok = True
+    for name in es.STAGE_CASES:
+        c, runs = es.stage_case(name), es.stage_models(name)
+        q = "trial" if name.startswith("exp-") else "err"
+        bound, spread, floor = ck.row_bounds([r[q] for r in runs])
+        big = np.nonzero(bound > 1e-10)[0]
+        m = runs[0]
+        print(f"STAGE {name:28s} {q:5s} rows {len(bound):3d} floor {floor:.3e} largest spread {spread.max():.3e} largest bound {bound.max():.3e} "
+              f"rows over 1e-10: {len(big)} ({100.0 * len(big) / len(bound):.1f} %)  log {m['branches']} pivot {m['paths']['pivot']} "
+              f"second {m['paths']['second']} exp {m['paths']['exp']} quat {m['paths']['quat']}")
+        for i in big:
+            print(f"    ROW {i} ({c['labels'][i]}) spread {spread[i]:.3e} bound {bound[i]:.3e}")
+        ok = ok and len(big) <= 0.02 * len(bound)
+    for mut, (check, kind) in ck.SEEN_BY.items():
+        for name in ck.MUTATION_CASES[mut]:
+            c, runs = es.stage_case(name), es.stage_models(name)
+            bad = es.stage_models(name, mut)[0]
+            if kind == "bytes":
+                found = ck.run_check(check, c["problem"], bad, c["lam"], runs[0])
+                print(f"MUTATION {mut:22s} {name:24s} check {check:8s} bytes: {found[0] if found else 'NOT SEEN'}")
+                ok = ok and bool(found)
+            else:
+                rows, ratio, change, bound = ck.margin(mut, runs, bad)
+                print(f"MUTATION {mut:22s} {name:24s} check {check:8s} bound: {len(rows)} rows, smallest change {change:.3e}, largest bound there "
+                      f"{bound:.3e}, smallest change / bound {ratio:.3e}")
+                ok = ok and len(rows) > 0 and ratio >= 16
+    return 0 if ok else 1
+
+
 def main():
     if "--mutations" in sys.argv:
         return mutations(es.all_tags())
+    if "--stages" in sys.argv:
+        return stages()
     ws = wx = wc = 0.0
     total = [0, 0, 0, 0]
     for tag in es.all_tags():
