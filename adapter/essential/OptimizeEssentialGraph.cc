@@ -1,5 +1,5 @@
 // adapter/essential/OptimizeEssentialGraph.cc -- ORB_SLAM2::Optimizer::OptimizeEssentialGraph (reference src/Optimizer.cc:885-1153) on the
-// device.  Vertices and edges are gathered as :914-1092 add them; ONE call of orbx_optimize_essential_graph replaces g2o between :891 and
+// device.  Vertices and edges are gathered as :914-1092 add them; ONE call of orbx_optimize_essential_graph2 replaces g2o between :891 and
 // :1096 and does the arithmetic of the two recovery loops; then, under mMutexMapUpdate, SetPose, SetWorldPos and UpdateNormalAndDepth as
 // :1098-1152.  Graph selection stays here because it walks KeyFrame pointers: GetWeight < minFeat, parents, GetLoopEdges,
 // GetCovisiblesByWeight, sInsertedEdges.  Its own sub-directory, like adapter/ba/: it needs Optimizer.h, Map.h and LoopClosing.h.
@@ -11,8 +11,12 @@
 //    default-constructed Sim3s.
 //  - The points' positions are read before the call, not under the lock behind it (LocalMapping stands still during CorrectLoop); a point
 //    that has turned bad by then is passed over, as :1126 does.
+// -DORBX_EG_ORDER_BY_ID: the keyframes are indexed in mnId order (g2o's own vertex ids are the mnIds), not in the order of
+// Map::GetAllKeyFrames, which is the pointer order of a std::set<KeyFrame*>.  The call's solver (ORBX_EG_SOLVER_AUTO) stores the system as
+// an envelope in keyframe order; that envelope is narrow in creation order only, and orbx_eg_envelope tells what an order costs.
 #include "Optimizer.h"
 
+#include <algorithm>
 #include <map>
 #include <set>
 #include <stdexcept>
@@ -27,6 +31,10 @@ using namespace std;
 namespace ORB_SLAM2
 {
 
+#ifdef ORBX_EG_ORDER_BY_ID
+static bool LessById(const KeyFrame *a, const KeyFrame *b) { return a->mnId < b->mnId; }
+#endif
+
 static void PushSim3(vector<double> &v, const g2o::Sim3 &S)
 {
     v.push_back(S.rotation().x()); v.push_back(S.rotation().y()); v.push_back(S.rotation().z()); v.push_back(S.rotation().w());
@@ -39,7 +47,12 @@ void Optimizer::OptimizeEssentialGraph(Map* pMap, KeyFrame* pLoopKF, KeyFrame* p
                                        const LoopClosing::KeyFrameAndPose &CorrectedSim3,
                                        const map<KeyFrame *, set<KeyFrame *> > &LoopConnections, const bool &bFixScale)
 {
+#ifdef ORBX_EG_ORDER_BY_ID
+    vector<KeyFrame*> vpKFs = pMap->GetAllKeyFrames();
+    sort(vpKFs.begin(), vpKFs.end(), LessById);
+#else
     const vector<KeyFrame*> vpKFs = pMap->GetAllKeyFrames();
+#endif
     const vector<MapPoint*> vpMPs = pMap->GetAllMapPoints();
     const int minFeat = 100;
 
@@ -141,9 +154,10 @@ void Optimizer::OptimizeEssentialGraph(Map* pMap, KeyFrame* pLoopKF, KeyFrame* p
     prob.n_edges = (int)edge_i.size(); prob.edge_i = edge_i.data(); prob.edge_j = edge_j.data(); prob.edge_kind = edge_kind.data();
     prob.n_points = (int)point_ref.size(); prob.Xw = Xw.data(); prob.point_ref = point_ref.data();
     prob.fix_scale = bFixScale;
-    orbx_eg_options opt;
+    orbx_eg_options2 opt;
     opt.iterations = 20;                                         // :1096
-    if (orbx_optimize_essential_graph(orbx_adapter::Device(), &prob, &opt, TcwOut.data(), XwOut.data(), NULL, NULL, NULL) != ORBX_OK)
+    opt.solver = ORBX_EG_SOLVER_AUTO;                            // the dense solve's bytes either way; beyond 1536 free keyframes the envelope
+    if (orbx_optimize_essential_graph2(orbx_adapter::Device(), &prob, &opt, TcwOut.data(), XwOut.data(), NULL, NULL, NULL) != ORBX_OK)
         throw runtime_error(string("Optimizer::OptimizeEssentialGraph: ") + orbx_last_error());   // ORBX_E_CAPACITY: a map beyond the limits
 
     unique_lock<mutex> lock(pMap->mMutexMapUpdate);

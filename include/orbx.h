@@ -1026,6 +1026,41 @@ int orbx_optimize_essential_graph(int device, const orbx_eg_problem *p, const or
                                   double *S_out /* [n_kf][8], may be NULL */, double *point_out /* [n_points][3], may be NULL */,
                                   orbx_eg_report *report /* may be NULL */);
 
+/* ---- the same call for large maps: the system as an ENVELOPE, 4095 free keyframes ---------------------------------------
+ * orbx_optimize_essential_graph2 is orbx_optimize_essential_graph with a choice of the solve.  Everything above holds but "solve" and the
+ * sizes.  opt->solver:
+ *   ORBX_EG_SOLVER_DENSE     the call above: the same launches, the same bytes, the same sizes and refusals.
+ *   ORBX_EG_SOLVER_ENVELOPE  the lower triangle is stored and factored as an envelope (skyline), rows in keyframe order as before.  The
+ *            envelope rule: the 7 rows of free keyframe r start at column 7 x (the smallest row r shares an edge with; r itself where
+ *            there is none), rounded down to a multiple of 32, the solver's panel width; row i holds its columns from there to i, the
+ *            rows one behind the other.  Only the envelope is zeroed and filled; every block of the system lies inside it.  The
+ *            factorisation (orbx_ldlt_env.hip) is the panel LDL^T on those entries: THE SAME OPERATIONS IN THE SAME ORDER AS THE DENSE
+ *            SOLVE, MINUS TERMS THAT ARE AN EXACT ZERO -- a factorisation in this row order fills nothing to the left of a row's first
+ *            entry, so what is left out are x - (l * 0) * d with l an entry the dense solve holds as 0.  The values are the dense
+ *            solve's; a -0 that the dense solve's x - (+-0) turns into +0 can stay a -0, which no later operation tells apart unless
+ *            it is divided by.  No reordering: the stated deviation from g2o does not grow, and the call stays byte-reproducible.
+ *            The cost follows the keyframe order: narrow where a keyframe's edges go to recent neighbours (creation order; the loop's
+ *            few long edges cost their rows only), the whole triangle for a shuffled list.  orbx_eg_envelope tells in advance.
+ *   ORBX_EG_SOLVER_AUTO      ENVELOPE where more than 1536 keyframes are free or the envelope holds at most half of the triangle's
+ *            entries, else DENSE.  opt == NULL: 20 iterations, AUTO.
+ * sizes: DENSE as above.  ENVELOPE and AUTO: n_kf 1 .. 4096, so up to 4095 free; the envelope at most ORBX_EG_MAX_ENVELOPE = 2^27 doubles
+ * (1 GiB, about the dense matrix at its limit); the other sizes as above.  Refusals before any device work, as above, and: ORBX_E_INVALID
+ * for a solver that is none of the three; ORBX_E_CAPACITY for an envelope beyond the limit, the message naming its size and the limit. */
+#define ORBX_EG_SOLVER_DENSE 0
+#define ORBX_EG_SOLVER_ENVELOPE 1
+#define ORBX_EG_SOLVER_AUTO 2
+#define ORBX_EG_MAX_ENVELOPE ((int64_t)1 << 27)
+typedef struct { int iterations; int solver; } orbx_eg_options2;
+int orbx_optimize_essential_graph2(int device, const orbx_eg_problem *p, const orbx_eg_options2 *opt /* may be NULL */,
+                                   float *Tcw_out /* [n_kf][16] */, float *Xw_out /* [n_points][3] */,
+                                   double *S_out /* [n_kf][8], may be NULL */, double *point_out /* [n_points][3], may be NULL */,
+                                   orbx_eg_report *report /* may be NULL */);
+/* what a keyframe order costs: *entries = the doubles of the envelope of p's system by the rule above, *triangle = those of its whole
+ * lower triangle, n (n + 1) / 2 with n = 7 x the free keyframes.  Host only, no device is opened.  The problem is checked as
+ * orbx_optimize_essential_graph2 checks it for ENVELOPE (Tcw_out and Xw_out apart); an envelope beyond ORBX_EG_MAX_ENVELOPE is reported,
+ * not refused.  ORBX_E_INVALID for a NULL entries or triangle. */
+int orbx_eg_envelope(const orbx_eg_problem *p, int64_t *entries, int64_t *triangle);
+
 /* ---- Optimizer::OptimizeSim3: the Sim3 between two keyframes (src/Optimizer.cc:1164-1365) ------------------------------
  * Step 4 of LoopClosing::ComputeSim3 (src/LoopClosing.cc:282-460), between SearchBySim3 and the Sim3 SearchByProjection.  Every
  * VertexSBAPointXYZ of the function is fixed: the one free vertex is a 7-DoF VertexSim3Expmap, and the whole function -- two rounds
@@ -1624,9 +1659,9 @@ int orbx_debug_match_timing(double *out4);
  * 10 k_lba_classify, 11 k_lba_finish.  Results are the same bytes with and without it.  The events belong to the thread's context and go
  * with it (orbx_thread_release, or the thread's end). */
 int orbx_debug_lba_profile(int enable, double *ms, int32_t *launches);
-/* the same hook for the calling thread's orbx_optimize_essential_graph calls (tools/bench_eg.py): ms[10], launches[10], returns 10.  Slots:
- * 0 k_eg_setup, 1 k_eg_edges<true>, 2 k_eg_rows, 3 k_eg_reduce, 4 k_eg_fill (both phases), 5 the panel solve, 6 k_eg_update,
- * 7 k_eg_edges<false>, 8 k_eg_finish, 9 k_eg_points. */
+/* the same hook for the calling thread's orbx_optimize_essential_graph and orbx_optimize_essential_graph2 calls (tools/bench_eg.py): ms[10],
+ * launches[10], returns 10.  Slots: 0 k_eg_setup, 1 k_eg_edges<true>, 2 k_eg_rows, 3 k_eg_reduce, 4 the fill (both phases, in either form),
+ * 5 the solve (the panels or the envelope), 6 k_eg_update, 7 k_eg_edges<false>, 8 k_eg_finish, 9 k_eg_points. */
 int orbx_debug_eg_profile(int enable, double *ms, int32_t *launches);
 /* test hook (tests/test_eg_stages.py): what every kernel of orbx_optimize_essential_graph leaves in device memory.  The problem is checked,
  * staged and set up as in that call and taken through ONE linearisation at the start estimates and, with trial != 0, ONE Levenberg trial
@@ -1675,6 +1710,11 @@ int orbx_debug_eg_stages(int device, const orbx_eg_problem *p, double lambda, co
 int orbx_debug_ldlt_solve(int device, int n, const double *S, const double *b, double *x, int form, int *ok);
 int orbx_debug_set_lba_solver(int form);
 int orbx_debug_ldlt_panel_width(void);
+/* test hook for the envelope form of the panel LDL^T (orbx_ldlt_env.hip, tests/test_ldlt_envelope.py).  S is dense [n][n] row major and
+ * first [n] gives every row's first column, 0 <= first[i] <= i, rounded down here to the panel width.  Only the entries first[i] <= j <= i
+ * are read: they are packed on the host, uploaded and solved by the envelope solver.  x and *ok as orbx_debug_ldlt_solve; n <= 12288, so
+ * that form 1 can be run beside it.  ORBX_E_INVALID for a NULL argument, n < 1 or a first[i] outside 0 .. i. */
+int orbx_debug_ldlt_solve_envelope(int device, int n, const int32_t *first, const double *S, const double *b, double *x, int *ok);
 /* process-wide: the per-thread search contexts (see orbx_thread_release) that are set up right now, over all threads, families and
  * devices.  A thread's share leaves the count when it calls orbx_thread_release or ends. */
 int orbx_debug_thread_contexts(void);

@@ -2,7 +2,8 @@
 // VertexSim3Expmap vertices and binary EdgeSim3 edges, no points, then the correction of the map points.  The contract, operation by
 // operation, is include/orbx.h (orbx_optimize_essential_graph); the numpy restatement is tests/eg_model.py.  The Levenberg loop runs on the
 // host as the bundle adjustments' does (lm_host_loop of orbx_lm.h), one status record per linearisation and per trial; the
-// system is dense, 7 x the free keyframes, and is solved by the panels of orbx_ldlt.hip.  fp64 on the plain VALU, no atomics.
+// system is 7 x the free keyframes: dense and solved by the panels of orbx_ldlt.hip, or (orbx_optimize_essential_graph2) the envelope of
+// its lower triangle, solved by orbx_ldlt_env.hip with the same values.  fp64 on the plain VALU, no atomics.
 //
 //   k_eg_setup        vScw of every keyframe (the start estimates), the measurement of every edge, the 14 transforms Sim3(+-delta e_d)
 //   k_eg_edges<true>  the linearisation.  An edge costs 29 evaluations of log(C * Si' * Sj'^-1): each gets its own lane, 32 lanes an edge,
@@ -14,13 +15,14 @@
 //                     free vertices (its off-diagonal block over the pair's edges, in edge order), from host-built lists
 //   k_eg_reduce       one workgroup: chi2, the sum of x (lambda x + b), the largest diagonal entry (for the report only)
 //   k_eg_fill         phase 0 zeroes the lower triangle of S; phase 1 scatters the blocks, adds lambda, copies b to y
+//   k_eg_fill_env     the envelope form of phase 1 (phase 0 is a memset of the envelope, one linear range)
 //   k_eg_update       trial estimate = Sim3(x_k) * S_k, and the vertex's part of x (lambda x + b)
 //   k_eg_finish       S_out and the SE3 recovery;  k_eg_points: a thread per map point
 //   k_eg_probe        orbx_debug_eg_stages only: the 29 evaluations of every edge, a thread each, for the stage tests
 #include "orbx_resident.h"
 #include "orbx_lm.h"
 #include "orbx_sim3.h"
-#include "orbx_ldlt.h"
+#include "orbx_ldlt_env.h"
 #include <float.h>
 #include <math.h>
 #include <algorithm>
@@ -37,6 +39,7 @@ struct Eg {
     const float *Xw; const int32_t *pref;
     const int32_t *row, *rowkf, *voff, *vedge, *poff, *pedge, *pair;   // vedge: 2 e + end; pedge: 2 e + (block read transposed); pair: hi row, lo row
     double *status;      // chi2, scale, largest diagonal, ok of the solve
+    const int64_t *rowptr; const int32_t *first;   // the envelope of S (orbx_ldlt_env.h), or null: S is dense [7 F][7 F]
     double *S_out; float *Tcw_out; double *point_out; float *Xw_out;
     double *est[2], *vS, *meas, *xf, *rec, *echi, *Hd, *bv, *Off, *sc, *S, *y, *x;
 };
@@ -253,6 +256,24 @@ __global__ __launch_bounds__(256) void k_eg_fill(Eg G, double lambda, int phase)
     G.S[(hi + a) * n + lo + c] = G.Off[49 * (size_t)p + t];
 }
 
+// grid F + NP: k_eg_fill's phase 1 into the envelope.  A pair's block lies inside it: the higher row's first column is at or in front of
+// 7 x the lowest row it is paired with (eg_envelope_rows).
+__global__ __launch_bounds__(64) void k_eg_fill_env(Eg G, double lambda)
+{
+    const int b = blockIdx.x, t = threadIdx.x;
+    if (t >= 49) return;
+    const int a = t / 7, c = t % 7;
+    if (b < G.F) {
+        const int o = 7 * b;
+        if (c <= a) G.S[G.rowptr[o + a] - G.first[o + a] + o + c] = a == c ? G.Hd[28 * (size_t)b + upk<7>(c, a)] + lambda : G.Hd[28 * (size_t)b + upk<7>(c, a)];
+        if (t < 7) G.y[o + t] = G.bv[o + t];
+        return;
+    }
+    const int p = b - G.F;
+    const int hi = 7 * G.pair[2 * p], lo = 7 * G.pair[2 * p + 1];
+    G.S[G.rowptr[hi + a] - G.first[hi + a] + lo + c] = G.Off[49 * (size_t)p + t];
+}
+
 // thread k: keyframe k's trial estimate (VertexSim3Expmap::oplusImpl for a row, a copy otherwise).  After a failed solve x is the previous one.
 __global__ __launch_bounds__(256) void k_eg_update(Eg G, int cur, double lambda)
 {
@@ -349,7 +370,8 @@ static thread_local LaunchProfile<EG_K_COUNT> g_eg_prof;
 
 extern "C" int orbx_debug_eg_profile(int enable, double *ms, int32_t *launches) { return g_eg_prof.entry(enable, ms, launches); }
 
-static int eg_check(const char *who, const orbx_eg_problem *p, const orbx_eg_options *opt, const float *Tcw_out, const float *Xw_out, int *n_free)
+// iterations: the options' where there are options; max_free: 1536 for the dense solve, 4095 (every n_kf that passes) for the envelope
+static int eg_check(const char *who, const orbx_eg_problem *p, const int *iterations, const float *Tcw_out, const float *Xw_out, int max_free, int *n_free)
 {
     if (!p || !Tcw_out) { orbx_set_error("%s: NULL problem or Tcw_out", who); return ORBX_E_INVALID; }
     if (p->n_kf < 1 || p->n_edges < 0 || p->n_points < 0 || p->n_corrected < 0 || p->n_noncorrected < 0) {
@@ -357,7 +379,7 @@ static int eg_check(const char *who, const orbx_eg_problem *p, const orbx_eg_opt
                        p->n_corrected, p->n_noncorrected);
         return ORBX_E_INVALID;
     }
-    if (opt && opt->iterations < 0) { orbx_set_error("%s: iterations = %d", who, opt->iterations); return ORBX_E_INVALID; }
+    if (iterations && *iterations < 0) { orbx_set_error("%s: iterations = %d", who, *iterations); return ORBX_E_INVALID; }
     if (p->n_kf > 4096 || p->n_edges > (1 << 18) || p->n_points > (1 << 20) || p->n_corrected > 4096 || p->n_noncorrected > 4096) {
         orbx_set_error("%s: n_kf = %d, n_edges = %d, n_points = %d, n_corrected = %d, n_noncorrected = %d beyond 4096, 2^18, 2^20, 4096, 4096", who,
                        p->n_kf, p->n_edges, p->n_points, p->n_corrected, p->n_noncorrected);
@@ -386,8 +408,44 @@ static int eg_check(const char *who, const orbx_eg_problem *p, const orbx_eg_opt
     }
     for (int q = 0; q < p->n_points; q++)
         if (p->point_ref[q] < 0 || p->point_ref[q] >= p->n_kf) { orbx_set_error("%s: point %d: reference keyframe %d out of range", who, q, p->point_ref[q]); return ORBX_E_INVALID; }
-    if (p->n_kf - 1 > 1536) { orbx_set_error("%s: %d keyframes with fixed == 0, more than 1536", who, p->n_kf - 1); return ORBX_E_CAPACITY; }
+    if (p->n_kf - 1 > max_free) { orbx_set_error("%s: %d keyframes with fixed == 0, more than %d", who, p->n_kf - 1, max_free); return ORBX_E_CAPACITY; }
     *n_free = p->n_kf - 1;
+    return ORBX_OK;
+}
+
+// The envelope of a checked problem's system, rows in keyframe order: block row r (a free keyframe's 7 rows) starts at 7 x the smallest
+// row it shares an edge with, itself where there is none; orbx_ldlt_env_shape rounds that down to the panel width.  Every pair's block
+// (higher row, lower row) and every diagonal block then lies inside.  Host only.
+static void eg_envelope_rows(const orbx_eg_problem *p, std::vector<int32_t> *first)
+{
+    std::vector<int32_t> row(p->n_kf), lowest(p->n_kf);
+    int F = 0;
+    for (int k = 0; k < p->n_kf; k++) { row[k] = p->fixed[k] ? -1 : F; if (!p->fixed[k]) { lowest[F] = F; F++; } }
+    for (int e = 0; e < p->n_edges; e++) {
+        const int ri = row[p->edge_i[e]], rj = row[p->edge_j[e]];
+        if (ri < 0 || rj < 0) continue;
+        const int hi = ri > rj ? ri : rj, lo = ri > rj ? rj : ri;
+        if (lo < lowest[hi]) lowest[hi] = lo;
+    }
+    first->resize(7 * (size_t)F);
+    for (int r = 0; r < F; r++)
+        for (int d = 0; d < 7; d++) (*first)[7 * (size_t)r + d] = 7 * lowest[r];
+}
+
+extern "C" int orbx_eg_envelope(const orbx_eg_problem *p, int64_t *entries, int64_t *triangle)
+{
+    const char *who = "orbx_eg_envelope";
+    if (!entries || !triangle) { orbx_set_error("%s: NULL entries or triangle", who); return ORBX_E_INVALID; }
+    int n_free = 0;
+    static const float none = 0.f;   // this call has no Tcw_out and no Xw_out for eg_check to ask for
+    const int rc = eg_check(who, p, nullptr, &none, &none, 4095, &n_free);
+    if (rc) return rc;
+    std::vector<int32_t> first;
+    eg_envelope_rows(p, &first);
+    LdltEnvPlan plan;
+    orbx_ldlt_env_shape(7 * n_free, first.data(), &plan);
+    *entries = plan.entries;
+    *triangle = (int64_t)(7 * n_free) * (7 * n_free + 1) / 2;
     return ORBX_OK;
 }
 
@@ -402,8 +460,10 @@ struct EgCall {
     size_t out = 0, w_Sout = 0, w_Tcw = 0, w_point = 0, w_Xw = 0;   // the download head and the outputs in it
     uint8_t *extra = nullptr;                                         // `extra_bytes` of device memory behind the work area (the probe's)
     std::vector<int32_t> pair;                                        // hi row, lo row of every unique pair, as the device has them
+    LdltEnvPlan *env = nullptr;                                       // the envelope solve's plan, or null: the dense solve
 
-    int stage(int device, const orbx_eg_problem *p, int n_free, size_t extra_bytes);
+    // env: the plan of the system's envelope (orbx_ldlt_env_plan over eg_envelope_rows): S is packed and solved by it
+    int stage(int device, const orbx_eg_problem *p, int n_free, size_t extra_bytes, LdltEnvPlan *env = nullptr);
 
     int setup()
     {
@@ -428,11 +488,19 @@ struct EgCall {
     int trial(int cur, double lambda, bool solve, Filled filled)
     {
         g_eg_prof.launch(EG_K_FILL, pc, [&] {
+            if (env) {
+                (void)hipMemsetAsync(G.S, 0, 8 * (size_t)env->entries, s);   // a failure shows at call_fetch's hipGetLastError
+                hipLaunchKernelGGL(k_eg_fill_env, dim3((unsigned)(F + NP)), dim3(64), 0, s, G, lambda);
+                return;
+            }
             hipLaunchKernelGGL(k_eg_fill, dim3(grid256((int)N), (unsigned)N), dim3(256), 0, s, G, lambda, 0);
             hipLaunchKernelGGL(k_eg_fill, dim3((unsigned)(F + NP)), dim3(64), 0, s, G, lambda, 1);
         });
         if (const int rc = filled()) return rc;
-        if (solve) g_eg_prof.launch(EG_K_SOLVE, pc, [&] { orbx_ldlt_panel_launch(G.S, G.y, G.x, G.status + 3, (int)N, s); });
+        if (solve) g_eg_prof.launch(EG_K_SOLVE, pc, [&] {
+            if (env) orbx_ldlt_env_launch(G.S, G.y, G.x, G.status + 3, *env, s);
+            else orbx_ldlt_panel_launch(G.S, G.y, G.x, G.status + 3, (int)N, s);
+        });
         g_eg_prof.launch(EG_K_UPDATE, pc, [&] { hipLaunchKernelGGL(k_eg_update, dim3(grid256((int)K)), dim3(256), 0, s, G, cur, lambda); });
         g_eg_prof.launch(EG_K_ERRORS, pc, [&] { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_eg_edges<false>), dim3(grid256((int)E)), dim3(256), 0, s, G, 1 - cur); });
         g_eg_prof.launch(EG_K_REDUCE, pc, [&] { hipLaunchKernelGGL(k_eg_reduce, dim3(1), dim3(256), 0, s, G, 1); });
@@ -440,9 +508,10 @@ struct EgCall {
     }
 };
 
-int EgCall::stage(int device, const orbx_eg_problem *p, int n_free, size_t extra_bytes)
+int EgCall::stage(int device, const orbx_eg_problem *p, int n_free, size_t extra_bytes, LdltEnvPlan *env_plan)
 {
     int rc;
+    env = env_plan;
     K = (size_t)p->n_kf; E = (size_t)p->n_edges; P = (size_t)p->n_points; F = (size_t)n_free; N = 7 * F;
     const size_t NC = (size_t)p->n_corrected, NN = (size_t)p->n_noncorrected;
 
@@ -493,6 +562,8 @@ int EgCall::stage(int device, const orbx_eg_problem *p, int n_free, size_t extra
                  o_ei = b.take(4 * E), o_ej = b.take(4 * E), o_kind = b.take(E), o_X = b.take(12 * P), o_ref = b.take(4 * P), o_row = b.take(4 * K),
                  o_rowkf = b.take(4 * rowkf.size()), o_voff = b.take(4 * voff.size()), o_vedge = b.take(4 * vedge.size()), o_poff = b.take(4 * poff.size()),
                  o_pedge = b.take(4 * pedge.size()), o_pair = b.take(4 * pair.size());
+    const size_t o_rowptr = b.take(env ? 8 * env->rowptr.size() : 0), o_first = b.take(env ? 4 * env->first.size() : 0),
+                 o_act = b.take(env ? 4 * env->act.size() : 0);
     const size_t blob = b.o;
     BlobCursor w = { nullptr, nullptr, 0 };
     const size_t w_status = w.take(64);
@@ -500,7 +571,7 @@ int EgCall::stage(int device, const orbx_eg_problem *p, int n_free, size_t extra
     out = w.o;
     const size_t w_e0 = w.take(64 * K), w_e1 = w.take(64 * K), w_vS = w.take(64 * K), w_meas = w.take(64 * E), w_xf = w.take(14 * 64),
                  w_rec = w.take(8 * EG_REC * E), w_echi = w.take(8 * E), w_Hd = w.take(224 * F), w_bv = w.take(56 * F), w_Off = w.take(392 * NP),
-                 w_sc = w.take(8 * F), w_S = w.take(8 * N * N), w_y = w.take(8 * N), w_x = w.take(8 * N);
+                 w_sc = w.take(8 * F), w_S = w.take(env ? 8 * (size_t)env->entries : 8 * N * N), w_y = w.take(8 * N), w_x = w.take(8 * N);
     const size_t w_extra = w.take(extra_bytes);
     if ((rc = call_reserve(c, blob, w.o, out))) return rc;
     uint8_t *h = c->h_blob;
@@ -512,6 +583,10 @@ int EgCall::stage(int device, const orbx_eg_problem *p, int n_free, size_t extra
     memcpy(h + o_row, row.data(), 4 * K); memcpy(h + o_rowkf, rowkf.data(), 4 * rowkf.size()); memcpy(h + o_voff, voff.data(), 4 * voff.size());
     memcpy(h + o_vedge, vedge.data(), 4 * vedge.size()); memcpy(h + o_poff, poff.data(), 4 * poff.size());
     memcpy(h + o_pedge, pedge.data(), 4 * pedge.size()); memcpy(h + o_pair, pair.data(), 4 * pair.size());
+    if (env) {
+        memcpy(h + o_rowptr, env->rowptr.data(), 8 * env->rowptr.size()); memcpy(h + o_first, env->first.data(), 4 * env->first.size());
+        memcpy(h + o_act, env->act.data(), 4 * env->act.size());
+    }
     if ((rc = call_upload(c, blob))) return rc;
     if ((rc = g_eg_prof.ctx(c, &pc))) return rc;
 
@@ -530,10 +605,25 @@ int EgCall::stage(int device, const orbx_eg_problem *p, int n_free, size_t extra
     G.xf = (double *)(wk + w_xf); G.rec = (double *)(wk + w_rec); G.echi = (double *)(wk + w_echi); G.Hd = (double *)(wk + w_Hd);
     G.bv = (double *)(wk + w_bv); G.Off = (double *)(wk + w_Off); G.sc = (double *)(wk + w_sc); G.S = (double *)(wk + w_S);
     G.y = (double *)(wk + w_y); G.x = (double *)(wk + w_x);
+    if (env) {
+        G.rowptr = env->d_rowptr = (const int64_t *)(d + o_rowptr); G.first = env->d_first = (const int32_t *)(d + o_first);
+        env->d_act = (const int32_t *)(d + o_act);
+    }
 
     extra = wk + w_extra;
     s = c->stream;
     return ORBX_OK;
+}
+
+static int eg_run(int device, const orbx_eg_problem *p, int n_free, int iterations, LdltEnvPlan *env, float *Tcw_out, float *Xw_out, double *S_out,
+                  double *point_out, orbx_eg_report *report);
+
+// ORBX_EG_SOLVER_AUTO: the envelope solve beyond the dense solve's 1536 free keyframes, and where the envelope holds at most half of the
+// lower triangle's entries
+static bool eg_auto_takes_envelope(int n_free, int64_t entries)
+{
+    const int64_t n = 7 * (int64_t)n_free;
+    return n_free > 1536 || 2 * entries <= n * (n + 1) / 2;
 }
 
 extern "C" int orbx_optimize_essential_graph(int device, const orbx_eg_problem *p, const orbx_eg_options *opt, float *Tcw_out, float *Xw_out,
@@ -541,11 +631,47 @@ extern "C" int orbx_optimize_essential_graph(int device, const orbx_eg_problem *
 {
     const char *who = "orbx_optimize_essential_graph";
     int n_free = 0;
-    int rc = eg_check(who, p, opt, Tcw_out, Xw_out, &n_free);
+    int rc = eg_check(who, p, opt ? &opt->iterations : nullptr, Tcw_out, Xw_out, 1536, &n_free);
     if (rc) return rc;
-    const int iterations = opt ? opt->iterations : 20;   // :1096
+    return eg_run(device, p, n_free, opt ? opt->iterations : 20 /* :1096 */, nullptr, Tcw_out, Xw_out, S_out, point_out, report);
+}
+
+extern "C" int orbx_optimize_essential_graph2(int device, const orbx_eg_problem *p, const orbx_eg_options2 *opt, float *Tcw_out, float *Xw_out,
+                                              double *S_out, double *point_out, orbx_eg_report *report)
+{
+    const char *who = "orbx_optimize_essential_graph2";
+    int solver = opt ? opt->solver : ORBX_EG_SOLVER_AUTO;
+    if (solver != ORBX_EG_SOLVER_DENSE && solver != ORBX_EG_SOLVER_ENVELOPE && solver != ORBX_EG_SOLVER_AUTO) {
+        orbx_set_error("%s: solver = %d", who, solver);
+        return ORBX_E_INVALID;
+    }
+    int n_free = 0;
+    int rc = eg_check(who, p, opt ? &opt->iterations : nullptr, Tcw_out, Xw_out, solver == ORBX_EG_SOLVER_DENSE ? 1536 : 4095, &n_free);
+    if (rc) return rc;
+    const int iterations = opt ? opt->iterations : 20;
+    if (solver == ORBX_EG_SOLVER_DENSE) return eg_run(device, p, n_free, iterations, nullptr, Tcw_out, Xw_out, S_out, point_out, report);
+    std::vector<int32_t> first;
+    eg_envelope_rows(p, &first);
+    LdltEnvPlan plan;
+    orbx_ldlt_env_shape(7 * n_free, first.data(), &plan);
+    if (solver == ORBX_EG_SOLVER_AUTO && !eg_auto_takes_envelope(n_free, plan.entries))
+        return eg_run(device, p, n_free, iterations, nullptr, Tcw_out, Xw_out, S_out, point_out, report);
+    if (plan.entries > ORBX_EG_MAX_ENVELOPE) {
+        orbx_set_error("%s: the envelope of the system holds %lld entries, more than %lld (%d keyframes with fixed == 0 in this order; orbx_eg_envelope)",
+                       who, (long long)plan.entries, (long long)ORBX_EG_MAX_ENVELOPE, n_free);
+        return ORBX_E_CAPACITY;
+    }
+    orbx_ldlt_env_plan(7 * n_free, first.data(), &plan);
+    return eg_run(device, p, n_free, iterations, &plan, Tcw_out, Xw_out, S_out, point_out, report);
+}
+
+// the call behind both entry points, on a checked problem.  env: the envelope solve's plan, or null for the dense solve.
+static int eg_run(int device, const orbx_eg_problem *p, int n_free, int iterations, LdltEnvPlan *env, float *Tcw_out, float *Xw_out, double *S_out,
+                  double *point_out, orbx_eg_report *report)
+{
+    int rc;
     EgCall q;
-    if ((rc = q.stage(device, p, n_free, 0))) return rc;
+    if ((rc = q.stage(device, p, n_free, 0, env))) return rc;
     const size_t K = q.K, E = q.E, P = q.P, F = q.F;
     CallCtx *c = q.c;
     orbx_eg_report rep;
@@ -583,7 +709,7 @@ extern "C" int orbx_debug_eg_stages(int device, const orbx_eg_problem *p, double
     if (!d) { orbx_set_error("%s: NULL dump", who); return ORBX_E_INVALID; }
     int n_free = 0;
     static const float none = 0.f;   // this call has no Tcw_out and no Xw_out for eg_check to ask for
-    int rc = eg_check(who, p, nullptr, &none, &none, &n_free);
+    int rc = eg_check(who, p, nullptr, &none, &none, 1536, &n_free);
     if (rc) return rc;
     if (!(lambda >= 0.0) || !std::isfinite(lambda)) { orbx_set_error("%s: lambda = %g", who, lambda); return ORBX_E_INVALID; }
     if (d->S && 7 * n_free > ORBX_EG_STAGES_MAX_N) {

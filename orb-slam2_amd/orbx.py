@@ -168,6 +168,15 @@ class EgOptions(C.Structure):
     _fields_ = [("iterations", C.c_int)]
 
 
+class EgOptions2(C.Structure):
+    """orbx_eg_options2 (include/orbx.h)"""
+    _fields_ = [("iterations", C.c_int), ("solver", C.c_int)]
+
+
+EG_SOLVER_DENSE, EG_SOLVER_ENVELOPE, EG_SOLVER_AUTO = 0, 1, 2
+EG_MAX_ENVELOPE = 1 << 27
+
+
 class EgReport(C.Structure):
     """orbx_eg_report (include/orbx.h)"""
     _fields_ = [("iterations", C.c_int), ("trials", C.c_int), ("n_free", C.c_int), ("n_solve_failed", C.c_int),
@@ -362,9 +371,12 @@ def lib():
     L.orbx_debug_lba_profile.argtypes = [i, vp, vp]
     L.orbx_bundle_adjustment.argtypes = [i, C.POINTER(LbaProblem), C.POINTER(BaOptions), vp, vp, vp, vp, vp, C.POINTER(BaReport)]
     L.orbx_optimize_essential_graph.argtypes = [i, C.POINTER(EgProblem), C.POINTER(EgOptions), vp, vp, vp, vp, C.POINTER(EgReport)]
+    L.orbx_optimize_essential_graph2.argtypes = [i, C.POINTER(EgProblem), C.POINTER(EgOptions2), vp, vp, vp, vp, C.POINTER(EgReport)]
+    L.orbx_eg_envelope.argtypes = [C.POINTER(EgProblem), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.orbx_debug_eg_profile.argtypes = [i, vp, vp]
     L.orbx_debug_eg_stages.argtypes = [i, C.POINTER(EgProblem), C.c_double, vp, i, C.POINTER(EgStages)]
     L.orbx_debug_ldlt_solve.argtypes = [i, i, vp, vp, vp, i, C.POINTER(C.c_int)]
+    L.orbx_debug_ldlt_solve_envelope.argtypes = [i, i, vp, vp, vp, vp, C.POINTER(C.c_int)]
     L.orbx_debug_set_lba_solver.argtypes = [i]
     L.orbx_debug_ldlt_panel_width.argtypes = []
     L.orbx_triangulate_pairs.argtypes = [i, C.POINTER(TriFeats), C.POINTER(TriView), C.POINTER(C.POINTER(TriFeats)), C.POINTER(TriView), i, vp, i, vp,
@@ -1185,18 +1197,33 @@ def _eg_problem(problem, who):
                      _p(ref), int(bool(problem["fix_scale"]))), keep
 
 
-def optimize_essential_graph(problem, iterations=20, device=0):
+def optimize_essential_graph(problem, iterations=20, device=0, solver=None):
     """Optimizer::OptimizeEssentialGraph (orbx_optimize_essential_graph): problem = dict(Tcw [K][4][4], fixed [K] (exactly one set: pLoopKF),
     corrected / noncorrected [K] (index into S_corrected / S_noncorrected [.][8] qx qy qz qw tx ty tz s, or -1), edge_i, edge_j, edge_kind [E]
     (0 loop-connection edge, 1 normal edge), Xw [P][3], point_ref [P], fix_scale) -> dict(Tcw [K][4][4], Xw [P][3], S [K][8], point [P][3],
-    iterations, trials, n_free, n_solve_failed, chi2_start, chi2, lambda)"""
+    iterations, trials, n_free, n_solve_failed, chi2_start, chi2, lambda).  solver: None is orbx_optimize_essential_graph (the dense solve, up
+    to 1536 free keyframes); EG_SOLVER_DENSE, EG_SOLVER_ENVELOPE or EG_SOLVER_AUTO goes to orbx_optimize_essential_graph2 (ENVELOPE and AUTO:
+    up to 4095 free keyframes, the same values as the dense solve)"""
     pr, keep = _eg_problem(problem, "optimize_essential_graph")
-    opt = EgOptions(int(iterations))
     Tcw = np.zeros((pr.n_kf, 4, 4), np.float32); Xw = np.zeros((pr.n_points, 3), np.float32)
     S = np.zeros((pr.n_kf, 8), np.float64); point = np.zeros((pr.n_points, 3), np.float64); rep = EgReport()
-    _check(lib().orbx_optimize_essential_graph(device, C.byref(pr), C.byref(opt), _p(Tcw), _p(Xw), _p(S), _p(point), C.byref(rep)))
+    if solver is None:
+        opt = EgOptions(int(iterations))
+        _check(lib().orbx_optimize_essential_graph(device, C.byref(pr), C.byref(opt), _p(Tcw), _p(Xw), _p(S), _p(point), C.byref(rep)))
+    else:
+        opt = EgOptions2(int(iterations), int(solver))
+        _check(lib().orbx_optimize_essential_graph2(device, C.byref(pr), C.byref(opt), _p(Tcw), _p(Xw), _p(S), _p(point), C.byref(rep)))
     return {"Tcw": Tcw, "Xw": Xw, "S": S, "point": point, "iterations": rep.iterations, "trials": rep.trials, "n_free": rep.n_free,
             "n_solve_failed": rep.n_solve_failed, "chi2_start": rep.chi2_start, "chi2": rep.chi2, "lambda": rep.lambda_}
+
+
+def eg_envelope(problem):
+    """orbx_eg_envelope: what the problem's keyframe order costs the envelope solve -> (entries, triangle): the doubles of the envelope of
+    the 7 F x 7 F system and of its whole lower triangle.  Host only: no device is opened."""
+    pr, keep = _eg_problem(problem, "eg_envelope")
+    entries, triangle = C.c_int64(-1), C.c_int64(-1)
+    _check(lib().orbx_eg_envelope(C.byref(pr), C.byref(entries), C.byref(triangle)))
+    return int(entries.value), int(triangle.value)
 
 
 EG_STAGES = ("vS", "meas", "xf", "rec", "echi", "Hd", "bv", "pair", "Off", "status_lin", "err", "S", "y", "solve_ok", "x", "trial", "sc",
@@ -1253,6 +1280,21 @@ def ldlt_solve(S, b, form, x0=None, device=0):
     x = np.zeros(n) if x0 is None else np.array(x0, np.float64).reshape(n)
     ok = C.c_int(-1)
     _check(lib().orbx_debug_ldlt_solve(device, n, _p(S), _p(b), _p(x), int(form), C.byref(ok)))
+    return x, bool(ok.value)
+
+
+def ldlt_solve_envelope(S, b, first, x0=None, device=0):
+    """orbx_debug_ldlt_solve_envelope: the envelope form of the panel LDL^T on S x = b.  S [n][n] dense, first [n] every row's first column
+    (0 <= first[i] <= i, rounded down to the panel width by the library): only the entries first[i] <= j <= i are read -> (x [n], ok) as
+    ldlt_solve"""
+    S = np.ascontiguousarray(S, np.float64); b = np.ascontiguousarray(b, np.float64).reshape(-1)
+    first = np.ascontiguousarray(first, np.int32).reshape(-1)
+    n = len(b)
+    if S.shape != (n, n) or len(first) != n:
+        raise OrbxError(-1, "ldlt_solve_envelope: S must be [n][n] and first [n] for b [n]")
+    x = np.zeros(n) if x0 is None else np.array(x0, np.float64).reshape(n)
+    ok = C.c_int(-1)
+    _check(lib().orbx_debug_ldlt_solve_envelope(device, n, _p(first), _p(S), _p(b), _p(x), C.byref(ok)))
     return x, bool(ok.value)
 
 
