@@ -734,6 +734,89 @@ int orbx_frame_search_local_points(orbx_frame *cur, const uint8_t *occupied, con
                                    float log_scale_factor, const float *scale_factors, int nlevels, float th, float nnratio,
                                    int32_t *match_cur, int *nmatches, uint8_t *in_view);
 
+/* ---- resident observation graph: covisibility votes and LocalMapping::KeyFrameCulling -----------------------------------
+ * Who observes what, in both views of the reference, kept independently because the reference lets them disagree:
+ *   keyframe view, per keyframe slot and feature: the point slot or -1 (mvpMapPoints[i]), the octave (mvKeysUn[i].octave), a
+ *     stereo bit (mvuRight[i] >= 0) and a close bit (0 <= mvDepth[i] <= mThDepth);
+ *   point view, per point slot: up to max_obs (keyframe slot, feature index) entries (mObservations), nObs with the reference's
+ *     weights (+2 stereo, +1 mono), a live bit and a bad bit.
+ * The order of the entries within a row is unobservable (the reference's is the order of KeyFrame addresses); mpRefKF is not
+ * modelled.  A point slot is free until its first observation makes it live; it goes bad through orbx_mapgraph_erase_points, or
+ * when an erasure leaves it at nObs <= 2 (src/MapPoint.cc:137-144); nObs of a bad point stays what it was, as in the reference.  An
+ * add_observations on a bad slot uses the slot again for a new point (nObs from 0, not bad): the caller's to do only once no match
+ * names the slot.  A row entry may outlive its keyframe (an observation without a match survives erase_keyframe, as a pointer to a
+ * bad KeyFrame does in the reference) and then still counts in the queries, with the attributes the slot last held; the slot is not
+ * given to a new keyframe before those entries are erased.
+ * Fixed capacities and ONE device allocation made at creation; nothing grows.  Bytes: 4 per keyframe slot, 5 per (keyframe slot,
+ * feature), 4 + 4 * max_obs per point slot -- at most 2^32 - 1 words of 4 bytes in all, more is ORBX_E_INVALID -- plus the staging of
+ * one edit upload (512 KiB + max_features, and a pinned host buffer of that size).  The host keeps a mirror of the same size, on which
+ * every refusal is decided: every refusal comes before any device work and leaves the graph unchanged.  The queries run on the
+ * device's copy alone.
+ * Each edit is one packed upload -- 8 bytes for every word of the graph that the edit changes, whatever the capacities -- and one
+ * scatter launch on the calling thread's own stream; the call does not wait for them, later calls on the graph are ordered behind
+ * them.  Calls on one handle serialise inside it (the reference holds mMutexFeatures). */
+typedef struct orbx_mapgraph orbx_mapgraph;
+/* ORBX_E_INVALID: out == NULL, max_keyframes or max_features outside [1, 65535], max_points outside [1, 2^24], max_obs outside [4, 256] */
+int orbx_mapgraph_create(int device, int max_keyframes, int max_features, int max_points, int max_obs, orbx_mapgraph **out);
+void orbx_mapgraph_destroy(orbx_mapgraph *g);
+int orbx_mapgraph_clear(orbx_mapgraph *g);   /* Map::clear: every keyframe slot and point slot free */
+/* A new keyframe of n features in the free slot kf, all matches -1.  octave[i] <= 31; stereo[i] / close[i]: any non-zero byte sets the bit.
+ * ORBX_E_INVALID: a negative slot, a slot in use, a free slot that observations still name, an octave above 31; ORBX_E_CAPACITY:
+ * kf >= max_keyframes, n > max_features. */
+int orbx_mapgraph_set_keyframe(orbx_mapgraph *g, int kf, int n, const uint8_t *octave, const uint8_t *stereo, const uint8_t *close);
+/* KeyFrame::AddMapPoint / EraseMapPointMatch / ReplaceMapPointMatch: match[kf][idx[j]] = point[j] (-1 erases); touches the keyframe view
+ * only.  ORBX_E_INVALID: kf not in use, a feature outside the keyframe or named twice, a point slot < -1; ORBX_E_CAPACITY: a point
+ * slot >= max_points. */
+int orbx_mapgraph_set_matches(orbx_mapgraph *g, int kf, const int32_t *idx, const int32_t *point, int n);
+/* MapPoint::AddObservation (src/MapPoint.cc:106-117), entry by entry in the given order: a keyframe already in the row is a no-op; a
+ * point's first observation makes it live.  ORBX_E_INVALID: a negative point slot, a keyframe slot not in use, a feature outside the
+ * keyframe, a (point, keyframe) pair named twice; ORBX_E_CAPACITY: a point slot >= max_points, a row beyond max_obs. */
+int orbx_mapgraph_add_observations(orbx_mapgraph *g, const int32_t *point, const int32_t *kf, const int32_t *idx, int n);
+/* MapPoint::EraseObservation (src/MapPoint.cc:119-145): nObs drops by the weight of the stored entry; a point that ends at nObs <= 2
+ * after losing an entry goes bad: its row is cleared and the match at every former observer's index is set to -1 (whatever it was:
+ * KeyFrame::EraseMapPointMatch does not look).  A keyframe that is not in the row is a no-op.  Several erasures of one point in a batch
+ * are order-free.  ORBX_E_INVALID: a negative slot, a pair named twice; ORBX_E_CAPACITY: a slot beyond its capacity. */
+int orbx_mapgraph_erase_observations(orbx_mapgraph *g, const int32_t *point, const int32_t *kf, int n);
+/* MapPoint::SetBadFlag (src/MapPoint.cc:159-176): bad, the row cleared, the observers' matches -1.  ORBX_E_INVALID: a negative slot, a
+ * slot named twice; ORBX_E_CAPACITY: a slot >= max_points. */
+int orbx_mapgraph_erase_points(orbx_mapgraph *g, const int32_t *point, int n);
+/* The map-point part of KeyFrame::SetBadFlag (src/KeyFrame.cc:505-507): EraseObservation(kf) on the point of every match, then the slot
+ * is free.  ORBX_E_INVALID: kf not in use. */
+int orbx_mapgraph_erase_keyframe(orbx_mapgraph *g, int kf);
+/* The row entries that name keyframe slot kf, in use or free (a negative code on error).  An observation without a match survives
+ * erase_keyframe, so a free slot may still be named; orbx_mapgraph_set_keyframe refuses such a slot, and a caller that hands out slots
+ * asks here first (or erases those observations). */
+int orbx_mapgraph_keyframe_observations(orbx_mapgraph *g, int kf);
+/* tests and debugging, read from the device's copy.  *n = the feature count, -1 for a free slot; point / octave / stereo / close[max_features]
+ * (NULL arguments are skipped). */
+int orbx_mapgraph_read_keyframe(orbx_mapgraph *g, int kf, int *n, int32_t *point, uint8_t *octave, uint8_t *stereo, uint8_t *close);
+/* point slots first .. first + n - 1: n_obs[n] = nObs, flags[n] bit 0 = live, bit 1 = bad, n_entries[n], and kf / idx[n][max_obs] = the rows,
+ * n_entries[p] words of each (NULL arrays are skipped) */
+int orbx_mapgraph_read_points(orbx_mapgraph *g, int first, int n, int32_t *n_obs, uint8_t *flags, int32_t *n_entries, int32_t *kf, int32_t *idx);
+/* keyframeCounter of Tracking::UpdateLocalKeyFrames (src/Tracking.cc:1519-1538): for every listed point that is live and not bad,
+ * counts[observer]++ for each entry of its row.  counts[max_keyframes] comes back dense, by keyframe slot; nz_slots[max_keyframes] / *n_nz
+ * (either may be NULL) receive the slots with a non-zero count, ascending.  Integer sums only: exact in any order.  One upload, one
+ * launch (a workgroup histogram in LDS up to 8192 keyframe slots, global integer atomics beyond), one download.  The threshold, the
+ * maximum and the sort stay with the caller: they depend on the reference's pointer order.  ORBX_E_INVALID: n outside [0, 2^20], a
+ * point slot outside [0, max_points). */
+int orbx_mapgraph_vote(orbx_mapgraph *g, const int32_t *points, int n, int32_t *counts, int32_t *nz_slots, int *n_nz);
+/* KFcounter of KeyFrame::UpdateConnections (src/KeyFrame.cc:305-338): the same kernel over kf's own matches, kf itself left out.  No
+ * upload.  ORBX_E_INVALID: kf not in use. */
+int orbx_mapgraph_covisibility(orbx_mapgraph *g, int kf, int32_t *counts, int32_t *nz_slots, int *n_nz);
+/* The loop of LocalMapping::KeyFrameCulling (src/LocalMapping.cc:713-774) over local[0 .. n_local) in the given order; the caller
+ * leaves out mnId == 0.  Per keyframe k: over its matches i with a live, not-bad point p, skipped unless `monocular` or close: nMPs++;
+ * if nObs(p) > 3, the row entries (k', i') with k' != k and octave(k', i') <= octave(k, i) + 1 are counted, and 3 or more make the
+ * feature redundant.  k is culled when (double)nRedundant > 0.9 * (double)nMPs, one fp64 product as the reference writes it.  A culled
+ * keyframe with not_erase[j] set gets culled[j] = 2 and the graph stays as it is (mbToBeErased); otherwise culled[j] = 1 and
+ * orbx_mapgraph_erase_keyframe, with its cascade of bad points, happens BEFORE the next keyframe is judged.  n_mps[j] / n_redundant[j]
+ * (may be NULL) are the values seen at that keyframe's turn; bad_points[cap] / *n_bad the point slots that went bad, ascending;
+ * ORBX_E_CAPACITY with *n_bad = the true count when there are more than cap (the call has run like any other, the graph has changed).
+ * One upload, two launches -- every (keyframe, feature) judged on the graph as it stands, then one workgroup that takes the keyframes in
+ * order and, behind a real cull, judges every later keyframe again -- one download.  n_local == 0: ORBX_OK, no launch.
+ * ORBX_E_INVALID: a keyframe slot not in use or named twice, n_local > 65535. */
+int orbx_mapgraph_cull_keyframes(orbx_mapgraph *g, const int32_t *local, const uint8_t *not_erase, int n_local, int monocular,
+                                 uint8_t *culled, int32_t *n_mps, int32_t *n_redundant, int32_t *bad_points, int cap, int *n_bad);
+
 /* ---- Optimizer::PoseOptimization: motion-only pose optimisation (src/Optimizer.cc:286-513) ---------------------------
  * The one per-frame step of Tracking that g2o solved on a host core (TrackWithMotionModel, TrackReferenceKeyFrame, TrackLocalMap;
  * Relocalization up to three times per candidate, src/Tracking.cc:1730-1800): one 6-DoF vertex, one unary edge per feature that

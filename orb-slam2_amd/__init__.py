@@ -16,6 +16,7 @@ sitting directly on the C ABI of liborbx.so (include/orbx.h):
   local_bundle_adjustment <- reference src/Optimizer.cc:528-862 (Optimizer::LocalBundleAdjustment, LocalMapping's optimisation)
   bundle_adjustment <- reference src/Optimizer.cc:48-281 (Optimizer::BundleAdjustment, the global bundle adjustment)
   optimize_essential_graph <- reference src/Optimizer.cc:885-1153 (Optimizer::OptimizeEssentialGraph, LoopClosing::CorrectLoop)
+  MapGraph <- reference src/LocalMapping.cc:704-775, src/KeyFrame.cc:303-338, src/Tracking.cc:1515-1538 (KeyFrameCulling and the covisibility votes)
   mono_init_hypotheses / mono_init_reconstruct / Initializer <- reference src/Initializer.cc:37-1026 (Tracking::MonocularInitialization)
 
 There is NO CPU fallback: importing works without a GPU (so that the ABI can be inspected), but
@@ -24,7 +25,7 @@ The directory name contains a '-', so load it with importlib (see tests/conftest
 """
 from . import orbx, streams
 from .orbx import (OrbxError, KP_DTYPE, lib, lib_path, ORBextractor, ORBmatcher, ComputeStereoMatches,
-                   FeatSet, make_featset, STAGES, BowDatabase, DeviceKeyFrame, DeviceFrame, MapPoints, BowFrames, KeyFrameDatabase, ORBVocabulary, ComputeDistinctiveDescriptors, Rectifier, UndistortKeyPoints,
+                   FeatSet, make_featset, STAGES, BowDatabase, DeviceKeyFrame, DeviceFrame, MapPoints, MapGraph, BowFrames, KeyFrameDatabase, ORBVocabulary, ComputeDistinctiveDescriptors, Rectifier, UndistortKeyPoints,
                    RGBDParams, depth_map_factor, rgbd_depth_batch_device, DEPTH_U16, DEPTH_F32, pose_optimize, pose_optimize_batch,
                    triangulate_pairs, frame_set_depth, frame_triangulate, sim3_hypotheses, sim3_hypotheses_batch, sim3_max_error, Sim3Ransac,
                    sim3_optimize, sim3_optimize_batch, sim3opt_camera_points, pnp_hypotheses, pnp_hypotheses_batch, PnPRansac,
@@ -32,7 +33,7 @@ from .orbx import (OrbxError, KP_DTYPE, lib, lib_path, ORBextractor, ORBmatcher,
                    local_bundle_adjustment, bundle_adjustment, optimize_essential_graph)
 
 __all__ = ["OrbxError", "KP_DTYPE", "lib", "lib_path", "ORBextractor", "ORBmatcher", "ComputeStereoMatches",
-           "FeatSet", "make_featset", "STAGES", "BowDatabase", "DeviceKeyFrame", "DeviceFrame", "MapPoints", "BowFrames", "KeyFrameDatabase", "ORBVocabulary", "ComputeDistinctiveDescriptors", "Rectifier", "UndistortKeyPoints",
+           "FeatSet", "make_featset", "STAGES", "BowDatabase", "DeviceKeyFrame", "DeviceFrame", "MapPoints", "MapGraph", "BowFrames", "KeyFrameDatabase", "ORBVocabulary", "ComputeDistinctiveDescriptors", "Rectifier", "UndistortKeyPoints",
            "RGBDParams", "depth_map_factor", "rgbd_depth_batch_device", "DEPTH_U16", "DEPTH_F32", "pose_optimize", "pose_optimize_batch",
            "triangulate_pairs", "frame_set_depth", "frame_triangulate", "sim3_hypotheses", "sim3_hypotheses_batch", "sim3_max_error", "Sim3Ransac",
            "sim3_optimize", "sim3_optimize_batch", "sim3opt_camera_points", "pnp_hypotheses", "pnp_hypotheses_batch", "PnPRansac",

@@ -363,6 +363,21 @@ def lib():
     L.orbx_mappoints_set.argtypes = [vp, vp, i, vp, vp, vp]
     L.orbx_mappoints_read.argtypes = [vp, vp, i, vp, vp]
     L.orbx_mappoints_frustum.argtypes = [vp, vp, vp, i, vp, vp, f, f, i, vp, vp, vp, vp, vp, vp]
+    L.orbx_mapgraph_create.argtypes = [i, i, i, i, i, C.POINTER(vp)]
+    L.orbx_mapgraph_destroy.argtypes = [vp]; L.orbx_mapgraph_destroy.restype = None
+    L.orbx_mapgraph_clear.argtypes = [vp]
+    L.orbx_mapgraph_set_keyframe.argtypes = [vp, i, i, vp, vp, vp]
+    L.orbx_mapgraph_set_matches.argtypes = [vp, i, vp, vp, i]
+    L.orbx_mapgraph_add_observations.argtypes = [vp, vp, vp, vp, i]
+    L.orbx_mapgraph_erase_observations.argtypes = [vp, vp, vp, i]
+    L.orbx_mapgraph_erase_points.argtypes = [vp, vp, i]
+    L.orbx_mapgraph_erase_keyframe.argtypes = [vp, i]
+    L.orbx_mapgraph_keyframe_observations.argtypes = [vp, i]
+    L.orbx_mapgraph_read_keyframe.argtypes = [vp, i, ip, vp, vp, vp, vp]
+    L.orbx_mapgraph_read_points.argtypes = [vp, i, i, vp, vp, vp, vp, vp]
+    L.orbx_mapgraph_vote.argtypes = [vp, vp, i, vp, vp, ip]
+    L.orbx_mapgraph_covisibility.argtypes = [vp, i, vp, vp, ip]
+    L.orbx_mapgraph_cull_keyframes.argtypes = [vp, vp, vp, i, i, vp, vp, vp, vp, i, ip]
     L.orbx_frame_search_local_points.argtypes = [vp, vp, vp, vp, vp, i, vp, vp, f, f, vp, i, f, f, vp, ip, vp]
     L.orbx_pose_optimize.argtypes = [i, C.POINTER(PoseObs), vp, vp, vp, vp, ip, C.POINTER(PoseReport)]
     L.orbx_pose_optimize_batch.argtypes = [i, C.POINTER(PoseJob), i]
@@ -1093,6 +1108,128 @@ class MapPoints:
                                             int(nlevels), _p(o["in_view"]), _p(o["u"]), _p(o["v"]), _p(o["xr"]), _p(o["level"]),
                                             _p(o["view_cos"])))
         return o
+
+
+class MapGraph:
+    """orbx_mapgraph: who observes what, resident in HBM in both views of the reference -- per keyframe slot and feature the point slot,
+    octave, stereo bit and close bit (KeyFrame::mvpMapPoints), per point slot the (keyframe, feature) entries, nObs and a bad bit
+    (MapPoint::mObservations).  Edited in small batches, one mutator of the reference each; vote() is keyframeCounter of
+    Tracking::UpdateLocalKeyFrames, covisibility() KFcounter of KeyFrame::UpdateConnections, cull_keyframes() the loop of
+    LocalMapping::KeyFrameCulling with its effects on the map applied between iterations."""
+
+    def __init__(self, max_keyframes, max_features, max_points, max_obs=256, device=0):
+        h = C.c_void_p()
+        _check(lib().orbx_mapgraph_create(device, int(max_keyframes), int(max_features), int(max_points), int(max_obs), C.byref(h)))
+        self._h, self.device = h, device
+        self.max_keyframes, self.max_features, self.max_points, self.max_obs = int(max_keyframes), int(max_features), int(max_points), int(max_obs)
+
+    def __del__(self):
+        try:
+            h, L = getattr(self, "_h", None), _lib
+            if h and L is not None:
+                L.orbx_mapgraph_destroy(h)
+            self._h = None
+        except Exception:
+            pass
+
+    @staticmethod
+    def _cols(who, *cols):
+        a = [np.ascontiguousarray(c, np.int32) for c in cols]
+        if any(c.ndim != 1 or len(c) != len(a[0]) for c in a):
+            raise OrbxError(-1, f"MapGraph.{who}: the lists must be one-dimensional and of one length")
+        return a
+
+    def clear(self):
+        _check(lib().orbx_mapgraph_clear(self._h))
+
+    def set_keyframe(self, kf, octave, stereo, close):
+        """a new keyframe in the free slot kf: per feature its octave, whether mvuRight >= 0, whether 0 <= mvDepth <= mThDepth"""
+        o, s, c = (np.ascontiguousarray(x, np.uint8) for x in (octave, stereo, close))
+        if o.ndim != 1 or s.shape != o.shape or c.shape != o.shape:
+            raise OrbxError(-1, "MapGraph.set_keyframe: octave, stereo and close must be one-dimensional and of one length")
+        _check(lib().orbx_mapgraph_set_keyframe(self._h, int(kf), len(o), _p(o), _p(s), _p(c)))
+
+    def set_matches(self, kf, idx, point):
+        i, p = self._cols("set_matches", idx, point)
+        _check(lib().orbx_mapgraph_set_matches(self._h, int(kf), _p(i), _p(p), len(i)))
+
+    def add_observations(self, point, kf, idx):
+        p, k, i = self._cols("add_observations", point, kf, idx)
+        _check(lib().orbx_mapgraph_add_observations(self._h, _p(p), _p(k), _p(i), len(p)))
+
+    def erase_observations(self, point, kf):
+        p, k = self._cols("erase_observations", point, kf)
+        _check(lib().orbx_mapgraph_erase_observations(self._h, _p(p), _p(k), len(p)))
+
+    def erase_points(self, point):
+        p, = self._cols("erase_points", point)
+        _check(lib().orbx_mapgraph_erase_points(self._h, _p(p), len(p)))
+
+    def erase_keyframe(self, kf):
+        _check(lib().orbx_mapgraph_erase_keyframe(self._h, int(kf)))
+
+    def keyframe_observations(self, kf):
+        """the row entries that name keyframe slot kf, in use or free"""
+        n = lib().orbx_mapgraph_keyframe_observations(self._h, int(kf))
+        if n < 0:
+            _check(n)
+        return n
+
+    def read_keyframe(self, kf):
+        """-> None for a free slot, else dict(point, octave, stereo, close), from the device's copy"""
+        n = C.c_int()
+        p = np.zeros(self.max_features, np.int32)
+        o, s, c = (np.zeros(self.max_features, np.uint8) for _ in range(3))
+        _check(lib().orbx_mapgraph_read_keyframe(self._h, int(kf), C.byref(n), _p(p), _p(o), _p(s), _p(c)))
+        if n.value < 0:
+            return None
+        return dict(point=p[:n.value], octave=o[:n.value], stereo=s[:n.value], close=c[:n.value])
+
+    def read_points(self, first=0, n=None):
+        """-> {slot: dict(n_obs, bad, obs = the row as a sorted list of (keyframe slot, feature index))} of the live slots among
+        first .. first + n - 1, from the device's copy"""
+        n = self.max_points - first if n is None else int(n)
+        nobs, ne = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        fl = np.zeros(n, np.uint8)
+        k, i = np.zeros((n, self.max_obs), np.int32), np.zeros((n, self.max_obs), np.int32)
+        _check(lib().orbx_mapgraph_read_points(self._h, int(first), n, _p(nobs), _p(fl), _p(ne), _p(k), _p(i)))
+        return {first + p: dict(n_obs=int(nobs[p]), bad=bool(fl[p] & 2), obs=sorted(zip(k[p, :ne[p]].tolist(), i[p, :ne[p]].tolist())))
+                for p in np.flatnonzero(fl & 1).tolist()}
+
+    def read_point(self, point):
+        """-> dict(n_obs, bad, obs), or None for a slot that is not live"""
+        return self.read_points(point, 1).get(int(point))
+
+    def _counts(self):
+        return np.zeros(self.max_keyframes, np.int32), np.zeros(self.max_keyframes, np.int32), C.c_int()
+
+    def vote(self, points):
+        """-> (counts[max_keyframes] by keyframe slot, the slots with a non-zero count)"""
+        p, = self._cols("vote", points)
+        cnt, nz, n = self._counts()
+        _check(lib().orbx_mapgraph_vote(self._h, _p(p), len(p), _p(cnt), _p(nz), C.byref(n)))
+        return cnt, nz[:n.value].copy()
+
+    def covisibility(self, kf):
+        """-> (counts[max_keyframes] over kf's own matches with kf left out, the slots with a non-zero count)"""
+        cnt, nz, n = self._counts()
+        _check(lib().orbx_mapgraph_covisibility(self._h, int(kf), _p(cnt), _p(nz), C.byref(n)))
+        return cnt, nz[:n.value].copy()
+
+    def cull_keyframes(self, local, not_erase, monocular, cap=None):
+        """-> dict(culled[n] 0 / 1 culled / 2 mbToBeErased, n_mps[n], n_redundant[n], bad_points ascending)"""
+        lo, = self._cols("cull_keyframes", local)
+        ne = np.ascontiguousarray(not_erase, np.uint8)
+        if ne.shape != lo.shape:
+            raise OrbxError(-1, f"MapGraph.cull_keyframes: {len(lo)} keyframes, {ne.size} not_erase bytes")
+        n = len(lo)
+        cap = self.max_points if cap is None else int(cap)
+        cu = np.zeros(n, np.uint8); mps = np.zeros(n, np.int32); red = np.zeros(n, np.int32)
+        bad = np.zeros(max(cap, 1), np.int32); nb = C.c_int()
+        rc = lib().orbx_mapgraph_cull_keyframes(self._h, _p(lo), _p(ne), n, 1 if monocular else 0, _p(cu), _p(mps), _p(red), _p(bad), cap, C.byref(nb))
+        self.last_n_bad = nb.value
+        _check(rc)
+        return dict(culled=cu, n_mps=mps, n_redundant=red, bad_points=bad[:nb.value].copy())
 
 
 def _pose_inputs(cam, Tcw, who):
