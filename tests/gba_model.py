@@ -6,7 +6,7 @@ tests/lba_model.py's (Problem, Groups, seq_sum, three, ldlt_solve are imported f
 optimize(problem, iterations=10, robust=True, order="asc", stop_at_trial=-1, stop_on_entry=False, mutation=None) -> dict:
   stopped (0, 1 = the flag was up on entry, 2 = it rose during the round), iterations, trials, n_active_kf, n_active_points, chi2, lambda,
   lambda_init, point_included [P] uint8, pose [K][3][4] double, point [P][3] double, Tcw [K][4][4] float32, Xw [P][3] float32,
-  decisions: one (iteration, trial, accepted) per damping trial.
+  decisions: one (iteration, trial, accepted) per damping trial, quat_flips (pose_model.count_flips).
 The sums whose order the contract leaves open are taken in `order`, one of lba_model.ORDERS.
 
 mutation names one deliberate error (tools/gba_spread.py --mutations measures what each changes):
@@ -22,7 +22,7 @@ import math
 import numpy as np
 
 from lba_model import ORDERS, Groups, Problem, ldlt_solve, seq_sum, three  # noqa: F401  (ORDERS, ldlt_solve: for the users of this module)
-from pose_model import DBL_MAX, DELTA_MONO, DELTA_STEREO, f32, huber, oplus, quat_to_matrix
+from pose_model import DBL_MAX, DELTA_MONO, DELTA_STEREO, count_flips, f32, huber, oplus, quat_to_matrix
 
 DELTA_MONO_BA = float(f32(math.sqrt(5.99)))      # src/Optimizer.cc:101 thHuber2D = sqrt(5.99): not LocalBundleAdjustment's 5.991
 MUTATIONS = ("invz_double", "float_rotation", "no_lambda_hll", "lambda_poses", "no_huber", "huber_5991")
@@ -69,6 +69,7 @@ def optimize(problem, iterations=10, robust=True, order="asc", stop_at_trial=-1,
     robust = bool(robust) and mutation != "no_huber"
     res = dict(stopped=0, iterations=0, trials=0, chi2=0.0, lambda_init=0.0, decisions=[])
     res["lambda"] = 0.0
+    flips = count_flips()
     st = M.start()
     kf_act = np.zeros(K, bool)
     kf_act[M.ek] = True
@@ -263,4 +264,5 @@ def optimize(problem, iterations=10, robust=True, order="asc", stop_at_trial=-1,
     T[:, :3, :] = pose.astype(f32)
     T[:, 3, 3] = 1
     res["pose"], res["point"], res["Tcw"], res["Xw"] = pose, st["X"].copy(), T, st["X"].astype(f32)
+    res["quat_flips"] = dict(flips)
     return res

@@ -15,7 +15,8 @@ optimize(problem, order="asc", stop_at_trial=-1, stop_on_entry=False, mutation=N
   stopped, iterations[2], trials[2], n_level1, n_erase, n_active_kf[2], n_active_points[2], chi2[2], lambda[2], edge_flags[E] (uint8),
   pose [K][3][4] double, point [P][3] double, Tcw [K][4][4] float32, Xw [P][3] float32,
   decisions: one (round, iteration, trial, accepted) per damping trial, lambda_init[2] (computeLambdaInit of each round),
-  margin_chi2 / margin_depth: the smallest |chi2 - threshold| and |Pc.z| over the edges at either classification.
+  margin_chi2 / margin_depth: the smallest |chi2 - threshold| and |Pc.z| over the edges at either classification,
+  quat_flips: how often SE3Quat::normalizeRotation met w < 0, by call site (pose_model.count_flips).
 problem = dict(Tcw [K][4][4], cam [K][5], fixed [K], Xw [P][3], edge_kf, edge_point, x, y, u_right, inv_sigma2)
 
 mutation names one deliberate error (tools/lba_spread.py --mutations measures what each changes):
@@ -215,12 +216,14 @@ def optimize(problem, order="asc", stop_at_trial=-1, stop_on_entry=False, mutati
     M = Problem(problem, mutation)
     K, P, E = M.K, M.P, M.E
     res = dict(stopped=0, iterations=[0, 0], trials=[0, 0], n_level1=0, n_erase=0, n_active_kf=[0, 0], n_active_points=[0, 0],
-               chi2=[0.0, 0.0], edge_flags=np.zeros(E, np.uint8), decisions=[], margin_chi2=math.inf, margin_depth=math.inf)
+               chi2=[0.0, 0.0], edge_flags=np.zeros(E, np.uint8), decisions=[], margin_chi2=math.inf, margin_depth=math.inf,
+               quat_flips={})
     res["lambda"] = [0.0, 0.0]
     res["lambda_init"] = [0.0, 0.0]
     if stop_on_entry:
         res["stopped"] = 1
         return res
+    flips = pm.count_flips()
     st = M.start()
     level1 = np.zeros(E, bool)
     echi = np.zeros(E)
@@ -454,4 +457,5 @@ def optimize(problem, order="asc", stop_at_trial=-1, stop_on_entry=False, mutati
     T[:, :3, :] = pose.astype(f32)
     T[:, 3, 3] = 1
     res["pose"], res["point"], res["Tcw"], res["Xw"] = pose, st["X"].copy(), T, st["X"].astype(f32)
+    res["quat_flips"] = dict(flips)
     return res

@@ -13,12 +13,14 @@ optimize(obs, cam, Tcw, order) -> dict:
   flags[rounds][n_corr], margin[rounds][n_corr] = |chi2 - threshold| / threshold of every edge at each classification,
   class_chi2[rounds][n_corr] (the chi2 each classification used), idx[n_corr] (feature index of each edge), stale_used (a round ended on a rejected trial: active edges were classified at that pose),
   decisions: one (round, iteration, trial, accepted, currentChi, tempChi, max |x_j|) per damping trial,
+  quat_flips: how often SE3Quat::normalizeRotation met w < 0, by call site (count_flips),
   stops: one (round, iteration, iniChi, currentChi) per evaluation of the added stop rule
 
 path_sensitivity(res) -> the largest step max |x_j| among the trials whose accept / reject decision hangs on rounding (|currentChi - tempChi|
   <= NOISE max(currentChi, 1)), and the smallest relative distance of a stop-rule evaluation from its threshold.  A scene whose every
   noise-decided trial moves the pose by less than the comparison bound gives the same pose whichever way those decisions fall.
 """
+import contextlib
 import math
 
 import numpy as np
@@ -34,8 +36,34 @@ NOISE = 1e-12                                  # path_sensitivity: a chi2 differ
 
 # ---------------------------------------------------------------- SE3Quat: q = (x, y, z, w), t
 
+QUAT_MUTATIONS = ("quat_branch1", "quat_branch2", "quat_branch3", "quat_tie_ge", "quat_no_flip")
+_quat = dict(mutation=None, flips=dict(input=0, exp=0, mul=0, other=0))
+
+
+@contextlib.contextmanager
+def quat_mutation(name):
+    """one deliberate error in the quaternion code below, for every model that uses it, while the block runs:
+      "quat_branch1" / 2 / 3   in the branch of quat_from_matrix whose largest diagonal entry is 0 / 1 / 2, one off-diagonal sum is a difference
+      "quat_tie_ge"            >= in the two comparisons of the diagonal entries
+      "quat_no_flip"           quat_normalize does not flip the sign where w < 0"""
+    assert name is None or name in QUAT_MUTATIONS, name
+    before, _quat["mutation"] = _quat["mutation"], name
+    try:
+        yield
+    finally:
+        _quat["mutation"] = before
+
+
+def count_flips():
+    """-> a fresh counter dict that quat_normalize fills from now on: how often w < 0 made it flip, by call site ("input": pose_from_Tcw,
+    "exp": se3_exp, "mul": pose_mul, "other").  The optimize() of each model puts it into its result as quat_flips."""
+    _quat["flips"] = dict(input=0, exp=0, mul=0, other=0)
+    return _quat["flips"]
+
+
 def quat_from_matrix(m):
     """Eigen's Quaternion(Matrix3)"""
+    mut = _quat["mutation"]
     t = (m[0, 0] + m[1, 1]) + m[2, 2]
     if t > 0.0:
         t = math.sqrt(t + 1.0)
@@ -43,9 +71,9 @@ def quat_from_matrix(m):
         t = 0.5 / t
         return np.array([(m[2, 1] - m[1, 2]) * t, (m[0, 2] - m[2, 0]) * t, (m[1, 0] - m[0, 1]) * t, w])
     i = 0
-    if m[1, 1] > m[0, 0]:
+    if m[1, 1] > m[0, 0] or (mut == "quat_tie_ge" and m[1, 1] == m[0, 0]):
         i = 1
-    if m[2, 2] > m[i, i]:
+    if m[2, 2] > m[i, i] or (mut == "quat_tie_ge" and m[2, 2] == m[i, i]):
         i = 2
     j = (i + 1) % 3
     k = (j + 1) % 3
@@ -56,13 +84,20 @@ def quat_from_matrix(m):
     q[3] = (m[k, j] - m[j, k]) * t
     q[j] = (m[j, i] + m[i, j]) * t
     q[k] = (m[k, i] + m[i, k]) * t
+    if mut == "quat_branch%d" % (i + 1):       # the sum that does not hold m01, which a look-at rotation with y down has as an exact zero
+        if i == 0:
+            q[k] = (m[k, i] - m[i, k]) * t
+        else:
+            q[j] = (m[j, i] - m[i, j]) * t
     return q
 
 
-def quat_normalize(q):
-    """SE3Quat::normalizeRotation"""
+def quat_normalize(q, where="other"):
+    """SE3Quat::normalizeRotation; `where` names the call site for count_flips()"""
     if q[3] < 0.0:
-        q = -q
+        _quat["flips"][where] += 1
+        if _quat["mutation"] != "quat_no_flip":
+            q = -q
     n = math.sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3])
     return q / n
 
@@ -89,7 +124,7 @@ def quat_rotate(q, v):
 def pose_from_Tcw(Tcw):
     """Converter::toSE3Quat: the float matrix widened, SE3Quat(R, t)"""
     T = np.asarray(Tcw, f32).reshape(4, 4).astype(np.float64)
-    return quat_normalize(quat_from_matrix(T[:3, :3])), T[:3, 3].copy()
+    return quat_normalize(quat_from_matrix(T[:3, :3]), "input"), T[:3, 3].copy()
 
 
 def se3_exp(x):
@@ -112,7 +147,7 @@ def se3_exp(x):
         V = (I + b * O) + cc * O2
     u = x[3:]
     t = np.array([(V[r, 0] * u[0] + V[r, 1] * u[1]) + V[r, 2] * u[2] for r in range(3)])
-    return quat_normalize(quat_from_matrix(R)), t
+    return quat_normalize(quat_from_matrix(R), "exp"), t
 
 
 def pose_mul(a, b):
@@ -125,7 +160,7 @@ def pose_mul(a, b):
                   ((aw * by + ay * bw) + az * bx) - ax * bz,
                   ((aw * bz + az * bw) + ax * by) - ay * bx,
                   ((aw * bw - ax * bx) - ay * by) - az * bz])
-    return quat_normalize(q), t
+    return quat_normalize(q, "mul"), t
 
 
 def oplus(pose, x):
@@ -301,10 +336,11 @@ def optimize(obs, cam, Tcw, order="asc", hook=None):
     n = len(np.asarray(obs["has_point"]))
     Tin = np.asarray(Tcw, f32).reshape(4, 4)
     res = dict(n_corr=E.n, rounds=0, n_bad=[0] * 4, iterations=[0] * 4, chi2=[0.0] * 4, ret=0, idx=E.idx, flags=[], margin=[],
-               outlier=np.zeros(n, np.uint8), stale_used=False, decisions=[], stops=[], class_chi2=[])
+               outlier=np.zeros(n, np.uint8), stale_used=False, decisions=[], stops=[], class_chi2=[], quat_flips=count_flips())
     if E.n < 3:                                                           # src/Optimizer.cc:423-424
         res["pose"] = Tin[:3, :].astype(np.float64)
         res["Tcw"] = Tin.copy()
+        res["quat_flips"] = dict(res["quat_flips"])
         return res
     start = pose_from_Tcw(Tin)
     out = np.zeros(E.n, bool)
@@ -387,6 +423,7 @@ def optimize(obs, cam, Tcw, order="asc", hook=None):
     res["pose"], res["Tcw"] = P, T
     res["outlier"][E.idx] = out
     res["ret"] = E.n - res["n_bad"][res["rounds"] - 1]
+    res["quat_flips"] = dict(res["quat_flips"])                           # the counter stops here
     return res
 
 
