@@ -2,6 +2,7 @@
 // vocabulary-guided search per neighbour / candidate keyframe, each as ONE call into liborbx (adapter/orbx_batch.h).
 // LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:241-309), LoopClosing::ComputeSim3 (src/LoopClosing.cc:293-323),
 // Tracking::Relocalization (src/Tracking.cc:1661-1682).
+#include "mappoint/MapPointRefresh.h"
 #include "orbx_batch.h"
 
 #include <stdexcept>
@@ -95,9 +96,14 @@ size_t KeyFrameCache::size()
 
 // ---------------------------------------------------------------- resident keyframes of the projection searches
 
+// orbx_adapter::RefreshMapPoints reads the descriptors of the registered keyframes on the device (mappoint/MapPointRefresh.h)
+static FrameRef refresh_frame_of(KeyFrame *pKF) { return KeyFrameFrames::instance().find(pKF); }
+
 KeyFrameFrames &KeyFrameFrames::instance()
 {
     static KeyFrameFrames c;
+    static const bool announced = (refresh_hooks().frame_of.store(&refresh_frame_of), true);   // once, at the registry's first use: a program that registers nothing sets nothing
+    (void)announced;
     return c;
 }
 

@@ -7,6 +7,7 @@
 #include <stdexcept>
 
 #include "LocalMapPoints.h"
+#include "mappoint/MapPointRefresh.h"
 #include "orbx_adapter.h"
 
 using namespace std;
@@ -39,6 +40,15 @@ namespace orbx_adapter
 using ORB_SLAM2::Frame;
 using ORB_SLAM2::MapPoint;
 
+static orbx_mappoints *refresh_begin() { return LocalMapPoints::instance().lend(); }
+static int refresh_slot(MapPoint *pMP) { return LocalMapPoints::instance().lent_slot(pMP); }
+static void refresh_refreshed(MapPoint *pMP, int slot, int what, const float *geom8, const unsigned char *desc32)
+{
+    LocalMapPoints::instance().lent_refreshed(pMP, slot, what, geom8, desc32);
+}
+static void refresh_end() { LocalMapPoints::instance().give_back(); }
+static const RefreshTable g_refresh_table = { &refresh_begin, &refresh_slot, &refresh_refreshed, &refresh_end };
+
 LocalMapPoints &LocalMapPoints::instance()
 {
     static LocalMapPoints *m = NULL;     // never destroyed: no HIP call from a static destructor
@@ -65,8 +75,33 @@ orbx_mappoints *LocalMapPoints::table()
             throw std::runtime_error(orbx_last_error());
         shadow_.resize((size_t)capacity_);
         known_.assign((size_t)capacity_, (unsigned char)UNKNOWN);
+        if (this == &instance()) refresh_hooks().table.store(&g_refresh_table);      // the process's table: RefreshMapPoints writes it in place from now on
     }
     return table_;
+}
+
+orbx_mappoints *LocalMapPoints::lend()
+{
+    mu_.lock();
+    if (!table_) mu_.unlock();
+    return table_;
+}
+
+void LocalMapPoints::give_back() { mu_.unlock(); }
+
+// (the caller holds mu_ through lend())
+int LocalMapPoints::lent_slot(MapPoint *pMP)
+{
+    std::unordered_map<MapPoint *, int>::iterator it = slot_of_.find(pMP);
+    return it == slot_of_.end() ? -1 : it->second;
+}
+
+void LocalMapPoints::lent_refreshed(MapPoint *pMP, int slot, int what, const float *geom8, const unsigned char *desc32)
+{
+    std::unordered_map<MapPoint *, int>::iterator it = slot_of_.find(pMP);
+    if (it == slot_of_.end() || it->second != slot || known_[slot] != SENT) return;    // nothing known about the slot: the next search sends it whole
+    if ((what & REFRESH_GEOM) && geom8) memcpy(shadow_[slot].geom, geom8, sizeof shadow_[slot].geom);
+    if ((what & REFRESH_DESC) && desc32) memcpy(shadow_[slot].desc, desc32, sizeof shadow_[slot].desc);
 }
 
 void LocalMapPoints::drop(MapPoint *pMP)

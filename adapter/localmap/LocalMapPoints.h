@@ -9,6 +9,7 @@
 //   MapPoint::SetBadFlag   orbx_adapter::LocalMapPoints::instance().drop(this);
 //   Map::clear             orbx_adapter::LocalMapPoints::instance().clear();
 //   include/MapPoint.h     void GetFrustumRecord(float *geom8, unsigned char *desc32);   (defined in LocalMapPoints.cc)
+// Once the table exists, orbx_adapter::RefreshMapPoints (adapter/mappoint/MapPointRefresh.h) writes refreshed records into it on the device.
 #ifndef ORBX_ADAPTER_LOCALMAPPOINTS_H
 #define ORBX_ADAPTER_LOCALMAPPOINTS_H
 
@@ -42,6 +43,16 @@ public:
     void drop(ORB_SLAM2::MapPoint *pMP);
     // Map::clear: every slot is free again; the device table is kept
     void clear();
+
+    // for orbx_adapter::RefreshMapPoints (adapter/mappoint/MapPointRefresh.h: RefreshTable), which writes the table in place.  lend()
+    // takes the lock that SearchLocalPoints holds and returns the table -- or NULL, with nothing held, while there is none; until
+    // give_back(), lent_slot() is the slot a point holds (-1: none; nothing is handed out) and lent_refreshed() records that the device
+    // now holds these halves of the point's record (what bit 0: geom8, bit 1: desc32), which the point's members equal by then.  No
+    // search runs in between, so a search never compares members against a shadow that lags the device.
+    orbx_mappoints *lend();
+    int lent_slot(ORB_SLAM2::MapPoint *pMP);
+    void lent_refreshed(ORB_SLAM2::MapPoint *pMP, int slot, int what, const float *geom8, const unsigned char *desc32);
+    void give_back();
 
     int size();                 // points that hold a slot
     int last_uploaded();        // records the most recent search re-sent (tests, tools)

@@ -41,6 +41,8 @@ class MapPoint;
 namespace orbx_adapter
 {
 
+struct RefreshStats;
+
 class MapGraph
 {
 public:
@@ -80,6 +82,7 @@ public:
 private:
     friend void CovisibilityCounts(ORB_SLAM2::KeyFrame *, std::map<ORB_SLAM2::KeyFrame *, int> &);
     friend void VoteLocalKeyFrames(ORB_SLAM2::Frame &, std::map<ORB_SLAM2::KeyFrame *, int> &);
+    friend RefreshStats RefreshMapPoints(const std::vector<ORB_SLAM2::MapPoint *> &, int);      // adapter/mappoint/MapPointRefresh.cc
     enum Kind { SET_KEYFRAME, SET_MATCH, ADD_OBS, ERASE_OBS, ERASE_POINT, ERASE_KEYFRAME, CLEAR };
     struct Rec { Kind kind; int32_t a, b, c; };     // SET_KEYFRAME: slot, index into attr_, n; SET_MATCH: kf, idx, point; ADD_OBS: point, kf, idx;
                                                     // ERASE_OBS: point, kf; ERASE_POINT: point; ERASE_KEYFRAME: kf

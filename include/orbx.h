@@ -817,6 +817,73 @@ int orbx_mapgraph_covisibility(orbx_mapgraph *g, int kf, int32_t *counts, int32_
 int orbx_mapgraph_cull_keyframes(orbx_mapgraph *g, const int32_t *local, const uint8_t *not_erase, int n_local, int monocular,
                                  uint8_t *culled, int32_t *n_mps, int32_t *n_redundant, int32_t *bad_points, int cap, int *n_bad);
 
+/* ---- map points refreshed on the device: MapPoint::UpdateNormalAndDepth and MapPoint::ComputeDistinctiveDescriptors -----------
+ * The loops over map points behind SearchInNeighbors, CreateNewMapPoints, the bundle adjustments and the essential-graph correction
+ * (src/LocalMapping.cc:187-188, :505-507, :595-596, src/Optimizer.cc:860, :1151, src/LoopClosing.cc) call src/MapPoint.cc:371-420 and
+ * :266-340 point by point.  Their inputs are resident: the rows, live and bad bits and octaves in the graph, the keyframes' descriptors
+ * in their orbx_frame, the positions in the orbx_mappoints table (or handed over by a bundle adjustment); their outputs are exactly the
+ * 64 bytes per slot of that table.  One call reads the graph and the frames and writes the table in place; the same values come back
+ * for the MapPoint members.
+ * Per listed point i:
+ *   status[i]   bit 0: the geometry was updated, bit 1: the descriptor was updated.  A point that is not live, is bad or has an empty row
+ *               gets 0 and nothing of it is written anywhere (the reference's early return).
+ *   GEOM        every row entry counts, bad keyframes and entries that outlived their keyframe included (the reference does not ask
+ *               isBad() here).  The reference feature is the row entry of ref_kf[i]; a row without one takes feature 0 of that
+ *               keyframe (observations[pRefKF] on the reference's local copy default-inserts 0).  geom[i][8] = X Y Z mfMinDistance nx
+ *               ny nz mfMaxDistance, the table's record: X Y Z are pos[i], or what the table held.
+ *   DESC        only entries whose keyframe has kf_bad == 0 take part; if none does, bit 1 stays clear and the descriptor is left alone.
+ *               best_kf[i] / best_idx[i] name the winning (keyframe slot, feature), desc[i][32] is its descriptor.
+ *   ORDER       entries are taken in ascending keyframe slot (a keyframe is in a row at most once).  The stored order of a row is
+ *               unobservable, so the result does not depend on it.  A STATED DEVIATION: the reference iterates in KeyFrame* address
+ *               order, whatever its allocator produced.  The order decides the rounding of the float sum, and the winner among equal
+ *               medians: the first in order, as `median < BestMedian` has it.
+ * All five output arrays may be NULL; rows whose status bit is clear are not written.  With m != NULL the updated halves go into the
+ * table's slots (table_slot[i], or point[i] when table_slot is NULL) on the device, with no host round trip between the compute and the
+ * write, and the table's "given" bitmap follows; a half whose status bit is clear stays byte for byte as it was.
+ * The arithmetic is fixed, float unless a step says double, every operation rounded on its own (no fused multiply-add), division and
+ * square root correctly rounded:
+ *   1. per entry k in order: d = P - Ow_k per component; nrm = sqrt(((double)dx*dx + (double)dy*dy) + (double)dz*dz); inv = 1.0 / nrm in
+ *      double; normal_c = normal_c + (float)((double)d_c * inv), from normal = 0
+ *   2. mNormalVector_c = (float)((double)normal_c * (1.0 / (double)N)), N = the entries of the row
+ *   3. dist = (float)sqrt(...) of P - Ow_ref as in step 1; mfMaxDistance = dist * scale_factors[octave(ref_kf, ref feature)];
+ *      mfMinDistance = mfMaxDistance / scale_factors[nlevels - 1]
+ *   4. the descriptor as orbx_distinctive_descriptors: the Hamming matrix of the entries that take part, per row the median
+ *      sorted[(int)(0.5 * (N - 1))], the first row with the smallest
+ * A zero distance gives the IEEE result (NaN or infinity), as in the reference.  Against OpenCV's own cv::Mat expression arithmetic this
+ * restatement is unpinned.
+ * Every refusal is decided on the graph's host mirror and the table's host state before any device work and leaves the graph, the table
+ * and the outputs unchanged.  ORBX_E_INVALID: `what` outside {1, 2, 3}; a negative slot or a slot listed twice (point, table_slot,
+ * kf_slot); a live, not-bad listed point whose row names a keyframe that is not in kf_slot; with GEOM, for such a point with a row, a
+ * ref_kf that is not listed or not in use, a reference feature outside the keyframe or of an octave >= nlevels, nlevels outside [1, 32],
+ * and pos == NULL while the table never got that slot's geometry (or without a table); with DESC, a keyframe with kf_bad == 0 in such a
+ * row whose kf_frame is NULL or has no feature of the entry's index; the graph, the table and the frames on different devices.  (GEOM
+ * alone into a table slot that never had a descriptor is fine, as is the converse.)  ORBX_E_CAPACITY: a slot beyond its capacity.
+ * n == 0: ORBX_OK, no launch.  "Unchanged" covers these refusals (ORBX_E_INVALID, ORBX_E_CAPACITY) only: ORBX_E_HIP -- a failing HIP
+ * call behind the launch, or a device status that differs from the one the mirror predicted -- is returned with the table possibly
+ * written and its "given" bits set, as a failing orbx_mappoints_set leaves it.
+ * One packed upload (the points, pos, ref_kf, scale_factors and a keyframe table indexed by slot: centre, bad, descriptor base, n), one
+ * launch of k_mp_refresh (a wave per point), one group of downloads -- only the arrays asked for -- behind one synchronisation, on
+ * `stream` (NULL: the calling thread's own).  The graph serialises as for every call; the table is held as orbx_mappoints_set holds it
+ * and its event is recorded; frames still pending are waited for through their events. */
+#define ORBX_REFRESH_GEOM 1   /* UpdateNormalAndDepth */
+#define ORBX_REFRESH_DESC 2   /* ComputeDistinctiveDescriptors */
+typedef struct {
+    int what;                          /* a non-empty OR of the two */
+    /* the points */
+    int n; const int32_t *point;       /* graph point slots, each at most once */
+    const int32_t *table_slot;         /* [n] slots of `m`; NULL: the same numbers as point[] */
+    const float *pos;                  /* [n][3] mWorldPos; NULL: X Y Z as the table holds them */
+    const int32_t *ref_kf;             /* [n] keyframe slot of mpRefKF (GEOM only) */
+    /* every keyframe that a row of a listed point may name, and every ref_kf */
+    int nk; const int32_t *kf_slot;    /* each at most once */
+    const float *kf_centre;            /* [nk][3] GetCameraCenter() */
+    const uint8_t *kf_bad;             /* [nk] KeyFrame::isBad() */
+    const orbx_frame *const *kf_frame; /* [nk] resident descriptors; needed for DESC on a keyframe that is not bad, else may be NULL */
+    const float *scale_factors; int nlevels;   /* mvScaleFactors, mnScaleLevels (GEOM) */
+} orbx_refresh_job;
+int orbx_mapgraph_refresh_points(orbx_mapgraph *g, orbx_mappoints *m /* may be NULL */, const orbx_refresh_job *job,
+                                 uint8_t *status, float *geom, int32_t *best_kf, int32_t *best_idx, uint8_t *desc, void *stream);
+
 /* ---- Optimizer::PoseOptimization: motion-only pose optimisation (src/Optimizer.cc:286-513) ---------------------------
  * The one per-frame step of Tracking that g2o solved on a host core (TrackWithMotionModel, TrackReferenceKeyFrame, TrackLocalMap;
  * Relocalization up to three times per candidate, src/Tracking.cc:1730-1800): one 6-DoF vertex, one unary edge per feature that

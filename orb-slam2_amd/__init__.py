@@ -17,6 +17,7 @@ sitting directly on the C ABI of liborbx.so (include/orbx.h):
   bundle_adjustment <- reference src/Optimizer.cc:48-281 (Optimizer::BundleAdjustment, the global bundle adjustment)
   optimize_essential_graph <- reference src/Optimizer.cc:885-1153 (Optimizer::OptimizeEssentialGraph, LoopClosing::CorrectLoop)
   MapGraph <- reference src/LocalMapping.cc:704-775, src/KeyFrame.cc:303-338, src/Tracking.cc:1515-1538 (KeyFrameCulling and the covisibility votes)
+  MapGraph.refresh_points <- reference src/MapPoint.cc:266-340, :371-420 (ComputeDistinctiveDescriptors, UpdateNormalAndDepth)
   mono_init_hypotheses / mono_init_reconstruct / Initializer <- reference src/Initializer.cc:37-1026 (Tracking::MonocularInitialization)
 
 There is NO CPU fallback: importing works without a GPU (so that the ABI can be inspected), but
@@ -30,7 +31,7 @@ from .orbx import (OrbxError, KP_DTYPE, lib, lib_path, ORBextractor, ORBmatcher,
                    triangulate_pairs, frame_set_depth, frame_triangulate, sim3_hypotheses, sim3_hypotheses_batch, sim3_max_error, Sim3Ransac,
                    sim3_optimize, sim3_optimize_batch, sim3opt_camera_points, pnp_hypotheses, pnp_hypotheses_batch, PnPRansac,
                    mono_init_hypotheses, mono_init_reconstruct, mono_init_initialize, mono_init_draw_sets, DUtilsRandom, Initializer,
-                   local_bundle_adjustment, bundle_adjustment, optimize_essential_graph)
+                   local_bundle_adjustment, bundle_adjustment, optimize_essential_graph, RefreshResult, REFRESH_GEOM, REFRESH_DESC)
 
 __all__ = ["OrbxError", "KP_DTYPE", "lib", "lib_path", "ORBextractor", "ORBmatcher", "ComputeStereoMatches",
            "FeatSet", "make_featset", "STAGES", "BowDatabase", "DeviceKeyFrame", "DeviceFrame", "MapPoints", "MapGraph", "BowFrames", "KeyFrameDatabase", "ORBVocabulary", "ComputeDistinctiveDescriptors", "Rectifier", "UndistortKeyPoints",
@@ -38,4 +39,4 @@ __all__ = ["OrbxError", "KP_DTYPE", "lib", "lib_path", "ORBextractor", "ORBmatch
            "triangulate_pairs", "frame_set_depth", "frame_triangulate", "sim3_hypotheses", "sim3_hypotheses_batch", "sim3_max_error", "Sim3Ransac",
            "sim3_optimize", "sim3_optimize_batch", "sim3opt_camera_points", "pnp_hypotheses", "pnp_hypotheses_batch", "PnPRansac",
            "mono_init_hypotheses", "mono_init_reconstruct", "mono_init_initialize", "mono_init_draw_sets", "DUtilsRandom", "Initializer",
-           "local_bundle_adjustment", "bundle_adjustment", "optimize_essential_graph"]
+           "local_bundle_adjustment", "bundle_adjustment", "optimize_essential_graph", "RefreshResult", "REFRESH_GEOM", "REFRESH_DESC"]

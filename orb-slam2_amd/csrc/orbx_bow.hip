@@ -29,14 +29,6 @@ __device__ __forceinline__ int find_node(const uint32_t *ids, int n, uint32_t ke
     return (lo < n && ids[lo] == key) ? lo : -1;
 }
 
-__device__ __forceinline__ void load_desc(const uint32_t *d, long long idx, uint32_t *out)
-{
-    const uint4 *s = reinterpret_cast<const uint4 *>(d + idx * 8);
-    const uint4 v0 = s[0], v1 = s[1];
-    out[0] = v0.x; out[1] = v0.y; out[2] = v0.z; out[3] = v0.w;
-    out[4] = v1.x; out[5] = v1.y; out[6] = v1.z; out[7] = v1.w;
-}
-
 // ComputeThreeMaxima (:1687-1728) on per-bin counts + clearing of the other bins (:282-300).
 // bins[i] = bin of match slot i or 255; match[] entries outside the 3 dominant bins become -1.
 // Returns (in *out_n, by thread 0) the number of surviving matches.

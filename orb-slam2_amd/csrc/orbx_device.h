@@ -256,6 +256,15 @@ __device__ __forceinline__ void dev_sincos(float angle_rad, float *s_out, float 
 // cvRound on a float that is known to be small: round-half-to-even
 __device__ __forceinline__ int dev_cv_round(float v) { return (int)rintf(v); }
 
+// descriptor idx of a [.][32]-byte array (16-byte aligned) as eight words: two 16-byte loads
+__device__ __forceinline__ void load_desc(const uint32_t *d, long long idx, uint32_t *out)
+{
+    const uint4 *s = reinterpret_cast<const uint4 *>(d + idx * 8);
+    const uint4 v0 = s[0], v1 = s[1];
+    out[0] = v0.x; out[1] = v0.y; out[2] = v0.z; out[3] = v0.w;
+    out[4] = v1.x; out[5] = v1.y; out[6] = v1.z; out[7] = v1.w;
+}
+
 __device__ __forceinline__ int hamming256(const uint32_t *a, const uint32_t *b)
 {
     int d = 0;

@@ -4,8 +4,9 @@
 //            Tracking::UpdateLocalKeyFrames, src/Tracking.cc:1515-1538, and KFcounter of KeyFrame::UpdateConnections, src/KeyFrame.cc:303-338),
 //            k_mg_judge + k_mg_walk (LocalMapping::KeyFrameCulling, src/LocalMapping.cc:704-775, with the map-point part of
 //            KeyFrame::SetBadFlag, src/KeyFrame.cc:505-507, and MapPoint::EraseObservation / SetBadFlag, src/MapPoint.cc:119-176, between
-//            its iterations)
-//   host:    the handle, its mirror, the edits, the queries
+//            its iterations), k_mp_refresh (MapPoint::UpdateNormalAndDepth, src/MapPoint.cc:371-420, and
+//            MapPoint::ComputeDistinctiveDescriptors, :266-340, from the rows, the resident keyframes and the map-point table)
+//   host:    the handle, its mirror, the edits, the queries, orbx_mapgraph_refresh_points
 //
 // LAYOUT.  One device allocation: a word space (uint32) kf_n[max_keyframes] | match[max_keyframes][max_features] | hdr[max_points] |
 // row[max_points][max_obs], then attr[max_keyframes][max_features] (bytes), then the staging of one edit upload.
@@ -20,6 +21,7 @@
 // queries never read the mirror: they run on the device's copy.  cull_keyframes changes the device's copy by itself, and the host then
 // replays the culled keyframes on the mirror (erase_keyframe without an upload) and checks that both name the same bad points.
 #include "orbx_resident.h"
+#include "orbx_device.h"
 #include <algorithm>
 #include <mutex>
 
@@ -203,6 +205,161 @@ __global__ __launch_bounds__(1024) void k_mg_walk(MgDev G, const int32_t *__rest
     }
 }
 
+// ---- MapPoint::UpdateNormalAndDepth and ComputeDistinctiveDescriptors (include/orbx.h: orbx_mapgraph_refresh_points states the arithmetic)
+
+// a keyframe as the refresh sees it, indexed by slot: the camera centre, bad (bit 31) | features of the resident frame, its descriptors
+struct RfKf { float cx, cy, cz; uint32_t bad_n; const uint32_t *desc; };
+#define RF_BAD 0x80000000u
+
+struct RfArgs {
+    MgDev G;
+    int n, what, cap, nkt, nlevels;          // cap: the longest row among the listed points (a multiple of 4): the LDS arrays are sized by it
+    const int32_t *pts, *tslot, *ref;        // tslot: NULL without a table
+    const float *pos, *sf;                   // pos: NULL = X Y Z from the table
+    const RfKf *kft;                         // [nkt]
+    float4 *tgeom; uint4 *tdesc;             // the table, or NULL
+    uint8_t *status; float4 *geom; int32_t *best_kf, *best_idx; uint4 *desc;   // the output records, [n] each
+};
+
+static inline size_t rf_lds_bytes(int cap) { return (size_t)cap * 56 + (size_t)cap * cap * 2; }
+
+// A wave per point, grid-stride.  The row is ranked by its entry word (keyframe slot << 16 | feature: a keyframe is in a row once, so
+// this is the order of the keyframe slots) by counting in LDS; everything behind that runs in rank order, whatever the stored order was.
+// GEOM: the lanes work out their entries' unit vectors, lane 0 adds them up in rank order (the order of the float sum is the contract).
+// DESC: the entries of keyframes that are not bad are compacted in rank order with their descriptors in LDS; the Hamming matrix (u16),
+// the row medians by bisection on the value and the wave minimum of median << 16 | rank are k_distinctive's.
+// LDS: key[cap] sorted[cap] good[cap] | unit[cap][3] | dsc[cap][8] | dm[cap][cap] u16 = 56 cap + 2 cap^2 bytes, 142 KiB at cap = 256.
+__global__ __launch_bounds__(64) void k_mp_refresh(RfArgs A)
+{
+    extern __shared__ __align__(16) unsigned char rf_smem[];
+    const int cap = A.cap, lane = threadIdx.x;
+    uint32_t *key = reinterpret_cast<uint32_t *>(rf_smem), *sorted = key + cap, *good = sorted + cap;
+    float *unit = reinterpret_cast<float *>(good + cap);
+    uint4 *dsc = reinterpret_cast<uint4 *>(unit + 3 * cap);
+    uint16_t *dm = reinterpret_cast<uint16_t *>(dsc + 2 * cap);
+    const MgDev &G = A.G;
+    for (int i = blockIdx.x; i < A.n; i += gridDim.x) {
+        __syncthreads();   // the previous point's LDS has been read
+        const int p = A.pts[i];
+        const uint32_t h = G.w[G.hdr(p)];
+        const int cnt = min(MG_CNT(h), cap);
+        if (!(h & MG_LIVE) || (h & MG_BAD) || cnt == 0) {   // the reference's early return
+            if (lane == 0) A.status[i] = 0;
+            continue;
+        }
+        for (int e = lane; e < cnt; e += 64) key[e] = G.w[G.row(p, e)];
+        __syncthreads();
+        for (int e = lane; e < cnt; e += 64) {
+            const uint32_t k = key[e];
+            int r = 0;
+            for (int j = 0; j < cnt; j++) r += key[j] < k;
+            sorted[r] = k;
+        }
+        __syncthreads();
+        const long long ts = A.tslot ? A.tslot[i] : 0;
+        unsigned st = 0;
+        if (A.what & ORBX_REFRESH_GEOM) {
+            float Px, Py, Pz;
+            if (A.pos) { Px = A.pos[3 * (long long)i]; Py = A.pos[3 * (long long)i + 1]; Pz = A.pos[3 * (long long)i + 2]; }
+            else { const float4 g0 = A.tgeom[2 * ts]; Px = g0.x; Py = g0.y; Pz = g0.z; }
+            for (int r = lane; r < cnt; r += 64) {
+                const int k = (int)(sorted[r] >> 16);
+                float ux = 0.f, uy = 0.f, uz = 0.f;
+                if (k < A.nkt) {
+                    const RfKf K = A.kft[k];
+                    const float dx = Px - K.cx, dy = Py - K.cy, dz = Pz - K.cz;
+                    const double inv = 1.0 / __dsqrt_rn(((double)dx * dx + (double)dy * dy) + (double)dz * dz);
+                    ux = (float)((double)dx * inv); uy = (float)((double)dy * inv); uz = (float)((double)dz * inv);
+                }
+                unit[3 * r] = ux; unit[3 * r + 1] = uy; unit[3 * r + 2] = uz;
+            }
+            __syncthreads();
+            if (lane == 0) {
+                float nx = 0.f, ny = 0.f, nz = 0.f;
+                for (int r = 0; r < cnt; r++) { nx = nx + unit[3 * r]; ny = ny + unit[3 * r + 1]; nz = nz + unit[3 * r + 2]; }
+                const double invn = 1.0 / (double)cnt;
+                nx = (float)((double)nx * invn); ny = (float)((double)ny * invn); nz = (float)((double)nz * invn);
+                const int ref = A.ref[i];
+                int ri = 0;   // observations[pRefKF] default-inserts 0
+                for (int r = 0; r < cnt; r++) if ((int)(sorted[r] >> 16) == ref) ri = (int)(sorted[r] & 0xFFFFu);
+                float dmax = 0.f, dmin = 0.f;
+                if (ref >= 0 && ref < A.nkt && ref < G.max_kf && ri < G.max_feat) {   // checked on the host
+                    const RfKf K = A.kft[ref];
+                    const float dx = Px - K.cx, dy = Py - K.cy, dz = Pz - K.cz;
+                    const float dist = (float)__dsqrt_rn(((double)dx * dx + (double)dy * dy) + (double)dz * dz);
+                    const int oct = min((int)(G.attr[G.at(ref, ri)] & MG_OCT), A.nlevels - 1);
+                    dmax = dist * A.sf[oct];
+                    dmin = dmax / A.sf[A.nlevels - 1];
+                }
+                const float4 g0 = make_float4(Px, Py, Pz, dmin), g1 = make_float4(nx, ny, nz, dmax);
+                if (A.tgeom) { A.tgeom[2 * ts] = g0; A.tgeom[2 * ts + 1] = g1; }
+                A.geom[2 * (long long)i] = g0; A.geom[2 * (long long)i + 1] = g1;
+            }
+            st |= ORBX_REFRESH_GEOM;
+        }
+        if (A.what & ORBX_REFRESH_DESC) {
+            int nn = 0;
+            for (int r0 = 0; r0 < cnt; r0 += 64) {   // the entries of keyframes that are not bad, compacted in rank order
+                const int r = r0 + lane;
+                bool take = false;
+                uint32_t k = 0;
+                const uint32_t *src = nullptr;
+                if (r < cnt) {
+                    k = sorted[r];
+                    const int kf = (int)(k >> 16);
+                    if (kf < A.nkt) {
+                        const RfKf K = A.kft[kf];
+                        take = !(K.bad_n & RF_BAD) && K.desc && (k & 0xFFFFu) < K.bad_n;   // the last two: checked on the host
+                        src = K.desc;
+                    }
+                }
+                const unsigned long long mask = __ballot(take);
+                if (take) {
+                    const int at = nn + __popcll(mask & ((1ull << lane) - 1ull));
+                    const uint4 *s = reinterpret_cast<const uint4 *>(src + 8 * (size_t)(k & 0xFFFFu));
+                    good[at] = k; dsc[2 * at] = s[0]; dsc[2 * at + 1] = s[1];
+                }
+                nn += __popcll(mask);
+            }
+            __syncthreads();
+            if (nn > 0) {
+                const uint32_t *dw = reinterpret_cast<const uint32_t *>(dsc);
+                for (int a = lane; a < nn; a += 64) {
+                    uint32_t da[8];
+#pragma unroll
+                    for (int q = 0; q < 8; q++) da[q] = dw[8 * a + q];
+                    for (int b = 0; b < nn; b++) dm[a * nn + b] = (uint16_t)hamming256(da, dw + 8 * b);
+                }
+                __syncthreads();
+                const int km = (int)(0.5 * (nn - 1));
+                unsigned best = 0xFFFFFFFFu;
+                for (int a = lane; a < nn; a += 64) {
+                    int lo = 0, hi = 256;   // the smallest v with #(d <= v) > km
+                    while (lo < hi) {
+                        const int mid = (lo + hi) >> 1;
+                        int c = 0;
+                        for (int b = 0; b < nn; b++) c += dm[a * nn + b] <= mid;
+                        if (c > km) hi = mid; else lo = mid + 1;
+                    }
+                    const unsigned kk = ((unsigned)lo << 16) | (unsigned)a;
+                    best = kk < best ? kk : best;
+                }
+                best = wave_min_u32(best);
+                if (lane == 0) {
+                    const int a = (int)(best & 0xFFFFu);
+                    const uint32_t k = good[a];
+                    const uint4 d0 = dsc[2 * a], d1 = dsc[2 * a + 1];
+                    if (A.tdesc) { A.tdesc[2 * ts] = d0; A.tdesc[2 * ts + 1] = d1; }
+                    A.desc[2 * (long long)i] = d0; A.desc[2 * (long long)i + 1] = d1;
+                    A.best_kf[i] = (int32_t)(k >> 16); A.best_idx[i] = (int32_t)(k & 0xFFFFu);
+                }
+                st |= ORBX_REFRESH_DESC;
+            }
+        }
+        if (lane == 0) A.status[i] = (uint8_t)st;
+    }
+}
+
 // ---------------------------------------------------------------- the handle
 
 struct MgUndo { size_t addr; uint32_t old; };
@@ -219,6 +376,7 @@ struct orbx_mapgraph {
     std::vector<int32_t> bad;      // the points that went bad in it
     std::vector<uint64_t> keys;    // duplicate check of a batch
     std::vector<size_t> touched;
+    std::vector<int32_t> kmap;     // refresh_points: per keyframe slot its place in the job's list, -1 between calls
     hipEvent_t ev; hipStream_t ev_stream; bool ev_set;
     std::mutex mu;
 };
@@ -382,6 +540,7 @@ extern "C" int orbx_mapgraph_create(int device, int max_keyframes, int max_featu
     std::fill(g->hw.begin(), g->hw.begin() + max_keyframes, 0xFFFFFFFFu);
     g->hattr.assign(feats, 0);
     g->refs.assign((size_t)max_keyframes, 0);
+    g->kmap.assign((size_t)max_keyframes, -1);
     *out = g;
     return ORBX_OK;
 }
@@ -687,5 +846,185 @@ extern "C" int orbx_mapgraph_cull_keyframes(orbx_mapgraph *g, const int32_t *loc
     *n_bad = (int)theirs.size();
     if ((int)theirs.size() > cap) { orbx_set_error("orbx_mapgraph_cull_keyframes: %zu points went bad, cap %d", theirs.size(), cap); return ORBX_E_CAPACITY; }
     if (!theirs.empty()) memcpy(bad_points, theirs.data(), 4 * theirs.size());
+    return ORBX_OK;
+}
+
+// ---- refresh: every refusal on the mirror and the table's host state, then one upload, one launch, one group of downloads
+
+#define RF_REFUSE(code, ...) do { for (int q_ = 0; q_ < job->nk; q_++) { const int s_ = job->kf_slot[q_]; if (s_ >= 0 && s_ < g->G.max_kf) g->kmap[s_] = -1; } \
+                                  orbx_set_error(__VA_ARGS__); return code; } while (0)
+
+extern "C" int orbx_mapgraph_refresh_points(orbx_mapgraph *g, orbx_mappoints *m, const orbx_refresh_job *job, uint8_t *status, float *geom,
+                                            int32_t *best_kf, int32_t *best_idx, uint8_t *desc, void *stream)
+{
+    static const char *who = "orbx_mapgraph_refresh_points";
+    if (!g || !job) { orbx_set_error("%s: null graph or job", who); return ORBX_E_INVALID; }
+    const int what = job->what, n = job->n, nk = job->nk;
+    const bool do_geom = (what & ORBX_REFRESH_GEOM) != 0, do_desc = (what & ORBX_REFRESH_DESC) != 0;
+    if (what < 1 || what > 3) { orbx_set_error("%s: what = %d, a non-empty OR of ORBX_REFRESH_GEOM and ORBX_REFRESH_DESC", who, what); return ORBX_E_INVALID; }
+    if (n < 0 || n > (1 << 24) || nk < 0 || nk > 65535 || (n && !job->point) || (nk && (!job->kf_slot || !job->kf_centre || !job->kf_bad)) ||
+        (n && do_geom && (!job->ref_kf || !job->scale_factors || job->nlevels < 1 || job->nlevels > 32)) || (n && do_geom && !job->pos && !m) ||
+        (!m && job->table_slot)) {
+        orbx_set_error("%s: invalid argument (n <= 2^24 points, nk <= 65535 keyframes with centre and bad; GEOM: ref_kf, scale_factors, 1 <= nlevels <= 32, pos or a table)", who);
+        return ORBX_E_INVALID;
+    }
+    if (n == 0) return ORBX_OK;
+    if (m && m->device != g->device) { orbx_set_error("%s: the graph is on device %d, the table on device %d", who, g->device, m->device); return ORBX_E_INVALID; }
+    std::lock_guard<std::mutex> lk(g->mu);
+    std::unique_lock<std::shared_timed_mutex> lm;
+    if (m) lm = std::unique_lock<std::shared_timed_mutex>(m->mu);
+    const MgDev &G = g->G;
+    // the keyframes
+    int nkt = 0;
+    for (int q = 0; q < nk; q++) {
+        const int s = job->kf_slot[q];
+        if (s < 0 || s >= G.max_kf || g->kmap[s] >= 0) {
+            for (int r = 0; r < q; r++) g->kmap[job->kf_slot[r]] = -1;
+            if (s < 0) orbx_set_error("%s: keyframe %d: negative slot %d", who, q, s);
+            else if (s >= G.max_kf) orbx_set_error("%s: keyframe %d: slot %d, max_keyframes %d", who, q, s, G.max_kf);
+            else orbx_set_error("%s: keyframe slot %d listed twice", who, s);
+            return s >= G.max_kf ? ORBX_E_CAPACITY : ORBX_E_INVALID;
+        }
+        g->kmap[s] = q;
+        nkt = std::max(nkt, s + 1);
+    }
+    for (int q = 0; q < nk && do_desc; q++) {
+        const orbx_frame *f = job->kf_frame ? job->kf_frame[q] : nullptr;
+        if (f && f->device != g->device) RF_REFUSE(ORBX_E_INVALID, "%s: the graph is on device %d, the frame of keyframe slot %d on device %d", who, g->device, job->kf_slot[q], f->device);
+    }
+    // the points
+    const int32_t *tsl = m ? (job->table_slot ? job->table_slot : job->point) : nullptr;
+    g->keys.clear();
+    for (int i = 0; i < n; i++) {
+        const int p = job->point[i];
+        if (p < 0) RF_REFUSE(ORBX_E_INVALID, "%s: entry %d: point slot %d", who, i, p);
+        if (p >= G.max_points) RF_REFUSE(ORBX_E_CAPACITY, "%s: entry %d: point slot %d, max_points %d", who, i, p, G.max_points);
+        g->keys.push_back((uint64_t)p);
+        if (tsl && tsl[i] < 0) RF_REFUSE(ORBX_E_INVALID, "%s: entry %d: table slot %d", who, i, tsl[i]);
+        if (tsl && tsl[i] >= m->capacity) RF_REFUSE(ORBX_E_CAPACITY, "%s: entry %d: table slot %d, capacity %d", who, i, tsl[i], m->capacity);
+    }
+    if (mg_twice(g)) RF_REFUSE(ORBX_E_INVALID, "%s: a point slot listed twice", who);
+    if (m && job->table_slot) {
+        g->keys.clear();
+        for (int i = 0; i < n; i++) g->keys.push_back((uint64_t)tsl[i]);
+        if (mg_twice(g)) RF_REFUSE(ORBX_E_INVALID, "%s: a table slot listed twice", who);
+    }
+    // the rows, on the mirror: what every point will report, and the longest row
+    std::vector<uint8_t> expect((size_t)n, 0);
+    int longest = 0;
+    bool any = false;
+    for (int i = 0; i < n; i++) {
+        const int p = job->point[i];
+        const uint32_t h = g->hw[G.hdr(p)];
+        const int cnt = MG_CNT(h);
+        if (!(h & MG_LIVE) || (h & MG_BAD) || cnt == 0) continue;
+        longest = std::max(longest, cnt);
+        int ref_idx = 0;
+        bool takes = false;
+        for (int e = 0; e < cnt; e++) {
+            const uint32_t ent = g->hw[G.row(p, e)];
+            const int k = (int)(ent >> 16), idx = (int)(ent & 0xFFFFu);
+            const int q = k < G.max_kf ? g->kmap[k] : -1;
+            if (q < 0) RF_REFUSE(ORBX_E_INVALID, "%s: entry %d: point slot %d is observed by keyframe slot %d, which is not listed", who, i, p, k);
+            if (do_geom && k == job->ref_kf[i]) ref_idx = idx;
+            if (do_desc && !job->kf_bad[q]) {
+                const orbx_frame *f = job->kf_frame ? job->kf_frame[q] : nullptr;
+                if (!f) RF_REFUSE(ORBX_E_INVALID, "%s: keyframe slot %d is not bad and has no resident frame", who, k);
+                if (idx >= f->n) RF_REFUSE(ORBX_E_INVALID, "%s: point slot %d names feature %d of keyframe slot %d, whose frame has %d", who, p, idx, k, f->n);
+                takes = true;
+            }
+        }
+        if (do_geom) {
+            const int ref = job->ref_kf[i];
+            if (!mg_kf_live(g, ref) || g->kmap[ref] < 0) RF_REFUSE(ORBX_E_INVALID, "%s: entry %d: the reference keyframe slot %d is not listed or not in use", who, i, ref);
+            if (ref_idx >= (int)g->hw[ref]) RF_REFUSE(ORBX_E_INVALID, "%s: entry %d: reference feature %d, keyframe slot %d has %d", who, i, ref_idx, ref, (int)g->hw[ref]);
+            const int oct = (int)(g->hattr[G.at(ref, ref_idx)] & MG_OCT);
+            if (oct >= job->nlevels) RF_REFUSE(ORBX_E_INVALID, "%s: entry %d: the reference feature's octave %d, nlevels %d", who, i, oct, job->nlevels);
+            if (!job->pos && !(m->have[tsl[i]] & 1)) RF_REFUSE(ORBX_E_INVALID, "%s: entry %d: pos is NULL and table slot %d has never been given its geometry", who, i, tsl[i]);
+            expect[i] |= ORBX_REFRESH_GEOM;
+        }
+        if (takes) expect[i] |= ORBX_REFRESH_DESC;
+        any = true;
+    }
+    for (int q = 0; q < nk; q++) g->kmap[job->kf_slot[q]] = -1;   // every refusal is behind us
+    CallCtx *c;
+    int rc = orbx_call_ctx(g->device, &c);
+    if (rc) return rc;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    const size_t np = (size_t)n;
+    const int cap = std::max(4, (longest + 3) & ~3);
+    // up: pts | tslot | ref | pos | sf | kft     work and down: status | geom | best_kf | best_idx | desc
+    BlobCursor up = { nullptr, nullptr, 0 };
+    const size_t u_pts = up.take(4 * np), u_ts = up.take(job->table_slot ? 4 * np : 0), u_ref = up.take(do_geom ? 4 * np : 0),
+                 u_pos = up.take(do_geom && job->pos ? 12 * np : 0), u_sf = up.take(do_geom ? 4 * (size_t)job->nlevels : 0),
+                 u_kft = up.take(sizeof(RfKf) * (size_t)nkt), blob = up.o;
+    const size_t o_st = 0, o_geom = a16(np), o_bk = o_geom + 32 * np, o_bi = o_bk + a16(4 * np), o_desc = o_bi + a16(4 * np), out = o_desc + 32 * np;
+    if ((rc = call_reserve(c, blob, out, out))) return rc;
+    uint8_t *hb = c->h_blob;
+    memcpy(hb + u_pts, job->point, 4 * np);
+    if (job->table_slot) memcpy(hb + u_ts, job->table_slot, 4 * np);
+    if (do_geom) {
+        memcpy(hb + u_ref, job->ref_kf, 4 * np);
+        if (job->pos) memcpy(hb + u_pos, job->pos, 12 * np);
+        memcpy(hb + u_sf, job->scale_factors, 4 * (size_t)job->nlevels);
+    }
+    RfKf *kft = (RfKf *)(hb + u_kft);
+    memset(kft, 0, sizeof(RfKf) * (size_t)nkt);
+    for (int s = 0; s < nkt; s++) kft[s].bad_n = RF_BAD;   // a slot that is not listed: named by no row that is worked on
+    if ((rc = mg_order_before(g, st))) return rc;
+    if (m && (rc = mappoints_order_before(m, st))) return rc;
+    for (int q = 0; q < nk; q++) {
+        RfKf &K = kft[job->kf_slot[q]];
+        K.cx = job->kf_centre[3 * q]; K.cy = job->kf_centre[3 * q + 1]; K.cz = job->kf_centre[3 * q + 2];
+        const orbx_frame *f = do_desc && job->kf_frame && !job->kf_bad[q] ? job->kf_frame[q] : nullptr;
+        K.bad_n = f ? (uint32_t)f->n : RF_BAD;
+        K.desc = f ? (const uint32_t *)(f->blk.d + f->o_desc) : nullptr;
+        if (f && (rc = frame_order_before(f, st))) return rc;
+    }
+    if (any) {
+        ORBX_HIP(hipMemcpyAsync(c->d_blob, c->h_blob, blob, hipMemcpyHostToDevice, st));
+        RfArgs A;
+        memset(&A, 0, sizeof A);
+        A.G = G; A.n = n; A.what = what; A.cap = cap; A.nkt = nkt; A.nlevels = job->nlevels;
+        const uint8_t *db = c->d_blob;
+        uint8_t *wk = c->d_work;
+        A.pts = (const int32_t *)(db + u_pts);
+        A.tslot = m ? (const int32_t *)(db + (job->table_slot ? u_ts : u_pts)) : nullptr;
+        A.ref = do_geom ? (const int32_t *)(db + u_ref) : nullptr;
+        A.pos = do_geom && job->pos ? (const float *)(db + u_pos) : nullptr;
+        A.sf = do_geom ? (const float *)(db + u_sf) : nullptr;
+        A.kft = (const RfKf *)(db + u_kft);
+        A.tgeom = m ? m->d_geom : nullptr; A.tdesc = m ? m->d_desc : nullptr;
+        A.status = wk + o_st; A.geom = (float4 *)(wk + o_geom); A.best_kf = (int32_t *)(wk + o_bk); A.best_idx = (int32_t *)(wk + o_bi);
+        A.desc = (uint4 *)(wk + o_desc);
+        const size_t lds = rf_lds_bytes(cap);
+        if (lds > 32768) ORBX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mp_refresh), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(k_mp_refresh, dim3((unsigned)std::min(n, 4096)), dim3(64), lds, st, A);
+        ORBX_HIP(hipGetLastError());
+        if (m) {
+            ORBX_HIP(hipEventRecord(m->ev, st));
+            m->ev_stream = st; m->ev_set = true;
+            for (int i = 0; i < n; i++) m->have[tsl[i]] |= expect[i];   // what has been enqueued is in the table for every later call
+        }
+        uint8_t *ho = (uint8_t *)c->h_out;
+        ORBX_HIP(hipMemcpyAsync(ho + o_st, wk + o_st, np, hipMemcpyDeviceToHost, st));
+        if (geom && do_geom) ORBX_HIP(hipMemcpyAsync(ho + o_geom, wk + o_geom, 32 * np, hipMemcpyDeviceToHost, st));
+        if (best_kf && do_desc) ORBX_HIP(hipMemcpyAsync(ho + o_bk, wk + o_bk, 4 * np, hipMemcpyDeviceToHost, st));
+        if (best_idx && do_desc) ORBX_HIP(hipMemcpyAsync(ho + o_bi, wk + o_bi, 4 * np, hipMemcpyDeviceToHost, st));
+        if (desc && do_desc) ORBX_HIP(hipMemcpyAsync(ho + o_desc, wk + o_desc, 32 * np, hipMemcpyDeviceToHost, st));
+        ORBX_HIP(hipStreamSynchronize(st));
+        for (int i = 0; i < n; i++)
+            if (ho[o_st + i] != expect[i]) { orbx_set_error("%s: entry %d: the device reports status %d, the host's mirror %d: the graph is inconsistent", who, i, ho[o_st + i], expect[i]); return ORBX_E_HIP; }
+        for (int i = 0; i < n; i++) {   // a row whose bit is clear stays as the caller left it
+            const size_t ii = (size_t)i;
+            if ((expect[i] & ORBX_REFRESH_GEOM) && geom) memcpy(geom + 8 * ii, ho + o_geom + 32 * ii, 32);
+            if (expect[i] & ORBX_REFRESH_DESC) {
+                if (best_kf) best_kf[i] = ((const int32_t *)(ho + o_bk))[i];
+                if (best_idx) best_idx[i] = ((const int32_t *)(ho + o_bi))[i];
+                if (desc) memcpy(desc + 32 * ii, ho + o_desc + 32 * ii, 32);
+            }
+        }
+    }
+    if (status) memcpy(status, expect.data(), np);
     return ORBX_OK;
 }

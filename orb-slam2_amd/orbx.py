@@ -263,6 +263,28 @@ class Sim3OptJob(C.Structure):
                 ("report", C.POINTER(Sim3OptReport))]
 
 
+class RefreshJob(C.Structure):
+    """orbx_refresh_job (include/orbx.h)"""
+    _fields_ = [("what", C.c_int), ("n", C.c_int), ("point", C.c_void_p), ("table_slot", C.c_void_p), ("pos", C.c_void_p),
+                ("ref_kf", C.c_void_p), ("nk", C.c_int), ("kf_slot", C.c_void_p), ("kf_centre", C.c_void_p), ("kf_bad", C.c_void_p),
+                ("kf_frame", C.POINTER(C.c_void_p)), ("scale_factors", C.c_void_p), ("nlevels", C.c_int)]
+
+
+REFRESH_GEOM, REFRESH_DESC = 1, 2
+
+
+class RefreshResult:
+    """what MapGraph.refresh_points hands back: status[n] (bit 0 geometry, bit 1 descriptor), geom[n][8] = X Y Z mfMinDistance nx ny nz
+    mfMaxDistance, best_kf[n], best_idx[n], desc[n][32]; a row whose status bit is clear is as it was before the call"""
+
+    def __init__(self, n, fill=0):
+        self.status = np.full(n, fill, np.uint8)
+        self.geom = np.full((n, 32), fill, np.uint8).view(np.float32)      # [n][8]; fill is a byte pattern
+        self.best_kf = np.full((n, 4), fill, np.uint8).view(np.int32).reshape(n)
+        self.best_idx = self.best_kf.copy()
+        self.desc = np.full((n, 32), fill, np.uint8)
+
+
 _lib = None
 
 
@@ -378,6 +400,7 @@ def lib():
     L.orbx_mapgraph_vote.argtypes = [vp, vp, i, vp, vp, ip]
     L.orbx_mapgraph_covisibility.argtypes = [vp, i, vp, vp, ip]
     L.orbx_mapgraph_cull_keyframes.argtypes = [vp, vp, vp, i, i, vp, vp, vp, vp, i, ip]
+    L.orbx_mapgraph_refresh_points.argtypes = [vp, vp, C.POINTER(RefreshJob), vp, vp, vp, vp, vp, vp]
     L.orbx_frame_search_local_points.argtypes = [vp, vp, vp, vp, vp, i, vp, vp, f, f, vp, i, f, f, vp, ip, vp]
     L.orbx_pose_optimize.argtypes = [i, C.POINTER(PoseObs), vp, vp, vp, vp, ip, C.POINTER(PoseReport)]
     L.orbx_pose_optimize_batch.argtypes = [i, C.POINTER(PoseJob), i]
@@ -1230,6 +1253,39 @@ class MapGraph:
         self.last_n_bad = nb.value
         _check(rc)
         return dict(culled=cu, n_mps=mps, n_redundant=red, bad_points=bad[:nb.value].copy())
+
+    def refresh_points(self, points, *, table=None, table_slots=None, pos=None, ref_kf=None, keyframes=None, scale_factors=None,
+                       what=REFRESH_GEOM | REFRESH_DESC, out=None, stream=None):
+        """MapPoint::UpdateNormalAndDepth (what & 1) and ComputeDistinctiveDescriptors (what & 2) of the listed point slots, written into
+        `table` (a MapPoints, slots table_slots or the point slots themselves) when there is one.  keyframes = dict(slot[nk], centre[nk][3],
+        bad[nk], frame = nk DeviceFrames or None): every keyframe a row may name, and every ref_kf.  pos[n][3] = mWorldPos (None: as the table
+        holds it).  out: a RefreshResult to write into (rows that are not updated stay as they are) -> RefreshResult"""
+        who = "MapGraph.refresh_points"
+        pt, = self._cols("refresh_points", points)
+        n = len(pt)
+        kf = keyframes or dict(slot=[], centre=np.zeros((0, 3)), bad=[], frame=[])
+        ks = np.ascontiguousarray(kf["slot"], np.int32).reshape(-1)
+        nk = len(ks)
+        kc = np.ascontiguousarray(kf["centre"], np.float32).reshape(-1, 3)
+        kb = np.ascontiguousarray(kf["bad"], np.uint8).reshape(-1)
+        frames = list(kf.get("frame") or [None] * nk)
+        if len(kc) != nk or len(kb) != nk or len(frames) != nk:
+            raise OrbxError(-1, f"{who}: {nk} keyframe slots need centre [{nk}][3], bad [{nk}] and {nk} frames")
+        fr = (C.c_void_p * max(nk, 1))(*[None if f is None else f._h for f in frames])
+        ts = None if table_slots is None else MapPoints._slots(table_slots)
+        po = None if pos is None else np.ascontiguousarray(pos, np.float32)
+        rk = None if ref_kf is None else np.ascontiguousarray(ref_kf, np.int32).reshape(-1)
+        sf = None if scale_factors is None else np.ascontiguousarray(scale_factors, np.float32).reshape(-1)
+        if (ts is not None and len(ts) != n) or (po is not None and po.shape != (n, 3)) or (rk is not None and len(rk) != n):
+            raise OrbxError(-1, f"{who}: {n} points need table_slots [{n}], pos [{n}][3] and ref_kf [{n}]")
+        job = RefreshJob(int(what), n, _p(pt), None if ts is None else _p(ts), None if po is None else _p(po), None if rk is None else _p(rk),
+                         nk, _p(ks), _p(kc), _p(kb), fr, None if sf is None else _p(sf), 0 if sf is None else len(sf))
+        r = RefreshResult(n) if out is None else out
+        if any(len(a) != n for a in (r.status, r.geom, r.best_kf, r.best_idx, r.desc)):
+            raise OrbxError(-1, f"{who}: out holds {len(r.status)} rows, {n} points are listed")
+        _check(lib().orbx_mapgraph_refresh_points(self._h, None if table is None else table._h, C.byref(job), _p(r.status), _p(r.geom),
+                                                  _p(r.best_kf), _p(r.best_idx), _p(r.desc), stream))
+        return r
 
 
 def _pose_inputs(cam, Tcw, who):
